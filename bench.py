@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — cell-updates/s of the WDPM Add module on a synthetic 16384 x 16384 DEM (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 16384] [--driver ranks|group]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 16384] [--driver ranks|group] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = one iteration (all 9 colour passes) over the whole raster.  The timed region is one
@@ -10,6 +10,14 @@ block of the reference's loop: threshold flush + snapshot, K iterations, max-|dw
 decomposition, one rank per GPU, the C driver wdpm_amd/csrc/wdpm_rowblock.c on every rank, halo rows
 by RCCL send/recv issued by the library on its own stream; total work is fixed, so scaling is strong.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what the headline
+does not need: the CPU baseline (`cpu_baseline`, unless --no-cpu-baseline) and, for short add runs, the same
+K steps once more after the card's clock ramp (`roofline.next_block`).  `--dump-outputs DIR` writes what the
+timed block left its caller as float64 .npy files: max_diff.npy, the water raster (water.npy, n x n, or
+water_sample.npy, a fixed seeded sample of DUMP_CELLS cells when the raster is larger) and, for the drain
+module, drain_stats.npy (|d totaldrain|, volume).  The inputs depend on the arguments only, so two builds
+can be compared file for file.
 
 `--gpus N` without a launcher (WORLD_SIZE unset) starts the N ranks itself, as child processes
 (`python -m torch.distributed.run ...` of this same file, before anything here has touched the GPU),
@@ -42,6 +50,8 @@ HBM_PEAK_GBS = 8000.0               # MI355X HBM3E spec peak (MI355X_MICROARCH.m
 THRES = 0.005 / 1000.0              # zero-depth threshold 0.005 mm
 ADD_M = 0.1                         # add 100 mm, runoff fraction 1.0
 MISSING = -99999.0
+DUMP_CELLS = 1 << 22                # --dump-outputs: at most this many water cells (32 MB of fp64)
+DUMP_SEED = 16384                   # ... picked by this seed when the raster has more
 
 
 class SharedDem:
@@ -244,6 +254,36 @@ def cpu_baseline(n=16384, full=False, quick=False):
             "samples": res}
 
 
+def dump_outputs(out_dir, n, rows, row0, max_diff, drain_stats=None, dist=None, device="cpu", rank=0):
+    """--dump-outputs: `rows` are padded rows row0 .. of the water raster that this rank owns (the whole padded raster at one rank).
+    Collective when `dist` is given: every interior cell is owned by exactly one rank, so a sum of the ranks' bit patterns (zero
+    where a rank does not own the cell) assembles the raster exactly.  Rank 0 writes the files."""
+    import torch
+    if n * n <= DUMP_CELLS:
+        idx = np.arange(n * n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n * n, DUMP_CELLS, replace=False, shuffle=False))
+    r, c = idx // n + 1, idx % n + 1
+    mine = (r >= row0) & (r < row0 + rows.shape[0])
+    bits = np.zeros(idx.size, dtype=np.int64)
+    bits[mine] = rows[r[mine] - row0, c[mine]].view(np.int64)
+    if dist is not None:
+        t = torch.from_numpy(bits).to(device)
+        dist.all_reduce(t)
+        bits = t.cpu().numpy()
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    water = bits.view(np.float64)
+    if idx.size == n * n:
+        np.save(os.path.join(out_dir, "water.npy"), water.reshape(n, n))
+    else:
+        np.save(os.path.join(out_dir, "water_sample.npy"), water)
+    np.save(os.path.join(out_dir, "max_diff.npy"), np.array([max_diff], dtype=np.float64))
+    if drain_stats is not None:
+        np.save(os.path.join(out_dir, "drain_stats.npy"), np.array(drain_stats, dtype=np.float64))
+
+
 def self_launch(args):
     """`python bench.py --gpus N` with no launcher: start the N ranks as CHILD processes (never exec: this
     process has not touched the GPU and will not), relay rank 0's JSON line, return the launcher's status.
@@ -361,12 +401,22 @@ def main():
     ap.add_argument("--module", choices=["add", "drain"], default="add",
                     help="drain = BASELINE config 5: water-in is the add-100-mm state after --drain-spinup iterations")
     ap.add_argument("--drain-spinup", type=int, default=1000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements the headline does not need: the CPU baseline and, for short add runs, "
+                         "roofline.next_block")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed block computed (max diff, water raster or a seeded sample of it) as .npy files")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-baseline-full", action="store_true",
-                    help="also time SURVEY §8d's 16384^2 x 10 iterations on the host (about a minute) and make it the headline")
+                    help="with --full: also time SURVEY §8d's 16384^2 x 10 iterations on the host (about a minute) and make it "
+                         "the headline")
     ap.add_argument("--cpu-baseline-quick", action="store_true",
-                    help="tests only: a few iterations per CPU sample (the line's shape, not a baseline to quote)")
+                    help="with --full, tests only: a few iterations per CPU sample (the line's shape, not a baseline to quote)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if (args.cpu_baseline_full or args.cpu_baseline_quick) and not args.full:
+        ap.error("--cpu-baseline-full and --cpu-baseline-quick only apply with --full")
 
     launched = "WORLD_SIZE" in os.environ
     if args.gpus > 1 and not launched and args.driver == "ranks":
@@ -462,9 +512,10 @@ def main():
             lib.check(lib.dll.wdpm_timing_reset(grp.rank_ctx(i)))
         t0 = time.perf_counter()
         max_diff = grp.run_block(args.steps, THRES)  # exactly K timed steps
+        drain_stats = None
         if args.module == "drain":
             ts = time.perf_counter()
-            grp.drain_stats()
+            drain_stats = grp.drain_stats()
             stats_s = time.perf_counter() - ts
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
@@ -498,6 +549,8 @@ def main():
         lib.check(lib.dll.wdpm_rank_slab(lib.dll.wdpm_group_rank(grp._h, 0), 0, C.byref(sl)))
         own_rows0 = sl.own_hi - sl.own_lo + 1 if ranks_used > 1 else n
         decomposition = f"row-block x{ranks_used}, one process, one host thread per GPU" if ranks_used > 1 else "single GPU"
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, n, grp.download_water(), 0, max_diff, drain_stats)
         closer = grp.close
     else:
         # ---- one process per GPU: wdpm_rank_* with RCCL halos (or host-staged ones when ranks share a GPU)
@@ -581,12 +634,13 @@ def main():
         solver.ctx.timing_reset()
         t0 = time.perf_counter()
         max_diff = solver.run_block(args.steps, THRES) # exactly K timed steps (ends with the ranks' all-gather of max diff)
+        drain_stats = None
         if args.module == "drain":
             # the drain module's per-block bookkeeping (WDPMCL.c:1257-1268) belongs to the block loop: |d totaldrain|
             # and the sequential row-major volume sum (evaluated exactly on the device; rank-chained at N > 1)
             torch.cuda.synchronize()
             ts = time.perf_counter()
-            solver.drain_stats()
+            drain_stats = solver.drain_stats()
             stats_s = time.perf_counter() - ts
         # the closing bracket.  Each rank stops its own clock when ITS device is idle, then all meet; the job's time is
         # the MAX over ranks (the block's last step is a collective, so no rank can be early by more than that step)
@@ -604,14 +658,17 @@ def main():
         if world > 1:
             per_rank = [None] * world
             dist.all_gather_object(per_rank, mine)
+        if args.dump_outputs:                          # before anything below moves the water on
+            dump_outputs(args.dump_outputs, n, solver.owned_water(), solver.slab.own_lo if world > 1 else 0, max_diff, drain_stats,
+                         dist if world > 1 else None, "cuda" if backend == "nccl" else "cpu", rank)
         # The same K steps ONCE MORE, outside the contract's timed region and reported beside it, never as `value`: an MI355X whose
         # compute units have idled for 5 ms runs this kernel 10 - 35 % slower and takes ~30 ms of THIS kernel to come back
         # (profiles/r04/first_iterations2.txt: no sleep, copy or other kernel shortens that), so `--warmup 5 --steps 20` times
         # the ramp itself - and at N = 8, where its 25 iterations last 4 ms, the slowest part of it.  After the timed block:
         # untimed iterations until 50 ms have gone by since the warm-up began (the same number on every rank), then K timed
         # ones - the same box at the clocks the reference's 1000-iteration blocks run at.  Short add runs only (a long one is
-        # past the ramp by itself).
-        if args.module == "add" and 1 <= args.steps <= 200 and not degraded:
+        # past the ramp by itself), and with --full only.
+        if args.full and args.module == "add" and 1 <= args.steps <= 200 and not degraded:
             per_step = dt / max(args.steps, 1)
             more = int(min(4000, max(0.0, 0.050 - dt - args.warmup * per_step) / per_step)) if per_step > 0 else 0
             if more > 0:
@@ -763,7 +820,7 @@ def main():
         if degraded:
             out["degraded"] = True
             out["degraded_reason"] = degraded
-        if not args.no_cpu_baseline and ranks_used == 1:   # rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and ranks_used == 1:   # rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(n, full=args.cpu_baseline_full, quick=args.cpu_baseline_quick)
         print(json.dumps(out), flush=True)
     if degraded:

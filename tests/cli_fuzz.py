@@ -3,7 +3,8 @@ header keys, %g / %e / signed numbers, trailing separators, blank last line, NOD
 all three modules, water file or NULL, scratch or NULL or an existing scratch raster to resume from, iteration limits,
 arguments on the command line or in a parameter file), run through two executables whose exit code,
 report text (minus the wall-clock column) and output files are compared.  Used by tests/test_cli_differential.py:
-the UNMODIFIED reference executable (oracle/_ref/WDPMCL_ref) against the product's command line."""
+the UNMODIFIED reference executable (oracle/_ref/WDPMCL_ref), or its results as tests/golden/cli_fuzz_ref.json.gz stores them,
+against the product's command line."""
 
 import os, subprocess, sys, random, hashlib, re, shutil
 import numpy as np
@@ -31,7 +32,9 @@ def write_asc(path, a, nodata, rng, style):
             f.write(sep.join(fmt_val(rng, a[r, c], style["num"]) for c in range(C)) + (sep if style["trail"] else "") + eol)
         if style["blank"]: f.write(eol)
 
-def one(seed, work, ref_exe, exe, vary_env=False):
+def one(seed, work, ref_exe, exe, vary_env=False, recorded=None):
+    """recorded: the reference's (exit code, report, output hashes) of this job as tests/golden/cli_fuzz_ref.json.gz stores
+    them; the reference executable is run only when it is not given"""
     rng = random.Random(seed); nrng = np.random.default_rng(seed)
     rng_amt = random.Random(seed * 7 + 1).choice([5, 50, 250.5])
     R, C = (rng.randint(1, 14), rng.randint(1, 17)) if rng.random() < 0.85 else (rng.randint(20, 70), rng.randint(20, 90))
@@ -53,14 +56,18 @@ def one(seed, work, ref_exe, exe, vary_env=False):
     limit = rng.choice([0, 1000, 3000])
     resume = scratch and rng.random() < 0.5
     as_param_file = rng.random() < 0.2
+    w = "w.asc" if usewater else "NULL"; s = "s.asc" if scratch else "NULL"
+    if module == "add": args = ["add", "dem.asc", w, "out.asc", s, str(rng_amt), "0.8", "1.0", "0", "0", "0.005", str(limit)]
+    elif module == "subtract": args = ["subtract", "dem.asc", w, "out.asc", s, str(rng_amt), "1.0", "0", "0", "0.005", str(limit)]
+    else: args = ["drain", "dem.asc", w, "out.asc", s, "1.0", "1.0", "0", "0", "0.005", str(limit)]
     for name, exe in (("ref", ref_exe), ("new", exe)):
+        if name == "ref" and recorded is not None:
+            rc, out, files = recorded
+            outs.append((rc, out, files, args))
+            continue
         d = os.path.join(work, name); shutil.rmtree(d, ignore_errors=True); os.makedirs(d)
         write_asc(os.path.join(d, "dem.asc"), dem, nodata, rng, style)
         if usewater: write_asc(os.path.join(d, "w.asc"), water, nodata, rng, dict(style, num=0))
-        w = "w.asc" if usewater else "NULL"; s = "s.asc" if scratch else "NULL"
-        if module == "add": args = ["add", "dem.asc", w, "out.asc", s, str(rng_amt), "0.8", "1.0", "0", "0", "0.005", str(limit)]
-        elif module == "subtract": args = ["subtract", "dem.asc", w, "out.asc", s, str(rng_amt), "1.0", "0", "0", "0.005", str(limit)]
-        else: args = ["drain", "dem.asc", w, "out.asc", s, "1.0", "1.0", "0", "0", "0.005", str(limit)]
         if resume:      # a scratch raster left by an earlier run: the reference resumes from it (WDPMCL.c:682-725)
             write_asc(os.path.join(d, "s.asc"), np.where(miss, nodata, np.round(water * 0.5, 6)), nodata, rng, dict(style, num=0))
         argv = args

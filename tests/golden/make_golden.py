@@ -27,6 +27,7 @@ reference executable, serial path cpu=0), and writes DATA only:
     python tests/golden/make_golden.py merge       (fold the settled parts into full_size.npz)
     python tests/golden/make_golden.py verify-oracle   (the CPU restatement against config 3's settled entries: 20 minutes)
     python tests/golden/make_golden.py synthcli    (synth_cli.json: the reference EXECUTABLE's add / drain / subtract chain on a synthetic 3072^2 DEM)
+    python tests/golden/make_golden.py clifuzz     (cli_fuzz_ref.json.gz: the reference EXECUTABLE on the random jobs of tests/cli_fuzz.py)
 """
 import ctypes as C
 import gzip
@@ -295,6 +296,24 @@ def make_synth_cli(n=3072):
         json.dump(res, f, indent=1)
 
 
+CLI_FUZZ_SEEDS = [*range(0, 120), *range(300, 420), *range(1000, 1060), *range(1300, 1360)]
+
+
+def make_cli_fuzz():
+    """The REFERENCE EXECUTABLE on the random jobs of tests/cli_fuzz.py that tests/test_cli_differential.py runs (CLI_FUZZ_SEEDS):
+    per seed the exit code, the report without its wall-clock parts and the sha256 of the output and scratch rasters.
+    -> cli_fuzz_ref.json.gz"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from cli_fuzz import one
+    res = {}
+    with tempfile.TemporaryDirectory() as td:
+        for seed in CLI_FUZZ_SEEDS:
+            _, ref, _, _, _ = one(seed, td, REF_EXE, REF_EXE)
+            res[str(seed)] = list(ref[:3])
+    with gzip.GzipFile(os.path.join(HERE, "cli_fuzz_ref.json.gz"), "wb", mtime=0) as g:
+        g.write(json.dumps(res, sort_keys=True).encode())
+
+
 def verify_oracle_settled():
     """The CPU restatement (oracle/wdpm_oracle.c) against the SETTLED golden of config 3: two blocks of 1000 iterations at 4096^2, the
     threshold flush between them - twenty minutes of one core, so not part of the test suite (which pins the oracle at 4096^2 x 20 and on
@@ -554,6 +573,9 @@ def main():
         return
     if len(sys.argv) > 1 and sys.argv[1] == "synthcli":
         make_synth_cli()
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "clifuzz":
+        make_cli_fuzz()
         return
     if len(sys.argv) > 1 and sys.argv[1] == "merge":
         merge_settled()

@@ -1,14 +1,21 @@
 """bench.py prints ONE JSON line with the fields the driver reads (metric, value, unit, n_gpus, steps,
 warmup, ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config.workload) plus the
-`roofline` and `cpu_baseline` objects; checked on a small raster so the test takes seconds."""
+`roofline` object (and with --full the `cpu_baseline` object and `roofline.next_block`); checked on a small raster so the
+test takes seconds.  --dump-outputs writes what the timed block computed."""
+import importlib.util
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
+
+spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+bench = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(bench)
 
 gpu = pytest.mark.gpu
 
@@ -24,7 +31,7 @@ def run_bench(*args):
 
 @gpu
 def test_bench_line_has_the_contract_fields():
-    d = run_bench("--size", "1024", "--steps", "7", "--warmup", "2", "--cpu-baseline-quick")
+    d = run_bench("--size", "1024", "--steps", "7", "--warmup", "2", "--full", "--cpu-baseline-quick")
     assert d["metric"] == "cell-updates/sec on Add module, 1024x1024 DEM" and d["unit"] == "cell-updates/s"
     assert d["n_gpus"] == 1 and d["steps"] == 7 and d["warmup"] == 2
     assert d["higher_is_better"] is True and d["scaling"] == "strong" and d["vs_baseline"] is None
@@ -34,7 +41,7 @@ def test_bench_line_has_the_contract_fields():
     assert r["bound"] == "hbm" and r["unit"] == "GB/s" and r["peak"] == 8000.0
     assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12 and r["achieved"] > 0
     assert list(r)[:2] == ["bound", "job_frac"] and 0 < r["job_frac"] <= r["frac_all_launches"] * 1.001
-    # a short run also reports the same K iterations once more, after the timed block and beside it (the card's clocks have come up by then)
+    # with --full a short run also reports the same K iterations once more, after the timed block and beside it (the card's clocks have come up by then)
     nb = r["next_block"]
     assert 0 < nb["job_frac"] < 1 and nb["ms_per_step"] > 0 and nb["kernel_ms_per_iteration"] > 0 and "not `value`" in nb["what"]
     assert nb["untimed_iterations_before"] > 100        # 1024^2: microseconds per iteration, 50 ms of ramp
@@ -54,7 +61,7 @@ def test_bench_line_has_the_contract_fields():
 
 
 def test_cpu_baseline_samples_of_the_default_command():
-    """which samples the un-flagged bench times (no GPU, nothing is run): the metric's own raster first"""
+    """which samples `--full` times without --cpu-baseline-full (no GPU, nothing is run): the metric's own raster first"""
     import importlib.util
     spec = importlib.util.spec_from_file_location("bench_samples", os.path.join(ROOT, "bench.py"))
     mod = importlib.util.module_from_spec(spec)
@@ -102,10 +109,75 @@ def test_counter_evidence_is_quoted_for_the_headline_configuration_and_build():
 
 
 @gpu
-def test_bench_drain_line():
+def test_bench_drain_line(tmp_path):
     d = run_bench("--module", "drain", "--size", "1024", "--steps", "5", "--warmup", "1", "--drain-spinup", "20",
-                  "--no-cpu-baseline")
+                  "--no-cpu-baseline", "--dump-outputs", str(tmp_path))
     assert d["metric"].startswith("cell-updates/sec on Drain module") and d["value"] > 0 and "cpu_baseline" not in d
+    stats = np.load(tmp_path / "drain_stats.npy")
+    assert stats.dtype == np.float64 and stats.shape == (2,) and stats[1] > 0          # |d totaldrain|, the volume left
+    assert np.load(tmp_path / "water.npy").shape == (1024, 1024)
+
+
+@gpu
+def test_plain_run_is_lean_and_dumps_what_the_timed_block_computed(oracle, tmp_path):
+    """no CPU baseline and no second block without --full; the dumped raster and max diff are the timed block's, bit for bit
+    the CPU oracle's after the same warm-up block and timed block"""
+    n, warmup, steps = 300, 2, 7
+    d = run_bench("--size", str(n), "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path))
+    assert "cpu_baseline" not in d and "next_block" not in d["roofline"] and d["steps"] == steps and d["ms_per_step"] > 0
+    water, md = np.load(tmp_path / "water.npy"), np.load(tmp_path / "max_diff.npy")
+    assert water.dtype == np.float64 and water.shape == (n, n) and md.tolist() == [d["config"]["max_diff_m"]]
+    assert sorted(os.listdir(tmp_path)) == ["max_diff.npy", "water.npy"]
+    bd = np.full((n + 2, n + 2), bench.MISSING)
+    bd[1:-1, 1:-1] = oracle.synth_dem(n, n)
+    bw = np.where(bd > bench.MISSING, bench.ADD_M, 0.0)
+    with oracle.context(module="add", nrows=n, ncols=n, missingvalue=bench.MISSING) as o:
+        o.upload(bd, bw)
+        o.run_block(warmup, bench.THRES)
+        mo = o.run_block(steps, bench.THRES)
+        wo = o.download_water()[1:-1, 1:-1]
+    assert md[0] == mo and np.array_equal(water.view(np.uint64), wo.view(np.uint64))
+
+
+def test_dump_outputs_whole_sampled_and_assembled_from_ranks(tmp_path):
+    """bench.dump_outputs (no GPU): a raster that fits is written whole; a larger one as the same seeded sample every time, never
+    more than DUMP_CELLS cells; row blocks of several ranks are put together exactly (signed zeros and NaNs included)"""
+    rng = np.random.default_rng(3)
+    n = 64
+    w = rng.standard_normal((n + 2, n + 2))
+    w[5, 7], w[9, 9] = -0.0, np.nan
+    bench.dump_outputs(str(tmp_path / "whole"), n, w, 0, 0.25)
+    got = np.load(tmp_path / "whole" / "water.npy")
+    assert np.array_equal(got.view(np.uint64), w[1:-1, 1:-1].view(np.uint64)) and np.load(tmp_path / "whole" / "max_diff.npy").tolist() == [0.25]
+
+    class TwoRanks:            # all_reduce as gloo does it over two ranks, the other rank's contribution given
+        def __init__(self, other):
+            self.other = other
+
+        def all_reduce(self, t):
+            t += self.other
+
+    top, bottom = w[:30], w[30:]                                         # rank 0 owns padded rows 0 .. 29, rank 1 the rest
+    seen = []
+
+    class Capture:
+        def all_reduce(self, t):
+            seen.append(t.clone())
+    bench.dump_outputs(str(tmp_path / "r1"), n, bottom, 30, 0.25, dist=Capture(), rank=1)
+    assert not os.path.exists(tmp_path / "r1")                           # only rank 0 writes
+    bench.dump_outputs(str(tmp_path / "two"), n, top, 0, 0.25, (1.0, 2.0), dist=TwoRanks(seen[0]), rank=0)
+    got = np.load(tmp_path / "two" / "water.npy")
+    assert np.array_equal(got.view(np.uint64), w[1:-1, 1:-1].view(np.uint64))
+    assert np.load(tmp_path / "two" / "drain_stats.npy").tolist() == [1.0, 2.0]
+
+    n = 2049                                                             # n^2 > DUMP_CELLS
+    w = rng.standard_normal((n + 2, n + 2))
+    for name in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / name), n, w, 0, 0.5)
+    a, b = np.load(tmp_path / "s1" / "water_sample.npy"), np.load(tmp_path / "s2" / "water_sample.npy")
+    assert a.dtype == np.float64 and a.size == bench.DUMP_CELLS and np.array_equal(a, b)
+    assert sorted(os.listdir(tmp_path / "s1")) == ["max_diff.npy", "water_sample.npy"]
+    assert np.isin(a, w[1:-1, 1:-1]).all()
 
 
 @gpu

@@ -27,7 +27,7 @@ profile)
 lines)
   for a in "--steps 20 --warmup 5:bench_steps20" "--steps 1000 --warmup 20:bench_default" "--size 4096 --steps 1000 --warmup 20:config3_4096" "--module drain --size 8192 --steps 1000 --warmup 20 --drain-spinup 1000:config5_drain_8192_1gpu"; do
     args=${a%%:*}; name=${a##*:}
-    timeout -k 10 400 python bench.py $args $( [ $name = bench_steps20 ] || echo --no-cpu-baseline ) > $O/$name.json 2> $O/$name.err || { echo "$name failed"; exit 1; }
+    timeout -k 10 400 python bench.py $args $( [ $name = bench_steps20 ] && echo --full || echo --no-cpu-baseline ) > $O/$name.json 2> $O/$name.err || { echo "$name failed"; exit 1; }
     line $O/$name.json $name
   done ;;
 scale)
