@@ -378,6 +378,26 @@ enum { WDPM_OPT_SIGNED_ZERO_SAFE = 1, WDPM_OPT_DEM32 = 2, WDPM_OPT_TILES = 3, WD
 int wdpm_get_option(wdpm_ctx *ctx, int32_t key, int64_t *value);
 int wdpm_set_option(wdpm_ctx *ctx, int32_t key, int64_t value);
 
+/* -- launch ledger (product library only): which kernel instantiation ran, counted where the launch is queued.
+ * One process-global counter per kernel instantiation the library contains; the table is complete from the moment the library is
+ * loaded (every count 0 until something is launched).  Counted: every launch the library queues - the iteration kernels, the
+ * colour passes, the set-up, flush, max-change, drain, statistics and balance kernels, the DPP self-check; a launch captured into
+ * a HIP graph counts once, when it is captured (the replays: WDPM_OPT_GRAPH_LAUNCHES).  Not counted: anything that only asks the
+ * dispatch which kernel it would take.  Names are the kernels' demangled names without namespace, return type or parameters,
+ * every template argument written out ("fused_iteration_kernel<0, false, 2, true, true, false>").
+ * Returns the number of entries; for 0 <= index < that number, also the entry's name (static storage), its launches and, if
+ * by_switches is given, its launches by the state of the switches the host handed the kernel (WDPM_LEDGER_SWITCH_STATES counts,
+ * indexed by the bits below; 0 for the kernels that take none).  Makes no HIP call: readable without a GPU.  The CPU
+ * restatement has no kernels and returns 0.
+ *   marching kernel (fused_iteration_kernel): NO_CLAMP the exact unclamped neighbour step (elevations not known to be bounded),
+ *     PRIO issue priorities between the two waves of a SIMD, TILE_FLAGS dry-tile flags kept, BALANCE the per-XCD chunk table
+ *   relay kernel (relay_iteration_kernel): its store_plain bits - 1 ordinary instead of non-temporal stores, 2 stage
+ *     priorities, 4 the unclamped step */
+enum { WDPM_LEDGER_NO_CLAMP = 1, WDPM_LEDGER_PRIO = 2, WDPM_LEDGER_TILE_FLAGS = 4, WDPM_LEDGER_BALANCE = 8,
+       WDPM_LEDGER_RELAY_ORDINARY_STORES = 1, WDPM_LEDGER_RELAY_PRIO = 2, WDPM_LEDGER_RELAY_NO_CLAMP = 4,
+       WDPM_LEDGER_SWITCH_STATES = 16 };
+int wdpm_launch_ledger(int32_t index, const char **name, int64_t *launches, int64_t *by_switches);
+
 /* -- host staging memory for whole rasters.  The HIP back-end returns page-locked memory, so that
  * wdpm_upload / wdpm_download_water / the scratch checkpoint move at PCIe rate instead of through a
  * pageable bounce buffer (the reference maps its host arrays with CL_MEM_USE_HOST_PTR,

@@ -20,6 +20,10 @@ OPT_SIGNED_ZERO_SAFE = 1
 OPT_DEM32 = 2
 OPT_TILES, OPT_TILES_SEEN, OPT_TILES_WORKED, OPT_SPARSE, OPT_GUARD_BAD, OPT_WATER_KINDS, OPT_PLAIN_WATER, OPT_DEM16 = 3, 4, 5, 6, 7, 8, 9, 10
 OPT_GRAPH_LAUNCHES = 11
+# launch ledger switch bits (include/wdpm.h: WDPM_LEDGER_*): marching kernel, relay kernel (its store_plain bits)
+LEDGER_NO_CLAMP, LEDGER_PRIO, LEDGER_TILE_FLAGS, LEDGER_BALANCE = 1, 2, 4, 8
+LEDGER_RELAY_ORDINARY_STORES, LEDGER_RELAY_PRIO, LEDGER_RELAY_NO_CLAMP = 1, 2, 4
+LEDGER_SWITCH_STATES = 16
 HALO_AUTO, HALO_RCCL, HALO_PEER, HALO_HOST = 0, 1, 2, 3
 HALO_NAMES = {0: "none", 1: "rccl", 2: "peer", 3: "host"}
 COMM_ID_BYTES = 128
@@ -162,6 +166,7 @@ SYMBOLS = {
     "wdpm_synth_dem": (C.c_int, [C.c_int32, C.c_uint64, _vp]),
     "wdpm_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(_vp)]),
     "wdpm_host_free": (None, [_vp]),
+    "wdpm_launch_ledger": (C.c_int, [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 
 
@@ -196,7 +201,7 @@ def _preload_torch_hip_runtime():
         pass
 
 
-_SINCE_ROUND_5 = {"wdpm_device_info"}
+_SINCE_ROUND_5 = {"wdpm_device_info", "wdpm_launch_ledger"}
 
 
 class Lib:
@@ -232,6 +237,19 @@ class Lib:
 
     def context(self, **kw) -> "Context":
         return Context(self, **kw)
+
+    def launch_ledger(self):
+        """The launch ledger (include/wdpm.h: wdpm_launch_ledger): ({kernel instantiation: launches},
+        {kernel instantiation: {switch bits: launches}} with the states that occurred).  No GPU needed."""
+        counts, switches = {}, {}
+        name, n, by = C.c_char_p(), C.c_int64(), (C.c_int64 * LEDGER_SWITCH_STATES)()
+        i = 0
+        while i < self.dll.wdpm_launch_ledger(i, C.byref(name), C.byref(n), by):
+            key = name.value.decode()
+            counts[key] = n.value
+            switches[key] = {b: by[b] for b in range(LEDGER_SWITCH_STATES) if by[b]}
+            i += 1
+        return counts, switches
 
 
 @dataclass

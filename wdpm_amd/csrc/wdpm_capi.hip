@@ -78,7 +78,55 @@ int wdpm_stream_sync(wdpm_ctx *x, hipStream_t s) {
                    "the communicator was aborted", limit_ms / 1000.0);
 }
 
+/* The launch ledger (wdpm_ledger.h): filled in by the static initialisers of the kernel units when the library is loaded, counted
+ * with relaxed atomics from then on.  Constant-initialised storage, so that registering from another unit's initialiser cannot
+ * come before it exists. */
+namespace {
+constexpr int kLedgerMax = 128;
+struct LedgerEntry {
+  char name[96];
+  std::atomic<long long> n[WDPM_LEDGER_SWITCH_STATES];
+};
+LedgerEntry g_ledger[kLedgerMax];
+int g_ledger_entries = 0;       /* written by the loader's thread only, before any launch */
+}  // namespace
+
+int wdpm_ledger_register(const char *pretty, const char *args) {
+  /* "const char *wdpm_ledger_pretty() [K = &(anonymous namespace)::fused_iteration_kernel]": the name after the last "::" */
+  const char *k = strstr(pretty, "K = &");
+  char name[96] = "?";
+  if (k) {
+    k += 5;
+    size_t len = strcspn(k, ",]");
+    for (const char *c = k; c < k + len; c++)
+      if (c[0] == ':' && c[1] == ':') { len -= (size_t)(c + 2 - k); k = c + 2; c = k - 1; }
+    snprintf(name, sizeof name, "%.*s%s", (int)len, k, args);
+  }
+  for (int i = 0; i < g_ledger_entries; i++)
+    if (!strcmp(g_ledger[i].name, name)) return i;      /* (a kernel of both units of wdpm_fused.hip) */
+  if (g_ledger_entries == kLedgerMax) return -1;       /* missing from the table: tests/test_launch_ledger.py says which */
+  snprintf(g_ledger[g_ledger_entries].name, sizeof g_ledger[0].name, "%s", name);
+  return g_ledger_entries++;
+}
+
+void wdpm_ledger_count(int slot, int switches) {
+  if (slot >= 0) g_ledger[slot].n[switches & (WDPM_LEDGER_SWITCH_STATES - 1)].fetch_add(1, std::memory_order_relaxed);
+}
+
 extern "C" {
+
+int wdpm_launch_ledger(int32_t index, const char **name, int64_t *launches, int64_t *by_switches) {
+  if (index < 0 || index >= g_ledger_entries) return g_ledger_entries;
+  long long total = 0;
+  for (int i = 0; i < WDPM_LEDGER_SWITCH_STATES; i++) {
+    const long long v = g_ledger[index].n[i].load(std::memory_order_relaxed);
+    total += v;
+    if (by_switches) by_switches[i] = v;
+  }
+  if (name) *name = g_ledger[index].name;
+  if (launches) *launches = total;
+  return g_ledger_entries;
+}
 
 const char *wdpm_last_error(void) { return g_err; }
 void wdpm_set_last_error(const char *msg) { snprintf(g_err, sizeof g_err, "%s", msg ? msg : ""); }

@@ -52,6 +52,7 @@
  * wdpm_launch_fused_rows picks by size, module and what is known about the raster.
  */
 #include "wdpm_kernels.h"
+#include "wdpm_ledger.h"
 #include "wdpm_stencil.h"
 
 #include <atomic>
@@ -1558,6 +1559,7 @@ static hipError_t dpp_selfcheck(hipStream_t s) {
   int h[128];
   hipError_t e = hipMalloc(&d, sizeof h);
   if (e != hipSuccess) return e;
+  WDPM_LEDGER(0, dpp_probe_kernel);
   hipLaunchKernelGGL(dpp_probe_kernel, dim3(1), dim3(64), 0, s, d);
   e = hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -1655,11 +1657,11 @@ hipError_t wdpm_launch_small_rows(int module, const double *w_in, double *w_out,
         if (env_rprio < 0) { const char *t = getenv("WDPM_RELAY_PRIO"); env_rprio = t ? atoi(t) : 1; }
         if (env_rprio == 2 || (env_rprio == 1 && nwg > cus && (tall ? r8 : r4) <= 4)) relay_plain |= 2;
         if (no_clamp) relay_plain |= 4;        // bit 2: the clamped neighbour step is not exact on this DEM (see the kernel)
-#define WDPM_RELAY_LAUNCH(...) hipLaunchKernelGGL((relay_iteration_kernel<__VA_ARGS__>), rgrid, rblock, 0, s, w_in, w_out, dem, g, nstr, (int)nwg, A0, out_last, thres, totaldrain, module == 2 ? drain_owed : 0, code, relay_plain)
+#define WDPM_RELAY_LAUNCH(...) do { WDPM_LEDGER_T(relay_plain, relay_iteration_kernel, __VA_ARGS__); hipLaunchKernelGGL((relay_iteration_kernel<__VA_ARGS__>), rgrid, rblock, 0, s, w_in, w_out, dem, g, nstr, (int)nwg, A0, out_last, thres, totaldrain, module == 2 ? drain_owed : 0, code, relay_plain); } while (0)
 #define WDPM_RELAY_PICK(NW)                                                                                        \
         do {                                                                                                       \
-          if (module == 2) { if (flush) WDPM_RELAY_LAUNCH(2, true, false, NW); else if (plain) WDPM_RELAY_LAUNCH(2, false, true, NW); else WDPM_RELAY_LAUNCH(2, false, false, NW); } \
-          else if (flush) WDPM_RELAY_LAUNCH(0, true, false, NW); else if (plain) WDPM_RELAY_LAUNCH(0, false, true, NW); else WDPM_RELAY_LAUNCH(0, false, false, NW); \
+          if (module == 2) { if (flush) WDPM_RELAY_LAUNCH(2, true, false, NW, false); else if (plain) WDPM_RELAY_LAUNCH(2, false, true, NW, false); else WDPM_RELAY_LAUNCH(2, false, false, NW, false); } \
+          else if (flush) WDPM_RELAY_LAUNCH(0, true, false, NW, false); else if (plain) WDPM_RELAY_LAUNCH(0, false, true, NW, false); else WDPM_RELAY_LAUNCH(0, false, false, NW, false); \
         } while (0)
         static std::atomic<int> env_r32{-1};     // WDPM_RELAY_DEM32=0: the fp64 DEM in the relay kernel (A/B)
         if (env_r32 < 0) { const char *t = getenv("WDPM_RELAY_DEM32"); env_r32 = t ? atoi(t) : 1; }
@@ -1685,11 +1687,11 @@ hipError_t wdpm_launch_small_rows(int module, const double *w_in, double *w_out,
       }
       const dim3 tgrid(((unsigned)((items + 3) / 4) + 7) / 8 * 8), tblock(256);
       const MaxDiffArgs tmd = fold_md ? *md : MaxDiffArgs{nullptr, 0.0, 0, 0, nullptr};
-#define WDPM_TRI_LAUNCH(...) hipLaunchKernelGGL((tri_iteration_kernel<__VA_ARGS__>), tgrid, tblock, 0, s, w_in, w_out, dem, g, nstr, (int)items, A0, out_last, totaldrain, thres, module == 2 ? drain_owed : 0, tmd)
+#define WDPM_TRI_LAUNCH(...) do { WDPM_LEDGER_T(0, tri_iteration_kernel, __VA_ARGS__); hipLaunchKernelGGL((tri_iteration_kernel<__VA_ARGS__>), tgrid, tblock, 0, s, w_in, w_out, dem, g, nstr, (int)items, A0, out_last, totaldrain, thres, module == 2 ? drain_owed : 0, tmd); } while (0)
       if (fold_md) { if (flush) WDPM_TRI_LAUNCH(0, true, 1, false, true); else WDPM_TRI_LAUNCH(0, false, 1, false, true); }
-      else if (module == 2) { if (flush) WDPM_TRI_LAUNCH(2, true); else if (plain) WDPM_TRI_LAUNCH(2, false, 1, true); else WDPM_TRI_LAUNCH(2, false); }
-      else if (two) { if (flush) WDPM_TRI_LAUNCH(0, true, 2); else if (plain) WDPM_TRI_LAUNCH(0, false, 2, true); else WDPM_TRI_LAUNCH(0, false, 2); }
-      else { if (flush) WDPM_TRI_LAUNCH(0, true); else if (plain) WDPM_TRI_LAUNCH(0, false, 1, true); else WDPM_TRI_LAUNCH(0, false); }
+      else if (module == 2) { if (flush) WDPM_TRI_LAUNCH(2, true, 1, false, false); else if (plain) WDPM_TRI_LAUNCH(2, false, 1, true, false); else WDPM_TRI_LAUNCH(2, false, 1, false, false); }
+      else if (two) { if (flush) WDPM_TRI_LAUNCH(0, true, 2, false, false); else if (plain) WDPM_TRI_LAUNCH(0, false, 2, true, false); else WDPM_TRI_LAUNCH(0, false, 2, false, false); }
+      else { if (flush) WDPM_TRI_LAUNCH(0, true, 1, false, false); else if (plain) WDPM_TRI_LAUNCH(0, false, 1, true, false); else WDPM_TRI_LAUNCH(0, false, 1, false, false); }
 #undef WDPM_TRI_LAUNCH
       *taken = true;
       return hipGetLastError();
@@ -1850,6 +1852,7 @@ hipError_t wdpm_launch_fused_rows(int module, const double *w_in, double *w_out,
       const bool same = bal->nstrips == nstrips && bal->nchunks == nchunks && bal->A0 == A0 && bal->out_last == out_last && bal->ipx == ipx;
       const bool update = bal->measured >= 3 && (same || bal->measured_uniform);
       if (!same || update) {
+        WDPM_LEDGER(0, xcd_rebalance_kernel);
         hipLaunchKernelGGL(xcd_rebalance_kernel, dim3(1), dim3(256), 0, s, bal->weight, bal->acc, bal->table, nstrips, nchunks, A0,
                            out_last, ipx, update ? 1 : 0, bal->measured_uniform, pair);
         bal->measured_uniform = 0;
@@ -1897,21 +1900,24 @@ hipError_t wdpm_launch_fused_rows(int module, const double *w_in, double *w_out,
   static std::atomic<int> env_prio{-1};
   if (env_prio < 0) { const char *e = getenv("WDPM_PRIO"); env_prio = e ? atoi(e) : 1; }
   const int prio = (wpb == 8 && env_prio.load(std::memory_order_relaxed) != 0) ? 1 : 0;
-#define WDPM_LAUNCH(...) hipLaunchKernelGGL((fused_iteration_kernel<__VA_ARGS__>), grid, block, lds_pad, s, w_in, w_out, dem, code, g, nstrips, nitems, H, A0, out_last, totaldrain, thres, module == 2 ? drain_owed : 0, tf, mda, prio, no_clamp, ba)
+  // the switches this launch hands the kernel, for the launch ledger (include/wdpm.h: WDPM_LEDGER_*)
+  const int ledger_sw = (no_clamp ? WDPM_LEDGER_NO_CLAMP : 0) | (prio ? WDPM_LEDGER_PRIO : 0) | (tf.zout ? WDPM_LEDGER_TILE_FLAGS : 0) |
+                        (ba.table ? WDPM_LEDGER_BALANCE : 0);
+#define WDPM_LAUNCH(...) do { WDPM_LEDGER_T(ledger_sw, fused_iteration_kernel, __VA_ARGS__); hipLaunchKernelGGL((fused_iteration_kernel<__VA_ARGS__>), grid, block, lds_pad, s, w_in, w_out, dem, code, g, nstrips, nitems, H, A0, out_last, totaldrain, thres, module == 2 ? drain_owed : 0, tf, mda, prio, no_clamp, ba); } while (0)
   // <module, -0.0-safe, DEM codes, flush on load, max diff folded in, gate-free>: which instantiation runs is decided here and
   // nowhere else (DESIGN.md §4 has the table)
-#define WDPM_LAUNCH_ADD(D32) do { if (fold_md) { if (flush) WDPM_LAUNCH(0, false, D32, true, true); else WDPM_LAUNCH(0, false, D32, false, true); } \
-                                  else if (plain) WDPM_LAUNCH(0, false, D32, false, false, true);                                                   \
-                                  else if (flush) WDPM_LAUNCH(0, false, D32, true, false); else WDPM_LAUNCH(0, false, D32, false, false); } while (0)
-#define WDPM_LAUNCH_DRAIN(D32) do { if (plain) WDPM_LAUNCH(2, false, D32, false, false, true);                                                      \
-                                    else if (flush) WDPM_LAUNCH(2, false, D32, true, false); else WDPM_LAUNCH(2, false, D32, false, false); } while (0)
+#define WDPM_LAUNCH_ADD(D32) do { if (fold_md) { if (flush) WDPM_LAUNCH(0, false, D32, true, true, false); else WDPM_LAUNCH(0, false, D32, false, true, false); } \
+                                  else if (plain) WDPM_LAUNCH(0, false, D32, false, false, true);                                                                 \
+                                  else if (flush) WDPM_LAUNCH(0, false, D32, true, false, false); else WDPM_LAUNCH(0, false, D32, false, false, false); } while (0)
+#define WDPM_LAUNCH_DRAIN(D32) do { if (plain) WDPM_LAUNCH(2, false, D32, false, false, true);                                                                    \
+                                    else if (flush) WDPM_LAUNCH(2, false, D32, true, false, false); else WDPM_LAUNCH(2, false, D32, false, false, false); } while (0)
   // the codes as 16-bit offsets (18.1 B of HBM traffic per cell-update) on launches of 10^8 cells and more: wdpm_kernels.h::wdpm_dem16_pays
   const bool dem16 = dem32 && code.h != nullptr && wdpm_dem16_pays((long long)wrows * g.ncp, code.force);
-  if (module == 2 && !fast) WDPM_LAUNCH(2, true, 0, false, false);
+  if (module == 2 && !fast) WDPM_LAUNCH(2, true, 0, false, false, false);
   else if (module == 2 && dem16) WDPM_LAUNCH_DRAIN(2);
   else if (module == 2 && dem32) WDPM_LAUNCH_DRAIN(1);
   else if (module == 2) WDPM_LAUNCH_DRAIN(0);
-  else if (!fast) WDPM_LAUNCH(0, true, 0, false, false);
+  else if (!fast) WDPM_LAUNCH(0, true, 0, false, false, false);
   else if (dem16) WDPM_LAUNCH_ADD(2);
   else if (dem32) WDPM_LAUNCH_ADD(1);
   else WDPM_LAUNCH_ADD(0);

@@ -10,6 +10,7 @@
  * same correctly-rounded value, subnormals included).
  */
 #include "wdpm_kernels.h"
+#include "wdpm_ledger.h"
 #include "wdpm_stencil.h"
 
 /* The device copy of the DEM holds +inf where bigdem <= missingvalue (wdpm_launch_mark_nodata), so
@@ -28,6 +29,7 @@ mark_nodata_kernel(double *__restrict__ dem, size_t cells, double miss) {
 hipError_t wdpm_launch_mark_nodata(double *dem, size_t cells, double miss, hipStream_t s) {
   size_t blocks = (cells + 255) / 256;
   if (blocks > 4096) blocks = 4096;
+  WDPM_LEDGER(0, mark_nodata_kernel);
   hipLaunchKernelGGL(mark_nodata_kernel, dim3((unsigned)blocks), dim3(256), 0, s, dem, cells, miss);
   return hipGetLastError();
 }
@@ -89,10 +91,13 @@ hipError_t wdpm_launch_pass(int module, double *w, const double *dem, const Slab
   if (rmax < rfirst || g.C < oj) return hipSuccess;
   const int nbr = (rmax - rfirst) / 3 + 1;
   dim3 grid((nbc + 63) / 64, (nbr + 3) / 4);
-  if (module == 2)
+  if (module == 2) {
+    WDPM_LEDGER_T(0, pass_kernel, 2);
     hipLaunchKernelGGL(pass_kernel<2>, grid, dim3(256), 0, s, w, dem, g, oi, oj, totaldrain);
-  else
+  } else {
+    WDPM_LEDGER_T(0, pass_kernel, 0);
     hipLaunchKernelGGL(pass_kernel<0>, grid, dim3(256), 0, s, w, dem, g, oi, oj, totaldrain);
+  }
   return hipGetLastError();
 }
 
@@ -118,6 +123,7 @@ __global__ void drain_outlet_kernel(double *__restrict__ w, const double *__rest
 hipError_t wdpm_launch_drain_outlet(double *w, const double *dem, const SlabGeom &g, double *totaldrain,
                                     hipStream_t s) {
   if (g.dr < 1 || g.dr > g.rows - 2 || g.dc < 1 || g.dc > g.ncp - 2) return hipSuccess;
+  WDPM_LEDGER(0, drain_outlet_kernel);
   hipLaunchKernelGGL(drain_outlet_kernel, dim3(1), dim3(64), 0, s, w, dem, g, totaldrain);
   return hipGetLastError();
 }
@@ -150,6 +156,7 @@ hipError_t wdpm_launch_flush_snapshot(double *w, double *old, size_t cells, doub
   size_t blocks = (cells / 2 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
+  WDPM_LEDGER(0, flush_snapshot_kernel);
   hipLaunchKernelGGL(flush_snapshot_kernel, dim3((unsigned)blocks), dim3(256), 0, s, w, old, cells, thres);
   return hipGetLastError();
 }
@@ -197,6 +204,7 @@ hipError_t wdpm_launch_dem_min(const double *dem, size_t cells, unsigned long lo
   if (e != hipSuccess || cells == 0) return e;
   size_t blocks = (cells + 255) / 256;
   if (blocks > 2048) blocks = 2048;
+  WDPM_LEDGER(0, dem_min_kernel);
   hipLaunchKernelGGL(dem_min_kernel, dim3((unsigned)blocks), dim3(256), 0, s, dem, cells, key);
   return hipGetLastError();
 }
@@ -227,6 +235,7 @@ hipError_t wdpm_launch_dem_encode(const double *dem, size_t cells, double k0, do
   if (e != hipSuccess || cells == 0) return e;
   size_t blocks = (cells + 255) / 256;
   if (blocks > 4096) blocks = 4096;
+  WDPM_LEDGER(0, dem_encode_kernel);
   hipLaunchKernelGGL(dem_encode_kernel, dim3((unsigned)blocks), dim3(256), 0, s, dem, cells, k0, D, rD, q, bad);
   return hipGetLastError();
 }
@@ -264,6 +273,7 @@ hipError_t wdpm_launch_dem16_encode(const int *q, int rows, int ncp, int ngroups
   if (e != hipSuccess || rows <= 0) return e;
   size_t blocks = ((size_t)rows * ngroups + 255) / 256;
   if (blocks > 65536) blocks = 65536;
+  WDPM_LEDGER(0, dem16_encode_kernel);
   hipLaunchKernelGGL(dem16_encode_kernel, dim3((unsigned)blocks), dim3(256), 0, s, q, rows, ncp, ngroups, h, gb, bad);
   return hipGetLastError();
 }
@@ -325,6 +335,7 @@ hipError_t wdpm_launch_seqsum_a(const double *w, const double *dem, size_t n, do
                                 hipStream_t s) {
   if (n == 0) return hipSuccess;
   const unsigned blocks = (unsigned)((n + kSeqSumChunk - 1) / kSeqSumChunk);
+  WDPM_LEDGER(0, seqsum_a_kernel);
   hipLaunchKernelGGL(seqsum_a_kernel, dim3(blocks), dim3(256), 0, s, w, dem, n, approx, dirty);
   return hipGetLastError();
 }
@@ -333,6 +344,7 @@ hipError_t wdpm_launch_seqsum_b(const double *w, const double *dem, size_t n, co
                                 unsigned *tie, hipStream_t s) {
   if (n == 0) return hipSuccess;
   const unsigned blocks = (unsigned)((n + kSeqSumChunk - 1) / kSeqSumChunk);
+  WDPM_LEDGER(0, seqsum_b_kernel);
   hipLaunchKernelGGL(seqsum_b_kernel, dim3(blocks), dim3(256), 0, s, w, dem, n, kexp, isum, tie);
   return hipGetLastError();
 }
@@ -360,6 +372,7 @@ hipError_t wdpm_launch_scan_water(const double *p, const double *dem, size_t n, 
   if (n == 0) return hipSuccess;
   size_t blocks = (n + 255) / 256;
   if (blocks > 2048) blocks = 2048;
+  WDPM_LEDGER(0, scan_water_kernel);
   hipLaunchKernelGGL(scan_water_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, dem, n, flag);
   return hipGetLastError();
 }
@@ -410,6 +423,7 @@ hipError_t wdpm_launch_max_diff(const double *w, const double *old, double old_t
   const size_t first = (size_t)row_lo * g.ncp, last = (size_t)row_hi * g.ncp;
   size_t blocks = (last - first + 255) / 256;
   if (blocks > 2048) blocks = 2048;
+  WDPM_LEDGER(0, max_diff_kernel);
   hipLaunchKernelGGL(max_diff_kernel, dim3((unsigned)blocks), dim3(256), 0, s, w, old, old_thres, dem, first, last,
                      row_lo == 0 ? 1 : 0, result_bits);
   return hipGetLastError();
@@ -454,6 +468,7 @@ hipError_t wdpm_launch_pad_setup(const double *fdem, const double *fwater, doubl
                                  int op, double add, double rof, double sub, hipStream_t s) {
   size_t blocks = ((size_t)g.rows * g.ncp + 255) / 256;
   if (blocks > 8192) blocks = 8192;
+  WDPM_LEDGER(0, pad_setup_kernel);
   hipLaunchKernelGGL(pad_setup_kernel, dim3((unsigned)blocks), dim3(256), 0, s, fdem, fwater, dem, w, g, op, add, rof, sub);
   return hipGetLastError();
 }
@@ -493,6 +508,7 @@ hipError_t wdpm_launch_count_stats(const double *w, const double *dem, size_t fi
   if (e != hipSuccess || last <= first) return e;
   size_t blocks = (last - first + 255) / 256;
   if (blocks > 4096) blocks = 4096;
+  WDPM_LEDGER(0, count_stats_kernel);
   hipLaunchKernelGGL(count_stats_kernel, dim3((unsigned)blocks), dim3(256), 0, s, w, dem, first, last, miss, out3);
   return hipGetLastError();
 }
@@ -542,7 +558,9 @@ hipError_t wdpm_launch_find_drain(const double *dem, size_t first, size_t last, 
   if (e != hipSuccess || last <= first) return e;
   size_t blocks = (last - first + 255) / 256;
   if (blocks > 4096) blocks = 4096;
+  WDPM_LEDGER(0, drain_min_kernel);
   hipLaunchKernelGGL(drain_min_kernel, dim3((unsigned)blocks), dim3(256), 0, s, dem, first, last, key_and_index);
+  WDPM_LEDGER(0, drain_first_kernel);
   hipLaunchKernelGGL(drain_first_kernel, dim3((unsigned)blocks), dim3(256), 0, s, dem, first, last, key_and_index,
                      key_and_index + 1);
   return hipGetLastError();
@@ -567,6 +585,7 @@ hipError_t wdpm_launch_unpad(const double *w, const double *dem, const SlabGeom 
   if (nrows <= 0) return hipSuccess;
   size_t blocks = ((size_t)nrows * g.C + 255) / 256;
   if (blocks > 8192) blocks = 8192;
+  WDPM_LEDGER(0, unpad_kernel);
   hipLaunchKernelGGL(unpad_kernel, dim3((unsigned)blocks), dim3(256), 0, s, w, dem, g, frow, nrows, mask, out);
   return hipGetLastError();
 }
