@@ -3,7 +3,7 @@ numpy: the two waves of a SIMD are work items four apart - strips s and s + 4 of
 rounded half a triple apart, so that a tall chunk of one sits beside a short chunk of the other.  Checked here: the property the
 kernel's comment claims (equal weights: the steps of the two waves of every SIMD add up to the same number to within one, where
 plain rounding pairs tall with tall), that boundaries stay monotone and complete under skewed weights, and the slot filling
-arithmetic of wdpm_launch_fused_rows for the shapes DESIGN.md quotes.  No GPU: results never depend on the table (the parity
+arithmetic of plan_iteration (wdpm_dispatch.h; tests/test_dispatch_plans.py ties this restatement to it) for the shapes DESIGN.md quotes.  No GPU: results never depend on the table (the parity
 suites run with deliberately skewed weights, WDPM_BALANCE=2); this is about what the table is FOR."""
 import numpy as np
 import pytest

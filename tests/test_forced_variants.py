@@ -1,6 +1,6 @@
 """Every kernel variant the dispatch can choose, FORCED onto the kernel parity suites.
 
-Which instantiation runs for a launch is decided by size thresholds (wdpm_launch_fused_rows / wdpm_launch_small_rows), so an
+Which instantiation runs for a launch is decided by size thresholds (plan_iteration, wdpm_dispatch.h), so an
 ordinary run of the suite meets each variant only on the sizes the dispatch gives it.  Rounds 1 - 3 forced them by hand (32
 tools/gpu_r03_*.sh sessions the driver's GPU test never saw).  Here each combination of the library's A/B switches runs the
 stencil golden vectors, the random rasters, the adversarial operand pools, every outlet position of a window and the clamped-step

@@ -276,9 +276,12 @@ int wdpm_create(wdpm_ctx **out, const wdpm_params *p) {
   if (ndev < 1) return fail("wdpm_create: no HIP device (this library has no CPU fallback)");
   if (p->device < 0 || p->device >= ndev) return fail("wdpm_create: device %d out of range (%d devices)", p->device, ndev);
   HIP_TRY(hipSetDevice(p->device));
+  const DeviceFacts *facts = wdpm_device_facts();       /* of p->device: queried when its first context is created */
+  if (!facts) return fail("wdpm_create: device %d: no facts for the launch planner", p->device);
 
   wdpm_ctx *x = new wdpm_ctx();
   x->p = *p;
+  x->facts = facts;
   x->g.rows = rows;
   x->g.ncp = p->ncols + 2;
   x->g.row0 = p->slab_row0;
@@ -455,18 +458,45 @@ static void flushed_whole(wdpm_ctx *x, double thres) {
   if (thres >= 0.0) x->w_negative = false;
 }
 
-/* wdpm_kernels.h: WDPM_LAUNCH_PLAIN | WDPM_LAUNCH_CLAMP_OK for the iteration launches of this context */
-static bool plain_water(const wdpm_ctx *x);
-static int launch_flags(const wdpm_ctx *x) {
-  static std::atomic<int> env{-1};
-  if (env < 0) { const char *e = getenv("WDPM_CLAMP"); env = e ? atoi(e) : 1; }      /* WDPM_CLAMP=0: the unclamped neighbour step everywhere (A/B, tests) */
-  return (plain_water(x) ? WDPM_LAUNCH_PLAIN : 0) | (env != 0 && x->dem_bounded ? WDPM_LAUNCH_CLAMP_OK : 0);
+/* the switches of the iteration dispatch (wdpm_dispatch.h): read from the environment once per process */
+static const Switches &wdpm_switches() {
+  static const Switches sw = wdpm_read_switches(getenv);      /* (initialised under the compiler's lock: rank threads launch concurrently) */
+  return sw;
 }
 
 static bool plain_water(const wdpm_ctx *x) {
-  static std::atomic<int> env{-1};
-  if (env < 0) { const char *e = getenv("WDPM_PLAIN"); env = e ? atoi(e) : 1; }      /* WDPM_PLAIN=0: gated variants only (A/B, tests) */
-  return env != 0 && !x->signed_zero_safe && !x->w_negative && !x->w_odd;
+  return wdpm_switches().plain != 0 && !x->signed_zero_safe && !x->w_negative && !x->w_odd;
+}
+
+/* wdpm_dispatch.h: WDPM_LAUNCH_PLAIN | WDPM_LAUNCH_CLAMP_OK for the iteration launches of this context */
+static int launch_flags(const wdpm_ctx *x) {
+  return wdpm_launch_flags(wdpm_switches(), !x->signed_zero_safe && !x->w_negative && !x->w_odd, x->dem_bounded);
+}
+
+/* What this context knows of an iteration launch over the window [A0, out_last] (wdpm_dispatch.h): `tiles` / `balanced` where the
+ * launch comes with the context's dry-tile flags / balance state (whole-slab launches of wdpm_iterate). */
+static LaunchRequest iteration_request(const wdpm_ctx *x, int A0, int out_last, int chunk_rows, bool max_diff, int leave_cus, const TilePlan *tiles,
+                                       bool balanced) {
+  LaunchRequest q{};
+  q.module = x->p.module;
+  q.g = x->g;
+  q.A0 = A0;
+  q.out_last = out_last;
+  q.chunk_rows = chunk_rows;
+  q.signed_zero_safe = x->signed_zero_safe;
+  q.flush = x->flush_pending;
+  q.max_diff = max_diff;
+  q.flags = launch_flags(x);
+  q.leave_cus = leave_cus;
+  q.codes32 = x->code.q != nullptr;
+  q.codes16 = x->code.h != nullptr;
+  q.force_codes = x->code.force;
+  q.tiles_offered = tiles != nullptr;
+  q.tile_capacity = tiles && tiles->zout ? tiles->capacity : 0;
+  q.wide_tri_ok = tiles && tiles->wide_tri_ok;
+  q.balance_mode = balanced ? x->bal.mode : 0;
+  q.balance_capacity = x->bal.capacity;
+  return q;
 }
 
 /* captured launches carry what they were given by value (wdpm_ctx::GraphEntry): a new DEM, other codes or another outlet end them */
@@ -953,10 +983,10 @@ int wdpm_iterate(wdpm_ctx *x, int32_t n_iter) {
         md.old = x->d_w[x->old];
         HIP_TRY(hipMemsetAsync(x->d_md, 0, sizeof(unsigned long long), x->stream));
       }
-      HIP_TRY(wdpm_launch_fused(x->p.module, x->d_w[x->cur], x->d_w[t], x->d_dem, x->code, x->g, chunk_rows,
-                                x->signed_zero_safe ? 1 : 0, x->flush_pending ? &x->flush_thres : nullptr,
-                                x->drain_owed ? 1 : 0, x->d_scal, x->stream, track ? &tp : nullptr, md.old ? &md : nullptr,
-                                launch_flags(x), x->bal.mode ? &x->bal : nullptr));
+      const LaunchRequest q = iteration_request(x, 0, x->g.rows - 1, chunk_rows, md.old != nullptr, 0, track ? &tp : nullptr, x->bal.mode != 0);
+      const IterationBuffers buf{x->d_w[x->cur], x->d_w[t], x->d_dem, &x->code, x->flush_pending ? x->flush_thres : 0.0, x->drain_owed ? 1 : 0,
+                                 x->d_scal, x->stream, track ? &tp : nullptr, &md, &x->bal};
+      HIP_TRY(wdpm_launch_iteration(q, plan_iteration(q, *x->facts, wdpm_switches()), buf));
       if (x->flush_pending) flushed_whole(x, x->flush_thres);   /* the launch flushed every value it loaded, and it loaded them all */
       if (md.old) x->md_valid = true;
       if (track && tp.maintained) {
@@ -1002,7 +1032,12 @@ int wdpm_iterate(wdpm_ctx *x, int32_t n_iter) {
     const bool track = x->tiles_mode != 0 && !x->signed_zero_safe && !balanced;
     const int chunk_rows = x->p.chunk_rows >= 3 ? x->p.chunk_rows : (track && x->sparse ? kSparseChunkRows : 0);
     TilePlan tq{nullptr, nullptr, 0, 0, nullptr, 0, 0, 0, 0, 0, x->wide_tri_ok ? 1 : 0};
-    if (x->graph_mode == 1 && wdpm_small_rows_take(x->p.module, x->g, chunk_rows, x->signed_zero_safe ? 1 : 0, track ? &tq : nullptr)) {
+    /* would a whole-slab steady launch (no flush, no folded max diff) of this context go to the relay / triangle kernels of small
+     * rasters?  Asks the dispatch itself. */
+    LaunchRequest steady = iteration_request(x, 0, x->g.rows - 1, chunk_rows, false, 0, track ? &tq : nullptr, false);
+    steady.flush = false;
+    const LaunchPlan sp = plan_iteration(steady, *x->facts, wdpm_switches());
+    if (x->graph_mode == 1 && !sp.error && sp.family != WDPM_FAMILY_MARCHING) {
       if (one_iteration(it++)) return 1;                   /* the block's first launch: as ever */
       while (n_iter - 1 - it >= kGraphIters && x->graph_mode == 1) {
         wdpm_ctx::GraphEntry key{x->cur, x->old, launch_flags(x), x->drain_owed ? 1 : 0, chunk_rows, x->g.dr, x->g.dc, x->wide_tri_ok ? 1 : 0,
@@ -1077,13 +1112,9 @@ int wdpm_iterate_overlapped(wdpm_ctx *x, int32_t n_iter, int32_t top_rows, int32
   const int t_slot = free_slot(x);
   const double *w_in = x->d_w[x->cur];
   double *w_out = x->d_w[t_slot];
-  const int szs = x->signed_zero_safe ? 1 : 0;
-  const double *flush = x->flush_pending ? &x->flush_thres : nullptr;
-  const int plain = launch_flags(x);
   const bool fold = x->md_hint && !x->signed_zero_safe;     /* (usable: fused kernel, not the drain module) */
   x->md_hint = x->md_valid = false;
   MaxDiffArgs md{fold ? x->d_w[x->old] : nullptr, x->flush_thres, x->md_lo, x->md_hi, x->d_md};
-  const MaxDiffArgs *mdp = fold ? &md : nullptr;
   if (fold) HIP_TRY(hipMemsetAsync(x->d_md, 0, sizeof(unsigned long long), x->stream));
   /* stencil timing of this iteration: from here on the main stream to the end of the interior launch
    * on the side stream (the longest of the three) */
@@ -1095,16 +1126,17 @@ int wdpm_iterate_overlapped(wdpm_ctx *x, int32_t n_iter, int32_t top_rows, int32
     HIP_TRY(hipEventRecord(ep.a, x->stream));
   }
   HIP_TRY(hipEventRecord(x->ev_fork, x->stream));               /* w_in is complete here */
-  if (t_last >= 0)
-    HIP_TRY(wdpm_launch_fused_rows(x->p.module, w_in, w_out, x->d_dem, x->code, x->g, 0, t_last, x->p.chunk_rows, szs, flush,
-                                   0, x->d_scal, x->stream, nullptr, mdp, 0, plain));
-  if (b_first < rows)
-    HIP_TRY(wdpm_launch_fused_rows(x->p.module, w_in, w_out, x->d_dem, x->code, x->g, b_first - 2, rows - 1, x->p.chunk_rows,
-                                   szs, flush, 0, x->d_scal, x->stream, nullptr, mdp, 0, plain));
+  /* one window of the three: no tile flags (not the tiling they are kept for), no balance table */
+  auto window = [&](const int A0, const int out_last, const int leave_cus, hipStream_t s) -> hipError_t {
+    const LaunchRequest q = iteration_request(x, A0, out_last, x->p.chunk_rows, fold, leave_cus, nullptr, false);
+    const IterationBuffers buf{w_in, w_out, x->d_dem, &x->code, x->flush_pending ? x->flush_thres : 0.0, 0, x->d_scal, s, nullptr, &md, nullptr};
+    return wdpm_launch_iteration(q, plan_iteration(q, *x->facts, wdpm_switches()), buf);
+  };
+  if (t_last >= 0) HIP_TRY(window(0, t_last, 0, x->stream));
+  if (b_first < rows) HIP_TRY(window(b_first - 2, rows - 1, 0, x->stream));
   HIP_TRY(hipStreamWaitEvent(x->side, x->ev_fork, 0));
-  HIP_TRY(wdpm_launch_fused_rows(x->p.module, w_in, w_out, x->d_dem, x->code, x->g, t_last >= 0 ? t_last - 1 : 0,
-                                 b_first < rows ? b_first - 1 : rows - 1, x->p.chunk_rows, szs, flush, 0, x->d_scal, x->side, nullptr, mdp,
-                                 x->comm ? 8 : 0, plain));   /* 8 of 256 CUs stay free for the RCCL kernels of the refresh that follows */
+  /* 8 of 256 CUs stay free for the RCCL kernels of the refresh that follows */
+  HIP_TRY(window(t_last >= 0 ? t_last - 1 : 0, b_first < rows ? b_first - 1 : rows - 1, x->comm ? 8 : 0, x->side));
   if (x->timing) {
     HIP_TRY(hipEventRecord(ep.b, x->side));
     x->pending.push_back(ep);

@@ -18,6 +18,7 @@ struct EventPair { hipEvent_t a, b; };
 
 struct wdpm_ctx {
   wdpm_params p;
+  const DeviceFacts *facts;     /* of p.device, for the launch planner (wdpm_dispatch.h) */
   SlabGeom g;
   size_t cells;
   hipStream_t stream;

@@ -49,26 +49,20 @@
  *                           through LDS: small and mid-size rasters (round 3; 482^2 add 7.3 -> 5.2 us, drain 12.1 -> 8.4)
  *   tri_iteration_kernel    one wave, nine (twelve) rows in, three (six) out, row blocks in lockstep: what is between the two,
  *                           and a small raster's last launch of a block (max diff folded in)
- * wdpm_launch_fused_rows picks by size, module and what is known about the raster.
+ * plan_iteration (wdpm_dispatch.h) picks by size, module and what is known about the raster.
  */
 #include "wdpm_kernels.h"
 #include "wdpm_ledger.h"
 #include "wdpm_stencil.h"
 
 #include <atomic>
-#include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <type_traits>
 
 namespace {
 
-constexpr int kLanes = 64;
-constexpr int kStripIn = 3 * kLanes;                     // 192 columns loaded per wave
-// Per fused iteration an error at a strip's edge travels at most 8 columns inward from the left and
-// 12 from the right (cell-level dependency simulation, tests/test_rowblock.py); 13 are given up on
-// the right so that the strip pitch, 171, is a multiple of 3 and every strip starts on a block edge.
-constexpr int kHaloL = 8, kHaloR = 13;
-constexpr int kStripOut = kStripIn - kHaloL - kHaloR;    // 171 columns stored per wave
+/* strip geometry (kLanes, kStripIn, kHaloL / kHaloR, kStripOut): wdpm_dispatch.h, which sizes the launches by it */
 
 #define WDPM_INF (__builtin_inf())
 
@@ -1505,54 +1499,14 @@ __global__ void dpp_probe_kernel(int *out) {
 
 }  // namespace
 
-/* Number of waves of the fused kernel the whole chip holds at once (CUs x blocks/CU x 4 waves),
- * from the occupancy API; cached per module.  All work items of a launch are made resident
- * together — one round, no tail — so the item count is sized to this. */
-template <int MODULE, bool SZ_SAFE, int DEM32 = 0>
-static int resident_waves() {
-  static std::atomic<int> cached{0};      // rank threads of one process launch concurrently: no plain statics
-  if (cached.load(std::memory_order_relaxed)) return cached.load(std::memory_order_relaxed);
-  int dev = 0, cus = 256, blocks = 2;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fused_iteration_kernel<MODULE, SZ_SAFE, DEM32>, 256, 0) != hipSuccess || blocks < 1)
-    blocks = 2;
-  // never more than the kernel was built for: the chunk heights and every threshold of the dispatch were measured at that
-  // occupancy, and the register count an instantiation ends up with may allow more from one compiler run to the next
-  constexpr int built_for = fused_built_for<MODULE, SZ_SAFE, DEM32, false>();
-  if (blocks > built_for) blocks = built_for;
-  cached.store(cus * blocks * 4, std::memory_order_relaxed);
-  return cus * blocks * 4;
-}
-
-/* chunk height in rows (multiple of 3): the rows are cut into as many chunks as keep
- * strips x chunks within one resident round; each chunk pays a 6-row warm-up. */
-static int pick_chunk_rows(const int rows, const int nstrips, const int override_rows, const int slots) {
-  static std::atomic<int> env_h{-1};
-  if (env_h < 0) {
-    const char *e = getenv("WDPM_CHUNK_ROWS");
-    env_h = e ? atoi(e) : 0;
-  }
-  int H;
-  if (override_rows >= 3) {
-    H = override_rows / 3 * 3;
-  } else if (env_h >= 3) {
-    H = env_h / 3 * 3;
-  } else {
-    int nch = slots / nstrips;
-    if (nch < 1) nch = 1;
-    H = ((rows - 2 + nch - 1) / nch + 2) / 3 * 3;
-    // small rasters cannot fill the chip: short chunks then cost redundant warm-up rows on CUs that
-    // would idle anyway and cut the launch's critical path (a wave's march) to a few steps - down to
-    // one 3-row step of output per wave (basin5-sized rasters: 12.3 us per iteration against 14.3 with
-    // 6-row chunks; the formula only gets there when all chunks still fit in one resident round)
-  }
-  if (H > rows) H = (rows + 2) / 3 * 3;
-  if (H < 3) H = 3;
-  return H;
-}
+/* One row of a family's launch table: the template arguments, the instantiation, its ledger slot.  Every instantiation of a family
+ * has the family's one signature (a row of another type does not compile); the tables are made from the variant lists of
+ * wdpm_dispatch.h and from nothing else, so those lists are also what the device code and the ledger contain. */
+template <class Fn> struct VariantRow { int targs[6]; Fn fn; const int *slot; };
+#define WDPM_VARIANT_ROW(KERNEL, ...) {{__VA_ARGS__}, &KERNEL<__VA_ARGS__>, &WdpmLedgerSlot<&KERNEL<__VA_ARGS__>, __VA_ARGS__>::slot},
 
 static hipError_t dpp_selfcheck(hipStream_t s) {
-  static std::atomic<int> state{0};   // 0 unknown, 1 ok, -1 bad
+  static std::atomic<int> state{0};   // 0 unknown, 1 ok, -1 bad; rank threads of one process launch concurrently: no plain statics
   if (state == 1) return hipSuccess;
   if (state == -1) return hipErrorUnknown;
   int *d = nullptr;
@@ -1574,356 +1528,161 @@ static hipError_t dpp_selfcheck(hipStream_t s) {
   return ok ? hipSuccess : hipErrorUnknown;
 }
 
-/* The launches of small and mid-size rasters (relay and triangle kernels): *taken says whether one was queued.  Compiled as a
+/* The launches of small and mid-size rasters (relay and triangle kernels).  Compiled as a
  * translation unit of its own (WDPM_TU == 2; the marching kernel and everything else: WDPM_TU == 1), because the two want different
  * instruction schedulers: the marching kernel is 2 % faster under the compiler's max-ILP strategy (-mllvm -amdgpu-sched-strategy=max-ilp:
  * add 16384^2 1.1425 -> 1.1189 ms), the eight-wave relay instantiations 2.4 % slower (profiles/r03/sched_strategy_ab.txt). */
-hipError_t wdpm_launch_small_rows(int module, const double *w_in, double *w_out, const double *dem, const DemCode &code,
-                                  const SlabGeom &g, int A0, int out_last, int chunk_rows, int signed_zero_safe, bool flush,
-                                  double thres, int drain_owed, double *totaldrain, hipStream_t s, TilePlan *tiles,
-                                  const MaxDiffArgs *md, bool fold_md, bool plain, int no_clamp, bool *taken, bool dry)
 #if !defined(WDPM_TU) || WDPM_TU == 2
-{
-  *taken = false;
-    // Small launches: if every 3-row chunk of the window fits on the chip at once, the triangle kernel's six
-    // lockstep stages beat the marching kernel's nine dependent ones (482 x 471: DESIGN.md §4.1c).
-    // WDPM_TRI=0 keeps the marching kernel (A/B runs), WDPM_TRI=2 forces the triangle kernel on any size.
-    static std::atomic<int> env_tri{-1}, tri_slots{0};
-    if (env_tri < 0) { const char *t = getenv("WDPM_TRI"); env_tri = t ? atoi(t) : 1; }
-    if (!tri_slots) {
-      int dev = 0, cus = 256, blocks = 1;
-      if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, tri_iteration_kernel<0, false>, 256, 0) != hipSuccess || blocks < 1) blocks = 1;
-      tri_slots = cus * blocks * 4;
-    }
-    int nstr = 1;
-    if (g.ncp > kStripIn - kHaloR) nstr = (g.ncp - (kStripIn - kHaloR) + kStripOut - 1) / kStripOut + 1;
-    int nch = (out_last - A0 - 1 + 2) / 3;
-    if (nch < 1) nch = 1;
-    long long items = (long long)nstr * nch;
-    static std::atomic<int> env_k{-1};      // WDPM_TRI_K=1|2 forces the triangle kernel's height (tuning, tests); 0 = automatic
-    if (env_k < 0) { const char *t = getenv("WDPM_TRI_K"); env_k = t ? atoi(t) : 0; }
-    // ... and somewhat beyond: up to 2.7 rounds of (three-row) triangle waves still beat the marching kernel, whose chunks are
-    // only a few steps high at these sizes - with six rows per wave (K = 2) for add / subtract once there is more than one round
-    // (1200^2: 24.5 -> 14.7 us per add iteration, 1600^2: 30.2 -> 24.6, 2000^2: 35.8 -> 33.7; drain 1200^2: 31.3 -> 20.8,
-    // 2000^2: 48.6 -> 46.8; profiles/r02/tri_sweep.txt)
-    // ... unless dry-tile flags are being kept and have not (yet, or lately) said that most of the raster works: the triangle
-    // kernel keeps no flags, and a mostly dry raster of this size is better off with the marching kernel skipping its dry tiles
-    const bool wide = !tiles || tiles->wide_tri_ok;
-    const long long slots_now = tri_slots.load(std::memory_order_relaxed);
-    const long long tri_limit = wide ? slots_now * 27 / 10 : slots_now;
-    // more than one round of waves: the launch is bound by instruction issue, and six rows per wave (K = 2: 9 block stages
-    // instead of 12 for them) are the cheaper way through; one round: three rows per wave is the shorter critical path
-    const bool two = module != 2 && (env_k == 2 || (env_k == 0 && items > slots_now));
-    {
-      // the relay kernel (four or eight waves per strip of six / eighteen rows): add 482^2 7.3 -> 5.2 us per iteration, 700^2
-      // 10.0 -> 7.3, 1200^2 14.8 -> 11.8, 1600^2 24.9 -> 23.2; drain 482^2 12.1 -> 8.2, 1000^2 16.3 -> 13.1, 1600^2 34.3 -> 25.5,
-      // 2400^2 51.6 -> 45.3, 3000^2 77.5 -> 67.3 (profiles/r03/relay_nw_sweep.txt)
-      static std::atomic<int> env_relay{-1};
-      if (env_relay < 0) { const char *t = getenv("WDPM_RELAY"); env_relay = t ? atoi(t) : 1; }
-      static std::atomic<int> env_nw{-1};     // WDPM_RELAY_NW=4|8 forces the workgroup's height (tuning); 0 = automatic
-      if (env_nw < 0) { const char *t = getenv("WDPM_RELAY_NW"); env_nw = t ? atoi(t) : 0; }
-      static std::atomic<int> ncus{0};
-      if (!ncus) {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        ncus = cus;
-      }
-      const long long cus = ncus.load(std::memory_order_relaxed);
-      const int rows_out = out_last - A0 - 1;
-      const long long nwg4 = (long long)nstr * ((rows_out + 5) / 6 > 0 ? (rows_out + 5) / 6 : 1);        // four waves: six rows out of twelve
-      const long long nwg8 = (long long)nstr * ((rows_out + 17) / 18 > 0 ? (rows_out + 17) / 18 : 1);    // eight waves: 18 out of 24
-      // rounds of workgroups at two waves per SIMD (a CU holds two workgroups of four waves or one of eight); the taller workgroup
-      // where it needs fewer rounds: fewer waves and less re-reading per row, but twice as many rows behind one barrier
-      const long long r4 = (nwg4 + 2 * cus - 1) / (2 * cus), r8 = (nwg8 + cus - 1) / cus;
-      const bool tall = env_nw == 8 || (env_nw == 0 && r8 < r4);
-      long long nwg = tall ? nwg8 : nwg4;
-      // With every wave on a SIMD of its own: always.  Beyond that, while the sweeps (profiles/r03/relay_nw_sweep.txt) have it ahead
-      // of the triangle / marching kernels - add / subtract up to eight rounds (1600^2 20.2 against 24.8 us, 2000^2 28.6 against 33.9,
-      // 2400^2 39.0 against 42.4, 3000^2 a tie), drain up to fourteen (3000^2 67 against 78 us, 3600^2 behind) - and where the triangle kernel would run in one
-      // round anyway or the raster is known to be mostly wet: like the triangle kernel this one keeps no dry-tile flags (`wide`)
-      // Round 4, after the marching kernel's gains (profiles/r04/relay_breakeven.txt, relay against marching, us per iteration): add
-      // 2000^2 27.5 / 37.8, 2200^2 (7 rounds) 32.6 / 33.3, 2400^2 (8) 38.4 / 37.4, 2700^2 47.8 / 47.1; drain 2400^2 (8) 51.6 / 57.4,
-      // 2700^2 (10) 62.7 / 66.3, 3000^2 (12) 75.9 / 73.6, the 1053 x 8190 slab (12) 74.4 / 72.2: seven and ten rounds.
-      const bool relay_ok = env_tri && !signed_zero_safe && chunk_rows < 3 &&
-                            (nwg4 * 4 <= 4 * cus || ((wide || items <= slots_now) && (tall ? r8 : r4) <= (module == 2 ? 10 : 7)) ||
-                             env_relay == 2);
-      if (env_relay && !fold_md && relay_ok) {
-        if (dry) { *taken = true; return hipSuccess; }      /* (wdpm_small_rows_take: the caller only asks) */
-        const dim3 rgrid(((unsigned)nwg + 7) / 8 * 8), rblock(tall ? 512 : 256);
-        int relay_plain = (module != 2 && tall && r8 >= 6) ? 1 : 0;   // 2000^2 25.8 -> 25.1 us, 3000^2 50.1 -> 46.1
-        // bit 1: stage priorities, where workgroups share SIMDs and the launch is a few rounds long (see the kernel; WDPM_RELAY_PRIO=0/2: never / always)
-        static std::atomic<int> env_rprio{-1};
-        if (env_rprio < 0) { const char *t = getenv("WDPM_RELAY_PRIO"); env_rprio = t ? atoi(t) : 1; }
-        if (env_rprio == 2 || (env_rprio == 1 && nwg > cus && (tall ? r8 : r4) <= 4)) relay_plain |= 2;
-        if (no_clamp) relay_plain |= 4;        // bit 2: the clamped neighbour step is not exact on this DEM (see the kernel)
-#define WDPM_RELAY_LAUNCH(...) do { WDPM_LEDGER_T(relay_plain, relay_iteration_kernel, __VA_ARGS__); hipLaunchKernelGGL((relay_iteration_kernel<__VA_ARGS__>), rgrid, rblock, 0, s, w_in, w_out, dem, g, nstr, (int)nwg, A0, out_last, thres, totaldrain, module == 2 ? drain_owed : 0, code, relay_plain); } while (0)
-#define WDPM_RELAY_PICK(NW)                                                                                        \
-        do {                                                                                                       \
-          if (module == 2) { if (flush) WDPM_RELAY_LAUNCH(2, true, false, NW, false); else if (plain) WDPM_RELAY_LAUNCH(2, false, true, NW, false); else WDPM_RELAY_LAUNCH(2, false, false, NW, false); } \
-          else if (flush) WDPM_RELAY_LAUNCH(0, true, false, NW, false); else if (plain) WDPM_RELAY_LAUNCH(0, false, true, NW, false); else WDPM_RELAY_LAUNCH(0, false, false, NW, false); \
-        } while (0)
-        static std::atomic<int> env_r32{-1};     // WDPM_RELAY_DEM32=0: the fp64 DEM in the relay kernel (A/B)
-        if (env_r32 < 0) { const char *t = getenv("WDPM_RELAY_DEM32"); env_r32 = t ? atoi(t) : 1; }
-        // from two rounds of workgroups on (700^2, one round: 7.05 against 7.5 us with the decode on the latency path; 1200^2 11.7 ->
-        // 10.95, 1600^2 22.0 -> 20.2, 2400^2 42.9 -> 39.0; profiles/r03/relay_dem32_ab.txt)
-        if (tall && module != 2 && code.q != nullptr && env_r32 && (r8 >= 2 || code.force)) {
-          if (flush) WDPM_RELAY_LAUNCH(0, true, false, 8, true); else if (plain) WDPM_RELAY_LAUNCH(0, false, true, 8, true); else WDPM_RELAY_LAUNCH(0, false, false, 8, true);
-        } else if (tall) WDPM_RELAY_PICK(8); else WDPM_RELAY_PICK(4);
-#undef WDPM_RELAY_PICK
-#undef WDPM_RELAY_LAUNCH
-        *taken = true;
-        return hipGetLastError();
-      }
-    }
-    // the block's last launch (max diff folded in) stays here where three rows per wave do (round 3); six-row waves have no
-    // registers left for the snapshot's rows: those launches go to the marching kernel as before
-    if (env_tri && !signed_zero_safe && !(fold_md && two) && chunk_rows < 3 && (items <= tri_limit || env_tri == 2)) {
-      if (dry) { *taken = true; return hipSuccess; }
-      if (two) {
-        nch = (out_last - A0 - 1 + 5) / 6;
-        if (nch < 1) nch = 1;
-        items = (long long)nstr * nch;
-      }
-      const dim3 tgrid(((unsigned)((items + 3) / 4) + 7) / 8 * 8), tblock(256);
-      const MaxDiffArgs tmd = fold_md ? *md : MaxDiffArgs{nullptr, 0.0, 0, 0, nullptr};
-#define WDPM_TRI_LAUNCH(...) do { WDPM_LEDGER_T(0, tri_iteration_kernel, __VA_ARGS__); hipLaunchKernelGGL((tri_iteration_kernel<__VA_ARGS__>), tgrid, tblock, 0, s, w_in, w_out, dem, g, nstr, (int)items, A0, out_last, totaldrain, thres, module == 2 ? drain_owed : 0, tmd); } while (0)
-      if (fold_md) { if (flush) WDPM_TRI_LAUNCH(0, true, 1, false, true); else WDPM_TRI_LAUNCH(0, false, 1, false, true); }
-      else if (module == 2) { if (flush) WDPM_TRI_LAUNCH(2, true, 1, false, false); else if (plain) WDPM_TRI_LAUNCH(2, false, 1, true, false); else WDPM_TRI_LAUNCH(2, false, 1, false, false); }
-      else if (two) { if (flush) WDPM_TRI_LAUNCH(0, true, 2, false, false); else if (plain) WDPM_TRI_LAUNCH(0, false, 2, true, false); else WDPM_TRI_LAUNCH(0, false, 2, false, false); }
-      else { if (flush) WDPM_TRI_LAUNCH(0, true, 1, false, false); else if (plain) WDPM_TRI_LAUNCH(0, false, 1, true, false); else WDPM_TRI_LAUNCH(0, false, 1, false, false); }
-#undef WDPM_TRI_LAUNCH
-      *taken = true;
-      return hipGetLastError();
-    }
-    return hipSuccess;
+using RelayFn = decltype(&relay_iteration_kernel<0, false, false, 4, false>);
+using TriangleFn = decltype(&tri_iteration_kernel<0, false, 1, false, false>);
+#define WDPM_ROW_RELAY(...) WDPM_VARIANT_ROW(relay_iteration_kernel, __VA_ARGS__)
+#define WDPM_ROW_TRIANGLE(...) WDPM_VARIANT_ROW(tri_iteration_kernel, __VA_ARGS__)
+static const VariantRow<RelayFn> kRelayTable[] = {WDPM_VARIANTS_RELAY(WDPM_ROW_RELAY)};
+static const VariantRow<TriangleFn> kTriangleTable[] = {WDPM_VARIANTS_TRIANGLE(WDPM_ROW_TRIANGLE)};
+
+/* this unit's part of DeviceFacts (cus is filled already) */
+void wdpm_small_device_facts(DeviceFacts *f) {
+  int blocks = 1;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, tri_iteration_kernel<0, false, 1, false, false>, 256, 0) != hipSuccess || blocks < 1) blocks = 1;
+  f->tri_slots = f->cus * blocks * 4;
 }
-#else
-;
+
+hipError_t wdpm_launch_small(const LaunchRequest &q, const LaunchPlan &p, const IterationBuffers &b) {
+  const int drain_owed = q.module == 2 ? b.drain_owed : 0;
+  if (p.family == WDPM_FAMILY_RELAY) {
+    const int at = wdpm_find_variant(kRelayVariants, p.targs);
+    if (at < 0) return hipErrorInvalidValue;
+    wdpm_ledger_count(*kRelayTable[at].slot, p.ledger_sw);
+    hipLaunchKernelGGL(kRelayTable[at].fn, dim3(p.grid), dim3(p.block), 0, b.stream, b.w_in, b.w_out, b.dem, q.g, p.nstrips, p.nitems, q.A0,
+                       q.out_last, b.thres, b.totaldrain, drain_owed, *b.code, p.relay_flags);
+  } else {
+    const int at = wdpm_find_variant(kTriangleVariants, p.targs);
+    if (at < 0) return hipErrorInvalidValue;
+    const MaxDiffArgs tmd = p.fold_md ? *b.md : MaxDiffArgs{nullptr, 0.0, 0, 0, nullptr};
+    wdpm_ledger_count(*kTriangleTable[at].slot, p.ledger_sw);
+    hipLaunchKernelGGL(kTriangleTable[at].fn, dim3(p.grid), dim3(p.block), 0, b.stream, b.w_in, b.w_out, b.dem, q.g, p.nstrips, p.nitems, q.A0,
+                       q.out_last, b.totaldrain, b.thres, drain_owed, tmd);
+  }
+  return hipGetLastError();
+}
 #endif
 
 #if !defined(WDPM_TU) || WDPM_TU == 1
-hipError_t wdpm_launch_fused(int module, const double *w_in, double *w_out, const double *dem, const DemCode &code,
-                             const SlabGeom &g, int chunk_rows, int signed_zero_safe, const double *flush,
-                             int drain_owed, double *totaldrain, hipStream_t s, TilePlan *tiles, const MaxDiffArgs *md,
-                             int plain_water, XcdBalance *bal) {
-  return wdpm_launch_fused_rows(module, w_in, w_out, dem, code, g, 0, g.rows - 1, chunk_rows, signed_zero_safe, flush,
-                                drain_owed, totaldrain, s, tiles, md, 0, plain_water, bal);
+using MarchingFn = decltype(&fused_iteration_kernel<0, false, 0, false, false, false>);
+#define WDPM_ROW_MARCHING(...) WDPM_VARIANT_ROW(fused_iteration_kernel, __VA_ARGS__)
+static const VariantRow<MarchingFn> kMarchingTable[] = {WDPM_VARIANTS_MARCHING(WDPM_ROW_MARCHING)};
+
+/* DeviceFacts::resident_waves of one occupancy class, from the occupancy API */
+template <int MODULE, bool SZ_SAFE, int DEM32>
+static int resident_waves(const int cus) {
+  int blocks = 2;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fused_iteration_kernel<MODULE, SZ_SAFE, DEM32, false, false, false>, 256, 0) != hipSuccess || blocks < 1)
+    blocks = 2;
+  constexpr int built_for = fused_built_for<MODULE, SZ_SAFE, DEM32, false>();
+  if (blocks > built_for) blocks = built_for;
+  return cus * blocks * 4;
 }
 
-/* would a whole-slab steady launch (no flush, no folded max diff) of this context go to the relay / triangle kernels of small rasters?
- * Those launches keep no state on the host between iterations (no tile flags, no balance table), which is what lets the caller
- * replay a run of them as a HIP graph (wdpm_capi.hip: GraphCache).  Asks the dispatch itself; launches nothing. */
-bool wdpm_small_rows_take(int module, const SlabGeom &g, int chunk_rows, int signed_zero_safe, TilePlan *tiles) {
-  bool taken = false;
-  const DemCode none{nullptr, 0.0, 1.0, 1.0, 0, nullptr, nullptr, 0};
-  if (wdpm_launch_small_rows(module, nullptr, nullptr, nullptr, none, g, 0, g.rows - 1, chunk_rows, signed_zero_safe, false, 0.0, 0, nullptr,
-                             nullptr, tiles, nullptr, false, false, 0, &taken, true) != hipSuccess) return false;
-  return taken;
+/* The facts of the calling thread's current device: queried when the first context on that device is created, never on the
+ * launch path.  nullptr: no current device, or an ordinal beyond the table. */
+const DeviceFacts *wdpm_device_facts() {
+  constexpr int kMaxDevices = 64;
+  static DeviceFacts facts[kMaxDevices];
+  static std::once_flag once[kMaxDevices];      // rank threads create their contexts concurrently
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return nullptr;
+  std::call_once(once[dev], [dev] {
+    DeviceFacts &f = facts[dev];
+    if (hipDeviceGetAttribute(&f.cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || f.cus < 1) f.cus = 256;
+    if (hipDeviceGetAttribute(&f.lds_per_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess || f.lds_per_cu < 65536)
+      f.lds_per_cu = 163840;
+    f.resident_waves[0][0] = resident_waves<0, false, 0>(f.cus);
+    f.resident_waves[0][1] = resident_waves<0, false, 1>(f.cus);
+    f.resident_waves[0][2] = resident_waves<0, true, 0>(f.cus);
+    f.resident_waves[1][0] = resident_waves<2, false, 0>(f.cus);
+    f.resident_waves[1][1] = resident_waves<2, false, 1>(f.cus);
+    f.resident_waves[1][2] = resident_waves<2, true, 0>(f.cus);
+    wdpm_small_device_facts(&f);
+  });
+  return &facts[dev];
 }
 
-/* one iteration restricted to the output rows [A0 + 2 (0 when A0 == 0), out_last]; A0 % 3 == 0 */
-hipError_t wdpm_launch_fused_rows(int module, const double *w_in, double *w_out, const double *dem,
-                                  const DemCode &code, const SlabGeom &g, int A0, int out_last, int chunk_rows,
-                                  int signed_zero_safe, const double *flush, int drain_owed, double *totaldrain,
-                                  hipStream_t s, TilePlan *tiles, const MaxDiffArgs *md, int leave_cus, int plain_water,
-                                  XcdBalance *bal) {
-  if (tiles) tiles->maintained = 0;
-  /* The gate-free variants (PLAIN, see block_update) run for the launches between a block's first (flush on load) and last
-   * (max diff), every module and kernel family, whenever the water kinds allow it (drain 8192^2 +4.5 %, 482^2 +3 %, add 16384^2
-   * +1.3 % once the two waves of a SIMD ran in step: profiles/r03/plain_water_ab.txt, plain_add_prio_ab.txt). */
-  const bool plain = (plain_water & WDPM_LAUNCH_PLAIN) && !signed_zero_safe && !flush && !(md && md->old);
-  const int no_clamp = (plain_water & WDPM_LAUNCH_CLAMP_OK) ? 0 : 1;     /* see `deep` in the marching kernel */
-  const bool fold_md = md && md->old && module != 2 && !signed_zero_safe;
-  if (md && md->old && !fold_md) return hipErrorInvalidValue;     /* the caller asks only where a folding variant exists */
-  hipError_t e = dpp_selfcheck(s);
-  if (e != hipSuccess) return e;
-  if (A0 < 0 || A0 % 3 != 0 || out_last > g.rows - 1 || out_last < A0) return hipErrorInvalidValue;
-  if (flush && signed_zero_safe) return hipErrorInvalidValue;   /* the caller flushes in place for that variant */
-  const double thres = flush ? *flush : 0.0;
-  {
-    bool taken = false;
-    e = wdpm_launch_small_rows(module, w_in, w_out, dem, code, g, A0, out_last, chunk_rows, signed_zero_safe, flush != nullptr, thres,
-                               drain_owed, totaldrain, s, tiles, md, fold_md, plain, no_clamp, &taken, false);
-    if (taken || e != hipSuccess) return e;
+/* The tile-flag hand-over of a marching launch that keeps dry-tile flags (LaunchPlan::tiles_fit): what the kernel gets, and the
+ * tiling the context's flags now stand for. */
+static hipError_t tiles_hand_over(TilePlan *tiles, const LaunchPlan &p, hipStream_t s, TileFlags *tf) {
+  // the flags describe one tiling: another chunk height or strip count makes the old ones meaningless
+  const bool same = tiles->nstrips == p.nstrips && tiles->H == p.H && tiles->nchunks == p.nchunks;
+  if (!same) {   /* new pitch: the output raster's flag array needs its border of 1s before the kernel fills the interior */
+    const hipError_t e = hipMemsetAsync(tiles->zout, 1, (size_t)tiles->capacity, s);
+    if (e != hipSuccess) return e;
   }
-  int nstrips = 1;
-  if (g.ncp > kStripIn - kHaloR) nstrips = (g.ncp - (kStripIn - kHaloR) + kStripOut - 1) / kStripOut + 1;
-  const bool fast = !signed_zero_safe;
-  // add / subtract with an encodable DEM: 20 B per cell-update instead of 24 (drain: see big_drain below)
-  // ... and only pays on launches big enough for two waves per SIMD (see below): at one wave per SIMD
-  // the wave's own latency chain is the limit and the nine decodes per step cost 3-5 % (size sweep in
-  // profiles/r01: 512^2 - 3072^2 slower with codes, 4096^2 and up 5-12 % faster).
-  // Chunk height at two waves per SIMD from which a launch fills every slot: 18 rows (add / subtract), 12 (drain).  Rounds 1 - 3 had
-  // 36 / 18; with the two waves of a SIMD keeping each other in step and chunk heights following the XCDs, the second wave pays on
-  // shorter chunks: add 2700^2 +3.4 %, 3000^2 +6.7 %, 3300^2 +9.7 %, 3600^2 +2.6 %; drain 2400^2 +2.0 %, 3000^2 +1.1 %
-  // (profiles/r04/tall_rows_sweep.txt).
-  constexpr long long tall_add = 18, tall_drain = 12;
-  const bool big = (long long)(out_last - A0 + 1) * nstrips >= (long long)tall_add * resident_waves<0, false>();
-  // Drain with the codes (round 4, late): "latency-bound, the decode would only add instructions" was round 1's reading of a kernel
-  // at one wave per SIMD; at two, and with the card at its power cap whatever the kernel does, four bytes per
-  // cell-update less are worth more than the nine decodes of a step - on launches that fill every slot at two waves per SIMD.
-  const bool big_drain = module == 2 && fast &&
-                         (long long)(out_last - A0 + 1) * nstrips >= (long long)tall_drain * resident_waves<2, false, 1>();
-  const bool dem32 = fast && code.q != nullptr && ((module == 2 ? big_drain : big) || code.force);
-  bool two_per_simd = false;      /* every slot filled: two waves per SIMD, workgroups of eight waves (one per CU) */
-  int slots = module == 2 ? (!fast ? resident_waves<2, true>() : dem32 ? resident_waves<2, false, 1>() : resident_waves<2, false>())
-              : dem32     ? resident_waves<0, false, 1>()
-              : fast      ? resident_waves<0, false>()
-                          : resident_waves<0, true>();
-  {
-    // (Round 1, fp64 DEM:) the kernel is bound by the memory system with ONE wave per SIMD already; a second wave per SIMD only adds
-    // concurrent DRAM row streams and, on rasters too small to fill the chip, makes the dispatcher
-    // double up waves on some SIMDs while others idle.  Filling half of the resident slots measured
-    // +4 % at 16384^2, +13 % at 6000^2, x1.9 at 1500^2, x2.3 at 1024^2 (-4 % at 4096^2).
-    // The drain variant is different: 16 instructions per neighbour step on one dependent chain per
-    // lane leave it latency-bound (59 % VALU issue at one wave per SIMD), and a second wave per SIMD
-    // fills the bubbles: +21 % at 8192^2, +30 % at 16384^2 - as long as the chunks stay tall enough
-    // for the 6-row warm-up of each not to eat the gain.
-    // With the DEM as 32-bit codes the add kernel is in the same position: fewer bytes, nine decodes
-    // more per step - one wave per SIMD 1.34 ms per 16384^2 launch (no gain), two waves 1.23 ms.
-    // Thresholds from tools/threshold_sweep.sh and tools/slab_sweep.sh (profiles/r01): chunk height at
-    // two waves per SIMD >= 36 rows for the DEM-code add kernel (3072^2 still loses, 3600^2 gains 12 %),
-    // >= 18 rows for drain (+11 % on a 1055 x 8190 slab, +15 % at 3072^2, a wash at 2048^2).
-    if (dem32 && big) two_per_simd = true;
-    if (module == 2 && fast && (long long)(out_last - A0 + 1) * nstrips >= (long long)tall_drain * slots) two_per_simd = true;
-    if (!two_per_simd && !(module == 2 && !fast)) slots = slots / 2;      /* (the -0.0-safe drain variant is built for one wave per SIMD) */
-    if (leave_cus > 0) {                               // room for somebody else's kernels (see wdpm_kernels.h)
-      int dev = 0, cus = 256;
-      if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-      if (leave_cus < cus / 2) slots = (int)((long long)slots * (cus - leave_cus) / cus);
-    }
-  }
-  const int wrows = out_last - A0 + 1;                       // rows of this launch's window
-  const int H = pick_chunk_rows(wrows, nstrips, chunk_rows, slots);
-  // chunk i stores rows [A0+H*i+2 (0 for A0+H*i = 0), A0+H*(i+1)+1]; the last must reach out_last
-  int nchunks = (out_last - A0 - 1 + H - 1) / H;
-  if (nchunks < 1) nchunks = 1;
-  int nitems = nstrips * nchunks;
-  const int wpb = two_per_simd ? 8 : 4;                            // waves per workgroup (see the kernel: `prio`)
-  dim3 grid(((nitems + wpb - 1) / wpb + 7) / 8 * 8), block(64 * wpb);   // multiple of 8: see the XCD remap
-  TileFlags tf{nullptr, nullptr, 0, nullptr, nchunks};
-  if (tiles && tiles->zout && fast && H >= 6 && A0 == 0 && out_last == g.rows - 1 &&
-      (nstrips + 2) * (nchunks + 2) <= tiles->capacity) {
-    // the flags describe one tiling: another chunk height or strip count makes the old ones meaningless
-    const bool same = tiles->nstrips == nstrips && tiles->H == H && tiles->nchunks == nchunks;
-    if (!same) {   /* new pitch: the output raster's flag array needs its border of 1s before the kernel fills the interior */
-      e = hipMemsetAsync(tiles->zout, 1, (size_t)tiles->capacity, s);
-      if (e != hipSuccess) return e;
-    }
-    tf.zin = same && tiles->zin_valid ? tiles->zin : nullptr;
-    tf.zout = tiles->zout;
-    tf.zout_known = same && tiles->zout_valid;
-    tf.active = tiles->active;
-    tiles->nstrips = nstrips; tiles->H = H; tiles->nchunks = nchunks;
-    tiles->maintained = 1;
-  }
-  const MaxDiffArgs mda = fold_md ? *md : MaxDiffArgs{nullptr, 0.0, 0, 0, nullptr};
-  if (fold_md) tf = TileFlags{nullptr, nullptr, 0, nullptr, nchunks};   /* every wave must look at its block: no skipping in this launch */
-  if (fold_md && tiles) tiles->maintained = 0;
-  // Chunk heights by what each XCD delivers (wdpm_kernels.h::XcdBalance): whole-slab launches of two waves per SIMD that keep no
-  // dry-tile flags.  Every launch may be measured (the block's first and last are other instantiations: not those); the table
-  // needs chunks of a dozen rows at least, so that whole row triples can follow weights a few per cent apart.
+  tf->zin = same && tiles->zin_valid ? tiles->zin : nullptr;
+  tf->zout = tiles->zout;
+  tf->zout_known = same && tiles->zout_valid;
+  tf->active = tiles->active;
+  tiles->nstrips = p.nstrips; tiles->H = p.H; tiles->nchunks = p.nchunks;
+  tiles->maintained = 1;
+  return hipSuccess;
+}
+
+/* The balance bookkeeping of a marching launch that may look at the balance state (LaunchPlan::balance): rebuilds the table where
+ * the geometry is new or three launches have been measured, keeps the measuring schedule, says what the kernel gets. */
+static BalanceArgs balance_step(XcdBalance *bal, const LaunchRequest &q, const LaunchPlan &p, hipStream_t s) {
   BalanceArgs ba{nullptr, nullptr, nullptr, 0};
-  const bool bal_forced = bal && bal->mode == 2;          /* tests: the table on launches of any size, from skewed weights */
-  if (bal && bal->mode && (two_per_simd || bal_forced) && A0 == 0 && out_last == g.rows - 1 && (chunk_rows < 3 || bal_forced) && nchunks >= 2) {
-    const bool can_table = !tf.zout && H >= (bal_forced ? 6 : 12) && (nchunks + 1) * nstrips <= bal->capacity;
-    // Round 5: with the table in charge a strip's chunks need not be equally tall, so a strip is cut into as many chunks as the
-    // resident round has slots for - equal heights in whole triples left slots empty (the 8-GPU drain slab, 1055 x 8190: 27-row
-    // chunks, 39 x 48 = 1872 waves on 2048 slots) - and the table pairs tall chunks with short ones on every SIMD (`pair` in
-    // xcd_rebalance_kernel).  WDPM_PAIR=0: round 4's geometry (A/B, tests).
-    static std::atomic<int> env_pair{-1};
-    if (env_pair < 0) { const char *t = getenv("WDPM_PAIR"); env_pair = t ? atoi(t) : 1; }
-    // (WDPM_PAIR=2, tests: also on forced tables and launches of one wave per SIMD, down to the table's minimum of two triples a chunk)
-    const int pair_mode = env_pair.load(std::memory_order_relaxed);
-    const int pair = ((wpb == 8 && !bal_forced && pair_mode != 0) || pair_mode == 2) ? 1 : 0;
-    if (can_table && pair) {
-      const int T = (out_last - 1 - A0 + 2) / 3, nc = slots / nstrips;
-      if (nc > nchunks && T / nc >= (pair_mode == 2 ? 2 : 4) && (nc + 1) * nstrips <= bal->capacity) {
-        nchunks = nc;
-        nitems = nstrips * nchunks;
-        grid = dim3(((nitems + wpb - 1) / wpb + 7) / 8 * 8);
-        tf.nchunks = nchunks;
-      }
+  if (p.table) {
+    const bool same = bal->nstrips == p.nstrips && bal->nchunks == p.nchunks && bal->A0 == q.A0 && bal->out_last == q.out_last && bal->ipx == p.ipx;
+    const bool update = bal->measured >= 3 && (same || bal->measured_uniform);
+    if (!same || update) {
+      WDPM_LEDGER(0, xcd_rebalance_kernel);
+      hipLaunchKernelGGL(xcd_rebalance_kernel, dim3(1), dim3(256), 0, s, bal->weight, bal->acc, bal->table, p.nstrips, p.nchunks, q.A0,
+                         q.out_last, p.ipx, update ? 1 : 0, bal->measured_uniform, p.pair);
+      bal->measured_uniform = 0;
+      bal->nstrips = p.nstrips; bal->nchunks = p.nchunks; bal->A0 = q.A0; bal->out_last = q.out_last; bal->ipx = p.ipx;
+      bal->measured = 0;
+      if (update) bal->updates++;
     }
-    const int ipx = wpb * (int)(grid.x / 8);
-    const bool steady = !flush && !fold_md;
-    if (can_table) {
-      const bool same = bal->nstrips == nstrips && bal->nchunks == nchunks && bal->A0 == A0 && bal->out_last == out_last && bal->ipx == ipx;
-      const bool update = bal->measured >= 3 && (same || bal->measured_uniform);
-      if (!same || update) {
-        WDPM_LEDGER(0, xcd_rebalance_kernel);
-        hipLaunchKernelGGL(xcd_rebalance_kernel, dim3(1), dim3(256), 0, s, bal->weight, bal->acc, bal->table, nstrips, nchunks, A0,
-                           out_last, ipx, update ? 1 : 0, bal->measured_uniform, pair);
-        bal->measured_uniform = 0;
-        bal->nstrips = nstrips; bal->nchunks = nchunks; bal->A0 = A0; bal->out_last = out_last; bal->ipx = ipx;
-        bal->measured = 0;
-        if (update) bal->updates++;
-      }
-      ba.table = bal->table;
-      static std::atomic<int> env_rot{-1};         // WDPM_ROT=0: shares and measurements by blockIdx % 8, as in round 4 (A/B)
-      if (env_rot < 0) { const char *t = getenv("WDPM_ROT"); env_rot = t ? atoi(t) : 1; }
-      if (env_rot.load(std::memory_order_relaxed) != 0) {
-        ba.rot = bal->acc + 2 * kBalClasses;          // shares and measurements by physical XCD (BalanceArgs::rot)
-        ba.parity = bal->seq++ & 1;
-      }
-      // measured: while the weights are young, every steady launch (an update every three); afterwards three launches in 256
-      if (steady && (bal->updates < 6 || (bal->launches & 255) < 3)) {
-        if (bal->measured == 0 || !bal->measured_uniform) { ba.acc = bal->acc; bal->measured_uniform = 0; bal->measured++; }
-      }
-      bal->launches++;
-    } else if (steady && bal->updates == 0 && H >= 12 && (bal->measured == 0 || bal->measured_uniform)) {
-      // equal heights (a block that keeps dry-tile flags): what the XCDs deliver can be learnt here already
-      ba.acc = bal->acc;
-      ba.rot = bal->acc + 2 * kBalClasses;
+    ba.table = bal->table;
+    if (p.rot) {
+      ba.rot = bal->acc + 2 * kBalClasses;          // shares and measurements by physical XCD (BalanceArgs::rot)
       ba.parity = bal->seq++ & 1;
-      bal->measured_uniform = 1;
-      bal->measured++;
     }
+    // measured: while the weights are young, every steady launch (an update every three); afterwards three launches in 256
+    if (p.steady && (bal->updates < 6 || (bal->launches & 255) < 3)) {
+      if (bal->measured == 0 || !bal->measured_uniform) { ba.acc = bal->acc; bal->measured_uniform = 0; bal->measured++; }
+    }
+    bal->launches++;
+  } else if (p.measure_equal && bal->updates == 0 && (bal->measured == 0 || bal->measured_uniform)) {
+    // equal heights (a block that keeps dry-tile flags): what the XCDs deliver can be learnt here already
+    ba.acc = bal->acc;
+    ba.rot = bal->acc + 2 * kBalClasses;
+    ba.parity = bal->seq++ & 1;
+    bal->measured_uniform = 1;
+    bal->measured++;
   }
-  // Workgroups per CU, whatever the register allocator ends up with (an instantiation at 166 VGPRs would let the dispatcher stack
-  // three four-wave workgroups on some CUs and one on others): unused dynamic LDS beside the 36 KiB of staging - four-wave
-  // workgroups 36 KiB (two fit a CU's 160 KiB, three do not), eight-wave workgroups 48 KiB (one fits).
-  // The pad follows the CU's LDS (not a constant tied to one architecture): an eight-wave workgroup takes just over half
-  // of it, a four-wave one just over a third; 160 KiB on gfx950: 45 KiB and 18 KiB beside the 36 KiB of staging.
-  static std::atomic<int> cu_lds{0};
-  if (!cu_lds) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess || v < 65536)
-      v = 163840;
-    cu_lds = v;
+  return ba;
+}
+
+/* queues what plan_iteration() decided for the request */
+hipError_t wdpm_launch_iteration(const LaunchRequest &q, const LaunchPlan &p, const IterationBuffers &b) {
+  if (b.tiles) b.tiles->maintained = 0;
+  if (p.error) return hipErrorInvalidValue;
+  hipError_t e = dpp_selfcheck(b.stream);
+  if (e != hipSuccess) return e;
+  if (p.family != WDPM_FAMILY_MARCHING) return wdpm_launch_small(q, p, b);
+  const int at = wdpm_find_variant(kMarchingVariants, p.targs);
+  if (at < 0) return hipErrorInvalidValue;
+  TileFlags tf{nullptr, nullptr, 0, nullptr, p.nchunks};
+  if (p.tiles_fit) {
+    e = tiles_hand_over(b.tiles, p, b.stream, &tf);
+    if (e != hipSuccess) return e;
   }
-  const int staging = 8 * 3 * kStripIn * (int)sizeof(double) + 64;
-  const int share = cu_lds.load(std::memory_order_relaxed) / (wpb == 8 ? 2 : 3) + 1024;
-  const unsigned lds_pad = share > staging ? (unsigned)(share - staging) : 0u;
-  // the two waves of a SIMD keep each other in step (see the marching loop); WDPM_PRIO=0: no priorities (A/B, tests)
-  static std::atomic<int> env_prio{-1};
-  if (env_prio < 0) { const char *e = getenv("WDPM_PRIO"); env_prio = e ? atoi(e) : 1; }
-  const int prio = (wpb == 8 && env_prio.load(std::memory_order_relaxed) != 0) ? 1 : 0;
-  // the switches this launch hands the kernel, for the launch ledger (include/wdpm.h: WDPM_LEDGER_*)
-  const int ledger_sw = (no_clamp ? WDPM_LEDGER_NO_CLAMP : 0) | (prio ? WDPM_LEDGER_PRIO : 0) | (tf.zout ? WDPM_LEDGER_TILE_FLAGS : 0) |
-                        (ba.table ? WDPM_LEDGER_BALANCE : 0);
-#define WDPM_LAUNCH(...) do { WDPM_LEDGER_T(ledger_sw, fused_iteration_kernel, __VA_ARGS__); hipLaunchKernelGGL((fused_iteration_kernel<__VA_ARGS__>), grid, block, lds_pad, s, w_in, w_out, dem, code, g, nstrips, nitems, H, A0, out_last, totaldrain, thres, module == 2 ? drain_owed : 0, tf, mda, prio, no_clamp, ba); } while (0)
-  // <module, -0.0-safe, DEM codes, flush on load, max diff folded in, gate-free>: which instantiation runs is decided here and
-  // nowhere else (DESIGN.md §4 has the table)
-#define WDPM_LAUNCH_ADD(D32) do { if (fold_md) { if (flush) WDPM_LAUNCH(0, false, D32, true, true, false); else WDPM_LAUNCH(0, false, D32, false, true, false); } \
-                                  else if (plain) WDPM_LAUNCH(0, false, D32, false, false, true);                                                                 \
-                                  else if (flush) WDPM_LAUNCH(0, false, D32, true, false, false); else WDPM_LAUNCH(0, false, D32, false, false, false); } while (0)
-#define WDPM_LAUNCH_DRAIN(D32) do { if (plain) WDPM_LAUNCH(2, false, D32, false, false, true);                                                                    \
-                                    else if (flush) WDPM_LAUNCH(2, false, D32, true, false, false); else WDPM_LAUNCH(2, false, D32, false, false, false); } while (0)
-  // the codes as 16-bit offsets (18.1 B of HBM traffic per cell-update) on launches of 10^8 cells and more: wdpm_kernels.h::wdpm_dem16_pays
-  const bool dem16 = dem32 && code.h != nullptr && wdpm_dem16_pays((long long)wrows * g.ncp, code.force);
-  if (module == 2 && !fast) WDPM_LAUNCH(2, true, 0, false, false, false);
-  else if (module == 2 && dem16) WDPM_LAUNCH_DRAIN(2);
-  else if (module == 2 && dem32) WDPM_LAUNCH_DRAIN(1);
-  else if (module == 2) WDPM_LAUNCH_DRAIN(0);
-  else if (!fast) WDPM_LAUNCH(0, true, 0, false, false, false);
-  else if (dem16) WDPM_LAUNCH_ADD(2);
-  else if (dem32) WDPM_LAUNCH_ADD(1);
-  else WDPM_LAUNCH_ADD(0);
-#undef WDPM_LAUNCH_DRAIN
-#undef WDPM_LAUNCH_ADD
-#undef WDPM_LAUNCH
+  const MaxDiffArgs mda = p.fold_md ? *b.md : MaxDiffArgs{nullptr, 0.0, 0, 0, nullptr};
+  if (p.fold_md) tf = TileFlags{nullptr, nullptr, 0, nullptr, p.nchunks};   /* every wave must look at its block: no skipping in this launch */
+  if (p.fold_md && b.tiles) b.tiles->maintained = 0;
+  const BalanceArgs ba = p.balance ? balance_step(b.bal, q, p, b.stream) : BalanceArgs{nullptr, nullptr, nullptr, 0};
+  wdpm_ledger_count(*kMarchingTable[at].slot, p.ledger_sw);
+  hipLaunchKernelGGL(kMarchingTable[at].fn, dim3(p.grid), dim3(p.block), p.lds, b.stream, b.w_in, b.w_out, b.dem, *b.code, q.g, p.nstrips, p.nitems,
+                     p.H, q.A0, q.out_last, b.totaldrain, b.thres, q.module == 2 ? b.drain_owed : 0, tf, mda, p.prio, p.no_clamp, ba);
   return hipGetLastError();
 }
 

@@ -8,16 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-/* A raster slab resident in HBM: rows x ncp doubles, row-major, row 0 of the slab is padded
- * row `row0` of the whole raster (row0 % 3 == 0). */
-struct SlabGeom {
-  int rows;      /* padded rows held */
-  int ncp;       /* padded columns (ncols + 2) */
-  int row0;      /* global padded row of slab row 0 */
-  int R, C;      /* file raster size (centres are global rows 1..R, cols 1..C) */
-  int dr, dc;    /* drain cell, slab-local row / column (drain module; may lie outside the slab) */
-  double miss;   /* NODATA value */
-};
+#include "wdpm_dispatch.h"   /* SlabGeom, the launch planner */
 
 /* The static DEM as 32-bit codes (4 B per cell instead of 8 in the iteration kernel's HBM traffic):
  * dem[i] == dem32_decode(q[i]) BIT FOR BIT for every cell, verified on the device when the DEM is
@@ -41,10 +32,6 @@ struct DemCode {
   int ngroups;
 };
 constexpr int kDemGroup = 48;
-/* ... and only where it pays: rasters far beyond the 256 MB Infinity Cache, where the bytes are what a launch waits for (16384^2
- * +2.5 %, 8192^2 +0.3 %, 4096^2 -2.2 %: nine integer adds more per step; profiles/r04/dem16_bench*_ab.txt) - or when forced (tests) */
-inline bool wdpm_dem16_pays(long long cells_of_the_launch, int force) { return cells_of_the_launch >= 100000000LL || force != 0; }
-
 /* smallest valid (finite) dem value, as an order-preserving uint64 key in key[0] (all ones: none), and the bit image of the
  * largest |dem| over the valid cells in key[1] (0: none) */
 hipError_t wdpm_launch_dem_min(const double *dem, size_t cells, unsigned long long *key, hipStream_t s);
@@ -92,7 +79,7 @@ struct TilePlan {                /* host side of it, kept by the context per lau
   int nstrips, H, nchunks;       /* in: the tiling the flags were made for; out: the tiling of this launch */
   int maintained;                /* out: this launch read / wrote the flags (marching kernel, whole slab, H >= 6) */
   int wide_tri_ok;               /* in: the last block with flags found most tiles working: the triangle kernel (which keeps no
-                                  * flags) may also take rasters of a few rounds of its waves (wdpm_launch_fused_rows) */
+                                  * flags) may also take rasters of a few rounds of its waves (plan_iteration) */
 };
 
 /* max |w - oldw| folded into an iteration launch (the last one of a block): the waves have the final values in
@@ -149,33 +136,29 @@ hipError_t wdpm_launch_mark_nodata(double *dem, size_t cells, double miss, hipSt
 /* one colour pass, in place (reference kernels add/subtract/ddrain, runoff.cl:137-183) */
 hipError_t wdpm_launch_pass(int module, double *w, const double *dem, const SlabGeom &g, int oi, int oj,
                             double *totaldrain, hipStream_t s);
-/* one whole iteration (9 passes) fused in one launch: w_in -> w_out (distinct buffers) */
-/* signed_zero_safe = 0 selects the faster add/subtract variant that is exact when the water raster
- * holds no -0.0 (wdpm_stencil.h::flow_add_nz) */
-/* drain_owed (drain module): the previous iteration's drain() has not been applied to w_in; this launch does it
- * (sum into totaldrain by the wave that owns the outlet, the nine cells read as 0).
- * flush != nullptr: every water value is replaced by 0 when it is < *flush as it is loaded (the block's
- * threshold flush, WDPMCL.c:1055-1065, riding on the first iteration; only with signed_zero_safe == 0) */
-hipError_t wdpm_launch_fused(int module, const double *w_in, double *w_out, const double *dem, const DemCode &code,
-                             const SlabGeom &g, int chunk_rows, int signed_zero_safe, const double *flush,
-                             int drain_owed, double *totaldrain, hipStream_t s, TilePlan *tiles = nullptr,
-                             const MaxDiffArgs *md = nullptr, int plain_water = 0, XcdBalance *bal = nullptr);
-/* whether a steady whole-slab launch of this geometry goes to the small-raster kernels (relay / triangle): see wdpm_fused.hip */
-bool wdpm_small_rows_take(int module, const SlabGeom &g, int chunk_rows, int signed_zero_safe, TilePlan *tiles);
-hipError_t wdpm_launch_fused_rows(int module, const double *w_in, double *w_out, const double *dem,
-                                  const DemCode &code, const SlabGeom &g, int A0, int out_last, int chunk_rows,
-                                  int signed_zero_safe, const double *flush, int drain_owed, double *totaldrain,
-                                  hipStream_t s, TilePlan *tiles = nullptr, const MaxDiffArgs *md = nullptr,
-                                  int leave_cus = 0, int plain_water = 0, XcdBalance *bal = nullptr);
-/* plain_water, bit 0 (WDPM_LAUNCH_PLAIN): the caller knows (wdpm_launch_scan_water, and nothing written since that could change
- * it) that every cell of w_in that may not give water holds +0.0: launches that have such a variant then run without the centre gate.
- * bit 1 (WDPM_LAUNCH_CLAMP_OK): every valid elevation is below 2^30 m in magnitude (wdpm_launch_dem_min), so that half an ulp of an
- * elevation is nothing against a depth: the kernels may take a flow's `max(x / 8, -0.0)` as one clamped instruction wherever
- * the depths they hold are shallow enough for it to be exact (wdpm_stencil.h::eighth_clamped, `deep` in wdpm_fused.hip). */
-enum { WDPM_LAUNCH_PLAIN = 1, WDPM_LAUNCH_CLAMP_OK = 2 };
-/* leave_cus: size the launch as if the chip had that many compute units fewer - the interior launch of an overlapped
- * iteration leaves room for the RCCL send/recv kernels queued beside it (a launch otherwise fills every slot for its
- * whole duration, and the transfer would start only when the first waves retire) */
+/* One whole iteration (9 passes) fused in one launch, w_in -> w_out (distinct buffers), restricted to the request's window:
+ * plan_iteration() (wdpm_dispatch.h) decides kernel, geometry and switches from the request, the device's facts and the
+ * process's switches; wdpm_launch_iteration() queues that plan on these buffers and keeps the tile / balance bookkeeping. */
+struct IterationBuffers {
+  const double *w_in;
+  double *w_out;
+  const double *dem;
+  const DemCode *code;
+  double thres;          /* LaunchRequest::flush: every water value is replaced by 0 when it is < thres as it is loaded (the block's
+                          * threshold flush, WDPMCL.c:1055-1065, riding on the first iteration) */
+  int drain_owed;        /* drain module: the previous iteration's drain() has not been applied to w_in; this launch does it
+                          * (sum into totaldrain by the wave that owns the outlet, the nine cells read as 0) */
+  double *totaldrain;
+  hipStream_t stream;
+  TilePlan *tiles;       /* LaunchRequest::tiles_offered */
+  const MaxDiffArgs *md; /* LaunchRequest::max_diff */
+  XcdBalance *bal;       /* LaunchRequest::balance_mode != 0 */
+};
+const DeviceFacts *wdpm_device_facts();      /* of the current device; nullptr: see wdpm_fused.hip */
+hipError_t wdpm_launch_iteration(const LaunchRequest &q, const LaunchPlan &p, const IterationBuffers &b);
+/* between the two translation units of wdpm_fused.hip */
+void wdpm_small_device_facts(DeviceFacts *f);
+hipError_t wdpm_launch_small(const LaunchRequest &q, const LaunchPlan &p, const IterationBuffers &b);
 /* What kinds of depth do the n cells at p hold (dem: the device DEM of the same cells, NODATA = +inf)?
  *   *flag |= 1  a -0.0                       (the exact-zero stencil variant must run, see signed_zero_safe)
  *   *flag |= 2  a negative depth             (gone once a threshold flush with thres >= 0 has been applied)
