@@ -390,12 +390,15 @@ int wdpm_set_option(wdpm_ctx *ctx, int32_t key, int64_t value);
  * indexed by the bits below; 0 for the kernels that take none).  Makes no HIP call: readable without a GPU.  The CPU
  * restatement has no kernels and returns 0.
  *   marching kernel (fused_iteration_kernel): NO_CLAMP the exact unclamped neighbour step (elevations not known to be bounded),
- *     PRIO issue priorities between the two waves of a SIMD, TILE_FLAGS dry-tile flags kept, BALANCE the per-XCD chunk table
+ *     PRIO issue priorities between the two waves of a SIMD, TILE_FLAGS dry-tile flags kept, BALANCE the per-XCD chunk table,
+ *     ITER2 the launch ran TWO iterations (producer and consumer waves, rows handed over through LDS; WDPM_ITER2 in the
+ *     environment: 0 never, 1 on launches of 3e7 cells and more, 2 wherever it fits) - PRIO then means the producers' priorities
  *   relay kernel (relay_iteration_kernel): its store_plain bits - 1 ordinary instead of non-temporal stores, 2 stage
  *     priorities, 4 the unclamped step */
 enum { WDPM_LEDGER_NO_CLAMP = 1, WDPM_LEDGER_PRIO = 2, WDPM_LEDGER_TILE_FLAGS = 4, WDPM_LEDGER_BALANCE = 8,
        WDPM_LEDGER_RELAY_ORDINARY_STORES = 1, WDPM_LEDGER_RELAY_PRIO = 2, WDPM_LEDGER_RELAY_NO_CLAMP = 4,
-       WDPM_LEDGER_SWITCH_STATES = 16 };
+       WDPM_LEDGER_ITER2 = 16,
+       WDPM_LEDGER_SWITCH_STATES = 32 };
 int wdpm_launch_ledger(int32_t index, const char **name, int64_t *launches, int64_t *by_switches);
 
 /* -- host staging memory for whole rasters.  The HIP back-end returns page-locked memory, so that

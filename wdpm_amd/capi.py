@@ -23,7 +23,8 @@ OPT_GRAPH_LAUNCHES = 11
 # launch ledger switch bits (include/wdpm.h: WDPM_LEDGER_*): marching kernel, relay kernel (its store_plain bits)
 LEDGER_NO_CLAMP, LEDGER_PRIO, LEDGER_TILE_FLAGS, LEDGER_BALANCE = 1, 2, 4, 8
 LEDGER_RELAY_ORDINARY_STORES, LEDGER_RELAY_PRIO, LEDGER_RELAY_NO_CLAMP = 1, 2, 4
-LEDGER_SWITCH_STATES = 16
+LEDGER_ITER2 = 16
+LEDGER_SWITCH_STATES = 32
 HALO_AUTO, HALO_RCCL, HALO_PEER, HALO_HOST = 0, 1, 2, 3
 HALO_NAMES = {0: "none", 1: "rccl", 2: "peer", 3: "host"}
 COMM_ID_BYTES = 128

@@ -52,10 +52,19 @@ static int ensure_flushed(wdpm_ctx *x);
 int wdpm_apply_owed_flush(wdpm_ctx *x) { return ensure_flushed(x); }
 static void flushed_whole(wdpm_ctx *x, double thres);
 
+/* Iter2Args::err: a wave of a two-iteration launch gave up waiting for another one - the rasters written since are wrong.  Sticky:
+ * every later wait of this context fails too. */
+static int wdpm_iter2_verdict(const wdpm_ctx *x) {
+  if (x->h_iter2_err && *(volatile unsigned *)x->h_iter2_err)
+    return wdpm_fail("a two-iteration launch (WDPM_ITER2) did not complete its hand-over between waves: results are invalid");
+  return 0;
+}
+
 int wdpm_stream_sync(wdpm_ctx *x, hipStream_t s) {
   if (!x->comm) {
     const hipError_t e = hipStreamSynchronize(s);
-    return e == hipSuccess ? 0 : wdpm_fail("hipStreamSynchronize failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return wdpm_fail("hipStreamSynchronize failed: %s", hipGetErrorString(e));
+    return wdpm_iter2_verdict(x);
   }
   static std::atomic<int> limit_ms{0};
   if (!limit_ms) { const char *t = getenv("WDPM_SYNC_TIMEOUT_S"); const double v = t ? atof(t) : 0.0; limit_ms = (int)((v > 0 ? v : 600.0) * 1000.0); }
@@ -63,7 +72,7 @@ int wdpm_stream_sync(wdpm_ctx *x, hipStream_t s) {
   clock_gettime(CLOCK_MONOTONIC, &t0);
   for (;;) {
     const hipError_t e = hipStreamQuery(s);
-    if (e == hipSuccess) return 0;
+    if (e == hipSuccess) return wdpm_iter2_verdict(x);
     if (e != hipErrorNotReady) return wdpm_fail("hipStreamQuery failed: %s", hipGetErrorString(e));
     timespec t;
     clock_gettime(CLOCK_MONOTONIC, &t);
@@ -327,7 +336,7 @@ int wdpm_create(wdpm_ctx **out, const wdpm_params *p) {
   x->d_md = nullptr; x->md_hint = x->md_valid = false; x->md_lo = x->md_hi = 0;
   x->drain_owed = false;
   x->flush_thres = -__builtin_inf();
-  x->d_scal = nullptr; x->d_bits = nullptr; x->h_pin = nullptr; x->d_stat = nullptr;
+  x->d_scal = nullptr; x->d_bits = nullptr; x->h_pin = nullptr; x->d_stat = nullptr; x->h_iter2_err = x->d_iter2_err = nullptr;
   x->d_dem32 = nullptr; x->code = DemCode{nullptr, 0.0, 1.0, 1.0, 0, nullptr, nullptr, 0}; x->dem32_encodable = false; x->dem_bounded = false;
   x->d_dem16 = nullptr; x->d_gbase = nullptr; x->dem16_encodable = false; x->dem16_wanted = true;
   x->graph_mode = -1; x->graph_launches = 0;
@@ -381,6 +390,8 @@ int wdpm_create(wdpm_ctx **out, const wdpm_params *p) {
     if (e == hipSuccess) e = hipMemsetAsync(x->d_active, 0, sizeof(unsigned), x->stream);
   }
   if (e == hipSuccess) e = hipHostMalloc(&x->h_pin, 4 * sizeof(double));
+  if (e == hipSuccess) e = hipHostMalloc(&x->h_iter2_err, sizeof(unsigned), hipHostMallocMapped);
+  if (e == hipSuccess) { *x->h_iter2_err = 0u; e = hipHostGetDevicePointer((void **)&x->d_iter2_err, x->h_iter2_err, 0); }
   if (e == hipSuccess) e = hipMemsetAsync(x->d_scal, 0, 2 * sizeof(double), x->stream);
   if (e == hipSuccess) e = hipMemsetAsync(x->d_w[2], 0, bytes, x->stream);   /* the snapshot before any block: zeros */
   if (e == hipSuccess) e = hipStreamSynchronize(x->stream);
@@ -417,6 +428,7 @@ void wdpm_destroy(wdpm_ctx *x) {
   (void)hipFree(x->bal.table); (void)hipFree(x->bal.acc); (void)hipFree(x->bal.weight);
   if (x->h_active) (void)hipHostFree(x->h_active);
   if (x->h_pin) (void)hipHostFree(x->h_pin);
+  if (x->h_iter2_err) (void)hipHostFree(x->h_iter2_err);
   (void)hipFree(x->d_sum_approx); (void)hipFree(x->d_sum_i); (void)hipFree(x->d_sum_k); (void)hipFree(x->d_sum_flag);
   if (x->own_stream && x->stream) (void)hipStreamDestroy(x->stream);
   delete x;
@@ -963,7 +975,8 @@ int wdpm_iterate(wdpm_ctx *x, int32_t n_iter) {
     if (!x->pool.empty()) { st = x->pool.back(); x->pool.pop_back(); }
     else { HIP_TRY(hipEventCreate(&st.a)); HIP_TRY(hipEventCreate(&st.b)); }
   }
-  auto one_iteration = [&](const int it) -> int {
+  /* *did: iterations this call advanced the raster by - two where the dispatch offers both in one launch (plan_iter2) */
+  auto one_iteration = [&](const int it, int *did = nullptr) -> int {
     if (steady && it == 1) HIP_TRY(hipEventRecord(st.a, x->stream));
     if (steady && it == n_iter - 1) HIP_TRY(hipEventRecord(st.b, x->stream));
     if (x->kernel == WDPM_KERNEL_FUSED) {
@@ -985,8 +998,16 @@ int wdpm_iterate(wdpm_ctx *x, int32_t n_iter) {
       }
       const LaunchRequest q = iteration_request(x, 0, x->g.rows - 1, chunk_rows, md.old != nullptr, 0, track ? &tp : nullptr, x->bal.mode != 0);
       const IterationBuffers buf{x->d_w[x->cur], x->d_w[t], x->d_dem, &x->code, x->flush_pending ? x->flush_thres : 0.0, x->drain_owed ? 1 : 0,
-                                 x->d_scal, x->stream, track ? &tp : nullptr, &md, &x->bal};
-      HIP_TRY(wdpm_launch_iteration(q, plan_iteration(q, *x->facts, wdpm_switches()), buf));
+                                 x->d_scal, x->stream, track ? &tp : nullptr, &md, &x->bal, x->d_iter2_err};
+      /* iterations from this one on that are launches like it: not the block's last where that folds the max diff - and, where the
+       * steady launches are timed, neither the call's first nor its last */
+      int alike = 0;
+      if (did && !x->flush_pending && !md.old && !(steady && it == 0))
+        alike = n_iter - it - ((fold || steady) ? 1 : 0);
+      const LaunchPlan plan = alike >= 2 ? plan_iter2(q, *x->facts, wdpm_switches(), alike) : plan_iteration(q, *x->facts, wdpm_switches());
+      const int advanced = plan.iter2 ? 2 : 1;
+      if (did) *did = advanced;
+      HIP_TRY(wdpm_launch_iteration(q, plan, buf));
       if (x->flush_pending) flushed_whole(x, x->flush_thres);   /* the launch flushed every value it loaded, and it loaded them all */
       if (md.old) x->md_valid = true;
       if (track && tp.maintained) {
@@ -1006,7 +1027,7 @@ int wdpm_iterate(wdpm_ctx *x, int32_t n_iter) {
       x->cur = t;
       x->flush_pending = false;
       x->drain_owed = x->p.module == WDPM_DRAIN;     /* this iteration's drain(): owed to the next launch or reader */
-      x->launches += 1;
+      x->launches += advanced;
       return 0;
     } else {
       for (int oi = 1; oi <= 3; oi++)
@@ -1078,8 +1099,11 @@ int wdpm_iterate(wdpm_ctx *x, int32_t n_iter) {
       }
     }
   }
-  for (; it < n_iter; it++)
-    if (one_iteration(it)) return 1;
+  while (it < n_iter) {
+    int did = 1;
+    if (one_iteration(it, &did)) return 1;
+    it += did;
+  }
   if (x->timing) {
     HIP_TRY(hipEventRecord(ep.b, x->stream));
     x->pending.push_back(ep);

@@ -52,6 +52,8 @@ struct wdpm_ctx {
   double *d_scal;               /* [0] totaldrain, [1] olddrain */
   unsigned long long *d_bits;   /* max-diff reduction cell */
   double *h_pin;                /* pinned staging: 4 doubles */
+  unsigned *h_iter2_err;        /* pinned, and written by the device: Iter2Args::err (looked at wherever the host waits for the stream) */
+  unsigned *d_iter2_err;        /* the same word as the device sees it */
   unsigned long long *d_stat;   /* wdpm_count_stats / wdpm_find_drain: 4 reduction cells */
   double *d_sum_approx;         /* wdpm_volume_partial: per-chunk approximate sums, integer sums, binades, flags */
   long long *d_sum_i;

@@ -30,6 +30,17 @@ constexpr int kStripIn = 3 * kLanes;                     // 192 columns loaded p
 // the right so that the strip pitch, 171, is a multiple of 3 and every strip starts on a block edge.
 constexpr int kHaloL = 8, kHaloR = 13;
 constexpr int kStripOut = kStripIn - kHaloL - kHaloR;    // 171 columns stored per wave
+// Two iterations per launch (plan_iter2): four neighbouring strips share their exact columns through LDS, so only the two outer
+// edges of the GROUP pay for the wider dependency cone: 3 x 171 + 192 columns in, 42 fewer out - 663 = 3 x 221, group origins stay
+// on block edges.  Over TWO iterations an error at the group's edge travels 17 columns inward from the left (not 2 x 8: the second
+// iteration's unknown columns end at column 7, which is no block edge) and 24 from the right (tests/test_pair_iterations.py runs
+// the cell-level dependency simulation); 25 are given up on the right so that the group pitch is a multiple of 3.
+constexpr int kGroupStrips = 4;
+constexpr int kGroupIn = (kGroupStrips - 1) * kStripOut + kStripIn;     // 705
+constexpr int kGroupHaloL = 17, kGroupHaloR = 25;
+constexpr int kGroupOut = kGroupIn - kGroupHaloL - kGroupHaloR;         // 663
+// A ring row is a group row and a few cells that take the columns a producer does not own.
+constexpr int kRingPitch = kGroupIn + 7;                                 // 712 doubles
 
 /* The switches that steer the iteration dispatch: (member, environment variable, default).  README has the table of meanings;
  * A/B runs and tests set them, nobody else. */
@@ -45,7 +56,10 @@ constexpr int kStripOut = kStripIn - kHaloL - kHaloR;    // 171 columns stored p
   X(rot, "WDPM_ROT", 1)                 /* 0: shares and measurements by blockIdx % 8, as in round 4 (A/B) */         \
   X(prio, "WDPM_PRIO", 1)               /* 0: no priorities (A/B, tests) */                                           \
   X(clamp, "WDPM_CLAMP", 1)             /* 0: the unclamped neighbour step everywhere (A/B, tests) */                 \
-  X(plain, "WDPM_PLAIN", 1)             /* 0: gated variants only (A/B, tests) */
+  X(plain, "WDPM_PLAIN", 1)             /* 0: gated variants only (A/B, tests) */                                     \
+  X(iter2, "WDPM_ITER2", 1)             /* two iterations per marching launch: 0 never, 1 where it pays, 2 wherever it fits */ \
+  X(iter2_ring, "WDPM_ITER2_RING", 0)   /* >= 6: group rows in its LDS ring (tuning); 0 = automatic */                \
+  X(iter2_prio, "WDPM_ITER2_PRIO", 1)   /* 0: its producers keep the default issue priority (A/B) */
 struct Switches {
 #define WDPM_SWITCH_MEMBER(member, name, dflt) int member = dflt;
   WDPM_SWITCHES(WDPM_SWITCH_MEMBER)
@@ -130,6 +144,9 @@ struct LaunchPlan {
   int pair, ipx;           /* xcd_rebalance_kernel's arguments */
   bool rot;                /* with the table: shares and measurements by physical XCD (BalanceArgs::rot) */
   int ledger_sw;           /* the switches this launch hands the kernel, for the launch ledger (include/wdpm.h: WDPM_LEDGER_*) */
+  int iter2;               /* plan_iter2: the launch runs two iterations (Iter2Args); nstrips then counts GROUPS of four strips and
+                            * nitems workgroups, one per group and chunk */
+  int ring_rows, iter2_prio;   /* Iter2Args */
 };
 
 /* One list per kernel family of the instantiations the library contains: wdpm_fused.hip instantiates the kernels, registers the
@@ -411,6 +428,77 @@ inline LaunchPlan plan_iteration(const LaunchRequest &q, const DeviceFacts &dev,
   const bool dem16 = dem32 && q.codes16 && wdpm_dem16_pays((long long)wrows * q.g.ncp, q.force_codes);
   const int targs[6] = {m2, !fast, dem16 ? 2 : dem32 ? 1 : 0, flush, fold_md, plain};
   for (int k = 0; k < 6; k++) p.targs[k] = targs[k];
+  return p;
+}
+
+/* groups of kGroupOut stored columns that cover ncp padded columns */
+inline int wdpm_groups(const int ncp) {
+  const int first = kGroupIn - kGroupHaloR;                // columns the first group covers (it stores from column 0)
+  return ncp <= first ? 1 : (ncp - first + kGroupOut - 1) / kGroupOut + 1;
+}
+
+/* Launches from which two iterations per launch pay (WDPM_ITER2=1), in cells.  The sweep over the shapes that matter, forced against
+ * the parent's single launches (profiles/r06/ab_shapes.txt, A/A spread 0.1 - 0.4 %): 4096^2 -1.0 %, the 2049 x 16384 add slab +9.2 %,
+ * 8192^2 +3.7 %, 16384^2 +3.9 %.  The threshold sits just under the smallest shape measured ahead. */
+constexpr long long kIter2MinCells = 30000000LL;
+
+/* Two iterations in ONE marching launch (wdpm_fused.hip::iter2_march), offered (LaunchPlan::iter2 == 1) or not (== 0: the caller
+ * launches plan_iteration()'s plan).  `iterations_left`: launches like this one the caller still has to queue, this one included -
+ * neither the block's first (flush) nor its last where that folds the max diff.  Offered only to the gate-free add / subtract
+ * instantiations that stream the DEM as codes, on whole-slab steady launches of two waves per SIMD that keep no dry-tile flags and
+ * have no chunk height of the caller's. */
+inline LaunchPlan plan_iter2(const LaunchRequest &q, const DeviceFacts &dev, const Switches &sw, const int iterations_left) {
+  LaunchPlan p = plan_iteration(q, dev, sw);
+  p.iter2 = 0;
+  if (p.error || sw.iter2 == 0 || iterations_left < 2) return p;
+  if (p.family != WDPM_FAMILY_MARCHING || q.module == 2 || !p.steady || (p.wpb != 8 && sw.iter2 != 2)) return p;
+  if (p.targs[0] != 0 || p.targs[1] != 0 || p.targs[2] == 0 || p.targs[3] != 0 || p.targs[4] != 0 || p.targs[5] != 1) return p;
+  if (q.A0 != 0 || q.out_last != q.g.rows - 1 || q.chunk_rows >= 3 || sw.chunk_rows >= 3 || p.tiles_fit || q.leave_cus > 0) return p;
+  if (sw.iter2 != 2 && (long long)q.g.rows * q.g.ncp < kIter2MinCells) return p;
+  // LDS: the eight staging slices and the words of the single loop (static), the ring and its dump row (dynamic).  As deep a ring
+  // as fits up to six row triples; one workgroup per CU needs more than half of the CU's LDS taken
+  const int fixed = 8 * 3 * kStripIn * (int)sizeof(double) + 256;
+  const int row_bytes = kRingPitch * (int)sizeof(double);
+  int ring = ((dev.lds_per_cu - fixed) / row_bytes - 1) / 3 * 3;
+  if (ring > 18) ring = 18;
+  if (sw.iter2_ring >= 6 && sw.iter2_ring / 3 * 3 < ring) ring = sw.iter2_ring / 3 * 3;
+  if (ring < 6) return p;
+  int lds = (ring + 1) * row_bytes;
+  const int half = dev.lds_per_cu / 2 + 1024 - fixed;
+  if (lds < half) lds = half;
+  const int rows = q.g.rows, ngroups = wdpm_groups(q.g.ncp);
+  // one workgroup per CU, all resident together: chunks twice as tall as the single launch's
+  int H = wdpm_chunk_rows(rows, ngroups, 0, dev.cus, 0);
+  if (H < 6) H = 6;                                        // (forced on a small raster: fewer workgroups than CUs)
+  int nchunks = (q.out_last - 1 + H - 1) / H;
+  if (nchunks < 1) nchunks = 1;
+  p.iter2 = 1;
+  p.ring_rows = ring;
+  p.iter2_prio = sw.iter2_prio != 0 ? 1 : 0;
+  p.lds = (unsigned)lds;
+  p.nstrips = ngroups;
+  p.prio = 0;
+  p.keep_tiles = false;
+  // chunk heights by what each XCD delivers, as in the single launch: a table row per group
+  const bool bal_forced = q.balance_mode == 2;
+  p.balance = p.table = p.measure_equal = false;
+  p.pair = 0;
+  if (q.balance_mode && nchunks >= 2) {
+    p.balance = true;
+    const int T = (q.out_last - 1 + 2) / 3, nc = dev.cus / ngroups;
+    bool can_table = H >= (bal_forced ? 6 : 12) && (nchunks + 1) * ngroups <= q.balance_capacity;
+    if (can_table && !bal_forced && nc > nchunks && T / nc >= 4 && (nc + 1) * ngroups <= q.balance_capacity) nchunks = nc;
+    p.table = can_table;
+    p.rot = sw.rot != 0;
+    p.measure_equal = !can_table && H >= 12;
+  }
+  p.nchunks = nchunks;
+  p.nitems = ngroups * nchunks;
+  p.grid = ((unsigned)p.nitems + 7) / 8 * 8;
+  p.ipx = (int)(p.grid / 8);
+  p.block = 512;
+  p.H = H;
+  p.ledger_sw = (p.no_clamp ? WDPM_LEDGER_NO_CLAMP : 0) | (p.iter2_prio ? WDPM_LEDGER_PRIO : 0) | (p.table ? WDPM_LEDGER_BALANCE : 0) | WDPM_LEDGER_ITER2;
   return p;
 }
 

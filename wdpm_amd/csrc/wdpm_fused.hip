@@ -323,6 +323,326 @@ constexpr int fused_built_for() {
   return (MODULE == 2 && SZ_SAFE) ? 1 : (MODULE != 2 && DEM32 != 0 && !MD && !SZ_SAFE) ? WDPM_FUSED_CODES_WAVES : WDPM_FUSED_MIN_WAVES;
 }
 
+/* ---------------------------------------------------------------------------------------------
+ * Two iterations per launch (Iter2Args; geometry: wdpm_dispatch.h::plan_iter2).  A second marching loop of the gate-free add /
+ * subtract instantiations that stream the DEM as codes, chosen by a kernel argument.
+ *
+ * A workgroup takes a GROUP of four neighbouring strips (kGroupIn = 705 columns in) and one chunk of rows.  Waves 0 - 3 are
+ * producers: today's loop on iteration k, strip j = wave, from one row triple above the chunk (sh) to two below it - but the rows a
+ * step finishes go into a ring of group rows in LDS instead of to memory, each producer depositing its exact columns (the group's
+ * outer producers also their halo, so that every ring cell holds a finite value).  Waves 4 - 7 are consumers: today's loop on iteration
+ * k + 1, strip j = wave - 4, whose water rows come out of the ring - all 192 columns of a consumer's strip lie in the ring row,
+ * exact except for the group's outer 8 / 13 columns - and whose DEM codes come from memory as before (an L2 hit behind the
+ * producer).  The group stores the 663 columns that are exact after both iterations (kGroupOut: all but 17 on the left and 25 on
+ * the right, wdpm_dispatch.h); groups tile the raster.
+ *
+ * Hand-over: one word per wave in LDS (hand[]).  A producer's word counts the steps whose rows it has deposited, a consumer's the
+ * row triples it has taken out of the ring.  Consumer triple t (rows 3t .. 3t+2 of the chunk) is complete after producer step
+ * t + 2 + sh/3 of its own producer and of its neighbours; a producer's step n overwrites what consumer triple n - sh/3 - R/3 - 1
+ * read.  A wave's LDS operations are carried out in order, so a word written behind the data (read behind the taking) needs no wait
+ * of its own.  Waits are s_sleep polls and BOUNDED: a wave that runs out sets Iter2Args::err, stops waiting for the rest of
+ * the launch (results are then wrong, the host fails the call) and the launch ends.  Producers wait for consumers only when the
+ * ring is full and consumers for producers only when it is empty, consumers always behind: no cycle.  Roles follow from the
+ * wave index alone; nothing depends on which SIMD a wave sits on.
+ * --------------------------------------------------------------------------------------------- */
+constexpr int kIter2Polls = 1 << 21;     /* of ~0.15 us each: a quarter of a second, against steps of a microsecond */
+
+template <int DEM32>
+__device__ __forceinline__ void iter2_march(const double *__restrict__ win, double *__restrict__ wout, const DemCode &code, const SlabGeom &g,
+                                            const int H, const int out_last, const int no_clamp, const BalanceArgs &bal, const Iter2Args &i2,
+                                            const int vb, const int wave, const int lane, const int share, const int xcc_phys,
+                                            double *const stage_lds) {
+  extern __shared__ double i2_ring[];                     // (ring_rows + 1) x kRingPitch
+  __shared__ int hand[8];
+  if (threadIdx.x < 8) hand[threadIdx.x] = 0;
+  __syncthreads();
+  if (vb >= i2.ngroups * i2.nchunks) return;              // workgroup-uniform
+#ifdef WDPM_WAVE_TIMES
+  const unsigned long long wt0 = wall_clock64();
+#endif
+  const int grp = vb % i2.ngroups, chunk = vb / i2.ngroups;
+  const bool producer = wave < 4;                         // wave-uniform (SGPRs), as everything derived from it
+  const int j = wave & 3;
+  const int c0 = kGroupOut * grp + kStripOut * j;
+  int A = H * chunk, A_next = A + H;
+  if (bal.table) {                                        // row boundaries per group (see the single loop): all four strips share them
+    A = bal.table[chunk * i2.ngroups + grp];
+    A_next = bal.table[(chunk + 1) * i2.ngroups + grp];
+    A = A < 0 ? 0 : (A > g.rows ? g.rows : A);
+    A = A / 3 * 3;
+    const int h = A_next - A;
+    A_next = A + (h < 3 ? 3 : (h > 30000 ? 30000 : h)) / 3 * 3;
+  }
+  const unsigned long long bal_t0 = bal.acc ? wall_clock64() : 0;
+  const int sh = A >= 3 ? 3 : 0;                          // the producer starts a row triple above the chunk (none above the raster)
+  const int lag = 2 + sh / 3;                             // consumer triple t needs producer step t + lag
+  const int NC = (A_next - A) / 3 + 2, NP = NC + lag;
+  const int As = producer ? A - sh : A;                   // this wave's first row ...
+  const int nsteps = producer ? NP : NC;                  // ... and its steps
+  const int R = i2.ring_rows;
+  const int or_lo = A == 0 ? 0 : A + 2;
+  int or_hi = A_next + 1;
+  if (or_hi > out_last) or_hi = out_last;
+  int deep = !no_clamp ? 0 : 8;
+  const int colb = c0 + 3 * lane;
+  // consumer: the strip-relative columns [lo, hi] it stores (see the single loop); a strip beyond the raster stores nothing
+  unsigned soff[3];
+  int scol[3];
+  bool store_any;
+  {
+    const int lo = j == 0 ? (grp == 0 ? 0 : kGroupHaloL) : kHaloL;
+    int hi = kStripIn - 1 - (j == 3 ? kGroupHaloR : kHaloR);
+    if (hi > g.ncp - 1 - c0) hi = g.ncp - 1 - c0;
+    store_any = hi >= lo;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      int c = lo + 64 * k + lane < hi ? lo + 64 * k + lane : hi;
+      c = store_any ? c : 0;
+      scol[k] = c;
+      soff[k] = 8u * (unsigned)c;
+    }
+  }
+  // producer: where its columns go in a ring row - its exact ones (and the group's outer halos); the others to the row's dump cells
+  int dcol[3];
+#pragma unroll
+  for (int jj = 0; jj < 3; jj++) {
+    const int cs = 3 * lane + jj;
+    const bool own = cs >= (j == 0 ? 0 : kHaloL) && cs <= (j == 3 ? kStripIn - 1 : kStripIn - 1 - kHaloR);
+    dcol[jj] = own ? kStripOut * j + cs : kGroupIn + jj;
+  }
+  const int rcol = kStripOut * j + 3 * lane;              // consumer: its first column in a ring row
+  volatile int *const hand_v = hand;
+  const int nb_lo = j > 0 ? j - 1 : 0, nb_hi = j < 3 ? j + 1 : 3;
+  bool broken = false;
+  // the smallest count of the (up to) three waves of the other role this one exchanges columns with, once it is >= need - or at once
+  // where need <= 0
+  auto await = [&](const int base, const int need) -> int {
+    int m = 0, polls = 0;
+    for (;;) {
+      const int a = hand_v[base + nb_lo], b = hand_v[base + j], c = hand_v[base + nb_hi];
+      m = a < b ? a : b;
+      m = m < c ? m : c;
+      m = __builtin_amdgcn_readfirstlane(m);
+      if (m >= need || broken) break;
+      if (++polls > kIter2Polls) {
+        broken = true;
+        if (lane == 0) *i2.err = 1u;
+        break;
+      }
+      __builtin_amdgcn_s_sleep(2);
+    }
+    asm volatile("" ::: "memory");
+    return m;
+  };
+  const size_t pitch = (size_t)g.ncp;
+  char *const dump = reinterpret_cast<char *>(wout + (size_t)g.rows * pitch);
+  const bool edge = (As + 3 * (nsteps + 1) > g.rows);
+  double W[7][3], D[7][3];
+#pragma unroll
+  for (int k = 0; k < 7; k++)
+#pragma unroll
+    for (int jj = 0; jj < 3; jj++) { W[k][jj] = 0.0; D[k][jj] = WDPM_INF; }
+  bool cdr[5];
+#pragma unroll
+  for (int k = 0; k < 5; k++) cdr[k] = false;
+  DrainState ds;
+  ds.td = 0.0;
+  ds.hit = false;
+
+  auto march = [&](auto edge_tag, auto role_tag) {
+    constexpr bool EDGE = decltype(edge_tag)::value;
+    constexpr bool PRODUCER = decltype(role_tag)::value;
+    const int voff0 = 8 * (colb < g.ncp ? colb : g.ncp - 1);
+    const int qoff0 = voff0 / 2, hoff0 = voff0 / 4, goff0 = 4 * ((voff0 / 8) / kDemGroup);
+    // as the single loop's prefetch: inline-asm loads a step ahead of their use; the water rows only for a producer
+    auto prefetch = [&](Prefetched &P, const int r0) {
+#pragma unroll
+      for (int i = 0; i < 3; i++) {
+        int r = r0 + i;
+        if (EDGE) r = r < g.rows ? r : g.rows - 1;
+        const double *bw = win + (size_t)r * pitch;
+        const int *bq = code.q + (size_t)r * pitch;
+        const unsigned short *bh = code.h + (size_t)r * pitch;
+        const int *bg = code.gb + (size_t)r * code.ngroups;
+        if (PRODUCER) {
+          asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(P.NW[i][0]) : "v"(voff0), "s"(bw) : "memory");
+          asm volatile("global_load_dwordx2 %0, %1, %2 offset:8" : "=v"(P.NW[i][1]) : "v"(voff0), "s"(bw) : "memory");
+          asm volatile("global_load_dwordx2 %0, %1, %2 offset:16" : "=v"(P.NW[i][2]) : "v"(voff0), "s"(bw) : "memory");
+        }
+        if (DEM32 == 2) {
+          asm volatile("global_load_ushort %0, %1, %2" : "=v"(P.qh[i][0]) : "v"(hoff0), "s"(bh) : "memory");
+          asm volatile("global_load_ushort %0, %1, %2 offset:2" : "=v"(P.qh[i][1]) : "v"(hoff0), "s"(bh) : "memory");
+          asm volatile("global_load_ushort %0, %1, %2 offset:4" : "=v"(P.qh[i][2]) : "v"(hoff0), "s"(bh) : "memory");
+          asm volatile("global_load_dword %0, %1, %2" : "=v"(P.gbv[i]) : "v"(goff0), "s"(bg) : "memory");
+        } else {
+          asm volatile("global_load_dwordx3 %0, %1, %2" : "=v"(P.qi[i]) : "v"(qoff0), "s"(bq) : "memory");
+        }
+      }
+    };
+#define WDPM_I2_W "+v"(P.NW[0][0]), "+v"(P.NW[0][1]), "+v"(P.NW[0][2]), "+v"(P.NW[1][0]), "+v"(P.NW[1][1]), \
+                  "+v"(P.NW[1][2]), "+v"(P.NW[2][0]), "+v"(P.NW[2][1]), "+v"(P.NW[2][2])
+#define WDPM_I2_H "+v"(P.qh[0][0]), "+v"(P.qh[0][1]), "+v"(P.qh[0][2]), "+v"(P.qh[1][0]), "+v"(P.qh[1][1]), "+v"(P.qh[1][2]), \
+                  "+v"(P.qh[2][0]), "+v"(P.qh[2][1]), "+v"(P.qh[2][2]), "+v"(P.gbv[0]), "+v"(P.gbv[1]), "+v"(P.gbv[2])
+#define WDPM_I2_Q "+v"(P.qi[0]), "+v"(P.qi[1]), "+v"(P.qi[2])
+    // YOUNGER: a producer issues no memory operation behind its loads, a consumer its nine stores
+#define WDPM_I2_WAIT(YOUNGER)                                                                               \
+  do {                                                                                                      \
+    if (PRODUCER && DEM32 == 2) asm volatile("s_waitcnt vmcnt(0)" : WDPM_I2_W, WDPM_I2_H : : "memory");     \
+    else if (PRODUCER) asm volatile("s_waitcnt vmcnt(0)" : WDPM_I2_W, WDPM_I2_Q : : "memory");              \
+    else if (DEM32 == 2) asm volatile("s_waitcnt vmcnt(" #YOUNGER ")" : WDPM_I2_H : : "memory");            \
+    else asm volatile("s_waitcnt vmcnt(" #YOUNGER ")" : WDPM_I2_Q : : "memory");                            \
+  } while (0)
+
+    int put_slot = 0;                                      // producer: ring row of chunk row rr, rr = 0, 1, 2 ... as they are deposited
+    int take_slot = 0;                                     // ring row of the next triple to take (triples never straddle the ring's end)
+    // consumer: row triple t out of the ring, once the producers have deposited it (the last trip asks for one more than there is and drops it)
+    auto take = [&](Prefetched &P, const int t) {
+      const int need = t + lag + 1;
+      await(0, need < NP ? need : NP);
+      const double *row = i2_ring + (size_t)take_slot * kRingPitch + rcol;
+      take_slot = take_slot + 3 >= R ? 0 : take_slot + 3;
+#pragma unroll
+      for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int jj = 0; jj < 3; jj++) P.NW[i][jj] = row[i * kRingPitch + jj];
+      asm volatile("" ::: "memory");
+      hand_v[4 + j] = t + 1;                              // carried out behind the reads
+    };
+    double staged[3][3];
+    auto read_staged = [&]() {
+#pragma unroll
+      for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int k = 0; k < 3; k++) staged[i][k] = stage_lds[i * kStripIn + scol[k]];
+    };
+    auto write_staged = [&](const int rb) {
+#pragma unroll
+      for (int i = 0; i < 3; i++) {
+        const int r = rb + i;
+        const bool row_ok = r >= or_lo && r <= or_hi && store_any;   // wave-uniform
+        char *const orow = row_ok ? reinterpret_cast<char *>(wout + (size_t)r * pitch + c0) : dump;
+#pragma unroll
+        for (int k = 0; k < 3; k++) asm volatile("global_store_dwordx2 %0, %1, %2" : : "v"(soff[k]), "v"(staged[i][k]), "s"(orow) : "memory");
+      }
+      __builtin_amdgcn_wave_barrier();
+    };
+
+    auto step = [&](const int n, Prefetched &P, auto nstages_tag) {
+      constexpr int NSTAGES = decltype(nstages_tag)::value;
+      if (!PRODUCER) read_staged();
+#pragma unroll
+      for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int jj = 0; jj < 3; jj++) {
+          W[4 + i][jj] = P.NW[i][jj];
+          if (DEM32 == 2) D[4 + i][jj] = dem16_decode_nan(P.qh[i][jj], P.gbv[i], code.k0, code.D, code.rD);
+          else D[4 + i][jj] = dem32_decode_nan(P.qi[i][jj], code.k0, code.D, code.rD);
+        }
+      if (EDGE) {
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+          const bool row_ok = As + 3 * n + i < g.rows;
+#pragma unroll
+          for (int jj = 0; jj < 3; jj++) {
+            const bool ok = row_ok & (colb + jj < g.ncp);
+            W[4 + i][jj] = ok ? W[4 + i][jj] : 0.0;
+            D[4 + i][jj] = ok ? D[4 + i][jj] : WDPM_INF;
+          }
+        }
+      }
+      {
+        auto hi = [](const double v) { return (unsigned)__double2hiint(v); };
+        auto max3 = [](const unsigned a, const unsigned b, const unsigned c) { const unsigned m = a > b ? a : b; return m > c ? m : c; };
+        unsigned hm = max3(hi(W[4][0]), hi(W[4][1]), hi(W[4][2]));
+        hm = max3(hm, hi(W[5][0]), hi(W[5][1]));
+        hm = max3(hm, hi(W[5][2]), hi(W[6][0]));
+        hm = max3(hm, hi(W[6][1]), hi(W[6][2]));
+        deep = (deep & 8) | ((deep & 3) << 1) | (__ballot(hm > 0x40080000u) != 0 ? 1 : 0);
+      }
+      if (!PRODUCER) take(P, n + 1);
+      prefetch(P, As + 3 * (n + 1));
+      if (!PRODUCER) write_staged(A + 3 * (n - 1) - 4);
+
+      const int rbase = As + 3 * n - 4;
+      if (deep) three_stages<0, false, NSTAGES, 1>(W, D, rbase, g.dr, cdr, ds);
+      else three_stages<0, false, NSTAGES, 1 | 2>(W, D, rbase, g.dr, cdr, ds);
+
+      if (PRODUCER) {
+        // rows rbase .. rbase + 2 are final: into the ring, once the consumers have taken what lies there (chunk rows < 0: nobody
+        // reads them, the dump row)
+        const int rr0 = 3 * n - 4 - sh;
+        const int taken = await(4, n - sh / 3 - R / 3);
+        if (i2.prio) {
+          const int ahead = n - lag - taken;              // row triples deposited and not taken
+          if (ahead <= 1) __builtin_amdgcn_s_setprio(3);  // the consumers are about to run dry: this wave first
+          else if (ahead >= R / 3 - 1) __builtin_amdgcn_s_setprio(0);
+          else __builtin_amdgcn_s_setprio(1);
+        }
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+          double *const row = i2_ring + (size_t)(rr0 + i >= 0 ? put_slot : R) * kRingPitch;
+          if (rr0 + i >= 0) put_slot = put_slot + 1 >= R ? 0 : put_slot + 1;
+#pragma unroll
+          for (int jj = 0; jj < 3; jj++) row[dcol[jj]] = W[i][jj];
+        }
+        asm volatile("" ::: "memory");
+        hand_v[j] = n + 1;                                // carried out behind the data
+      } else {
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+          for (int jj = 0; jj < 3; jj++) stage_lds[i * kStripIn + 3 * lane + jj] = W[i][jj];
+        __builtin_amdgcn_wave_barrier();
+      }
+      WDPM_I2_WAIT(9);
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+#pragma unroll
+        for (int jj = 0; jj < 3; jj++) { W[k][jj] = W[k + 3][jj]; D[k][jj] = D[k + 3][jj]; }
+    };
+
+    Prefetched P;
+    if (!PRODUCER) take(P, 0);
+    prefetch(P, As);
+    WDPM_I2_WAIT(0);
+    step(0, P, std::integral_constant<int, 1>{});
+    step(1, P, std::integral_constant<int, 2>{});
+    for (int n = 2; n < nsteps; n++) step(n, P, std::integral_constant<int, 3>{});
+    if (!PRODUCER) {
+      read_staged();
+      write_staged(A + 3 * (nsteps - 1) - 4);
+    }
+#undef WDPM_I2_WAIT
+#undef WDPM_I2_Q
+#undef WDPM_I2_H
+#undef WDPM_I2_W
+  };
+  if (producer) {
+    if (edge) march(std::true_type{}, std::true_type{});
+    else march(std::false_type{}, std::true_type{});
+  } else {
+    if (edge) march(std::true_type{}, std::false_type{});
+    else march(std::false_type{}, std::false_type{});
+  }
+  if (bal.acc && lane == 0) {
+    const int x = chunk == i2.nchunks - 1 ? 8 : chunk == 0 ? 9 : (bal.rot ? xcc_phys : (int)(blockIdx.x & 7));
+    if (!bal.rot || share == xcc_phys) {
+      atomicAdd(bal.acc + x, wall_clock64() - bal_t0);
+      atomicAdd(bal.acc + kBalClasses + x, 1ull);
+    }
+  }
+#ifdef WDPM_WAVE_TIMES
+  const int item = vb * 8 + wave;
+  if (lane == 0 && item < 8192) {
+    __builtin_amdgcn_s_waitcnt(0);
+    g_wave_times[4 * item] = wt0;
+    g_wave_times[4 * item + 1] = wall_clock64();
+    g_wave_times[4 * item + 2] = __builtin_amdgcn_s_getreg((31 << 11) | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | 20) << 32);
+    g_wave_times[4 * item + 3] = ((unsigned long long)(4 * grp + j + (producer ? 0 : 0x4000)) << 48) | ((unsigned long long)(nsteps & 0xffff) << 32) | (unsigned)chunk;
+  }
+#endif
+}
+
 /* DEM32: 0 = the fp64 DEM, 1 = verified 32-bit codes, 2 = those as 16-bit offsets + group bases (wdpm_kernels.h::DemCode) */
 template <int MODULE, bool SZ_SAFE, int DEM32, bool FLUSH = false, bool MD = false, bool PLAIN = false>
 __global__ void __launch_bounds__((fused_built_for<MODULE, SZ_SAFE, DEM32, MD>() >= 2 ? 512 : 256), (fused_built_for<MODULE, SZ_SAFE, DEM32, MD>()))
@@ -330,7 +650,7 @@ fused_iteration_kernel(const double *__restrict__ win, double *__restrict__ wout
                        const double *__restrict__ dem, const DemCode code, const SlabGeom g, const int nstrips,
                        const int nitems, const int H, const int A0, const int out_last,
                        double *__restrict__ totaldrain, const double thres, const int drain_owed,
-                       const TileFlags tf, const MaxDiffArgs md, const int prio, const int no_clamp, const BalanceArgs bal) {
+                       const TileFlags tf, const MaxDiffArgs md, const int prio, const int no_clamp, const BalanceArgs bal, const Iter2Args i2) {
   const int lane = threadIdx.x & 63;
   // Workgroups are dealt round-robin over the 8 XCDs (b and b+8 share an L2; placement is only a
   // speed matter, never correctness): give each XCD a contiguous run of work items so that the
@@ -381,6 +701,13 @@ fused_iteration_kernel(const double *__restrict__ win, double *__restrict__ wout
     my_word = 2 * simd + (seat & 1);
   }
   const int use_prio = paired ? 1 : 0;
+  __shared__ double stage_all[8][3 * kStripIn];          // 4.5 KiB per wave, private to the wave
+  if constexpr (MODULE == 0 && !SZ_SAFE && DEM32 != 0 && !FLUSH && !MD && PLAIN) {
+    if (i2.on) {                                         // the same in every wave of the launch: two iterations (iter2_march)
+      iter2_march<DEM32>(win, wout, code, g, H, out_last, no_clamp, bal, i2, vb, wave, lane, share, xcc_phys, stage_all[wave & 3]);
+      return;
+    }
+  }
   if (item >= nitems) return;                       // wave-uniform
 #ifdef WDPM_WAVE_TIMES
   const unsigned long long wt0 = wall_clock64();
@@ -461,7 +788,6 @@ fused_iteration_kernel(const double *__restrict__ win, double *__restrict__ wout
 #pragma unroll
     for (int k = 0; k < 3; k++) { scol[k] = lo + 64 * k + lane < hi ? lo + 64 * k + lane : hi; soff[k] = 8u * (unsigned)scol[k]; }
   }
-  __shared__ double stage_all[8][3 * kStripIn];          // 4.5 KiB per wave, private to the wave
   double *const stage_lds = stage_all[wave];
   volatile int *const my_progress = progress_all + my_word;
   volatile int *const partner_progress = progress_all + (my_word ^ 1);
@@ -1680,9 +2006,11 @@ hipError_t wdpm_launch_iteration(const LaunchRequest &q, const LaunchPlan &p, co
   if (p.fold_md) tf = TileFlags{nullptr, nullptr, 0, nullptr, p.nchunks};   /* every wave must look at its block: no skipping in this launch */
   if (p.fold_md && b.tiles) b.tiles->maintained = 0;
   const BalanceArgs ba = p.balance ? balance_step(b.bal, q, p, b.stream) : BalanceArgs{nullptr, nullptr, nullptr, 0};
+  if (p.iter2 && !b.iter2_err) return hipErrorInvalidValue;
+  const Iter2Args i2{p.iter2, p.nstrips, p.nchunks, p.ring_rows, p.iter2_prio, b.iter2_err};
   wdpm_ledger_count(*kMarchingTable[at].slot, p.ledger_sw);
   hipLaunchKernelGGL(kMarchingTable[at].fn, dim3(p.grid), dim3(p.block), p.lds, b.stream, b.w_in, b.w_out, b.dem, *b.code, q.g, p.nstrips, p.nitems,
-                     p.H, q.A0, q.out_last, b.totaldrain, b.thres, q.module == 2 ? b.drain_owed : 0, tf, mda, p.prio, p.no_clamp, ba);
+                     p.H, q.A0, q.out_last, b.totaldrain, b.thres, q.module == 2 ? b.drain_owed : 0, tf, mda, p.prio, p.no_clamp, ba, i2);
   return hipGetLastError();
 }
 

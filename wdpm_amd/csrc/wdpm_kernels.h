@@ -117,6 +117,17 @@ struct BalanceArgs {             /* kernel argument */
   unsigned long long *rot;
   int parity;
 };
+/* Two iterations in one marching launch (wdpm_fused.hip::iter2_march): the eight waves of a workgroup are four
+ * producers (iteration k on four neighbouring strips) and four consumers (iteration k + 1 on the same strips and rows), the
+ * producers' exact rows pass through a ring of group rows in LDS and iteration k's raster never reaches memory.  on == 0: the
+ * launch is an ordinary one. */
+struct Iter2Args {               /* kernel argument */
+  int on;
+  int ngroups, nchunks;          /* groups of four strips across the raster, chunks down it: ngroups * nchunks workgroups work */
+  int ring_rows;                 /* group rows the ring holds (a multiple of 3; one more row behind them takes what nobody reads) */
+  int prio;                      /* 1: a producer's issue priority follows how far ahead of its consumers it is */
+  unsigned *err;                 /* set to 1 by a wave whose bounded wait for another wave ran out (the host fails the call) */
+};
 struct XcdBalance {              /* host side, per context */
   int *table;                    /* device */
   unsigned long long *acc;       /* device: 2 * kBalClasses cells, and two more behind them: BalanceArgs::rot */
@@ -153,6 +164,7 @@ struct IterationBuffers {
   TilePlan *tiles;       /* LaunchRequest::tiles_offered */
   const MaxDiffArgs *md; /* LaunchRequest::max_diff */
   XcdBalance *bal;       /* LaunchRequest::balance_mode != 0 */
+  unsigned *iter2_err;   /* Iter2Args::err (launches of plan_iter2) */
 };
 const DeviceFacts *wdpm_device_facts();      /* of the current device; nullptr: see wdpm_fused.hip */
 hipError_t wdpm_launch_iteration(const LaunchRequest &q, const LaunchPlan &p, const IterationBuffers &b);
