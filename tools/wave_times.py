@@ -57,6 +57,24 @@ with lib.context(module=module, nrows=(R + 2 * row0 if row0 else R), ncols=C, mi
             if m.any():
                 print("   XCD %d: %4d waves, median duration %.1f, mean %.1f, last end %.1f us; steps per wave mean %.2f (%s); us per step %.3f" %
                       (x, m.sum(), np.median(dur[m]), dur[m].mean(), e[m].max(), nst[m].mean(), dict(zip(*np.unique(nst[m], return_counts=True))), dur[m].sum() / nst[m].sum()))
+        # two-iteration launches: what the waves spent asleep in await(), by role (a producer waits for a full ring, a consumer for an
+        # empty one) and by where in the chunk (start: steps 0 - 3, end: the last four, steady between)
+        if hasattr(raw, "wdpm_debug_wave_waits") and (strip >= 0x4000).any():
+            wb = np.zeros((8192, 4), dtype=np.uint64)
+            assert raw.wdpm_debug_wave_waits(wb.ctypes.data_as(ctypes.c_void_p), 8192) == 0
+            wv = wb[buf[:, 1] > 0]
+            lo32 = np.uint64(0xffffffff); s32 = np.uint64(32)
+            polls = np.stack([wv[:, 0] & lo32, wv[:, 0] >> s32, wv[:, 1] & lo32], 1).astype(np.int64)
+            waits = (wv[:, 1] >> s32).astype(np.int64)
+            ticks = np.stack([wv[:, 2] & lo32, wv[:, 2] >> s32, wv[:, 3] & lo32], 1).astype(np.int64) / 100.0    # us
+            for role, m in (("producers (ring full)", (strip < 0x4000) & (nst > 0)), ("consumers (ring empty)", strip >= 0x4000)):
+                if not m.any():
+                    continue
+                life = dur[m].sum()
+                print("   await, %-22s %4d waves: asleep %.2f %% of wave time (start %.2f %%, steady %.2f %%, end %.2f %%); per wave: "
+                      "%.1f awaits that polled of %.0f steps, %.0f polls, asleep median %.1f us, p90 %.1f, max %.1f us" %
+                      (role + ":", m.sum(), 100 * ticks[m].sum() / life, *(100 * ticks[m].sum(0) / life), waits[m].mean(), nst[m].mean(),
+                       polls[m].sum(1).mean(), np.median(ticks[m].sum(1)), np.percentile(ticks[m].sum(1), 90), ticks[m].sum(1).max()))
         print("   balance:", c.balance_info())
         # logical XCD of a work item (the kernel's remap: item -> workgroup vb -> XCD share vb // (grid / 8), grid a multiple of 8) against
         # the physical one it ran on: a constant difference = the dispatcher's round-robin started at another XCD in this launch

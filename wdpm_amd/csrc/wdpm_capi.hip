@@ -337,7 +337,7 @@ int wdpm_create(wdpm_ctx **out, const wdpm_params *p) {
   x->drain_owed = false;
   x->flush_thres = -__builtin_inf();
   x->d_scal = nullptr; x->d_bits = nullptr; x->h_pin = nullptr; x->d_stat = nullptr; x->h_iter2_err = x->d_iter2_err = nullptr;
-  x->d_dem32 = nullptr; x->code = DemCode{nullptr, 0.0, 1.0, 1.0, 0, nullptr, nullptr, 0}; x->dem32_encodable = false; x->dem_bounded = false;
+  x->d_dem32 = nullptr; x->code = DemCode{nullptr, 0.0, 1.0, 1.0, 0.0, 0, nullptr, nullptr, 0}; x->dem32_encodable = false; x->dem_bounded = false;
   x->d_dem16 = nullptr; x->d_gbase = nullptr; x->dem16_encodable = false; x->dem16_wanted = true;
   x->graph_mode = -1; x->graph_launches = 0;
   x->d_sum_approx = nullptr; x->d_sum_i = nullptr; x->d_sum_k = nullptr; x->d_sum_flag = nullptr;
@@ -527,7 +527,7 @@ static int encode_dem(wdpm_ctx *x) {
   /* every level starts from "not encodable": a DEM uploaded over an earlier one inherits nothing (a smooth DEM, then a
    * rough one that passes only the 32-bit check, left dem16_encodable set and d_dem16 holding truncated offsets) */
   x->dem32_encodable = false; x->dem16_encodable = false; x->dem_bounded = false; x->dem16_wanted = true;
-  x->code = DemCode{nullptr, 0.0, 1.0, 1.0, 0, nullptr, nullptr, 0};
+  x->code = DemCode{nullptr, 0.0, 1.0, 1.0, 0.0, 0, nullptr, nullptr, 0};
   HIP_TRY(wdpm_launch_dem_min(x->d_dem, x->cells, x->d_bits, x->stream));
   HIP_TRY(hipMemcpyAsync(x->h_pin, x->d_bits, 2 * sizeof(double), hipMemcpyDeviceToHost, x->stream));
   if (wdpm_stream_sync(x, x->stream)) return 1;
@@ -542,15 +542,18 @@ static int encode_dem(wdpm_ctx *x) {
   static const double p10[7] = {1.0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6};
   for (int e = 0; e <= 6; e++) {
     const double D = p10[e], rD = 1.0 / D, k0 = rint(vmin * D);
+    /* the reciprocal's second word: 1 - rD * D is exact in one FMA (|.| < 2^-52 on the grid of the product's last bit), so the one
+     * rounding of the division makes this RN(1 / D - rD) */
+    const double rDlo = fma(-rD, D, 1.0) / D;
     if (!(fabs(k0) < 4.0e15)) break;                           /* k = q + k0 must stay an exact integer */
-    HIP_TRY(wdpm_launch_dem_encode(x->d_dem, x->cells, k0, D, rD, x->d_dem32, x->d_bits, x->stream));
+    HIP_TRY(wdpm_launch_dem_encode(x->d_dem, x->cells, k0, D, rD, rDlo, x->d_dem32, x->d_bits, x->stream));
     HIP_TRY(hipMemcpyAsync(x->h_pin, x->d_bits, sizeof(double), hipMemcpyDeviceToHost, x->stream));
     if (wdpm_stream_sync(x, x->stream)) return 1;
     unsigned long long bad;
     memcpy(&bad, x->h_pin, sizeof bad);
     if (!bad) {
       x->dem32_encodable = true;
-      x->code = DemCode{x->d_dem32, k0, D, rD, (env && atoi(env) == 2) ? 1 : 0, nullptr, nullptr, 0};   /* WDPM_DEM32=2: on launches of any size */
+      x->code = DemCode{x->d_dem32, k0, D, rD, rDlo, (env && atoi(env) == 2) ? 1 : 0, nullptr, nullptr, 0};   /* WDPM_DEM32=2: on launches of any size */
       break;
     }
   }
@@ -558,7 +561,7 @@ static int encode_dem(wdpm_ctx *x) {
   const char *env16 = getenv("WDPM_DEM16");
   if (x->dem32_encodable && !(env16 && atoi(env16) == 0)) {
     const int ngroups = (x->g.ncp + kDemGroup - 1) / kDemGroup;
-    HIP_TRY(wdpm_launch_dem16_encode(x->d_dem32, x->g.rows, x->g.ncp, ngroups, x->d_dem16, x->d_gbase, x->d_bits, x->stream));
+    HIP_TRY(wdpm_launch_dem16_encode(x->code, x->g.rows, x->g.ncp, ngroups, x->d_dem16, x->d_gbase, x->d_bits, x->stream));
     HIP_TRY(hipMemcpyAsync(x->h_pin, x->d_bits, sizeof(double), hipMemcpyDeviceToHost, x->stream));
     if (wdpm_stream_sync(x, x->stream)) return 1;
     unsigned long long bad;

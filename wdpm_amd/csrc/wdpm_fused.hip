@@ -294,6 +294,10 @@ __device__ __forceinline__ void three_stages(double (&W)[7][3], const double (&D
 
 #ifdef WDPM_WAVE_TIMES   /* timing builds only (tools/wave_times.py): when each wave of the marching kernel starts and ends, and where */
 static __device__ unsigned long long g_wave_times[4 * 8192];   /* one per translation unit (WDPM_TU): each has its accessor */
+/* two-iteration launches: what each wave spent in await(), by where in its chunk (start: steps 0 - 3, end: the last four, steady between).
+ * A producer only ever waits for a full ring, a consumer for an empty one.  Per wave: [0] polls start | steady << 32, [1] polls end |
+ * awaits that had to poll << 32, [2] 100 MHz ticks from first poll to release, start | steady << 32, [3] the same at the end */
+static __device__ unsigned long long g_wave_waits[4 * 8192];
 /* relay kernel: eight stamps per wave (tools/relay_times.py); the wait in front of each makes the stamp mean "everything before is done" */
 #define WDPM_RSTAMP(k) do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0); rst[k] = wall_clock64(); __builtin_amdgcn_s_waitcnt(0); __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
@@ -346,6 +350,7 @@ constexpr int fused_built_for() {
  * wave index alone; nothing depends on which SIMD a wave sits on.
  * --------------------------------------------------------------------------------------------- */
 constexpr int kIter2Polls = 1 << 21;     /* of ~0.15 us each: a quarter of a second, against steps of a microsecond */
+constexpr int kIter2Retired = 1 << 30;   /* hand word of a wave that has left: above every step count, far from overflow in `n - lag - taken` */
 
 template <int DEM32>
 __device__ __forceinline__ void iter2_march(const double *__restrict__ win, double *__restrict__ wout, const DemCode &code, const SlabGeom &g,
@@ -411,13 +416,26 @@ __device__ __forceinline__ void iter2_march(const double *__restrict__ win, doub
     dcol[jj] = own ? kStripOut * j + cs : kGroupIn + jj;
   }
   const int rcol = kStripOut * j + 3 * lane;              // consumer: its first column in a ring row
+  // The hand words through a pointer that says LDS: ds_read / ds_write in the wave's in-order LDS queue.  Through a generic pointer
+  // they were FLAT operations, each volatile store followed by a wait for every global load and store of the wave in flight.
+#ifdef WDPM_ITER2_FLAT_HAND                               /* A/B builds: as it was */
   volatile int *const hand_v = hand;
+#else
+  volatile __attribute__((address_space(3))) int *const hand_v = (volatile __attribute__((address_space(3))) int *)hand;
+#endif
   const int nb_lo = j > 0 ? j - 1 : 0, nb_hi = j < 3 ? j + 1 : 3;
   bool broken = false;
   // the smallest count of the (up to) three waves of the other role this one exchanges columns with, once it is >= need - or at once
   // where need <= 0
+#ifdef WDPM_WAVE_TIMES
+  unsigned wt_polls0 = 0, wt_polls1 = 0, wt_polls2 = 0, wt_ticks0 = 0, wt_ticks1 = 0, wt_ticks2 = 0, wt_waits = 0;
+  int wt_phase = 0;
+#endif
   auto await = [&](const int base, const int need) -> int {
     int m = 0, polls = 0;
+#ifdef WDPM_WAVE_TIMES
+    unsigned long long wt_a = 0;
+#endif
     for (;;) {
       const int a = hand_v[base + nb_lo], b = hand_v[base + j], c = hand_v[base + nb_hi];
       m = a < b ? a : b;
@@ -429,11 +447,43 @@ __device__ __forceinline__ void iter2_march(const double *__restrict__ win, doub
         if (lane == 0) *i2.err = 1u;
         break;
       }
+#ifdef WDPM_WAVE_TIMES
+      if (polls == 1) wt_a = wall_clock64();
+#endif
       __builtin_amdgcn_s_sleep(2);
     }
+#ifdef WDPM_WAVE_TIMES
+    if (polls) {
+      const unsigned dt = (unsigned)(wall_clock64() - wt_a);
+      wt_waits++;
+      if (wt_phase == 0) { wt_polls0 += polls; wt_ticks0 += dt; }
+      else if (wt_phase == 1) { wt_polls1 += polls; wt_ticks1 += dt; }
+      else { wt_polls2 += polls; wt_ticks2 += dt; }
+    }
+#endif
     asm volatile("" ::: "memory");
     return m;
   };
+  // Strips beyond the raster's right edge (the last group rarely fills: at 16384^2 one strip of its four lies outside) retire at once
+  // instead of marching on clamped loads: a consumer that stores nothing, a producer none of whose ring columns lies inside the raster.
+  // Nothing stored depends on their columns - they lie beyond the border column, whose DEM is NODATA and lets nothing across (DESIGN 4.2,
+  // tests/test_iter2_retired_strips.py) - but the neighbours read them: the producer leaves +0.0 in its columns of every ring row, so that
+  // every ring cell holds a finite value, and either leaves a hand word no await() can exceed, written behind the zeros.
+#ifdef WDPM_ITER2_NO_RETIRE                               /* A/B builds: every wave marches, as it was */
+  const bool retire = false;
+#else
+  const bool retire = producer ? c0 + (j == 0 ? 0 : kHaloL) >= g.ncp : !store_any;     // wave-uniform
+#endif
+  if (retire) {
+    if (producer) {
+      for (int r = 0; r < R; r++)
+#pragma unroll
+        for (int jj = 0; jj < 3; jj++) i2_ring[(size_t)r * kRingPitch + dcol[jj]] = 0.0;
+      asm volatile("" ::: "memory");
+    }
+    hand_v[wave] = kIter2Retired;
+    return;                                               // no barrier follows; no duration into the balance counters
+  }
   const size_t pitch = (size_t)g.ncp;
   char *const dump = reinterpret_cast<char *>(wout + (size_t)g.rows * pitch);
   const bool edge = (As + 3 * (nsteps + 1) > g.rows);
@@ -529,14 +579,17 @@ __device__ __forceinline__ void iter2_march(const double *__restrict__ win, doub
 
     auto step = [&](const int n, Prefetched &P, auto nstages_tag) {
       constexpr int NSTAGES = decltype(nstages_tag)::value;
+#ifdef WDPM_WAVE_TIMES
+      wt_phase = n < 4 ? 0 : (n >= nsteps - 4 ? 2 : 1);
+#endif
       if (!PRODUCER) read_staged();
 #pragma unroll
       for (int i = 0; i < 3; i++)
 #pragma unroll
         for (int jj = 0; jj < 3; jj++) {
           W[4 + i][jj] = P.NW[i][jj];
-          if (DEM32 == 2) D[4 + i][jj] = dem16_decode_nan(P.qh[i][jj], P.gbv[i], code.k0, code.D, code.rD);
-          else D[4 + i][jj] = dem32_decode_nan(P.qi[i][jj], code.k0, code.D, code.rD);
+          if (DEM32 == 2) D[4 + i][jj] = dem16_decode_nan(P.qh[i][jj], P.gbv[i], code.k0, code.D, code.rD, code.rDlo);
+          else D[4 + i][jj] = dem32_decode_nan(P.qi[i][jj], code.k0, code.D, code.rD, code.rDlo);
         }
       if (EDGE) {
 #pragma unroll
@@ -559,13 +612,21 @@ __device__ __forceinline__ void iter2_march(const double *__restrict__ win, doub
         hm = max3(hm, hi(W[6][1]), hi(W[6][2]));
         deep = (deep & 8) | ((deep & 3) << 1) | (__ballot(hm > 0x40080000u) != 0 ? 1 : 0);
       }
+#ifdef WDPM_ITER2_EARLY_TAKE                               /* A/B builds: the take a whole step ahead of its use, as it was */
       if (!PRODUCER) take(P, n + 1);
+#endif
       prefetch(P, As + 3 * (n + 1));
       if (!PRODUCER) write_staged(A + 3 * (n - 1) - 4);
 
       const int rbase = As + 3 * n - 4;
       if (deep) three_stages<0, false, NSTAGES, 1>(W, D, rbase, g.dr, cdr, ds);
       else three_stages<0, false, NSTAGES, 1 | 2>(W, D, rbase, g.dr, cdr, ds);
+#ifndef WDPM_ITER2_EARLY_TAKE
+      // The next triple just in time: its latency is an LDS read, which the staging writes, the wait for the codes and the window
+      // slide below cover.  Taken before the stages it kept nine doubles alive across them and asked the producers for their step
+      // n + lag + 2 a step early - three rows of the ring's slack given away.
+      if (!PRODUCER) take(P, n + 1);
+#endif
 
       if (PRODUCER) {
         // rows rbase .. rbase + 2 are final: into the ring, once the consumers have taken what lies there (chunk rows < 0: nobody
@@ -639,6 +700,10 @@ __device__ __forceinline__ void iter2_march(const double *__restrict__ win, doub
     g_wave_times[4 * item + 1] = wall_clock64();
     g_wave_times[4 * item + 2] = __builtin_amdgcn_s_getreg((31 << 11) | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | 20) << 32);
     g_wave_times[4 * item + 3] = ((unsigned long long)(4 * grp + j + (producer ? 0 : 0x4000)) << 48) | ((unsigned long long)(nsteps & 0xffff) << 32) | (unsigned)chunk;
+    g_wave_waits[4 * item] = wt_polls0 | ((unsigned long long)wt_polls1 << 32);
+    g_wave_waits[4 * item + 1] = wt_polls2 | ((unsigned long long)wt_waits << 32);
+    g_wave_waits[4 * item + 2] = wt_ticks0 | ((unsigned long long)wt_ticks1 << 32);
+    g_wave_waits[4 * item + 3] = wt_ticks2;
   }
 #endif
 }
@@ -991,8 +1056,8 @@ fused_iteration_kernel(const double *__restrict__ win, double *__restrict__ wout
         for (int j = 0; j < 3; j++) {
           // FLUSH: the block's threshold flush (WDPMCL.c:1059-1062) applied to the water as it arrives
           W[4 + i][j] = FLUSH && P.NW[i][j] < thres ? 0.0 : P.NW[i][j];
-          if (DEM32 == 2) D[4 + i][j] = dem16_decode_nan(P.qh[i][j], P.gbv[i], code.k0, code.D, code.rD);
-          else if (DEM32) D[4 + i][j] = dem32_decode_nan(P.qi[i][j], code.k0, code.D, code.rD);
+          if (DEM32 == 2) D[4 + i][j] = dem16_decode_nan(P.qh[i][j], P.gbv[i], code.k0, code.D, code.rD, code.rDlo);
+          else if (DEM32) D[4 + i][j] = dem32_decode_nan(P.qi[i][j], code.k0, code.D, code.rD, code.rDlo);
           else D[4 + i][j] = P.ND[i][j];
         }
       if (MODULE == 2 && owed_here && A + 3 * n + 2 >= g.dr - 1 && A + 3 * n <= g.dr + 1) {   // wave-uniform, rare
@@ -1549,7 +1614,7 @@ relay_iteration_kernel(const double *__restrict__ win, double *__restrict__ wout
     for (int j = 0; j < 3; j++) {
       // DEM32: the elevations as verified-lossless 32-bit codes (wdpm_kernels.h::DemCode): launches of several rounds are bound
       // by the memory system, and four bytes per cell less are worth nine decodes per wave there
-      if (DEM32) D[i][j] = dem32_decode_nan(*reinterpret_cast<const int *>(bq + voff[j] / 2), code.k0, code.D, code.rD);
+      if (DEM32) D[i][j] = dem32_decode_nan(*reinterpret_cast<const int *>(bq + voff[j] / 2), code.k0, code.D, code.rD, code.rDlo);
       else D[i][j] = *reinterpret_cast<const double *>(bd + voff[j]);
       W[i][j] = i < 3 ? *reinterpret_cast<const double *>(bw + voff[j]) : 0.0;
     }
@@ -2021,6 +2086,10 @@ hipError_t wdpm_launch_iteration(const LaunchRequest &q, const LaunchPlan &p, co
 extern "C" int wdpm_debug_wave_times(unsigned long long *out, int nwaves) {
   if (hipDeviceSynchronize() != hipSuccess) return 1;
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wave_times), (size_t)nwaves * 32) != hipSuccess;
+}
+extern "C" int wdpm_debug_wave_waits(unsigned long long *out, int nwaves) {
+  if (hipDeviceSynchronize() != hipSuccess) return 1;
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wave_waits), (size_t)nwaves * 32) != hipSuccess;
 }
 #endif
 #if !defined(WDPM_TU) || WDPM_TU == 2

@@ -19,6 +19,7 @@ struct DemCode {
   const int *q;      /* rows x ncp codes, or nullptr when the raster is not encodable */
   double k0;         /* integer offset: k = q + k0 */
   double D, rD;      /* 10^e and its correctly rounded reciprocal */
+  double rDlo;       /* RN(1 / D - rD): the reciprocal's second word (wdpm_stencil.h::dem_quotient) */
   int force;         /* use the codes on launches of any size (tests); normally only where they pay */
   /* Second level (tried in round 3 at +0.7 % when the kernel was bound by instruction issue alone; kept in round 4, when it
    * is as close to the memory system's roof): the same codes as 16-bit offsets from one 32-bit base per group of kDemGroup
@@ -37,11 +38,12 @@ constexpr int kDemGroup = 48;
 hipError_t wdpm_launch_dem_min(const double *dem, size_t cells, unsigned long long *key, hipStream_t s);
 double wdpm_dem_key_to_double(unsigned long long key);
 /* q[i] = code of dem[i]; *bad |= 1 if any cell does not decode to exactly dem[i] */
-hipError_t wdpm_launch_dem_encode(const double *dem, size_t cells, double k0, double D, double rD, int *q,
+hipError_t wdpm_launch_dem_encode(const double *dem, size_t cells, double k0, double D, double rD, double rDlo, int *q,
                                   unsigned long long *bad, hipStream_t s);
 
-/* h / gb of DemCode from the verified 32-bit codes q (rows x ncp); *bad |= 1 if some group spans more than 65 534 quanta */
-hipError_t wdpm_launch_dem16_encode(const int *q, int rows, int ncp, int ngroups, unsigned short *h, int *gb,
+/* h / gb of DemCode from the verified 32-bit codes q (rows x ncp) of `code`; *bad |= 1 if some group spans more than 65 534 quanta
+ * or some cell's 16-bit decode is not, bit for bit, its 32-bit one */
+hipError_t wdpm_launch_dem16_encode(const DemCode &code, int rows, int ncp, int ngroups, unsigned short *h, int *gb,
                                     unsigned long long *bad, hipStream_t s);
 
 /* The reference's SEQUENTIAL volume sum (WDPMCL.c:1259-1266) evaluated in parallel, see

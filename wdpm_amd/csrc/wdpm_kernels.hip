@@ -210,7 +210,7 @@ hipError_t wdpm_launch_dem_min(const double *dem, size_t cells, unsigned long lo
 }
 
 __global__ void __launch_bounds__(256)
-dem_encode_kernel(const double *__restrict__ dem, size_t n, double k0, double D, double rD, int *__restrict__ q,
+dem_encode_kernel(const double *__restrict__ dem, size_t n, double k0, double D, double rD, double rDlo, int *__restrict__ q,
                   unsigned long long *bad) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   bool miss = false;
@@ -221,7 +221,7 @@ dem_encode_kernel(const double *__restrict__ dem, size_t n, double k0, double D,
       const double kk = rint(v * D) - k0;
       const bool fits = fabs(kk) < 2147483647.0;
       code = fits ? (int)kk : 0;
-      const bool same = __double_as_longlong(dem32_decode(code, k0, D, rD)) == __double_as_longlong(v);
+      const bool same = __double_as_longlong(dem32_decode(code, k0, D, rD, rDlo)) == __double_as_longlong(v);
       miss |= !(fits && same);
     }
     q[i] = code;
@@ -229,22 +229,23 @@ dem_encode_kernel(const double *__restrict__ dem, size_t n, double k0, double D,
   if (__ballot(miss) && (threadIdx.x & 63) == 0) atomicOr(bad, 1ull);
 }
 
-hipError_t wdpm_launch_dem_encode(const double *dem, size_t cells, double k0, double D, double rD, int *q,
+hipError_t wdpm_launch_dem_encode(const double *dem, size_t cells, double k0, double D, double rD, double rDlo, int *q,
                                   unsigned long long *bad, hipStream_t s) {
   hipError_t e = hipMemsetAsync(bad, 0, sizeof(unsigned long long), s);
   if (e != hipSuccess || cells == 0) return e;
   size_t blocks = (cells + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   WDPM_LEDGER(0, dem_encode_kernel);
-  hipLaunchKernelGGL(dem_encode_kernel, dim3((unsigned)blocks), dim3(256), 0, s, dem, cells, k0, D, rD, q, bad);
+  hipLaunchKernelGGL(dem_encode_kernel, dim3((unsigned)blocks), dim3(256), 0, s, dem, cells, k0, D, rD, rDlo, q, bad);
   return hipGetLastError();
 }
 
 // the 32-bit codes as 16-bit offsets from one base per group of kDemGroup columns of a row (DemCode::h, ::gb); one thread
-// per group - a one-off at upload
+// per group - a one-off at upload.  q == gb + h is an integer identity; what the iteration kernels compute from (h, gb) is checked all
+// the same, cell by cell, with their own decoder against the 32-bit one dem_encode_kernel has verified
 __global__ void __launch_bounds__(256)
-dem16_encode_kernel(const int *__restrict__ q, int rows, int ncp, int ngroups, unsigned short *__restrict__ h,
-                    int *__restrict__ gb, unsigned long long *bad) {
+dem16_encode_kernel(const int *__restrict__ q, int rows, int ncp, int ngroups, double k0, double D, double rD, double rDlo,
+                    unsigned short *__restrict__ h, int *__restrict__ gb, unsigned long long *bad) {
   const size_t total = (size_t)rows * ngroups, stride = (size_t)gridDim.x * blockDim.x;
   bool miss = false;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
@@ -261,20 +262,24 @@ dem16_encode_kernel(const int *__restrict__ q, int rows, int ncp, int ngroups, u
     gb[i] = (int)lo;
     for (int c = c0; c < c1; c++) {
       const int v = row[c];
-      h[(size_t)r * ncp + c] = v == (int)0x80000000 ? (unsigned short)0xFFFF : (unsigned short)((long long)v - lo);
+      const unsigned short hv = v == (int)0x80000000 ? (unsigned short)0xFFFF : (unsigned short)((long long)v - lo);
+      h[(size_t)r * ncp + c] = hv;
+      if (v != (int)0x80000000)
+        miss |= __double_as_longlong(dem16_decode_nan((int)hv, (int)lo, k0, D, rD, rDlo)) != __double_as_longlong(dem32_decode_nan(v, k0, D, rD, rDlo));
     }
   }
   if (__ballot(miss) && (threadIdx.x & 63) == 0) atomicOr(bad, 1ull);
 }
 
-hipError_t wdpm_launch_dem16_encode(const int *q, int rows, int ncp, int ngroups, unsigned short *h, int *gb,
+hipError_t wdpm_launch_dem16_encode(const DemCode &code, int rows, int ncp, int ngroups, unsigned short *h, int *gb,
                                     unsigned long long *bad, hipStream_t s) {
   hipError_t e = hipMemsetAsync(bad, 0, sizeof(unsigned long long), s);
   if (e != hipSuccess || rows <= 0) return e;
   size_t blocks = ((size_t)rows * ngroups + 255) / 256;
   if (blocks > 65536) blocks = 65536;
   WDPM_LEDGER(0, dem16_encode_kernel);
-  hipLaunchKernelGGL(dem16_encode_kernel, dim3((unsigned)blocks), dim3(256), 0, s, q, rows, ncp, ngroups, h, gb, bad);
+  hipLaunchKernelGGL(dem16_encode_kernel, dim3((unsigned)blocks), dim3(256), 0, s, code.q, rows, ncp, ngroups, code.k0, code.D, code.rD,
+                     code.rDlo, h, gb, bad);
   return hipGetLastError();
 }
 

@@ -19,15 +19,27 @@
 
 #include <hip/hip_runtime.h>
 
-/* DEM code -> elevation (wdpm_kernels.h::DemCode).  n = q + k0 is an exact integer in fp64; n * rD is
- * within an ulp of n / D and the two fused steps (a Newton correction on the residual n - q0 * D,
- * which the FMA computes exactly) land on the correctly rounded quotient — but nothing rests on
- * that argument: the encoder runs this very function on every cell and compares bits. */
-__device__ __forceinline__ double dem32_decode(const int q, const double k0, const double D, const double rD) {
-  const double n = (double)q + k0;
+/* DEM code -> elevation (wdpm_kernels.h::DemCode).  n = q + k0 is an exact integer in fp64 and the elevation is RN(n / D), D = 10^e.
+ * The quotient in two operations: rD = RN(1 / D) and rDlo = RN(1 / D - rD) (the host computes both, wdpm_capi.hip::encode_dem), and
+ * n * rD + n * rDlo is n / D to about 2^-104 relative - the product n * rDlo is rounded once (2^-53 of a term that is 2^-53 of the
+ * sum) and the FMA rounds the sum once.  A quotient of an integer below 2^53 by a 20-bit denominator cannot lie that close to a
+ * rounding boundary without lying on it, so the FMA lands on RN(n / D); for e = 0 rDlo is 0 and the result is n itself.
+ * tests/test_decode_forms.py holds this form and the one it replaced (a Newton correction: q0 = n * rD, r = fma(-q0, D, n),
+ * v = fma(r, rD, q0), one more dependent fp64 operation per value) against exact rational arithmetic.  Nothing rests on that
+ * argument: the encoders run these very functions on every cell and compare bits (dem_encode_kernel, dem16_encode_kernel).
+ * -DWDPM_DECODE_NEWTON builds the earlier form (A/B builds, tools/build_variant.sh). */
+__device__ __forceinline__ double dem_quotient(const double n, const double D, const double rD, const double rDlo) {
+#ifdef WDPM_DECODE_NEWTON
   const double q0 = n * rD;
   const double r = __builtin_fma(-q0, D, n);
-  const double v = __builtin_fma(r, rD, q0);
+  return __builtin_fma(r, rD, q0);
+#else
+  return __builtin_fma(n, rD, n * rDlo);
+#endif
+}
+
+__device__ __forceinline__ double dem32_decode(const int q, const double k0, const double D, const double rD, const double rDlo) {
+  const double v = dem_quotient((double)q + k0, D, rD, rDlo);
   return q == (int)0x80000000 ? __builtin_inf() : v;
 }
 
@@ -44,21 +56,24 @@ __device__ __forceinline__ double dem32_decode(const int q, const double k0, con
  * +inf: a NODATA cell is never drained into) and the outlet itself is found among cells with dem > 0 on the fp64 DEM, never on the
  * codes; drain()'s owed sum reads the fp64 DEM.  tests/test_hip_parity.py::test_drain_on_codes_with_nodata_around_the_outlet puts
  * NODATA at a centre, at a neighbour and on three sides of the outlet and forces the codes on the marching and the relay kernel. */
-__device__ __forceinline__ double dem32_decode_nan(const int q, const double k0, const double D, const double rD) {
-  const double n = (double)q + k0;
-  const double q0 = n * rD;
-  const double r = __builtin_fma(-q0, D, n);
-  const double v = __builtin_fma(r, rD, q0);
+__device__ __forceinline__ double dem32_decode_nan(const int q, const double k0, const double D, const double rD, const double rDlo) {
+  const double v = dem_quotient((double)q + k0, D, rD, rDlo);
   const int hi = q == (int)0x80000000 ? 0x7ff80000 : __double2hiint(v);
   return __hiloint2double(hi, __double2loint(v));
 }
 
-/* ... and from a 16-bit offset and its group's base (wdpm_kernels.h::DemCode::h, ::gb): q = gb + h, NODATA is h == 0xFFFF */
-__device__ __forceinline__ double dem16_decode_nan(const int h, const int gb, const double k0, const double D, const double rD) {
+/* ... and from a 16-bit offset and its group's base (wdpm_kernels.h::DemCode::h, ::gb): q = gb + h, NODATA is h == 0xFFFF.
+ * n = (gb + k0) + h, summed in fp64: both sums are exact integers wherever (double)(gb + h) + k0 was (|gb| < 2^31, |k0| < 4e15,
+ * h < 2^16), so n is the same number - and gb + k0 is what a lane's three columns of a row share (they lie in one group), which
+ * the compiler computes once per row: per value one unsigned conversion, an add, the two operations of the quotient and the
+ * NODATA select. */
+__device__ __forceinline__ double dem16_decode_nan(const int h, const int gb, const double k0, const double D, const double rD, const double rDlo) {
+#ifdef WDPM_DECODE_NEWTON
   const double n = (double)(gb + h) + k0;
-  const double q0 = n * rD;
-  const double r = __builtin_fma(-q0, D, n);
-  const double v = __builtin_fma(r, rD, q0);
+#else
+  const double n = ((double)gb + k0) + (double)(unsigned)h;
+#endif
+  const double v = dem_quotient(n, D, rD, rDlo);
   const int hi = h == 0xFFFF ? 0x7ff80000 : __double2hiint(v);
   return __hiloint2double(hi, __double2loint(v));
 }
