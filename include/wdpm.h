@@ -337,12 +337,18 @@ int  wdpm_group_enqueue_stats(wdpm_group *grp, double *seconds, double *exchange
  *   flag over all ranks and set it (wdpm_amd/rowblock.py does).
  * WDPM_OPT_DEM32 (get/set): 1 = the iteration kernel streams the static DEM as 32-bit codes
  *   (4 bytes per cell-update of HBM traffic instead of 8).  Switched on by wdpm_upload when the device
- *   has verified, cell by cell and bit for bit, that the DEM is k / 10^e with 32-bit k (DEMs read
- *   from decimal text are); results are identical either way.  Setting 0 forces the fp64 DEM,
+ *   has verified, cell by cell and bit for bit, that the DEM is k / D with 32-bit k: D = 10^e, e = 0..6 (DEMs read
+ *   from decimal text are) or, where no decimal grid holds it, D = 2^s, s = 1..52, the grid of the lowest bit set in any
+ *   elevation (DEMs that were binary all along are: a Float32 raster written with all its digits or widened float -> double lies
+ *   on 2^-15 m around 500 m); results are identical either way.  Setting 0 forces the fp64 DEM,
  *   setting 1 is honoured only for a DEM that passed the check; the kernel then uses the codes on
  *   launches large enough for them to pay (add / subtract >= 4096^2 or so; drain, from round 4, on launches of two waves per SIMD),
  *   setting 2 on launches of any size.  WDPM_DEM32=0 in the environment
- *   disables the encoding altogether, WDPM_DEM32=2 makes 2 the default.  The CPU restatement reports 0.
+ *   disables the encoding altogether, WDPM_DEM32=2 makes 2 the default, WDPM_DEM_BINARY=0 keeps to the decimal grids.  The CPU
+ *   restatement reports 0.
+ * WDPM_OPT_DEM_GRID / WDPM_OPT_DEM_GRID_EXP (get): the grid the last upload found the DEM on - 10 and e for k / 10^e, 2 and s for
+ *   k / 2^s, 0 and 0 where the fp64 DEM is in charge.  What upload found, not what runs: setting WDPM_OPT_DEM32 to 0 afterwards
+ *   does not change them.  The CPU restatement reports 0.
  * WDPM_OPT_DEM16 (get/set; round 4): 1 = the marching kernel streams those codes as 16-bit offsets from one 32-bit base per 48
  *   columns of a row (2.08 B per cell: 18.1 B of HBM traffic per cell-update) - an exact integer identity with the verified 32-bit
  *   codes, possible where no such group spans more than 65 534 quanta; checked at upload, results identical either way.  The get returns
@@ -374,7 +380,8 @@ int  wdpm_group_enqueue_stats(wdpm_group *grp, double *seconds, double *exchange
  *   without the variable).  A debugging aid: the GPU pool has no address sanitizer. */
 enum { WDPM_OPT_SIGNED_ZERO_SAFE = 1, WDPM_OPT_DEM32 = 2, WDPM_OPT_TILES = 3, WDPM_OPT_TILES_SEEN = 4,
        WDPM_OPT_TILES_WORKED = 5, WDPM_OPT_SPARSE = 6, WDPM_OPT_GUARD_BAD = 7, WDPM_OPT_WATER_KINDS = 8,
-       WDPM_OPT_PLAIN_WATER = 9, WDPM_OPT_DEM16 = 10, WDPM_OPT_GRAPH_LAUNCHES = 11 };
+       WDPM_OPT_PLAIN_WATER = 9, WDPM_OPT_DEM16 = 10, WDPM_OPT_GRAPH_LAUNCHES = 11, WDPM_OPT_DEM_GRID = 12,
+       WDPM_OPT_DEM_GRID_EXP = 13 };
 int wdpm_get_option(wdpm_ctx *ctx, int32_t key, int64_t *value);
 int wdpm_set_option(wdpm_ctx *ctx, int32_t key, int64_t value);
 

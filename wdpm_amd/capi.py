@@ -20,6 +20,7 @@ OPT_SIGNED_ZERO_SAFE = 1
 OPT_DEM32 = 2
 OPT_TILES, OPT_TILES_SEEN, OPT_TILES_WORKED, OPT_SPARSE, OPT_GUARD_BAD, OPT_WATER_KINDS, OPT_PLAIN_WATER, OPT_DEM16 = 3, 4, 5, 6, 7, 8, 9, 10
 OPT_GRAPH_LAUNCHES = 11
+OPT_DEM_GRID, OPT_DEM_GRID_EXP = 12, 13   # get only: 10 / e, 2 / s or 0 / 0 (include/wdpm.h)
 # launch ledger switch bits (include/wdpm.h: WDPM_LEDGER_*): marching kernel, relay kernel (its store_plain bits)
 LEDGER_NO_CLAMP, LEDGER_PRIO, LEDGER_TILE_FLAGS, LEDGER_BALANCE = 1, 2, 4, 8
 LEDGER_RELAY_ORDINARY_STORES, LEDGER_RELAY_PRIO, LEDGER_RELAY_NO_CLAMP = 1, 2, 4

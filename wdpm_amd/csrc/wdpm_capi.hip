@@ -337,7 +337,7 @@ int wdpm_create(wdpm_ctx **out, const wdpm_params *p) {
   x->drain_owed = false;
   x->flush_thres = -__builtin_inf();
   x->d_scal = nullptr; x->d_bits = nullptr; x->h_pin = nullptr; x->d_stat = nullptr; x->h_iter2_err = x->d_iter2_err = nullptr;
-  x->d_dem32 = nullptr; x->code = DemCode{nullptr, 0.0, 1.0, 1.0, 0.0, 0, nullptr, nullptr, 0}; x->dem32_encodable = false; x->dem_bounded = false;
+  x->d_dem32 = nullptr; x->code = DemCode{nullptr, 0.0, 1.0, 1.0, 0.0, 0, nullptr, nullptr, 0}; x->dem32_encodable = false; x->dem_bounded = false; x->dem_grid = x->dem_grid_exp = 0;
   x->d_dem16 = nullptr; x->d_gbase = nullptr; x->dem16_encodable = false; x->dem16_wanted = true;
   x->graph_mode = -1; x->graph_launches = 0;
   x->d_sum_approx = nullptr; x->d_sum_i = nullptr; x->d_sum_k = nullptr; x->d_sum_flag = nullptr;
@@ -362,7 +362,7 @@ int wdpm_create(wdpm_ctx **out, const wdpm_params *p) {
   if (e == hipSuccess) e = guarded_malloc(x, (void **)&x->d_dem16, x->cells * sizeof(unsigned short) + 64);
   if (e == hipSuccess) e = guarded_malloc(x, (void **)&x->d_gbase, (size_t)x->g.rows * ((x->g.ncp + kDemGroup - 1) / kDemGroup) * sizeof(int) + 64);
   if (e == hipSuccess) e = hipMalloc(&x->d_scal, 2 * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&x->d_bits, 2 * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMalloc(&x->d_bits, 3 * sizeof(unsigned long long));
   if (e == hipSuccess) e = hipMalloc(&x->d_md, sizeof(unsigned long long));
   if (e == hipSuccess) {
     /* chunk heights by what each XCD delivers (wdpm_kernels.h::XcdBalance).  WDPM_BALANCE=0: equal heights always; 2: the table on
@@ -519,26 +519,46 @@ static void drop_graphs(wdpm_ctx *x) {
   x->graphs.clear();
 }
 
-/* Try to express the DEM just uploaded as 32-bit codes k with dem == (k + k0) / 10^e bit for bit
- * (e = 0..6, the smallest that works; real DEMs are decimal text).  The device checks every cell
+/* One attempt at the grid D: codes q with dem == (q + k0) / D, checked by the device on every cell with the decoder the
+ * iteration kernels use.  *ok says whether every cell came back bit for bit; the codes are then in charge. */
+static int try_dem_grid(wdpm_ctx *x, double k0, double D, double rD, double rDlo, int force, bool *ok) {
+  HIP_TRY(wdpm_launch_dem_encode(x->d_dem, x->cells, k0, D, rD, rDlo, x->d_dem32, x->d_bits, x->stream));
+  HIP_TRY(hipMemcpyAsync(x->h_pin, x->d_bits, sizeof(double), hipMemcpyDeviceToHost, x->stream));
+  if (wdpm_stream_sync(x, x->stream)) return 1;
+  unsigned long long bad;
+  memcpy(&bad, x->h_pin, sizeof bad);
+  *ok = !bad;
+  if (!bad) {
+    x->dem32_encodable = true;
+    x->code = DemCode{x->d_dem32, k0, D, rD, rDlo, force, nullptr, nullptr, 0};
+  }
+  return 0;
+}
+
+/* Try to express the DEM just uploaded as 32-bit codes k with dem == (k + k0) / D bit for bit.  First D = 10^e (e = 0..6, the
+ * smallest that works: DEMs read from decimal text), then once D = 2^s with 2^-s the weight of the lowest bit set in any
+ * elevation (DEMs that were binary all along: a Float32 raster around 500 m lies on 2^-15 m).  The device checks every cell
  * with the decoder the iteration kernel uses; any miss leaves the fp64 DEM in charge. */
 static int encode_dem(wdpm_ctx *x) {
   drop_graphs(x);
   /* every level starts from "not encodable": a DEM uploaded over an earlier one inherits nothing (a smooth DEM, then a
    * rough one that passes only the 32-bit check, left dem16_encodable set and d_dem16 holding truncated offsets) */
   x->dem32_encodable = false; x->dem16_encodable = false; x->dem_bounded = false; x->dem16_wanted = true;
+  x->dem_grid = x->dem_grid_exp = 0;
   x->code = DemCode{nullptr, 0.0, 1.0, 1.0, 0.0, 0, nullptr, nullptr, 0};
   HIP_TRY(wdpm_launch_dem_min(x->d_dem, x->cells, x->d_bits, x->stream));
-  HIP_TRY(hipMemcpyAsync(x->h_pin, x->d_bits, 2 * sizeof(double), hipMemcpyDeviceToHost, x->stream));
+  HIP_TRY(hipMemcpyAsync(x->h_pin, x->d_bits, 3 * sizeof(double), hipMemcpyDeviceToHost, x->stream));
   if (wdpm_stream_sync(x, x->stream)) return 1;
-  unsigned long long key, amax;
+  unsigned long long key, amax, low;
   memcpy(&key, x->h_pin, sizeof key);
   memcpy(&amax, x->h_pin + 1, sizeof amax);
+  memcpy(&low, x->h_pin + 2, sizeof low);
   x->dem_bounded = amax < 0x41d0000000000000ull;               /* |dem| < 2^30 on every valid cell (none at all: 0) */
   const char *env = getenv("WDPM_DEM32");
   if (env && atoi(env) == 0) return 0;
   if (key == ~0ull) return 0;                                  /* no valid cell at all */
   const double vmin = wdpm_dem_key_to_double(key);
+  const int force = (env && atoi(env) == 2) ? 1 : 0;           /* WDPM_DEM32=2: on launches of any size */
   static const double p10[7] = {1.0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6};
   for (int e = 0; e <= 6; e++) {
     const double D = p10[e], rD = 1.0 / D, k0 = rint(vmin * D);
@@ -546,15 +566,31 @@ static int encode_dem(wdpm_ctx *x) {
      * rounding of the division makes this RN(1 / D - rD) */
     const double rDlo = fma(-rD, D, 1.0) / D;
     if (!(fabs(k0) < 4.0e15)) break;                           /* k = q + k0 must stay an exact integer */
-    HIP_TRY(wdpm_launch_dem_encode(x->d_dem, x->cells, k0, D, rD, rDlo, x->d_dem32, x->d_bits, x->stream));
-    HIP_TRY(hipMemcpyAsync(x->h_pin, x->d_bits, sizeof(double), hipMemcpyDeviceToHost, x->stream));
-    if (wdpm_stream_sync(x, x->stream)) return 1;
-    unsigned long long bad;
-    memcpy(&bad, x->h_pin, sizeof bad);
-    if (!bad) {
-      x->dem32_encodable = true;
-      x->code = DemCode{x->d_dem32, k0, D, rD, rDlo, (env && atoi(env) == 2) ? 1 : 0, nullptr, nullptr, 0};   /* WDPM_DEM32=2: on launches of any size */
+    bool ok;
+    if (try_dem_grid(x, k0, D, rD, rDlo, force, &ok)) return 1;
+    if (ok) {
+      x->dem_grid = 10;
+      x->dem_grid_exp = e;
       break;
+    }
+  }
+  /* no decimal grid: one attempt at the binary grid the elevations themselves name.  2^-s is the coarsest power of two all of
+   * them are multiples of (zeros lie on every grid), so vmin * 2^s is an exact integer and rD = 2^-s needs no second word.
+   * s <= 52: a finer grid cannot hold real terrain in 31 bits of relief, and D stays finite whatever vmin is; s >= 1: an
+   * integer grid was e = 0's to take.  WDPM_DEM_BINARY=0: never (the decimal grids alone, for A/B runs) */
+  const char *envb = getenv("WDPM_DEM_BINARY");
+  if (!x->dem32_encodable && low != ~0ull && !(envb && atoi(envb) == 0)) {
+    const long long s = 1075 - (long long)low;
+    if (s >= 1 && s <= 52) {
+      const double D = ldexp(1.0, (int)s), rD = ldexp(1.0, -(int)s), k0 = rint(vmin * D);
+      if (fabs(k0) < 4.0e15) {
+        bool ok;
+        if (try_dem_grid(x, k0, D, rD, 0.0, force, &ok)) return 1;
+        if (ok) {
+          x->dem_grid = 2;
+          x->dem_grid_exp = (int)s;
+        }
+      }
     }
   }
   /* second level: the codes as 16-bit offsets from one base per 48 columns of a row - where the terrain allows it (WDPM_DEM16=0: never) */
@@ -804,6 +840,8 @@ int wdpm_get_option(wdpm_ctx *x, int32_t key, int64_t *value) {
   else if (key == WDPM_OPT_TILES_WORKED) *value = x->stat_active;
   else if (key == WDPM_OPT_SPARSE) *value = x->sparse ? 1 : 0;
   else if (key == WDPM_OPT_GRAPH_LAUNCHES) *value = x->graph_launches;
+  else if (key == WDPM_OPT_DEM_GRID) *value = x->dem_grid;          /* what upload found, whatever WDPM_OPT_DEM32 was set to since */
+  else if (key == WDPM_OPT_DEM_GRID_EXP) *value = x->dem_grid_exp;
   else if (key == WDPM_OPT_GUARD_BAD) return guard_damage(x, value);
   else return fail("wdpm_get_option: unknown option %d", key);
   return 0;

@@ -50,7 +50,7 @@ struct wdpm_ctx {
   double flush_thres;           /* the threshold of the current block: the flush still owed to d_w[cur] (flush_pending)
                                    and to the snapshot when wdpm_max_diff reads it; -inf = none */
   double *d_scal;               /* [0] totaldrain, [1] olddrain */
-  unsigned long long *d_bits;   /* max-diff reduction cell */
+  unsigned long long *d_bits;   /* max-diff reduction cell; three words for wdpm_launch_dem_min */
   double *h_pin;                /* pinned staging: 4 doubles */
   unsigned *h_iter2_err;        /* pinned, and written by the device: Iter2Args::err (looked at wherever the host waits for the stream) */
   unsigned *d_iter2_err;        /* the same word as the device sees it */
@@ -69,6 +69,7 @@ struct wdpm_ctx {
   int *d_dem32;                 /* the DEM as verified-lossless 32-bit codes (wdpm_kernels.h::DemCode) */
   DemCode code;                 /* code.q == d_dem32 while the uploaded DEM is encodable and the option is on */
   bool dem32_encodable;
+  int dem_grid, dem_grid_exp;   /* what upload found: D = dem_grid ^ dem_grid_exp (10^e or 2^s), 0 / 0 while the fp64 DEM is in charge (WDPM_OPT_DEM_GRID, _EXP) */
   unsigned short *d_dem16;      /* the codes once more as 16-bit offsets from d_gbase (DemCode::h, ::gb); code.h is set while they are in use */
   int *d_gbase;
   bool dem16_encodable;

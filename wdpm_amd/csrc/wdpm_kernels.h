@@ -12,14 +12,16 @@
 
 /* The static DEM as 32-bit codes (4 B per cell instead of 8 in the iteration kernel's HBM traffic):
  * dem[i] == dem32_decode(q[i]) BIT FOR BIT for every cell, verified on the device when the DEM is
- * uploaded (wdpm_launch_dem_encode); NODATA is INT32_MIN.  Real DEMs are decimal text, i.e.
- * v = k / 10^e for an integer k, and the decode is the correctly rounded quotient; a raster that
- * is not of that form (any cell fails the check for e = 0..6) simply keeps the fp64 DEM. */
+ * uploaded (wdpm_launch_dem_encode); NODATA is INT32_MIN.  DEMs read from decimal text are
+ * v = k / 10^e for an integer k, and the decode is the correctly rounded quotient; DEMs that were
+ * binary all along (Float32 rasters written with full digits, float -> double) are v = k / 2^s
+ * exactly, on the grid of their lowest set bit.  D is 10^e (e = 0..6, tried first) or 2^s
+ * (s = 1..52); a raster that is of neither form (some cell fails every check) keeps the fp64 DEM. */
 struct DemCode {
   const int *q;      /* rows x ncp codes, or nullptr when the raster is not encodable */
   double k0;         /* integer offset: k = q + k0 */
-  double D, rD;      /* 10^e and its correctly rounded reciprocal */
-  double rDlo;       /* RN(1 / D - rD): the reciprocal's second word (wdpm_stencil.h::dem_quotient) */
+  double D, rD;      /* 10^e or 2^s, and its correctly rounded reciprocal (exact for 2^s) */
+  double rDlo;       /* RN(1 / D - rD): the reciprocal's second word (wdpm_stencil.h::dem_quotient); 0 for 2^s */
   int force;         /* use the codes on launches of any size (tests); normally only where they pay */
   /* Second level (tried in round 3 at +0.7 % when the kernel was bound by instruction issue alone; kept in round 4, when it
    * is as close to the memory system's roof): the same codes as 16-bit offsets from one 32-bit base per group of kDemGroup
@@ -34,7 +36,8 @@ struct DemCode {
 };
 constexpr int kDemGroup = 48;
 /* smallest valid (finite) dem value, as an order-preserving uint64 key in key[0] (all ones: none), and the bit image of the
- * largest |dem| over the valid cells in key[1] (0: none) */
+ * largest |dem| over the valid cells in key[1] (0: none); in key[2] the smallest t + 1075 over the valid cells v != 0, 2^t being the
+ * weight of v's lowest set bit - every valid cell is a multiple of 2^(key[2] - 1075) (all ones: no valid cell other than zeros) */
 hipError_t wdpm_launch_dem_min(const double *dem, size_t cells, unsigned long long *key, hipStream_t s);
 double wdpm_dem_key_to_double(unsigned long long key);
 /* q[i] = code of dem[i]; *bad |= 1 if any cell does not decode to exactly dem[i] */

@@ -176,10 +176,19 @@ double wdpm_dem_key_to_double(unsigned long long key) {
   return pun.d;
 }
 
+// biased exponent of the lowest set bit of a non-zero |v| (bit image ab): v is a multiple of 2^(dem_grid_word - 1075) and of no higher
+// power of two.  A subnormal's exponent field is 0 and stands for 1 without the implicit bit, so both kinds land on one scale.
+__device__ __forceinline__ int dem_grid_word(const unsigned long long ab) {
+  const int ex = (int)(ab >> 52);
+  const unsigned long long sig = (ab & 0x000fffffffffffffull) | (ex ? 0x0010000000000000ull : 0ull);
+  return (ex ? ex : 1) + __ffsll((long long)sig) - 1;
+}
+
 __global__ void __launch_bounds__(256)
 dem_min_kernel(const double *__restrict__ dem, size_t n, unsigned long long *key) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   unsigned long long m = ~0ull, a = 0;
+  int t = 0x7fffffff;                                         // coarsest binary grid all non-zero valid cells lie on; zeros lie on every grid
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     const double v = dem[i];
     if (cell_valid(v)) {
@@ -187,20 +196,31 @@ dem_min_kernel(const double *__restrict__ dem, size_t n, unsigned long long *key
       m = kx < m ? kx : m;
       const unsigned long long ab = (unsigned long long)__double_as_longlong(v) & 0x7fffffffffffffffull;   // |v|: monotone as an integer
       a = ab > a ? ab : a;
+      if (ab) {
+        const int tv = dem_grid_word(ab);
+        t = tv < t ? tv : t;
+      }
     }
   }
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) {
     const unsigned long long o = __shfl_xor(m, off, 64), oa = __shfl_xor(a, off, 64);
+    const int ot = __shfl_xor(t, off, 64);
     m = o < m ? o : m;
     a = oa > a ? oa : a;
+    t = ot < t ? ot : t;
   }
-  if ((threadIdx.x & 63) == 0 && m != ~0ull) { atomicMin(key, m); atomicMax(key + 1, a); }
+  if ((threadIdx.x & 63) == 0 && m != ~0ull) {
+    atomicMin(key, m);
+    atomicMax(key + 1, a);
+    if (t != 0x7fffffff) atomicMin(key + 2, (unsigned long long)t);
+  }
 }
 
 hipError_t wdpm_launch_dem_min(const double *dem, size_t cells, unsigned long long *key, hipStream_t s) {
   hipError_t e = hipMemsetAsync(key, 0xff, sizeof(unsigned long long), s);
   if (e == hipSuccess) e = hipMemsetAsync(key + 1, 0, sizeof(unsigned long long), s);
+  if (e == hipSuccess) e = hipMemsetAsync(key + 2, 0xff, sizeof(unsigned long long), s);
   if (e != hipSuccess || cells == 0) return e;
   size_t blocks = (cells + 255) / 256;
   if (blocks > 2048) blocks = 2048;

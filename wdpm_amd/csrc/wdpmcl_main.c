@@ -17,6 +17,7 @@
  *     12/13 arguments, short parameter file) print the usage text and exit 42 instead.
  *   - WDPM_REPORT_BACKEND=1 adds one line to the report (after the "Using ... for Computation" lines) naming the
  *     back-end, the devices and the decomposition actually used; off by default so that stdout stays the reference's.
+ *     With it, stderr also says per row block how the DEM is streamed (fp64, 32-bit or 16-bit codes, the grid 10^-e or 2^-s).
  *   - WDPM_COLOR_RELIEF=<colour map file> hands the output raster to `gdaldem color-relief` once it is written,
  *     as the reference's src/cmap_black.sh does for the GUI's PNG button (<output>.png; the .aux.xml is removed).
  *   - WDPM_DEVICE=<n> selects the HIP device (default 0).  WDPM_GPUS=<N> spreads the raster over
@@ -761,6 +762,21 @@ int main(int argc, char **argv) {
     if (getenv("WDPM_REPORT_BACKEND") && atoi(getenv("WDPM_REPORT_BACKEND")) != 0)   /* opt-in: the report is no longer the reference's */
       printf("%41s %s, %d device%s%s\n", "Computation back-end:", wdpm_backend_name(), ndev, ndev == 1 ? "" : "s (row blocks)",
              ndev > 1 && hk >= 0 && hk < 4 ? halo_name[hk] : "");
+    /* ... and, on stderr, how each row block streams its DEM (include/wdpm.h: WDPM_OPT_DEM32, _DEM16, _DEM_GRID): every block
+     * encodes its own rows and may find a grid of its own */
+    if (getenv("WDPM_REPORT_BACKEND") && atoi(getenv("WDPM_REPORT_BACKEND")) != 0)
+      for (int i = 0; i < nblk; i++) {
+        int64_t c32 = 0, c16 = 0, grid = 0, gexp = 0;
+        wdpm_ctx *bc = wdpm_rank_ctx(wdpm_group_rank(ctx, i));
+        ABI_TRY(wdpm_get_option(bc, WDPM_OPT_DEM32, &c32));
+        ABI_TRY(wdpm_get_option(bc, WDPM_OPT_DEM16, &c16));
+        ABI_TRY(wdpm_get_option(bc, WDPM_OPT_DEM_GRID, &grid));
+        ABI_TRY(wdpm_get_option(bc, WDPM_OPT_DEM_GRID_EXP, &gexp));
+        if (c32 && grid)
+          fprintf(stderr, "WDPMCL: block %d DEM: %s codes on the grid %d^-%d m\n", i, c16 == 1 ? "16-bit" : "32-bit", (int)grid, (int)gexp);
+        else
+          fprintf(stderr, "WDPMCL: block %d DEM: fp64\n", i);
+      }
   }
   {
     int64_t valid = 0;
