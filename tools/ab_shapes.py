@@ -2,7 +2,8 @@
 """interleaved A/B of HIP library builds over the shapes that matter (tools/shape_bench.py per run, one process each):
     ab_shapes.py <rounds> <variant> [<variant> ...]      variant = "base" (the tree's library) or the <name> of
     wdpm_amd/csrc/alt_<name>_libwdpm_hip.so, optionally followed by NAME=VALUE words exported for it ("base WDPM_CLAMP=0")
-    SHAPES="4096x4096:add 2116x16384:add ..." overrides the default list."""
+    SHAPES="4096x4096:add 2116x16384:add ..." overrides the default list.
+    Stops with a non-zero exit status at the first run that fails or times out."""
 import os, re, statistics, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 rounds = int(sys.argv[1]); variants = sys.argv[2:]
@@ -18,11 +19,15 @@ for sh in shapes:
             if words[0] != "base": env["WDPM_HIP_LIB"] = os.path.join(root, "wdpm_amd/csrc/alt_%s_libwdpm_hip.so" % words[0])
             for w in words[1:]:
                 k, val = w.split("=", 1); env[k] = val
-            out = subprocess.run([sys.executable, os.path.join(root, "tools/shape_bench.py"), R, C, iters, "fused", module], env=env,
-                                 capture_output=True, text=True, timeout=300)
+            try:
+                out = subprocess.run([sys.executable, os.path.join(root, "tools/shape_bench.py"), R, C, iters, "fused", module], env=env,
+                                     capture_output=True, text=True, timeout=300)
+            except subprocess.TimeoutExpired:
+                sys.exit("TIMED OUT %s %s: stopping, nothing more is started on the card" % (sh, v))
             m = re.search(r"([\d.]+) us/iteration", out.stdout)
-            if m: res[v].append(float(m.group(1)))
-            else: print("FAILED", sh, v, out.stderr[-300:], flush=True)
+            if out.returncode or not m:    # a run that failed may have faulted the card: start nothing more on it
+                sys.exit("FAILED %s %s (exit status %d): stopping\n%s" % (sh, v, out.returncode, out.stderr[-300:]))
+            res[v].append(float(m.group(1)))
     line = "%-18s" % sh
     base = None
     for v in variants:

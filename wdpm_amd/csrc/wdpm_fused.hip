@@ -49,6 +49,10 @@
  *                           through LDS: small and mid-size rasters (round 3; 482^2 add 7.3 -> 5.2 us, drain 12.1 -> 8.4)
  *   tri_iteration_kernel    one wave, nine (twelve) rows in, three (six) out, row blocks in lockstep: what is between the two,
  *                           and a small raster's last launch of a block (max diff folded in)
+ * The marching kernel has two loops: its own, and iter2_march for launches that run two iterations (producer and consumer waves).
+ * What a step of either does with its rows - the lane offsets, the inline-asm prefetch and its exact wait, the decode into the
+ * window, the edge mask, `deep`, the staged stores, the window slide - is written once, in the functions in front of iter2_march;
+ * the loops themselves hold what is theirs alone.  owed_drain_sum, fold_max_diff and any_above_3m serve all three kernels.
  * plan_iteration (wdpm_dispatch.h) picks by size, module and what is known about the raster.
  */
 #include "wdpm_kernels.h"
@@ -328,6 +332,255 @@ constexpr int fused_built_for() {
 }
 
 /* ---------------------------------------------------------------------------------------------
+ * The parts of a marching step that the single loop (fused_iteration_kernel) and the loop of two-iteration launches (iter2_march)
+ * share - one implementation, templated on what differs: DEM32 (0 / 1 / 2), EDGE (a wave that can touch cells outside the slab) and
+ * WATER (the water rows come from memory: the single loop and a two-iteration producer; a consumer takes them out of the ring).
+ * A step of either loop keeps this order: the new rows' loads issued (prefetch_rows), the previous step's stores behind them
+ * (StoreSide::write_staged), the stages, the wait for the loads (wait_rows), the slide (slide_window).
+ * --------------------------------------------------------------------------------------------- */
+
+/* lane byte offsets inside a row: interior waves use one offset + immediates, edge waves clamp
+ * every column into the raster (values of clamped cells are masked on use) */
+/* Edge waves clamp the row (scalar) and the lane's first column into the raster and read their three columns with the same
+ * one-offset loads as everybody else: a lane whose columns straddle the row's end reads up to two cells past it - the next
+ * row's first cells, or, in the slab's last row, the 192 spare cells behind every raster wdpm_create allocates (16 codes behind
+ * the DEM codes) - and masks them on use, as it masks whole lanes beyond the raster.  (Rounds 1 - 3 clamped column by column:
+ * nine loads per row instead of three, and the edge waves were the last of every launch to end, round 4.) */
+struct RowOffsets {
+  int voff0;     // the lane's first column in an 8-byte raster row; loop-invariant: the clamp costs the interior waves nothing
+  int qoff0;     // the same for the 4-byte dem codes,
+  int hoff0;     // the 2-byte offsets
+  int goff0;     // and the 4-byte group bases (one per kDemGroup columns)
+  __device__ __forceinline__ RowOffsets(const int colb, const int ncp)
+      : voff0(8 * (colb < ncp ? colb : ncp - 1)), qoff0(voff0 / 2), hoff0(voff0 / 4), goff0(4 * ((voff0 / 8) / kDemGroup)) {}
+};
+
+/* Prefetch of the three rows starting at r0 into raw registers.  The loads are issued with
+ * inline asm (saddr form: wave-uniform row base in SGPRs + a per-lane byte offset) so that
+ * they stay exactly here, one whole step ahead of their use, and are waited for with an exact
+ * `s_waitcnt vmcnt(9)` (the 9 stores of the step are the only younger memory operations).
+ * Left to the compiler the loads get sunk next to their consumer or guarded by vmcnt(0), which
+ * exposes a full memory round trip per step.  The registers are not read before wait_rows().
+ * `dem` is read only where DEM32 == 0. */
+template <int DEM32, bool EDGE, bool WATER>
+__device__ __forceinline__ void prefetch_rows(Prefetched &P, const int r0, const RowOffsets &o, const double *__restrict__ win,
+                                              const double *__restrict__ dem, const DemCode &code, const SlabGeom g) {
+  const size_t pitch = (size_t)g.ncp;
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    int r = r0 + i;
+    if (EDGE) r = r < g.rows ? r : g.rows - 1;
+#ifdef WDPM_ABLATE_HBM   /* timing experiments only (tools/build_variant.sh ablateN -DWDPM_ABLATE_HBM=N, then tools/ab_interleaved.sh): what the kernel costs when its rows come from / go to the caches
+                            instead of HBM.  Bits: 1 = the water loads come from the raster's first 48 rows, 2 = the stores land there,
+                            4 = the DEM loads come from there.  Same instructions, same number of memory operations, wrong results. */
+    const int rw = (WDPM_ABLATE_HBM & 1) ? r % 48 : r, rdm = (WDPM_ABLATE_HBM & 4) ? r % 48 : r;
+#else
+    const int rw = r, rdm = r;
+#endif
+    if (WATER) {
+      const double *bw = win + (size_t)rw * pitch;     // wave-uniform, as every row base
+      asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(P.NW[i][0]) : "v"(o.voff0), "s"(bw) : "memory");
+      asm volatile("global_load_dwordx2 %0, %1, %2 offset:8" : "=v"(P.NW[i][1]) : "v"(o.voff0), "s"(bw) : "memory");
+      asm volatile("global_load_dwordx2 %0, %1, %2 offset:16" : "=v"(P.NW[i][2]) : "v"(o.voff0), "s"(bw) : "memory");
+    }
+    if (DEM32 == 2) {
+      const unsigned short *bh = code.h + (size_t)rdm * pitch;
+      const int *bg = code.gb + (size_t)rdm * code.ngroups;
+      asm volatile("global_load_ushort %0, %1, %2" : "=v"(P.qh[i][0]) : "v"(o.hoff0), "s"(bh) : "memory");
+      asm volatile("global_load_ushort %0, %1, %2 offset:2" : "=v"(P.qh[i][1]) : "v"(o.hoff0), "s"(bh) : "memory");
+      asm volatile("global_load_ushort %0, %1, %2 offset:4" : "=v"(P.qh[i][2]) : "v"(o.hoff0), "s"(bh) : "memory");
+      asm volatile("global_load_dword %0, %1, %2" : "=v"(P.gbv[i]) : "v"(o.goff0), "s"(bg) : "memory");
+    } else if (DEM32) {
+      const int *bq = code.q + (size_t)rdm * pitch;
+      asm volatile("global_load_dwordx3 %0, %1, %2" : "=v"(P.qi[i]) : "v"(o.qoff0), "s"(bq) : "memory");
+    } else {
+      const double *bd = dem + (size_t)rdm * pitch;
+      asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(P.ND[i][0]) : "v"(o.voff0), "s"(bd) : "memory");
+      asm volatile("global_load_dwordx2 %0, %1, %2 offset:8" : "=v"(P.ND[i][1]) : "v"(o.voff0), "s"(bd) : "memory");
+      asm volatile("global_load_dwordx2 %0, %1, %2 offset:16" : "=v"(P.ND[i][2]) : "v"(o.voff0), "s"(bd) : "memory");
+    }
+  }
+}
+
+/* the wait that makes the prefetched registers readable; every register is an in/out operand so
+ * no use can be scheduled above it.  YOUNGER = memory operations issued after the loads, counted exactly: 0, or the 9 stores of a
+ * step (a two-iteration producer issues no memory operation behind its loads, a consumer its nine stores). */
+template <int DEM32, bool WATER, int YOUNGER>
+__device__ __forceinline__ void wait_rows(Prefetched &P) {
+#define WDPM_ROWS_W "+v"(P.NW[0][0]), "+v"(P.NW[0][1]), "+v"(P.NW[0][2]), "+v"(P.NW[1][0]), "+v"(P.NW[1][1]), \
+                    "+v"(P.NW[1][2]), "+v"(P.NW[2][0]), "+v"(P.NW[2][1]), "+v"(P.NW[2][2])
+#define WDPM_ROWS_D "+v"(P.ND[0][0]), "+v"(P.ND[0][1]), "+v"(P.ND[0][2]), "+v"(P.ND[1][0]), "+v"(P.ND[1][1]), \
+                    "+v"(P.ND[1][2]), "+v"(P.ND[2][0]), "+v"(P.ND[2][1]), "+v"(P.ND[2][2])
+#define WDPM_ROWS_H "+v"(P.qh[0][0]), "+v"(P.qh[0][1]), "+v"(P.qh[0][2]), "+v"(P.qh[1][0]), "+v"(P.qh[1][1]), "+v"(P.qh[1][2]), \
+                    "+v"(P.qh[2][0]), "+v"(P.qh[2][1]), "+v"(P.qh[2][2]), "+v"(P.gbv[0]), "+v"(P.gbv[1]), "+v"(P.gbv[2])
+#define WDPM_ROWS_Q "+v"(P.qi[0]), "+v"(P.qi[1]), "+v"(P.qi[2])
+#define WDPM_WAIT_ROWS(...) asm volatile("s_waitcnt vmcnt(%[younger])" : __VA_ARGS__ : [younger] "n"(YOUNGER) : "memory")
+  static_assert(WATER || DEM32 != 0, "a wave that loads neither water nor DEM rows has nothing to wait for");
+  if constexpr (WATER && DEM32 == 0) WDPM_WAIT_ROWS(WDPM_ROWS_W, WDPM_ROWS_D);
+  else if constexpr (WATER && DEM32 == 2) WDPM_WAIT_ROWS(WDPM_ROWS_W, WDPM_ROWS_H);
+  else if constexpr (WATER) WDPM_WAIT_ROWS(WDPM_ROWS_W, WDPM_ROWS_Q);
+  else if constexpr (DEM32 == 2) WDPM_WAIT_ROWS(WDPM_ROWS_H);
+  else WDPM_WAIT_ROWS(WDPM_ROWS_Q);
+#undef WDPM_WAIT_ROWS
+#undef WDPM_ROWS_Q
+#undef WDPM_ROWS_H
+#undef WDPM_ROWS_D
+#undef WDPM_ROWS_W
+}
+
+/* consume the prefetched rows into window slots 4..6; the device DEM already holds +inf for
+ * NODATA cells, so only edge waves have anything to mask (mask_outside) */
+template <int DEM32, bool FLUSH>
+__device__ __forceinline__ void decode_rows(double (&W)[7][3], double (&D)[7][3], const Prefetched &P, const DemCode &code, const double thres) {
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      // FLUSH: the block's threshold flush (WDPMCL.c:1059-1062) applied to the water as it arrives
+      W[4 + i][j] = FLUSH && P.NW[i][j] < thres ? 0.0 : P.NW[i][j];
+      if (DEM32 == 2) D[4 + i][j] = dem16_decode_nan(P.qh[i][j], P.gbv[i], code.k0, code.D, code.rD, code.rDlo);
+      else if (DEM32) D[4 + i][j] = dem32_decode_nan(P.qi[i][j], code.k0, code.D, code.rD, code.rDlo);
+      else D[4 + i][j] = P.ND[i][j];
+    }
+}
+
+/* edge waves: cells of window slots 4..6 (slab rows r0 .. r0 + 2) outside the slab hold dem = +inf, w = 0 */
+__device__ __forceinline__ void mask_outside(double (&W)[7][3], double (&D)[7][3], const int r0, const int colb, const SlabGeom g) {
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    const bool row_ok = r0 + i < g.rows;
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      const bool ok = row_ok & (colb + j < g.ncp);
+      W[4 + i][j] = ok ? W[4 + i][j] : 0.0;
+      D[4 + i][j] = ok ? D[4 + i][j] : WDPM_INF;
+    }
+  }
+}
+
+/* "does any lane hold a depth above 3 m in these three rows?" - the high words of the nine values compared as integers: a negative
+ * or NaN depth counts as deep.  Wave-uniform. */
+__device__ __forceinline__ bool any_above_3m(const double (*w)[3]) {
+  auto hi = [](const double v) { return (unsigned)__double2hiint(v); };
+  auto max3 = [](const unsigned a, const unsigned b, const unsigned c) { const unsigned m = a > b ? a : b; return m > c ? m : c; };
+  unsigned hm = max3(hi(w[0][0]), hi(w[0][1]), hi(w[0][2]));
+  hm = max3(hm, hi(w[1][0]), hi(w[1][1]));
+  hm = max3(hm, hi(w[1][2]), hi(w[2][0]));
+  hm = max3(hm, hi(w[2][1]), hi(w[2][2]));
+  return __ballot(hm > 0x40080000u) != 0;               // 0x40080000'00000000 = 3.0
+}
+
+/* CLAMP (round 4; wdpm_stencil.h::eighth_clamped): one instruction less per neighbour step, exact while no flow of the step
+ * exceeds 1 m.  A flow is at most (the centre's depth + half an ulp of its elevation) / 8, a cell receives in at most eight
+ * of an iteration's nine passes (it is the centre of the ninth), and within one pass in at most one block: if every depth of
+ * the window was <= M when it was loaded, every depth the window holds during the iteration is <= M (9/8)^8 + 8 ulp < 2.566 M + 8 ulp.
+ * With M < 3.000002 m (any_above_3m on the nine values a step loads) and elevations below 2^30 m in magnitude (the host's part:
+ * `no_clamp`) that is < 7.7 m.  The seven rows of a step's window were loaded by this step and the two before it: bits 0..2 of
+ * `deep`; bit 3 = no_clamp.  A step with any of them set runs the unclamped stages - same results, the round-3 instruction
+ * count.  Wave-uniform: one scalar branch per step. */
+__device__ __forceinline__ int deep_next(const int deep, const double (&W)[7][3]) {
+  return (deep & 8) | ((deep & 3) << 1) | (any_above_3m(&W[4]) ? 1 : 0);
+}
+
+/* slide the window down three rows */
+__device__ __forceinline__ void slide_window(double (&W)[7][3], double (&D)[7][3]) {
+#pragma unroll
+  for (int k = 0; k < 4; k++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) { W[k][j] = W[k + 3][j]; D[k][j] = D[k + 3][j]; }
+}
+
+/* Store side of a marching wave: after the LDS transpose, store instruction k = 0,1,2 writes the strip-relative
+ * columns lo + 64k + lane of the exact output range [lo, hi].  Lanes past hi are clamped to hi:
+ * they read the same LDS word and write the same address with the same value as the last valid
+ * lane, so every store is unconditional (fixed instruction count) and nothing is written twice
+ * with different data. */
+struct StoreSide {
+  double *wout;
+  // Cells a wave must not write (outside its exact output block) are redirected to a 64-double
+  // dump area behind the raster instead of being branched around: the loop then issues the same
+  // number of loads and stores on every trip, so the compiler can wait with exact vmcnt counts
+  // (with conditional memory operations it falls back to vmcnt(0) at the top of each step, which
+  // exposes the full latency of the stores just issued — measured 27 % of the kernel).
+  // (192 doubles behind the raster, allocated by wdpm_create: a dumped row goes there at the same lane offsets as a stored one, so
+  // that every store is "uniform base + lane offset" - the saddr form, no 64-bit address arithmetic on the vector unit: nine
+  // v_lshl_add_u64 per step less, round 4)
+  char *dump;
+  size_t pitch;
+  int c0;                 // the strip's first column
+  int or_lo, or_hi;       // the slab rows this wave stores
+  bool any;               // false: nothing of this strip is stored (a two-iteration consumer whose strip lies beyond the raster)
+  int scol[3];
+  unsigned soff[3];       // the same as byte offsets: a store's address is a wave-uniform row base (SGPRs) + this
+
+  __device__ __forceinline__ StoreSide(double *const wout_, const SlabGeom g, const int c0_, const int or_lo_, const int or_hi_)
+      : wout(wout_), dump(reinterpret_cast<char *>(wout_ + (size_t)g.rows * g.ncp)), pitch((size_t)g.ncp), c0(c0_), or_lo(or_lo_),
+        or_hi(or_hi_), any(true) {}
+  /* [lo, hi]: the strip-relative columns of the exact output range */
+  __device__ __forceinline__ void columns(const int lo, const int hi, const int lane) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) { scol[k] = lo + 64 * k + lane < hi ? lo + 64 * k + lane : hi; soff[k] = 8u * (unsigned)scol[k]; }
+  }
+  // the three staged rows [rb, rb+2] from LDS to HBM: 9 unconditional stores.  In two halves: the LDS reads go out at
+  // the very top of a step, ahead of the decode work, so that their round trip is over when the stores want the values
+  // (issued right in front of the stores, each step stalled on it: +0.4 % at 8192^2, profiles/r02/early_lds_ab.txt)
+  __device__ __forceinline__ void read_staged(double (&staged)[3][3], const double *stage_lds) const {
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int k = 0; k < 3; k++) staged[i][k] = stage_lds[i * kStripIn + scol[k]];
+  }
+  __device__ __forceinline__ void write_staged(const double (&staged)[3][3], const int rb) const {
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+      const int r = rb + i;
+      const bool row_ok = r >= or_lo && r <= or_hi && any;       // wave-uniform
+      // rows outside the chunk's output range (first / last trips only) go to the dump area
+#ifdef WDPM_ABLATE_HBM
+      char *const orow = row_ok ? reinterpret_cast<char *>(wout + (size_t)((WDPM_ABLATE_HBM & 2) ? r % 48 : r) * pitch + c0) : dump;
+#else
+      char *const orow = row_ok ? reinterpret_cast<char *>(wout + (size_t)r * pitch + c0) : dump;   // wave-uniform
+#endif
+      // Stores as inline asm, saddr form: a wave-uniform row base in SGPRs + the lane's byte offset, no address arithmetic on
+      // the vector unit.  Ordinary stores, not non-temporal ones (round 4).  Rounds 1 - 3 believed they were choosing between
+      // the two by size: left to the compiler, the two arms of that branch (the same store with and without !nontemporal)
+      // had been merged into ONE plain store with a 64-bit VALU address - round 3's final ISA has no `nt` store in this
+      // kernel at all.  With real `nt` stores measured against plain ones (profiles/r04/stores_shapes_ab.txt): add 4096^2
+      // 108.0 against 103.1 us, 3000^2 65.9 against 62.9, drain 8192^2 401.6 against 397.8, the 1053-row drain slab 77.7
+      // against 75.2; a tie at 8192^2 add, on the 2116-row add slab and at 16384^2; drain 4096^2 128.9 against 130.3.
+#pragma unroll
+      for (int k = 0; k < 3; k++) asm volatile("global_store_dwordx2 %0, %1, %2" : : "v"(soff[k]), "v"(staged[i][k]), "s"(orow) : "memory");
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+};
+
+/* Drain: the sum the previous iteration's drain() (WDPMCL.c:1089 -> :1859-1897) owes to totaldrain - the outlet's 3x3, row-major
+ * from 0.0, valid cells with water (:1877-1884).  The caller knows that the outlet lies inside the slab's border. */
+__device__ __forceinline__ double owed_drain_sum(const double *__restrict__ win, const double *__restrict__ dem, const SlabGeom g) {
+  double sum = 0.0;
+#pragma unroll
+  for (int i = -1; i <= 1; i++)
+#pragma unroll
+    for (int j = -1; j <= 1; j++) {
+      const size_t k = (size_t)(g.dr + i) * g.ncp + (g.dc + j);
+      const double wk = win[k];
+      if (dem[k] < WDPM_INF && wk > 0) sum += wk;
+    }
+  return sum;
+}
+
+/* MD: the lanes' max |w - oldw| folded over the wave, one atomicMax per wave on the uint64 image (>= 0: order-preserving) */
+__device__ __forceinline__ void fold_max_diff(double md_max, const MaxDiffArgs &md, const int lane) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const double o = __shfl_xor(md_max, off, 64);
+    md_max = o > md_max ? o : md_max;
+  }
+  if (lane == 0 && md_max > 0.0) atomicMax(md.bits, (unsigned long long)__double_as_longlong(md_max));
+}
+
+/* ---------------------------------------------------------------------------------------------
  * Two iterations per launch (Iter2Args; geometry: wdpm_dispatch.h::plan_iter2).  A second marching loop of the gate-free add /
  * subtract instantiations that stream the DEM as codes, chosen by a kernel argument.
  *
@@ -391,21 +644,13 @@ __device__ __forceinline__ void iter2_march(const double *__restrict__ win, doub
   int deep = !no_clamp ? 0 : 8;
   const int colb = c0 + 3 * lane;
   // consumer: the strip-relative columns [lo, hi] it stores (see the single loop); a strip beyond the raster stores nothing
-  unsigned soff[3];
-  int scol[3];
-  bool store_any;
+  StoreSide st(wout, g, c0, or_lo, or_hi);
   {
     const int lo = j == 0 ? (grp == 0 ? 0 : kGroupHaloL) : kHaloL;
     int hi = kStripIn - 1 - (j == 3 ? kGroupHaloR : kHaloR);
     if (hi > g.ncp - 1 - c0) hi = g.ncp - 1 - c0;
-    store_any = hi >= lo;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-      int c = lo + 64 * k + lane < hi ? lo + 64 * k + lane : hi;
-      c = store_any ? c : 0;
-      scol[k] = c;
-      soff[k] = 8u * (unsigned)c;
-    }
+    st.any = hi >= lo;
+    st.columns(st.any ? lo : 0, st.any ? hi : 0, lane);   // nothing to store: column 0 throughout
   }
   // producer: where its columns go in a ring row - its exact ones (and the group's outer halos); the others to the row's dump cells
   int dcol[3];
@@ -418,11 +663,7 @@ __device__ __forceinline__ void iter2_march(const double *__restrict__ win, doub
   const int rcol = kStripOut * j + 3 * lane;              // consumer: its first column in a ring row
   // The hand words through a pointer that says LDS: ds_read / ds_write in the wave's in-order LDS queue.  Through a generic pointer
   // they were FLAT operations, each volatile store followed by a wait for every global load and store of the wave in flight.
-#ifdef WDPM_ITER2_FLAT_HAND                               /* A/B builds: as it was */
-  volatile int *const hand_v = hand;
-#else
   volatile __attribute__((address_space(3))) int *const hand_v = (volatile __attribute__((address_space(3))) int *)hand;
-#endif
   const int nb_lo = j > 0 ? j - 1 : 0, nb_hi = j < 3 ? j + 1 : 3;
   bool broken = false;
   // the smallest count of the (up to) three waves of the other role this one exchanges columns with, once it is >= need - or at once
@@ -469,11 +710,7 @@ __device__ __forceinline__ void iter2_march(const double *__restrict__ win, doub
   // Nothing stored depends on their columns - they lie beyond the border column, whose DEM is NODATA and lets nothing across (DESIGN 4.2,
   // tests/test_iter2_retired_strips.py) - but the neighbours read them: the producer leaves +0.0 in its columns of every ring row, so that
   // every ring cell holds a finite value, and either leaves a hand word no await() can exceed, written behind the zeros.
-#ifdef WDPM_ITER2_NO_RETIRE                               /* A/B builds: every wave marches, as it was */
-  const bool retire = false;
-#else
-  const bool retire = producer ? c0 + (j == 0 ? 0 : kHaloL) >= g.ncp : !store_any;     // wave-uniform
-#endif
+  const bool retire = producer ? c0 + (j == 0 ? 0 : kHaloL) >= g.ncp : !st.any;        // wave-uniform
   if (retire) {
     if (producer) {
       for (int r = 0; r < R; r++)
@@ -484,8 +721,6 @@ __device__ __forceinline__ void iter2_march(const double *__restrict__ win, doub
     hand_v[wave] = kIter2Retired;
     return;                                               // no barrier follows; no duration into the balance counters
   }
-  const size_t pitch = (size_t)g.ncp;
-  char *const dump = reinterpret_cast<char *>(wout + (size_t)g.rows * pitch);
   const bool edge = (As + 3 * (nsteps + 1) > g.rows);
   double W[7][3], D[7][3];
 #pragma unroll
@@ -502,46 +737,9 @@ __device__ __forceinline__ void iter2_march(const double *__restrict__ win, doub
   auto march = [&](auto edge_tag, auto role_tag) {
     constexpr bool EDGE = decltype(edge_tag)::value;
     constexpr bool PRODUCER = decltype(role_tag)::value;
-    const int voff0 = 8 * (colb < g.ncp ? colb : g.ncp - 1);
-    const int qoff0 = voff0 / 2, hoff0 = voff0 / 4, goff0 = 4 * ((voff0 / 8) / kDemGroup);
-    // as the single loop's prefetch: inline-asm loads a step ahead of their use; the water rows only for a producer
-    auto prefetch = [&](Prefetched &P, const int r0) {
-#pragma unroll
-      for (int i = 0; i < 3; i++) {
-        int r = r0 + i;
-        if (EDGE) r = r < g.rows ? r : g.rows - 1;
-        const double *bw = win + (size_t)r * pitch;
-        const int *bq = code.q + (size_t)r * pitch;
-        const unsigned short *bh = code.h + (size_t)r * pitch;
-        const int *bg = code.gb + (size_t)r * code.ngroups;
-        if (PRODUCER) {
-          asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(P.NW[i][0]) : "v"(voff0), "s"(bw) : "memory");
-          asm volatile("global_load_dwordx2 %0, %1, %2 offset:8" : "=v"(P.NW[i][1]) : "v"(voff0), "s"(bw) : "memory");
-          asm volatile("global_load_dwordx2 %0, %1, %2 offset:16" : "=v"(P.NW[i][2]) : "v"(voff0), "s"(bw) : "memory");
-        }
-        if (DEM32 == 2) {
-          asm volatile("global_load_ushort %0, %1, %2" : "=v"(P.qh[i][0]) : "v"(hoff0), "s"(bh) : "memory");
-          asm volatile("global_load_ushort %0, %1, %2 offset:2" : "=v"(P.qh[i][1]) : "v"(hoff0), "s"(bh) : "memory");
-          asm volatile("global_load_ushort %0, %1, %2 offset:4" : "=v"(P.qh[i][2]) : "v"(hoff0), "s"(bh) : "memory");
-          asm volatile("global_load_dword %0, %1, %2" : "=v"(P.gbv[i]) : "v"(goff0), "s"(bg) : "memory");
-        } else {
-          asm volatile("global_load_dwordx3 %0, %1, %2" : "=v"(P.qi[i]) : "v"(qoff0), "s"(bq) : "memory");
-        }
-      }
-    };
-#define WDPM_I2_W "+v"(P.NW[0][0]), "+v"(P.NW[0][1]), "+v"(P.NW[0][2]), "+v"(P.NW[1][0]), "+v"(P.NW[1][1]), \
-                  "+v"(P.NW[1][2]), "+v"(P.NW[2][0]), "+v"(P.NW[2][1]), "+v"(P.NW[2][2])
-#define WDPM_I2_H "+v"(P.qh[0][0]), "+v"(P.qh[0][1]), "+v"(P.qh[0][2]), "+v"(P.qh[1][0]), "+v"(P.qh[1][1]), "+v"(P.qh[1][2]), \
-                  "+v"(P.qh[2][0]), "+v"(P.qh[2][1]), "+v"(P.qh[2][2]), "+v"(P.gbv[0]), "+v"(P.gbv[1]), "+v"(P.gbv[2])
-#define WDPM_I2_Q "+v"(P.qi[0]), "+v"(P.qi[1]), "+v"(P.qi[2])
-    // YOUNGER: a producer issues no memory operation behind its loads, a consumer its nine stores
-#define WDPM_I2_WAIT(YOUNGER)                                                                               \
-  do {                                                                                                      \
-    if (PRODUCER && DEM32 == 2) asm volatile("s_waitcnt vmcnt(0)" : WDPM_I2_W, WDPM_I2_H : : "memory");     \
-    else if (PRODUCER) asm volatile("s_waitcnt vmcnt(0)" : WDPM_I2_W, WDPM_I2_Q : : "memory");              \
-    else if (DEM32 == 2) asm volatile("s_waitcnt vmcnt(" #YOUNGER ")" : WDPM_I2_H : : "memory");            \
-    else asm volatile("s_waitcnt vmcnt(" #YOUNGER ")" : WDPM_I2_Q : : "memory");                            \
-  } while (0)
+    // a producer loads water and codes as the single loop does (WATER), a consumer the codes alone, its nine stores behind them
+    const RowOffsets off(colb, g.ncp);
+    auto prefetch = [&](Prefetched &P, const int r0) { prefetch_rows<DEM32, EDGE, PRODUCER>(P, r0, off, win, nullptr, code, g); };
 
     int put_slot = 0;                                      // producer: ring row of chunk row rr, rr = 0, 1, 2 ... as they are deposited
     int take_slot = 0;                                     // ring row of the next triple to take (triples never straddle the ring's end)
@@ -559,74 +757,26 @@ __device__ __forceinline__ void iter2_march(const double *__restrict__ win, doub
       hand_v[4 + j] = t + 1;                              // carried out behind the reads
     };
     double staged[3][3];
-    auto read_staged = [&]() {
-#pragma unroll
-      for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int k = 0; k < 3; k++) staged[i][k] = stage_lds[i * kStripIn + scol[k]];
-    };
-    auto write_staged = [&](const int rb) {
-#pragma unroll
-      for (int i = 0; i < 3; i++) {
-        const int r = rb + i;
-        const bool row_ok = r >= or_lo && r <= or_hi && store_any;   // wave-uniform
-        char *const orow = row_ok ? reinterpret_cast<char *>(wout + (size_t)r * pitch + c0) : dump;
-#pragma unroll
-        for (int k = 0; k < 3; k++) asm volatile("global_store_dwordx2 %0, %1, %2" : : "v"(soff[k]), "v"(staged[i][k]), "s"(orow) : "memory");
-      }
-      __builtin_amdgcn_wave_barrier();
-    };
 
     auto step = [&](const int n, Prefetched &P, auto nstages_tag) {
       constexpr int NSTAGES = decltype(nstages_tag)::value;
 #ifdef WDPM_WAVE_TIMES
       wt_phase = n < 4 ? 0 : (n >= nsteps - 4 ? 2 : 1);
 #endif
-      if (!PRODUCER) read_staged();
-#pragma unroll
-      for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int jj = 0; jj < 3; jj++) {
-          W[4 + i][jj] = P.NW[i][jj];
-          if (DEM32 == 2) D[4 + i][jj] = dem16_decode_nan(P.qh[i][jj], P.gbv[i], code.k0, code.D, code.rD, code.rDlo);
-          else D[4 + i][jj] = dem32_decode_nan(P.qi[i][jj], code.k0, code.D, code.rD, code.rDlo);
-        }
-      if (EDGE) {
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-          const bool row_ok = As + 3 * n + i < g.rows;
-#pragma unroll
-          for (int jj = 0; jj < 3; jj++) {
-            const bool ok = row_ok & (colb + jj < g.ncp);
-            W[4 + i][jj] = ok ? W[4 + i][jj] : 0.0;
-            D[4 + i][jj] = ok ? D[4 + i][jj] : WDPM_INF;
-          }
-        }
-      }
-      {
-        auto hi = [](const double v) { return (unsigned)__double2hiint(v); };
-        auto max3 = [](const unsigned a, const unsigned b, const unsigned c) { const unsigned m = a > b ? a : b; return m > c ? m : c; };
-        unsigned hm = max3(hi(W[4][0]), hi(W[4][1]), hi(W[4][2]));
-        hm = max3(hm, hi(W[5][0]), hi(W[5][1]));
-        hm = max3(hm, hi(W[5][2]), hi(W[6][0]));
-        hm = max3(hm, hi(W[6][1]), hi(W[6][2]));
-        deep = (deep & 8) | ((deep & 3) << 1) | (__ballot(hm > 0x40080000u) != 0 ? 1 : 0);
-      }
-#ifdef WDPM_ITER2_EARLY_TAKE                               /* A/B builds: the take a whole step ahead of its use, as it was */
-      if (!PRODUCER) take(P, n + 1);
-#endif
+      if (!PRODUCER) st.read_staged(staged, stage_lds);
+      decode_rows<DEM32, false>(W, D, P, code, 0.0);
+      if (EDGE) mask_outside(W, D, As + 3 * n, colb, g);
+      deep = deep_next(deep, W);
       prefetch(P, As + 3 * (n + 1));
-      if (!PRODUCER) write_staged(A + 3 * (n - 1) - 4);
+      if (!PRODUCER) st.write_staged(staged, A + 3 * (n - 1) - 4);
 
       const int rbase = As + 3 * n - 4;
       if (deep) three_stages<0, false, NSTAGES, 1>(W, D, rbase, g.dr, cdr, ds);
       else three_stages<0, false, NSTAGES, 1 | 2>(W, D, rbase, g.dr, cdr, ds);
-#ifndef WDPM_ITER2_EARLY_TAKE
       // The next triple just in time: its latency is an LDS read, which the staging writes, the wait for the codes and the window
       // slide below cover.  Taken before the stages it kept nine doubles alive across them and asked the producers for their step
       // n + lag + 2 a step early - three rows of the ring's slack given away.
       if (!PRODUCER) take(P, n + 1);
-#endif
 
       if (PRODUCER) {
         // rows rbase .. rbase + 2 are final: into the ring, once the consumers have taken what lies there (chunk rows < 0: nobody
@@ -655,28 +805,21 @@ __device__ __forceinline__ void iter2_march(const double *__restrict__ win, doub
           for (int jj = 0; jj < 3; jj++) stage_lds[i * kStripIn + 3 * lane + jj] = W[i][jj];
         __builtin_amdgcn_wave_barrier();
       }
-      WDPM_I2_WAIT(9);
-#pragma unroll
-      for (int k = 0; k < 4; k++)
-#pragma unroll
-        for (int jj = 0; jj < 3; jj++) { W[k][jj] = W[k + 3][jj]; D[k][jj] = D[k + 3][jj]; }
+      wait_rows<DEM32, PRODUCER, PRODUCER ? 0 : 9>(P);
+      slide_window(W, D);
     };
 
     Prefetched P;
     if (!PRODUCER) take(P, 0);
     prefetch(P, As);
-    WDPM_I2_WAIT(0);
+    wait_rows<DEM32, PRODUCER, 0>(P);
     step(0, P, std::integral_constant<int, 1>{});
     step(1, P, std::integral_constant<int, 2>{});
     for (int n = 2; n < nsteps; n++) step(n, P, std::integral_constant<int, 3>{});
     if (!PRODUCER) {
-      read_staged();
-      write_staged(A + 3 * (nsteps - 1) - 4);
+      st.read_staged(staged, stage_lds);
+      st.write_staged(staged, A + 3 * (nsteps - 1) - 4);
     }
-#undef WDPM_I2_WAIT
-#undef WDPM_I2_Q
-#undef WDPM_I2_H
-#undef WDPM_I2_W
   };
   if (producer) {
     if (edge) march(std::true_type{}, std::true_type{});
@@ -730,13 +873,7 @@ fused_iteration_kernel(const double *__restrict__ win, double *__restrict__ wout
     if (blockIdx.x == 0 && threadIdx.x == 0) bal.rot[bal.parity ^ 1] = (unsigned long long)xcc_phys;   // workgroup 0's XCD = this launch's rotation
   }
   const int share = (int)((blockIdx.x + (unsigned)rot_prev) % 8);
-#ifdef WDPM_XCD_REVERSE   /* timing experiments: XCD x takes the raster's band 7 - x (does a slow XCD stay slow, or the band?) */
-  const int vb = (7 - share) * (gridDim.x / 8) + blockIdx.x / 8;
-#elif defined(WDPM_ORDER_REVERSE)   /* timing experiments: an XCD's workgroups take its band from the bottom up (is it the first rows of the raster that are slow, or the workgroups dispatched first?) */
-  const int vb = share * (gridDim.x / 8) + (gridDim.x / 8 - 1 - blockIdx.x / 8);
-#else
   const int vb = share * (gridDim.x / 8) + blockIdx.x / 8;
-#endif
   // the wave number is the same in all 64 lanes: say so, and everything derived from it (strip,
   // chunk, row bases, loop bounds) lives in SGPRs and is computed on the scalar unit
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -829,30 +966,12 @@ fused_iteration_kernel(const double *__restrict__ win, double *__restrict__ wout
     }
   }
   unsigned long long nzmask = 0;        // lanes that staged a value other than 0.0 (no -0.0 exists where tiles are tracked)
-  // CLAMP (round 4; wdpm_stencil.h::eighth_clamped): one instruction less per neighbour step, exact while no flow of the step
-  // exceeds 1 m.  A flow is at most (the centre's depth + half an ulp of its elevation) / 8, a cell receives in at most eight
-  // of an iteration's nine passes (it is the centre of the ninth), and within one pass in at most one block: if every depth of
-  // the window was <= M when it was loaded, every depth the window holds during the iteration is <= M (9/8)^8 + 8 ulp < 2.566 M + 8 ulp.
-  // With M < 3.000002 m (the high words of the nine values a step loads, compared as integers: a negative or NaN depth counts as
-  // deep) and elevations below 2^30 m in magnitude (the host's part: `no_clamp`) that is < 7.7 m.  The seven rows of a step's
-  // window were loaded by this step and the two before it: bits 0..2 of `deep`; bit 3 = no_clamp.  A step with any of them set
-  // runs the unclamped stages - same results, the round-3 instruction count.  Wave-uniform: one scalar branch per step.
+  // CLAMP: which of the window's rows may hold a depth too large for the clamped neighbour step (see deep_next)
   int deep = (!SZ_SAFE && !no_clamp) ? 0 : 8;
   double md_max = 0.0;                  // MD: this lane's max |w - oldw| over the cells of its output block (WDPMCL.c:1239-1254)
   const int colb = c0 + 3 * lane;
-  // store side: after the LDS transpose, store instruction k = 0,1,2 writes the strip-relative
-  // columns lo + 64k + lane of the exact output range [lo, hi].  Lanes past hi are clamped to hi:
-  // they read the same LDS word and write the same address with the same value as the last valid
-  // lane, so every store is unconditional (fixed instruction count) and nothing is written twice
-  // with different data.
-  int scol[3];
-  unsigned soff[3];                     // the same as byte offsets: a store's address is a wave-uniform row base (SGPRs) + this
-  {
-    const int lo = oc_lo - c0;
-    const int hi = (oc_hi < g.ncp - 1 ? oc_hi : g.ncp - 1) - c0;
-#pragma unroll
-    for (int k = 0; k < 3; k++) { scol[k] = lo + 64 * k + lane < hi ? lo + 64 * k + lane : hi; soff[k] = 8u * (unsigned)scol[k]; }
-  }
+  StoreSide st(wout, g, c0, or_lo, or_hi);
+  st.columns(oc_lo - c0, (oc_hi < g.ncp - 1 ? oc_hi : g.ncp - 1) - c0, lane);
   double *const stage_lds = stage_all[wave];
   volatile int *const my_progress = progress_all + my_word;
   volatile int *const partner_progress = progress_all + (my_word ^ 1);
@@ -871,18 +990,7 @@ fused_iteration_kernel(const double *__restrict__ win, double *__restrict__ wout
     // drain_owed: the previous iteration's drain() (WDPMCL.c:1089 -> :1859-1897) has not been applied to `win`
     // yet - there is no launch of its own for it.  Its sum enters totaldrain here (row-major from 0.0, valid
     // cells with water, :1877-1884), its zeroing of the nine cells (:1885-1889) happens as rows are loaded.
-    if (drain_owed && owner && g.dr >= 1 && g.dr <= g.rows - 2 && g.dc >= 1 && g.dc <= g.ncp - 2) {
-      double sum = 0.0;
-#pragma unroll
-      for (int i = -1; i <= 1; i++)
-#pragma unroll
-        for (int j = -1; j <= 1; j++) {
-          const size_t k = (size_t)(g.dr + i) * g.ncp + (g.dc + j);
-          const double wk = win[k];
-          if (dem[k] < WDPM_INF && wk > 0) sum += wk;
-        }
-      ds.td = ds.td + sum;
-    }
+    if (drain_owed && owner && g.dr >= 1 && g.dr <= g.rows - 2 && g.dc >= 1 && g.dc <= g.ncp - 2) ds.td = ds.td + owed_drain_sum(win, dem, g);
   }
   const bool owed_here = MODULE == 2 && drain_owed && g.dr >= 1 && g.dr <= g.rows - 2 && g.dc >= 1 && g.dc <= g.ncp - 2;
   bool owed_col[3];
@@ -907,138 +1015,16 @@ fused_iteration_kernel(const double *__restrict__ win, double *__restrict__ wout
   // runs centres on every column, the border's included.  Rounds 1 - 4 sent those waves down the masking instantiation of the
   // marching loop: one wave per workgroup, alone on a code path nobody shared its instruction-cache misses with - they ended 3.5 %
   // (8192^2 drain) to 12 % (the 8-GPU drain slab) after everybody else, the last waves of almost every launch
-  // (profiles/r05/first_chunk_row.txt, wave_times_coledge.txt).  -DWDPM_COL_EDGE_MASKS: as before (A/B).
-#ifdef WDPM_COL_EDGE_MASKS
-  const bool edge = (c0 + kStripIn > g.ncp) || (A + 3 * (nsteps + 1) > g.rows);
-#else
+  // (profiles/r05/first_chunk_row.txt, wave_times_coledge.txt).
   const bool edge = (A + 3 * (nsteps + 1) > g.rows);
-#endif
   const size_t pitch = (size_t)g.ncp;
-  // Cells a wave must not write (outside its exact output block) are redirected to a 64-double
-  // dump area behind the raster instead of being branched around: the loop then issues the same
-  // number of loads and stores on every trip, so the compiler can wait with exact vmcnt counts
-  // (with conditional memory operations it falls back to vmcnt(0) at the top of each step, which
-  // exposes the full latency of the stores just issued — measured 27 % of the kernel).
-  // (192 doubles behind the raster, allocated by wdpm_create: a dumped row goes there at the same lane offsets as a stored one, so
-  // that every store is "uniform base + lane offset" - the saddr form, no 64-bit address arithmetic on the vector unit: nine
-  // v_lshl_add_u64 per step less, round 4)
-  char *const dump = reinterpret_cast<char *>(wout + (size_t)g.rows * pitch);
 
   // The marching loop, instantiated for interior (EDGE = false) and edge waves.
   auto march = [&](auto edge_tag) {
     constexpr bool EDGE = decltype(edge_tag)::value;
-    // lane byte offsets inside a row: interior waves use one offset + immediates, edge waves clamp
-    // every column into the raster (values of clamped cells are masked on use)
-    // Edge waves clamp the row (scalar) and the lane's first column into the raster and read their three columns with the same
-    // one-offset loads as everybody else: a lane whose columns straddle the row's end reads up to two cells past it - the next
-    // row's first cells, or, in the slab's last row, the 192 spare cells behind every raster wdpm_create allocates (16 codes behind
-    // the DEM codes) - and masks them on use, as it masks whole lanes beyond the raster.  (Rounds 1 - 3 clamped column by column:
-    // nine loads per row instead of three, and the edge waves were the last of every launch to end, round 4.)
-    const int voff0 = 8 * (colb < g.ncp ? colb : g.ncp - 1);      // loop-invariant: the clamp costs the interior waves nothing
-    const int qoff0 = voff0 / 2;                     // the same for the 4-byte dem codes,
-    const int hoff0 = voff0 / 4;                     // the 2-byte offsets
-    const int goff0 = 4 * ((voff0 / 8) / kDemGroup); // and the 4-byte group bases (one per kDemGroup columns)
-
-    // Prefetch of the three rows starting at r0 into raw registers.  The loads are issued with
-    // inline asm (saddr form: wave-uniform row base in SGPRs + a per-lane byte offset) so that
-    // they stay exactly here, one whole step ahead of their use, and are waited for with an exact
-    // `s_waitcnt vmcnt(9)` (the 9 stores of the step are the only younger memory operations).
-    // Left to the compiler the loads get sunk next to their consumer or guarded by vmcnt(0), which
-    // exposes a full memory round trip per step.  The registers are not read before wait_rows().
-    auto prefetch = [&](Prefetched &P, const int r0) {
-#pragma unroll
-      for (int i = 0; i < 3; i++) {
-        int r = r0 + i;
-        if (EDGE) r = r < g.rows ? r : g.rows - 1;
-#ifdef WDPM_ABLATE_HBM   /* timing experiments only (tools/build_variant.sh ablateN -DWDPM_ABLATE_HBM=N, then tools/ab_interleaved.sh): what the kernel costs when its rows come from / go to the caches
-                            instead of HBM.  Bits: 1 = the water loads come from the raster's first 48 rows, 2 = the stores land there,
-                            4 = the DEM loads come from there.  Same instructions, same number of memory operations, wrong results. */
-        const int rw = (WDPM_ABLATE_HBM & 1) ? r % 48 : r, rdm = (WDPM_ABLATE_HBM & 4) ? r % 48 : r;
-#else
-        const int rw = r, rdm = r;
-#endif
-        const double *bw = win + (size_t)rw * pitch;     // wave-uniform
-        const double *bd = dem + (size_t)rdm * pitch;
-        const int *bq = code.q + (size_t)rdm * pitch;
-        const unsigned short *bh = code.h + (size_t)rdm * pitch;
-        const int *bg = code.gb + (size_t)rdm * code.ngroups;
-        asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(P.NW[i][0]) : "v"(voff0), "s"(bw) : "memory");
-        asm volatile("global_load_dwordx2 %0, %1, %2 offset:8" : "=v"(P.NW[i][1]) : "v"(voff0), "s"(bw) : "memory");
-        asm volatile("global_load_dwordx2 %0, %1, %2 offset:16" : "=v"(P.NW[i][2]) : "v"(voff0), "s"(bw) : "memory");
-        if (DEM32 == 2) {
-          asm volatile("global_load_ushort %0, %1, %2" : "=v"(P.qh[i][0]) : "v"(hoff0), "s"(bh) : "memory");
-          asm volatile("global_load_ushort %0, %1, %2 offset:2" : "=v"(P.qh[i][1]) : "v"(hoff0), "s"(bh) : "memory");
-          asm volatile("global_load_ushort %0, %1, %2 offset:4" : "=v"(P.qh[i][2]) : "v"(hoff0), "s"(bh) : "memory");
-          asm volatile("global_load_dword %0, %1, %2" : "=v"(P.gbv[i]) : "v"(goff0), "s"(bg) : "memory");
-        } else if (DEM32) {
-          asm volatile("global_load_dwordx3 %0, %1, %2" : "=v"(P.qi[i]) : "v"(qoff0), "s"(bq) : "memory");
-        } else {
-          asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(P.ND[i][0]) : "v"(voff0), "s"(bd) : "memory");
-          asm volatile("global_load_dwordx2 %0, %1, %2 offset:8" : "=v"(P.ND[i][1]) : "v"(voff0), "s"(bd) : "memory");
-          asm volatile("global_load_dwordx2 %0, %1, %2 offset:16" : "=v"(P.ND[i][2]) : "v"(voff0), "s"(bd) : "memory");
-        }
-      }
-    };
-    // the wait that makes the prefetched registers readable; every register is an in/out operand so
-    // no use can be scheduled above it.  YOUNGER = memory operations issued after the loads.
-#define WDPM_WAIT_W "+v"(P.NW[0][0]), "+v"(P.NW[0][1]), "+v"(P.NW[0][2]), "+v"(P.NW[1][0]), "+v"(P.NW[1][1]), \
-                    "+v"(P.NW[1][2]), "+v"(P.NW[2][0]), "+v"(P.NW[2][1]), "+v"(P.NW[2][2])
-#define WDPM_WAIT_ROWS(YOUNGER)                                                                        \
-  do {                                                                                                 \
-    if (!DEM32)                                                                                        \
-      asm volatile("s_waitcnt vmcnt(" #YOUNGER ")"                                                     \
-                   : WDPM_WAIT_W, "+v"(P.ND[0][0]), "+v"(P.ND[0][1]), "+v"(P.ND[0][2]), "+v"(P.ND[1][0]), \
-                     "+v"(P.ND[1][1]), "+v"(P.ND[1][2]), "+v"(P.ND[2][0]), "+v"(P.ND[2][1]),           \
-                     "+v"(P.ND[2][2])                                                                  \
-                   :                                                                                   \
-                   : "memory");                                                                        \
-    else if (DEM32 == 2)                                                                               \
-      asm volatile("s_waitcnt vmcnt(" #YOUNGER ")"                                                     \
-                   : WDPM_WAIT_W, "+v"(P.qh[0][0]), "+v"(P.qh[0][1]), "+v"(P.qh[0][2]), "+v"(P.qh[1][0]), "+v"(P.qh[1][1]), \
-                     "+v"(P.qh[1][2]), "+v"(P.qh[2][0]), "+v"(P.qh[2][1]), "+v"(P.qh[2][2]), "+v"(P.gbv[0]), "+v"(P.gbv[1]), \
-                     "+v"(P.gbv[2])                                                                    \
-                   :                                                                                   \
-                   : "memory");                                                                        \
-    else                                                                                               \
-      asm volatile("s_waitcnt vmcnt(" #YOUNGER ")"                                                     \
-                   : WDPM_WAIT_W, "+v"(P.qi[0]), "+v"(P.qi[1]), "+v"(P.qi[2])                          \
-                   :                                                                                   \
-                   : "memory");                                                                        \
-  } while (0)
-
-    // the three staged rows [rb, rb+2] from LDS to HBM: 9 unconditional stores.  In two halves: the LDS reads go out at
-    // the very top of a step, ahead of the decode work, so that their round trip is over when the stores want the values
-    // (issued right in front of the stores, each step stalled on it: +0.4 % at 8192^2, profiles/r02/early_lds_ab.txt)
+    const RowOffsets off(colb, g.ncp);
+    auto prefetch = [&](Prefetched &P, const int r0) { prefetch_rows<DEM32, EDGE, true>(P, r0, off, win, dem, code, g); };
     double staged[3][3];
-    auto read_staged = [&]() {
-#pragma unroll
-      for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int k = 0; k < 3; k++) staged[i][k] = stage_lds[i * kStripIn + scol[k]];
-    };
-    auto write_staged = [&](const int rb) {
-#pragma unroll
-      for (int i = 0; i < 3; i++) {
-        const int r = rb + i;
-        const bool row_ok = r >= or_lo && r <= or_hi;             // wave-uniform
-        // rows outside the chunk's output range (first / last trips only) go to the dump area
-#ifdef WDPM_ABLATE_HBM
-        char *const orow = row_ok ? reinterpret_cast<char *>(wout + (size_t)((WDPM_ABLATE_HBM & 2) ? r % 48 : r) * pitch + c0) : dump;
-#else
-        char *const orow = row_ok ? reinterpret_cast<char *>(wout + (size_t)r * pitch + c0) : dump;   // wave-uniform
-#endif
-        // Stores as inline asm, saddr form: a wave-uniform row base in SGPRs + the lane's byte offset, no address arithmetic on
-        // the vector unit.  Ordinary stores, not non-temporal ones (round 4).  Rounds 1 - 3 believed they were choosing between
-        // the two by size: left to the compiler, the two arms of that branch (the same store with and without !nontemporal)
-        // had been merged into ONE plain store with a 64-bit VALU address - round 3's final ISA has no `nt` store in this
-        // kernel at all.  With real `nt` stores measured against plain ones (profiles/r04/stores_shapes_ab.txt): add 4096^2
-        // 108.0 against 103.1 us, 3000^2 65.9 against 62.9, drain 8192^2 401.6 against 397.8, the 1053-row drain slab 77.7
-        // against 75.2; a tie at 8192^2 add, on the 2116-row add slab and at 16384^2; drain 4096^2 128.9 against 130.3.
-#pragma unroll
-        for (int k = 0; k < 3; k++) asm volatile("global_store_dwordx2 %0, %1, %2" : : "v"(soff[k]), "v"(staged[i][k]), "s"(orow) : "memory");
-      }
-      __builtin_amdgcn_wave_barrier();
-    };
 
     auto step = [&](const int n, Prefetched &P, auto nstages_tag) {
       constexpr int NSTAGES = decltype(nstages_tag)::value;
@@ -1047,19 +1033,8 @@ fused_iteration_kernel(const double *__restrict__ win, double *__restrict__ wout
         *my_progress = n;                                // every lane the same word
         partner_at = *partner_progress;                  // read back after the step's arithmetic
       }
-      read_staged();
-      // consume the prefetched rows into window slots 4..6; the device DEM already holds +inf for
-      // NODATA cells, so only edge waves have anything to mask (outside the slab: dem=+inf, w=0)
-#pragma unroll
-      for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-          // FLUSH: the block's threshold flush (WDPMCL.c:1059-1062) applied to the water as it arrives
-          W[4 + i][j] = FLUSH && P.NW[i][j] < thres ? 0.0 : P.NW[i][j];
-          if (DEM32 == 2) D[4 + i][j] = dem16_decode_nan(P.qh[i][j], P.gbv[i], code.k0, code.D, code.rD, code.rDlo);
-          else if (DEM32) D[4 + i][j] = dem32_decode_nan(P.qi[i][j], code.k0, code.D, code.rD, code.rDlo);
-          else D[4 + i][j] = P.ND[i][j];
-        }
+      st.read_staged(staged, stage_lds);
+      decode_rows<DEM32, FLUSH>(W, D, P, code, thres);
       if (MODULE == 2 && owed_here && A + 3 * n + 2 >= g.dr - 1 && A + 3 * n <= g.dr + 1) {   // wave-uniform, rare
 #pragma unroll
         for (int i = 0; i < 3; i++) {
@@ -1068,32 +1043,13 @@ fused_iteration_kernel(const double *__restrict__ win, double *__restrict__ wout
           for (int j = 0; j < 3; j++) W[4 + i][j] = owed_row && owed_col[j] ? 0.0 : W[4 + i][j];
         }
       }
-      if (EDGE) {
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-          const bool row_ok = A + 3 * n + i < g.rows;
-#pragma unroll
-          for (int j = 0; j < 3; j++) {
-            const bool ok = row_ok & (colb + j < g.ncp);
-            W[4 + i][j] = ok ? W[4 + i][j] : 0.0;
-            D[4 + i][j] = ok ? D[4 + i][j] : WDPM_INF;
-          }
-        }
-      }
-      if constexpr (!SZ_SAFE) {
-        auto hi = [](const double v) { return (unsigned)__double2hiint(v); };
-        auto max3 = [](const unsigned a, const unsigned b, const unsigned c) { const unsigned m = a > b ? a : b; return m > c ? m : c; };
-        unsigned hm = max3(hi(W[4][0]), hi(W[4][1]), hi(W[4][2]));
-        hm = max3(hm, hi(W[5][0]), hi(W[5][1]));
-        hm = max3(hm, hi(W[5][2]), hi(W[6][0]));
-        hm = max3(hm, hi(W[6][1]), hi(W[6][2]));
-        deep = (deep & 8) | ((deep & 3) << 1) | (__ballot(hm > 0x40080000u) != 0 ? 1 : 0);   // 0x40080000'00000000 = 3.0
-      }
+      if (EDGE) mask_outside(W, D, A + 3 * n, colb, g);
+      if constexpr (!SZ_SAFE) deep = deep_next(deep, W);
       // always issued (the last trips re-read clamped / following rows and drop them)
       prefetch(P, A + 3 * (n + 1));
       // the rows the previous step staged in LDS go out now, behind the new loads and ahead of a
       // whole step of arithmetic (+1 % over storing at the end of the step); n = 0 has none: dump
-      write_staged(A + 3 * (n - 1) - 4);
+      st.write_staged(staged, A + 3 * (n - 1) - 4);
 
       const int rbase = A + 3 * n - 4;                 // slab row of window slot 0
 #ifndef WDPM_ABLATE_COMPUTE                            /* timing experiments only: memory pattern alone */
@@ -1152,12 +1108,8 @@ fused_iteration_kernel(const double *__restrict__ win, double *__restrict__ wout
       // The rows requested at the top of this step must have landed before the compiler may touch
       // their registers (it copies them around the loop back-edge): wait here, where the only
       // younger memory operations are the 9 stores issued right after them.
-      WDPM_WAIT_ROWS(9);
-      // slide the window down three rows
-#pragma unroll
-      for (int k = 0; k < 4; k++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) { W[k][j] = W[k + 3][j]; D[k][j] = D[k + 3][j]; }
+      wait_rows<DEM32, true, 9>(P);
+      slide_window(W, D);
     };
 
     // The SIMD's arbiter serves the OLDER of its two waves first whenever both have an instruction ready.  Left alone, the older
@@ -1176,28 +1128,19 @@ fused_iteration_kernel(const double *__restrict__ win, double *__restrict__ wout
     // `prio` = 0 (WDPM_PRIO=0, or a launch of four-wave workgroups): no priorities.
     Prefetched P;
     prefetch(P, A);
-    WDPM_WAIT_ROWS(0);
+    wait_rows<DEM32, true, 0>(P);
     // The dead stages of a chunk's first two steps are left out (see three_stages): 3 of 3 (H/3 + 2) stage executions.
     step(0, P, std::integral_constant<int, 1>{});      // nsteps >= 3: H >= 3
     step(1, P, std::integral_constant<int, 2>{});
     for (int n = 2; n < nsteps; n++) step(n, P, std::integral_constant<int, 3>{});
-    read_staged();
-    write_staged(A + 3 * (nsteps - 1) - 4);    // the last step's rows
-#undef WDPM_WAIT_ROWS
-#undef WDPM_WAIT_W
+    st.read_staged(staged, stage_lds);
+    st.write_staged(staged, A + 3 * (nsteps - 1) - 4);    // the last step's rows
   };
   if (edge) march(std::true_type{});
   else march(std::false_type{});
 
   if (MODULE == 2 && owner && lane == 0) *totaldrain = ds.td;
-  if (MD) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      const double o = __shfl_xor(md_max, off, 64);
-      md_max = o > md_max ? o : md_max;
-    }
-    if (lane == 0 && md_max > 0.0) atomicMax(md.bits, (unsigned long long)__double_as_longlong(md_max));   // >= 0: order-preserving
-  }
+  if (MD) fold_max_diff(md_max, md, lane);
   if (tf.zout && lane == 0) {
     // every staged row went into the mask, the warm-up rows above the block included: a flag of 0 only says "unknown"
     tf.zout[tile] = nzmask ? 0 : 1;
@@ -1349,18 +1292,7 @@ tri_iteration_kernel(const double *__restrict__ win, double *__restrict__ wout, 
   const bool outlet_inside = g.dr >= 1 && g.dr <= g.rows - 2 && g.dc >= 1 && g.dc <= g.ncp - 2;
   if (MODULE == 2) {
     owner = g.dr >= or_lo && g.dr <= or_hi && g.dc >= oc_lo && g.dc <= oc_hi;
-    if (drain_owed && owner && outlet_inside) {                              // the previous iteration's drain(), see above
-      double sum = 0.0;
-#pragma unroll
-      for (int i = -1; i <= 1; i++)
-#pragma unroll
-        for (int j = -1; j <= 1; j++) {
-          const size_t k = (size_t)(g.dr + i) * g.ncp + (g.dc + j);
-          const double wk = win[k];
-          if (dem[k] < WDPM_INF && wk > 0) sum += wk;
-        }
-      ds.td = ds.td + sum;
-    }
+    if (drain_owed && owner && outlet_inside) ds.td = ds.td + owed_drain_sum(win, dem, g);   // the previous iteration's drain(), see above
   }
 
   // nine rows x three columns per lane; cells outside the slab: dem = +inf, water = 0.  Row bases are
@@ -1541,12 +1473,7 @@ tri_iteration_kernel(const double *__restrict__ win, double *__restrict__ wout, 
         md_max = (cell & (dd > md_max)) ? dd : md_max;
       }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      const double o = __shfl_xor(md_max, off, 64);
-      md_max = o > md_max ? o : md_max;
-    }
-    if (lane == 0 && md_max > 0.0) atomicMax(md.bits, (unsigned long long)__double_as_longlong(md_max));
+    fold_max_diff(md_max, md, lane);
   }
 }
 
@@ -1646,18 +1573,8 @@ relay_iteration_kernel(const double *__restrict__ win, double *__restrict__ wout
     owner = g.dr >= or_lo && g.dr <= or_hi && g.dc >= oc_lo && g.dc <= oc_hi;
     ds.td = *totaldrain;
     if (drain_owed && outlet_inside) {
-      if (owner) {                                // the previous iteration's drain() (see fused_iteration_kernel): every wave of the
-        double sum = 0.0;                         // owning workgroup adds it up for itself
-#pragma unroll
-        for (int i = -1; i <= 1; i++)
-#pragma unroll
-          for (int j = -1; j <= 1; j++) {
-            const size_t k = (size_t)(g.dr + i) * g.ncp + (g.dc + j);
-            const double wk = win[k];
-            if (dem[k] < WDPM_INF && wk > 0) sum += wk;
-          }
-        ds.td = ds.td + sum;
-      }
+      // the previous iteration's drain() (see fused_iteration_kernel): every wave of the owning workgroup adds it up for itself
+      if (owner) ds.td = ds.td + owed_drain_sum(win, dem, g);
       if (R0 + 2 >= g.dr - 1 && R0 <= g.dr + 1) {                                   // wave-uniform, rare
 #pragma unroll
         for (int i = 0; i < 3; i++)
@@ -1686,15 +1603,8 @@ relay_iteration_kernel(const double *__restrict__ win, double *__restrict__ wout
   // bound).  A wave tests the three rows it loaded: enough for the first alignment, which stays inside them; the rows it takes
   // over afterwards have been through other waves' blocks, so from the first barrier on the workgroup's OR decides.  Wave-uniform.
   bool deep = (store_plain & 4) != 0;              // the host's part: elevations too large (WDPM_LAUNCH_CLAMP_OK not given)
-  {
-    unsigned hm = 0;
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++) { const unsigned h = (unsigned)__double2hiint(W[i][j]); hm = h > hm ? h : hm; }
-    deep = deep || __ballot(hm > 0x40080000u) != 0;
-    if (lane == 0) deep_sh[wave] = deep ? 1 : 0;
-  }
+  deep = deep || any_above_3m(&W[0]);
+  if (lane == 0) deep_sh[wave] = deep ? 1 : 0;
   // one row alignment on this wave's block at slots S0 .. S0+2 (st = S0): the outlet's block takes block_update's outlet form
 #define WDPM_RELAY_STAGE(S0)                                                                               \
   do {                                                                                                     \

@@ -27,16 +27,9 @@
  * rounding boundary without lying on it, so the FMA lands on RN(n / D); for e = 0 rDlo is 0 and the result is n itself.
  * tests/test_decode_forms.py holds this form and the one it replaced (a Newton correction: q0 = n * rD, r = fma(-q0, D, n),
  * v = fma(r, rD, q0), one more dependent fp64 operation per value) against exact rational arithmetic.  Nothing rests on that
- * argument: the encoders run these very functions on every cell and compare bits (dem_encode_kernel, dem16_encode_kernel).
- * -DWDPM_DECODE_NEWTON builds the earlier form (A/B builds, tools/build_variant.sh). */
+ * argument: the encoders run these very functions on every cell and compare bits (dem_encode_kernel, dem16_encode_kernel). */
 __device__ __forceinline__ double dem_quotient(const double n, const double D, const double rD, const double rDlo) {
-#ifdef WDPM_DECODE_NEWTON
-  const double q0 = n * rD;
-  const double r = __builtin_fma(-q0, D, n);
-  return __builtin_fma(r, rD, q0);
-#else
   return __builtin_fma(n, rD, n * rDlo);
-#endif
 }
 
 __device__ __forceinline__ double dem32_decode(const int q, const double k0, const double D, const double rD, const double rDlo) {
@@ -69,11 +62,7 @@ __device__ __forceinline__ double dem32_decode_nan(const int q, const double k0,
  * the compiler computes once per row: per value one unsigned conversion, an add, the two operations of the quotient and the
  * NODATA select. */
 __device__ __forceinline__ double dem16_decode_nan(const int h, const int gb, const double k0, const double D, const double rD, const double rDlo) {
-#ifdef WDPM_DECODE_NEWTON
-  const double n = (double)(gb + h) + k0;
-#else
   const double n = ((double)gb + k0) + (double)(unsigned)h;
-#endif
   const double v = dem_quotient(n, D, rD, rDlo);
   const int hi = h == 0xFFFF ? 0x7ff80000 : __double2hiint(v);
   return __hiloint2double(hi, __double2loint(v));
