@@ -1,0 +1,131 @@
+#!/usr/bin/env python3
+"""Time the pond inventory (wdpm_amd/ponds.py) on one GPU, one job per process invocation:
+
+    python tools/ponds_bench.py wet N [--out FILE]     the bench workload: synthetic DEM, add 100 mm, 1000 iterations -
+                                                       still entirely wet, ONE pond (every cell wants the same table row)
+    python tools/ponds_bench.py ponds N [--out FILE]   the mostly dry raster of tests/test_settled_golden.py: 12 m on one
+                                                       256 x 256 block in eight, 100 iterations - many ponds
+
+Per job: one untimed label call, then five timed ones (wall clock around the call, which ends with the stream idle; HIP events
+around every kernel with WDPM_PONDS_TIMING=1), medians; one steady iteration launch of the same context as the unit; the bytes
+each phase has to move, against what tools/hbm_yardstick.hip streams on the same box (--yardstick FILE, the output of
+tools/_build/hbm_yardstick); scipy.ndimage.label on the downloaded raster where scipy is there.  Appends one JSON object per job to
+--out (default profiles/r10/ponds.json) and prints it.  Run each job under a time limit of its own.
+"""
+import argparse
+import json
+import os
+import re
+import statistics
+import sys
+import time
+
+os.environ["WDPM_PONDS_TIMING"] = "1"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+import wdpm_amd  # noqa: E402
+from wdpm_amd.ponds import PHASES, Ponds  # noqa: E402
+
+MISS = -99999.0
+
+
+def bytes_model(rows, ncp, wet_cells, n):
+    """what each phase must move at least, in bytes"""
+    cells, segs = rows * ncp, rows * ((ncp + 63) // 64)
+    return {
+        "mask": 16 * cells + 8 * segs,                       # water + DEM in, masks out (run-start parents on top)
+        "merge": 4 * 8 * segs + 4 * segs,                    # own mask and three neighbours, union counts out
+        "flatten": 8 * segs + 12 * segs,                     # masks in, root masks and counts out
+        "scan": 3 * 4 * segs + 4 * segs,                     # counts and union counts in, counts in, offsets out
+        "table": 8 * wet_cells + 4 * cells + 8 * segs + 48 * n,   # wet water in, labels out, masks in, table
+        "finish": 16 * n,
+    }
+
+
+def yardstick_gbps(path):
+    """the best rate tools/hbm_yardstick.hip reached on this box (its lines end in `<ms> ms  <rate> GB/s`)"""
+    rates = [float(m.group(1)) for m in re.finditer(r"([0-9.]+) GB/s\s*$", open(path).read(), flags=re.M)]
+    if not rates:
+        raise SystemExit(f"{path}: no `GB/s` line of tools/_build/hbm_yardstick")
+    return max(rates)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("job", choices=["wet", "ponds"])
+    ap.add_argument("n", type=int)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r10", "ponds.json"))
+    ap.add_argument("--no-scipy", action="store_true")
+    ap.add_argument("--yardstick", metavar="FILE",
+                    help="output of tools/_build/hbm_yardstick from the same box: its best streaming rate goes into the record")
+    a = ap.parse_args()
+    hip = wdpm_amd.load_hip()
+    n = a.n
+    dem = hip.synth_dem(n, n)
+    if a.job == "wet":
+        water, iters = np.full((n, n), 0.1), 1000
+    else:
+        bi, bj = np.mgrid[0:n, 0:n] // 256
+        water, iters = np.where((3 * bi + 5 * bj) % 8 == 0, 12.0, 0.0), 100
+    bd = np.full((n + 2, n + 2), MISS)
+    bd[1:-1, 1:-1] = dem
+    bw = np.zeros((n + 2, n + 2))
+    bw[1:-1, 1:-1] = water
+    del dem, water
+    rec = dict(job=a.job, n=n, iterations=iters, build=hip.dll.wdpm_build_info().decode())
+    if a.yardstick:
+        rec["hbm_yardstick_gbps"] = yardstick_gbps(a.yardstick)
+    with hip.context(module="add", nrows=n, ncols=n, missingvalue=MISS) as ctx:
+        ctx.upload(bd, bw)
+        ctx.run_block(iters, 0.005 / 1000)
+        ctx.timing_reset()
+        ctx.run_block(20, 0.005 / 1000)
+        launches, ms = ctx.timing_steady()
+        rec["iteration_launch_ms"] = ms / max(launches, 1)
+        with Ponds(ctx) as p:
+            npond = p.label(0.001)                             # untimed: allocates
+            wall, phases = [], {k: [] for k in PHASES}
+            for _ in range(5):
+                ctx.synchronize()
+                t0 = time.perf_counter()
+                p.label(0.001)
+                wall.append((time.perf_counter() - t0) * 1e3)
+                for k, v in p.phase_ms().items():
+                    phases[k].append(v)
+            table, stats = p.table(), p.stats()
+            rec.update(ponds=npond, stats=stats, label_wall_ms=statistics.median(wall), label_wall_ms_all=wall,
+                       phase_ms={k: statistics.median(v) for k, v in phases.items()}, guard_bad=p.guard_bad())
+            rec["kernels_ms"] = sum(rec["phase_ms"].values())
+            rec["in_iteration_launches"] = rec["kernels_ms"] / rec["iteration_launch_ms"]
+            wet = int(table["cells"].sum())
+            rec["wet_cells"], rec["largest_pond_cells"] = wet, int(table["cells"].max()) if npond else 0
+            model = bytes_model(n + 2, n + 2, wet, npond)
+            rec["bytes_model"] = model
+            rec["bytes_per_cell"] = sum(model.values()) / ((n + 2) * (n + 2))
+            rec["gbps"] = {k: model[k] / (rec["phase_ms"][k] * 1e6) if rec["phase_ms"][k] > 0 else None for k in PHASES}
+            if rec.get("hbm_yardstick_gbps"):
+                rec["of_yardstick"] = {k: v / rec["hbm_yardstick_gbps"] if v else None for k, v in rec["gbps"].items()}
+        if not a.no_scipy:
+            try:
+                import scipy.ndimage as ndi
+                t0 = time.perf_counter()
+                w = ctx.download_water()
+                rec["download_ms"] = (time.perf_counter() - t0) * 1e3
+                t0 = time.perf_counter()
+                _, nref = ndi.label((bd > MISS) & (w > 0.001), structure=np.ones((3, 3), dtype=int))
+                rec["scipy_label_ms"] = (time.perf_counter() - t0) * 1e3
+                rec["scipy_ponds"] = int(nref)
+            except ImportError:
+                rec["scipy_label_ms"] = None
+    line = json.dumps(rec)
+    print(line)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "a") as f:
+        f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -3,3 +3,4 @@ from .capi import (ADD, SUBTRACT, DRAIN, MODULES, KERNEL_AUTO, KERNEL_PASS, KERN
                    OPT_DEM_GRID, OPT_DEM_GRID_EXP,
                    HALO_AUTO, HALO_RCCL, HALO_PEER, HALO_HOST, HALO_NAMES,
                    Context, Lib, WdpmError, load, load_hip, HIP_LIB_PATH)
+from .ponds import Ponds  # noqa: F401

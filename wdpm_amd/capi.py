@@ -279,9 +279,15 @@ class Context:
         h = C.c_void_p()
         lib.check(lib.dll.wdpm_create(C.byref(h), C.byref(p)))
         self._h = h
+        self._dependents = []   # weak references to handles that live on this context (wdpm_amd.ponds.Ponds): closed before it
 
     # -- lifetime
     def close(self):
+        for ref in reversed(getattr(self, "_dependents", [])):
+            dep = ref()
+            if dep is not None:
+                dep.close()
+        self._dependents = []
         if self._h:
             self.lib.dll.wdpm_destroy(self._h)
             self._h = None
@@ -383,6 +389,13 @@ class Context:
         v = C.c_double()
         self.lib.check(self.lib.dll.wdpm_volume_partial(self._h, row_lo, row_hi, start, C.byref(v)))
         return v.value
+
+    def count_stats(self, row_lo: int = 0, row_hi: int | None = None):
+        """(valid cells, cells with water > 0.001 m, deepest water) of rows [row_lo, row_hi) - the reference's final statistics"""
+        nv, nw, mx = C.c_int64(), C.c_int64(), C.c_double()
+        hi = self.slab.rows if row_hi is None else row_hi
+        self.lib.check(self.lib.dll.wdpm_count_stats(self._h, row_lo, hi, C.byref(nv), C.byref(nw), C.byref(mx)))
+        return nv.value, nw.value, mx.value
 
     def run_block(self, n_iter: int, thres: float) -> float:
         v = C.c_double()

@@ -37,6 +37,14 @@
 #include <unistd.h>
 
 #include "../../include/wdpm.h"
+#include "../../include/wdpm_ponds.h"
+/* the pond inventory is the HIP library's alone: weak references, so that this file also links against a back-end that
+ * exports include/wdpm.h and nothing else (WDPM_PONDS then says so and writes no file) */
+#pragma weak wdpm_ponds_create
+#pragma weak wdpm_ponds_destroy
+#pragma weak wdpm_ponds_label
+#pragma weak wdpm_ponds_table
+#pragma weak wdpm_ponds_guard_bad
 #include "arcascii.h"
 
 #define ITER_PER_BLOCK 1000 /* IterationNum, WDPMCL.c:597 */
@@ -621,6 +629,62 @@ static void relief_finish(relief_helper *h) {
   }
 }
 
+/* ---- pond inventory (include/wdpm_ponds.h) ----
+ * WDPM_PONDS=<path>: the 8-connected water bodies of the final water, one CSV line per pond, numbered by first cell.  A pond
+ * cell holds more than WDPM_PONDS_MIN_DEPTH_MM of water (default 1.0: the reference's own wet threshold, water > 0.001,
+ * WDPMCL.c:1397-1404, so the cells column sums to the wet count of the final statistics).  Nothing of it goes to stdout. */
+typedef struct { wdpm_pond *rows; int64_t n; int64_t guard_bad; } pond_inventory;
+
+static int take_inventory(wdpm_ctx *c, double min_depth, pond_inventory *inv) {
+  wdpm_ponds *h = NULL;
+  inv->rows = NULL;
+  inv->n = 0;
+  inv->guard_bad = 0;
+  if (!wdpm_ponds_create || !wdpm_ponds_destroy || !wdpm_ponds_label || !wdpm_ponds_table || !wdpm_ponds_guard_bad) {
+    fprintf(stderr, "WDPMCL: pond inventory: back-end %s has none, no file written\n", wdpm_backend_name());
+    return 1;
+  }
+  int rc = wdpm_ponds_create(&h, c);
+  if (!rc) rc = wdpm_ponds_label(h, min_depth, &inv->n);
+  if (!rc) {
+    inv->rows = (wdpm_pond *)malloc((size_t)(inv->n > 0 ? inv->n : 1) * sizeof(wdpm_pond));
+    if (!inv->rows) { wdpm_set_last_error("out of host memory for the pond table"); rc = 1; }
+  }
+  if (!rc) rc = wdpm_ponds_table(h, inv->rows, inv->n);
+  if (!rc && getenv("WDPM_GUARD_KB")) rc = wdpm_ponds_guard_bad(h, &inv->guard_bad);
+  if (rc) {
+    fprintf(stderr, "WDPMCL: pond inventory failed, no file written: %s\n", wdpm_last_error());
+    free(inv->rows);
+    inv->rows = NULL;
+  }
+  wdpm_ponds_destroy(h);
+  return rc;
+}
+
+/* coordinates leave as file coordinates, 0-based (padded - 1); doubles as %.17g so that they read back exactly */
+static int write_inventory(const char *path, const pond_inventory *inv, double cellarea) {
+  FILE *f = fopen(path, "w");
+  if (!f) {
+    fprintf(stderr, "WDPMCL: cannot write pond inventory %s\n", path);
+    return 1;
+  }
+  fprintf(f, "label,row,col,cells,area_m2,volume_q,volume_m3,max_depth_m,row_min,row_max,col_min,col_max\n");
+  for (int64_t k = 0; k < inv->n; k++) {
+    const wdpm_pond *q = &inv->rows[k];
+    fprintf(f, "%lld,%d,%d,%lld,%.17g,%llu,%.17g,%.17g,%d,%d,%d,%d\n", (long long)(k + 1), q->first_row - 1, q->first_col - 1,
+            (long long)q->cells, (double)q->cells * cellarea, (unsigned long long)q->volume_q,
+            ldexp((double)q->volume_q, -24) * cellarea, q->max_depth, q->row_min - 1, q->row_max - 1, q->col_min - 1,
+            q->col_max - 1);
+  }
+  const int bad = ferror(f);
+  if (fclose(f) != 0 || bad) {
+    fprintf(stderr, "WDPMCL: error writing pond inventory %s\n", path);
+    return 1;
+  }
+  fprintf(stderr, "WDPMCL: pond inventory: %lld pond%s written to %s\n", (long long)inv->n, inv->n == 1 ? "" : "s", path);
+  return 0;
+}
+
 #define ABI_TRY(call)                                                      \
   do {                                                                     \
     if ((call) != 0) {                                                     \
@@ -845,7 +909,36 @@ int main(int argc, char **argv) {
   ABI_TRY(wdpm_group_count_stats(ctx, NULL, &wet, &dev_max));
   ABI_TRY(wdpm_group_download_unpadded(ctx, 1, st.water));
   if (cfg.module == WDPM_DRAIN) ABI_TRY(wdpm_group_get_totaldrain(ctx, &totaldrain));
-  int64_t guard_bad = 0;
+  /* the pond inventory of the final water (WDPM_PONDS): on the one context of the default group here; a raster in several row
+   * blocks keeps its unmasked depths on the host and is labelled in one piece once the group is gone (below) */
+  const char *ponds_path = getenv("WDPM_PONDS");
+  if (ponds_path && !*ponds_path) ponds_path = NULL;
+  const double ponds_min_depth = (getenv("WDPM_PONDS_MIN_DEPTH_MM") ? atof(getenv("WDPM_PONDS_MIN_DEPTH_MM")) : 1.0) / 1000.0;
+  pond_inventory inv;
+  memset(&inv, 0, sizeof inv);
+  int ponds_failed = 0;
+  double *ponds_water = NULL;
+  if (ponds_path) {
+    phase("statistics + download");
+    if (ndev == 1) {
+      ponds_failed = take_inventory(wdpm_rank_ctx(wdpm_group_rank(ctx, 0)), ponds_min_depth, &inv);
+      if (!ponds_failed) ponds_failed = write_inventory(ponds_path, &inv, st.cellarea);
+      free(inv.rows);
+      phase("pond inventory");
+    } else if (((double)st.R + 2) * ((double)st.C + 2) > 2.0e9) {
+      fprintf(stderr, "WDPMCL: pond inventory: the raster is larger than one context (2e9 cells): no file written\n");
+      ponds_path = NULL;
+    } else {
+      ponds_water = (double *)malloc(ncell * sizeof(double));
+      if (!ponds_water) {
+        fprintf(stderr, "WDPMCL: pond inventory: out of host memory, no file written\n");
+        ponds_failed = 1;
+      } else {
+        ABI_TRY(wdpm_group_download_unpadded(ctx, 0, ponds_water));   /* unmasked: the output raster carries NODATA marks */
+      }
+    }
+  }
+  int64_t guard_bad = inv.guard_bad;
   if (getenv("WDPM_GUARD_KB")) {   /* debugging aid (include/wdpm.h: WDPM_OPT_GUARD_BAD): did any kernel write outside its buffer? */
     for (int i = 0; i < ndev; i++) {
       int64_t bad = 0;
@@ -857,6 +950,34 @@ int main(int argc, char **argv) {
   wdpm_group_destroy(ctx);
   if (guard_bad) return 3;
   phase("statistics + download + destroy");
+  if (ponds_water) {
+    /* several row blocks: one whole-raster context on the first device, made from the host rasters, only to be labelled */
+    wdpm_params pp = p;
+    pp.module = WDPM_ADD;
+    pp.drainrow = pp.draincol = 0;
+    pp.slab_row0 = pp.slab_rows = 0;
+    pp.device = devices[0];
+    wdpm_setup none;
+    memset(&none, 0, sizeof none);
+    wdpm_ctx *whole = NULL;
+    int64_t bad = 0;
+    if (wdpm_create(&whole, &pp) != 0 || wdpm_upload_unpadded(whole, st.dem, ponds_water, &none) != 0) {
+      fprintf(stderr, "WDPMCL: pond inventory failed, no file written: %s\n", wdpm_last_error());
+      ponds_failed = 1;
+    } else {
+      ponds_failed = take_inventory(whole, ponds_min_depth, &inv);
+      if (!ponds_failed) ponds_failed = write_inventory(ponds_path, &inv, st.cellarea);
+      free(inv.rows);
+      if (getenv("WDPM_GUARD_KB")) ABI_TRY(wdpm_get_option(whole, WDPM_OPT_GUARD_BAD, &bad));
+    }
+    if (whole) wdpm_destroy(whole);
+    free(ponds_water);
+    if (bad + inv.guard_bad) {
+      fprintf(stderr, "WDPMCL: guard bands of the pond inventory: %lld bytes overwritten\n", (long long)(bad + inv.guard_bad));
+      return 3;
+    }
+    phase("pond inventory");
+  }
 
   const int watercount = (int)wet;
   const double final_vol = watertotal * st.cellarea;
@@ -894,5 +1015,5 @@ int main(int argc, char **argv) {
   printf("%20s %10.2f %s\n", "Run Time", seconds_since(&t0), "s");
   free(st.dem);
   if (pinned) wdpm_host_free(st.water); else free(st.water);
-  return 0;
+  return ponds_failed ? 4 : 0;   /* the run and its raster are complete; only the inventory asked for is missing */
 }

@@ -1,0 +1,140 @@
+"""ctypes binding of include/wdpm_ponds.h: the pond inventory of a context's current water raster.
+
+Product library only (the symbols are not part of the ABI of include/wdpm.h, and ``capi.SYMBOLS`` does not list them).
+
+    with hip.context(...) as ctx, Ponds(ctx) as ponds:
+        n = ponds.label(0.001)
+        table = ponds.table()       # structured array, one row per pond, numbered by first cell
+        labels = ponds.labels()     # int32, padded layout like the water raster
+"""
+from __future__ import annotations
+
+import ctypes as C
+import weakref
+
+import numpy as np
+
+from . import capi
+
+VOLUME_QUANTUM = 2.0 ** -24   # metres per unit of volume_q
+PHASES = ("mask", "merge", "flatten", "scan", "table", "finish")   # wdpm_ponds_phase_ms
+
+
+class PondStruct(C.Structure):
+    """struct wdpm_pond"""
+    _fields_ = [("first_row", C.c_int32), ("first_col", C.c_int32), ("cells", C.c_int64), ("volume_q", C.c_uint64),
+                ("max_depth", C.c_double), ("row_min", C.c_int32), ("row_max", C.c_int32), ("col_min", C.c_int32),
+                ("col_max", C.c_int32)]
+
+
+class StatsStruct(C.Structure):
+    """struct wdpm_pond_stats"""
+    _fields_ = [("segments", C.c_int64), ("unions", C.c_int64), ("seam_unions", C.c_int64), ("passes", C.c_int64),
+                ("rows_per_wave", C.c_int64), ("ponds", C.c_int64)]
+
+
+POND_DTYPE = np.dtype([("first_row", "<i4"), ("first_col", "<i4"), ("cells", "<i8"), ("volume_q", "<u8"), ("max_depth", "<f8"),
+                       ("row_min", "<i4"), ("row_max", "<i4"), ("col_min", "<i4"), ("col_max", "<i4")])
+assert POND_DTYPE.itemsize == C.sizeof(PondStruct) == 48
+
+_vp = C.c_void_p
+# name -> (restype, argtypes); every symbol include/wdpm_ponds.h declares
+SYMBOLS = {
+    "wdpm_ponds_create": (C.c_int, [C.POINTER(_vp), _vp]),
+    "wdpm_ponds_destroy": (None, [_vp]),
+    "wdpm_ponds_label": (C.c_int, [_vp, C.c_double, C.POINTER(C.c_int64)]),
+    "wdpm_ponds_table": (C.c_int, [_vp, _vp, C.c_int64]),
+    "wdpm_ponds_labels": (C.c_int, [_vp, _vp]),
+    "wdpm_ponds_guard_bad": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "wdpm_ponds_stats": (C.c_int, [_vp, C.POINTER(StatsStruct)]),
+    "wdpm_ponds_phase_ms": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+}
+
+
+def bind(lib: capi.Lib):
+    """Set the prototypes on a loaded product library; a library without the symbols is an error (no fallback)."""
+    if getattr(lib, "_ponds_bound", False):
+        return lib.dll
+    for name, (res, args) in SYMBOLS.items():
+        try:
+            fn = getattr(lib.dll, name)
+        except AttributeError:
+            raise capi.WdpmError(f"{lib.path} does not export {name}: the pond inventory needs the HIP product library") from None
+        fn.restype = res
+        fn.argtypes = args
+    lib._ponds_bound = True
+    return lib.dll
+
+
+class Ponds:
+    """The inventory handle of one whole-raster context — wraps wdpm_ponds.  The C handle must go before its context: the
+    object keeps its Context alive, and a Context that is closed first closes the handles that live on it."""
+
+    def __init__(self, ctx: capi.Context):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        self.dll = bind(ctx.lib)
+        self.shape = ctx.shape
+        self.n = None
+        self._h = None
+        h = C.c_void_p()
+        self.lib.check(self.dll.wdpm_ponds_create(C.byref(h), ctx._h))
+        self._h = h
+        deps = getattr(ctx, "_dependents", None)
+        if deps is not None:
+            deps.append(weakref.ref(self))
+
+    def close(self):
+        if self._h:
+            self.dll.wdpm_ponds_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def label(self, min_depth: float) -> int:
+        """Label the ponds deeper than min_depth (metres, strict) on the context's current water; returns their number."""
+        n = C.c_int64()
+        self.n = None
+        self.lib.check(self.dll.wdpm_ponds_label(self._h, float(min_depth), C.byref(n)))
+        self.n = n.value
+        return n.value
+
+    def table(self, capacity: int | None = None) -> np.ndarray:
+        """One row per pond (POND_DTYPE).  `capacity` is what the C call is told the buffer holds (default: exactly N)."""
+        if self.n is None:
+            raise capi.WdpmError("Ponds.table: label() has not succeeded on this handle")
+        cap = self.n if capacity is None else int(capacity)
+        out = np.zeros(max(cap, 0), dtype=POND_DTYPE)
+        self.lib.check(self.dll.wdpm_ponds_table(self._h, out.ctypes.data, cap))
+        return out[:self.n]
+
+    def labels(self) -> np.ndarray:
+        out = np.empty(self.shape, dtype=np.int32)
+        self.lib.check(self.dll.wdpm_ponds_labels(self._h, out.ctypes.data))
+        return out
+
+    def stats(self) -> dict:
+        s = StatsStruct()
+        self.lib.check(self.dll.wdpm_ponds_stats(self._h, C.byref(s)))
+        return {name: int(getattr(s, name)) for name, _ in StatsStruct._fields_}
+
+    def phase_ms(self) -> dict:
+        """milliseconds per kernel phase of the last label call (handles made with WDPM_PONDS_TIMING=1 in the environment)"""
+        ms = (C.c_double * len(PHASES))()
+        self.lib.check(self.dll.wdpm_ponds_phase_ms(self._h, ms))
+        return dict(zip(PHASES, (float(v) for v in ms)))
+
+    def guard_bad(self) -> int:
+        v = C.c_int64()
+        self.lib.check(self.dll.wdpm_ponds_guard_bad(self._h, C.byref(v)))
+        return v.value
