@@ -10,7 +10,11 @@ Per job: one untimed label call, then five timed ones (wall clock around the cal
 around every kernel with WDPM_PONDS_TIMING=1), medians; one steady iteration launch of the same context as the unit; the bytes
 each phase has to move, against what tools/hbm_yardstick.hip streams on the same box (--yardstick FILE, the output of
 tools/_build/hbm_yardstick); scipy.ndimage.label on the downloaded raster where scipy is there.  Appends one JSON object per job to
---out (default profiles/r10/ponds.json) and prints it.  Run each job under a time limit of its own.
+--out (default profiles/r10/ponds.json; with --devices profiles/r11/ponds_group.json) and prints it.  Run each job under a time limit of its own.
+
+    python tools/ponds_bench.py wet N --devices 0,0 [--out FILE]    the same jobs over row blocks (wdpm_amd.ponds.GroupPonds), one
+                                                                    per device named (a device may repeat): per-rank phase times,
+                                                                    the host's stitch_ms and the wall clock of the whole call
 """
 import argparse
 import json
@@ -27,7 +31,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 import wdpm_amd  # noqa: E402
-from wdpm_amd.ponds import PHASES, Ponds  # noqa: E402
+from wdpm_amd.ponds import PHASES, GroupPonds, Ponds  # noqa: E402
 
 MISS = -99999.0
 
@@ -53,15 +57,46 @@ def yardstick_gbps(path):
     return max(rates)
 
 
+def group_job(hip, a, bd, bw, iters, rec):
+    """the job over row blocks: one untimed label call, five timed ones"""
+    from wdpm_amd.rowblock import Group
+    n = a.n
+    devices = [int(d) for d in a.devices.split(",")]
+    rec["devices"] = devices
+    with Group(hip, "add", n, n, MISS, devices) as grp:
+        grp.upload(bd, bw)
+        grp.run_block(iters, 0.005 / 1000)
+        with GroupPonds(grp) as p:
+            npond = p.label(0.001)                             # untimed: allocates
+            wall, stitch = [], []
+            phases = [{k: [] for k in PHASES} for _ in devices]
+            for _ in range(5):
+                t0 = time.perf_counter()
+                p.label(0.001)
+                wall.append((time.perf_counter() - t0) * 1e3)
+                stitch.append(p.stats()["stitch_ms"])
+                for i in range(len(devices)):
+                    for k, v in p.phase_ms(i).items():
+                        phases[i][k].append(v)
+            rec.update(ponds=npond, stats=p.stats(), rank_stats=[p.rank_stats(i) for i in range(len(devices))],
+                       label_wall_ms=statistics.median(wall), label_wall_ms_all=wall, stitch_ms=statistics.median(stitch),
+                       rank_phase_ms=[{k: statistics.median(v) for k, v in ph.items()} for ph in phases], guard_bad=p.guard_bad())
+            rec["rank_kernels_ms"] = [sum(ph.values()) for ph in rec["rank_phase_ms"]]
+            rec["wet_cells"] = int(p.table()["cells"].sum())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("job", choices=["wet", "ponds"])
     ap.add_argument("n", type=int)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r10", "ponds.json"))
+    ap.add_argument("--out", help="default: profiles/r10/ponds.json, with --devices profiles/r11/ponds_group.json")
     ap.add_argument("--no-scipy", action="store_true")
     ap.add_argument("--yardstick", metavar="FILE",
                     help="output of tools/_build/hbm_yardstick from the same box: its best streaming rate goes into the record")
+    ap.add_argument("--devices", metavar="a,b,...", help="label over row blocks, one per device named (wdpm_amd.ponds.GroupPonds)")
     a = ap.parse_args()
+    if not a.out:
+        a.out = os.path.join(ROOT, "profiles", *(("r11", "ponds_group.json") if a.devices else ("r10", "ponds.json")))
     hip = wdpm_amd.load_hip()
     n = a.n
     dem = hip.synth_dem(n, n)
@@ -78,6 +113,14 @@ def main():
     rec = dict(job=a.job, n=n, iterations=iters, build=hip.dll.wdpm_build_info().decode())
     if a.yardstick:
         rec["hbm_yardstick_gbps"] = yardstick_gbps(a.yardstick)
+    if a.devices:
+        group_job(hip, a, bd, bw, iters, rec)
+        line = json.dumps(rec)
+        print(line)
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
+        return
     with hip.context(module="add", nrows=n, ncols=n, missingvalue=MISS) as ctx:
         ctx.upload(bd, bw)
         ctx.run_block(iters, 0.005 / 1000)

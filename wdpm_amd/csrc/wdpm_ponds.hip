@@ -28,9 +28,12 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <ctime>
+#include <string>
 #include <vector>
 
 #include "wdpm_ctx.h"
+#include "wdpm_ponds_stitch.h"
 
 #define HIP_TRY(expr)                                                                                  \
   do {                                                                                                 \
@@ -38,7 +41,7 @@
     if (e_ != hipSuccess) return wdpm_fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 #endif
-#include "../../include/wdpm_ponds.h"
+#include "../../include/wdpm_group_ponds.h"
 
 namespace {
 
@@ -364,11 +367,24 @@ __device__ __forceinline__ void send(PondRow *table, const Carry &c) {
   atomic_max_if(&t->col_max, c.col_max);
 }
 
-/* A wave owns segment column s of rows [r0, r0 + rpw).  Everything that steers the loops below is wave-uniform. */
-__global__ __launch_bounds__(kBlock) void ponds_table_kernel(const double *__restrict__ w, const unsigned long long *__restrict__ masks,
-                                                             const int *__restrict__ parent, const int *__restrict__ base,
-                                                             const unsigned long long *__restrict__ rootmask, Geom g, int rpw,
-                                                             int nwaves, int *__restrict__ labels, PondRow *table) {
+/* the label of the run that starts at cell idx: its root's rank among the roots, from 1 */
+__device__ __forceinline__ int label_of_run(const int *__restrict__ parent, const int *__restrict__ base,
+                                            const unsigned long long *__restrict__ rootmask, const Geom &g, int idx, int &root) {
+  root = parent[idx];
+  const int rr = root / g.ncp, rc = root - rr * g.ncp;
+  const int rseg = rr * g.nsc + rc / kSeg, rbit = rc % kSeg;
+  return base[rseg] + __popcll(rootmask[rseg] & ((1ull << rbit) - 1ull)) + 1;
+}
+
+/* A wave owns segment column s of rows [r0, r0 + rpw).  Everything that steers the loops below is wave-uniform.
+ * kMapped (row blocks): the label raster takes map[label - 1], the pond's number in the whole raster, looked up once per run
+ * where its label is computed; the table stays indexed by the label itself. */
+template <bool kMapped>
+__device__ __forceinline__ void ponds_table_body(const double *__restrict__ w, const unsigned long long *__restrict__ masks,
+                                                 const int *__restrict__ parent, const int *__restrict__ base,
+                                                 const unsigned long long *__restrict__ rootmask, const Geom g, const int rpw,
+                                                 const int nwaves, int *__restrict__ labels, PondRow *table,
+                                                 const int *__restrict__ map) {
   const int wid = blockIdx.x * kWaves + (threadIdx.x >> 6);
   if (wid >= nwaves) return;
   const int lane = threadIdx.x & 63;
@@ -389,17 +405,22 @@ __global__ __launch_bounds__(kBlock) void ponds_table_kernel(const double *__res
     }
     const bool wet = bit(m, lane);
     const int st = wet ? run_start(m, lane) : lane;
-    int label = 0;
+    int label = 0, shown = 0;
     if (wet && st == lane) {               /* a run start: where is its root among the roots? */
-      const int root = parent[idx];
-      const int rr = root / g.ncp, rc = root - rr * g.ncp;
-      const int rseg = rr * g.nsc + rc / kSeg, rbit = rc % kSeg;
-      label = base[rseg] + __popcll(rootmask[rseg] & ((1ull << rbit) - 1ull)) + 1;
+      int root;
+      label = label_of_run(parent, base, rootmask, g, idx, root);
       if (root == idx) { table[label - 1].first_row = r; table[label - 1].first_col = c; }
+      if (kMapped) shown = map[label - 1];
     }
     label = __shfl(label, st);
     if (!wet) label = 0;
-    if (inside) labels[idx] = label;
+    if (kMapped) {
+      shown = __shfl(shown, st);
+      if (!wet) shown = 0;
+    } else {
+      shown = label;
+    }
+    if (inside) labels[idx] = shown;
 
     /* per run: a segmented scan leaves each run's sum and maximum in its last lane */
     unsigned long long q = 0ull, k = 0ull;
@@ -446,6 +467,46 @@ __global__ __launch_bounds__(kBlock) void ponds_table_kernel(const double *__res
   if (cy.label != 0 && lane == 0) send(table, cy);
 }
 
+__global__ __launch_bounds__(kBlock) void ponds_table_kernel(const double *__restrict__ w, const unsigned long long *__restrict__ masks,
+                                                             const int *__restrict__ parent, const int *__restrict__ base,
+                                                             const unsigned long long *__restrict__ rootmask, Geom g, int rpw,
+                                                             int nwaves, int *__restrict__ labels, PondRow *table) {
+  ponds_table_body<false>(w, masks, parent, base, rootmask, g, rpw, nwaves, labels, table, nullptr);
+}
+
+__global__ __launch_bounds__(kBlock) void ponds_table_mapped_kernel(const double *__restrict__ w, const unsigned long long *__restrict__ masks,
+                                                                    const int *__restrict__ parent, const int *__restrict__ base,
+                                                                    const unsigned long long *__restrict__ rootmask, Geom g, int rpw,
+                                                                    int nwaves, int *__restrict__ labels, PondRow *table,
+                                                                    const int *__restrict__ map) {
+  ponds_table_body<true>(w, masks, parent, base, rootmask, g, rpw, nwaves, labels, table, map);
+}
+
+/* ---- seam rows (row blocks) -------------------------------------------------------------------------------------------------- */
+/* After the scan: the labels of the view's first and last inner row (rows 1 and g.rows - 2), g.ncp int32 each, for the host
+ * that joins neighbouring row blocks.  One wave per segment of either row. */
+__global__ __launch_bounds__(kBlock) void ponds_seam_kernel(const unsigned long long *__restrict__ masks, const int *__restrict__ parent,
+                                                            const int *__restrict__ base, const unsigned long long *__restrict__ rootmask,
+                                                            Geom g, int *__restrict__ seam) {
+  const int wid = blockIdx.x * kWaves + (threadIdx.x >> 6);
+  if (wid >= 2 * g.nsc) return;
+  const int lane = threadIdx.x & 63;
+  const int side = wid / g.nsc, s = wid - side * g.nsc;
+  const int r = side ? g.rows - 2 : 1;
+  const int c = s * kSeg + lane;
+  const unsigned long long m = masks[r * g.nsc + s];
+  const bool wet = bit(m, lane);
+  const int st = wet ? run_start(m, lane) : lane;
+  int label = 0;
+  if (wet && st == lane) {
+    int root;
+    label = label_of_run(parent, base, rootmask, g, r * g.ncp + c, root);
+  }
+  label = __shfl(label, st);
+  if (!wet) label = 0;
+  if (c < g.ncp) seam[side * g.ncp + c] = label;
+}
+
 }  // namespace
 
 #ifndef WDPM_PONDS_EMULATION
@@ -455,9 +516,14 @@ struct Guarded { char *base; size_t bytes; };
 
 }  // namespace
 
+/* The handle labels a VIEW of its context: rows [row_off, row_off + g.rows) of the context's rasters, whose first and last row the
+ * kernels take for the dry border.  wdpm_ponds_create views a whole-raster context; a row block of a group (wdpm_group_ponds_*) is
+ * viewed as its owned rows with one row either side. */
 struct wdpm_ponds {
   wdpm_ctx *x;
   Geom g;
+  int row_off;                      /* context row of the view's row 0 */
+  bool seams;                       /* a row block: the labels of rows 1 and g.rows - 2 come to the host with the status */
   size_t guard;                     /* bytes of each guard band (WDPM_GUARD_KB when the handle was made) */
   std::vector<Guarded> guards;
   bool allocated;
@@ -465,10 +531,18 @@ struct wdpm_ponds {
   int *d_parent, *d_labels, *d_cnt, *d_bsum;
   unsigned *d_ucnt;
   Status *d_status, *h_status;      /* h_status pinned */
+  int *d_seam, *h_seam;             /* 2 x g.ncp labels (seams); h_seam pinned */
+  int *d_map;                       /* local label - 1 -> label in the whole raster (seams) */
+  long long map_cap;
+  int *h_map;                       /* pinned staging (seams): the map on its way up, the finished table on its way down - */
+  wdpm_pond *h_table;               /* a copy to or from pageable memory would make the host wait inside the queueing step */
+  long long stage_cap;
   PondRow *d_table;
   long long table_cap;
   int nb;                           /* blocks of the scan */
   int forced_rpw;                   /* WDPM_PONDS_ROWS_PER_WAVE when the handle was made, 0: the library chooses */
+  int rpw;                          /* of the call under way */
+  Status last;                      /* status words of the call under way */
   bool valid;                       /* the last label call succeeded */
   bool timing;                      /* WDPM_PONDS_TIMING=1 when the handle was made: HIP events around every kernel */
   hipEvent_t ev[WDPM_PONDS_PHASES + 2];   /* the host reads the status between scan and table: two marks there */
@@ -504,13 +578,21 @@ void guarded_free(wdpm_ponds *h, void *p) {
 void release(wdpm_ponds *h) {
   guarded_free(h, h->d_masks); guarded_free(h, h->d_rootmask); guarded_free(h, h->d_parent); guarded_free(h, h->d_labels);
   guarded_free(h, h->d_cnt); guarded_free(h, h->d_ucnt); guarded_free(h, h->d_bsum); guarded_free(h, h->d_busum);
-  guarded_free(h, h->d_table);
+  guarded_free(h, h->d_table); guarded_free(h, h->d_seam); guarded_free(h, h->d_map);
   (void)hipFree(h->d_status);
   if (h->h_status) (void)hipHostFree(h->h_status);
+  if (h->h_seam) (void)hipHostFree(h->h_seam);
+  if (h->h_map) (void)hipHostFree(h->h_map);
+  if (h->h_table) (void)hipHostFree(h->h_table);
+  h->h_map = nullptr;
+  h->h_table = nullptr;
+  h->stage_cap = 0;
   h->d_masks = h->d_rootmask = h->d_busum = nullptr;
   h->d_parent = h->d_labels = h->d_cnt = h->d_bsum = nullptr;
   h->d_ucnt = nullptr;
   h->d_status = h->h_status = nullptr;
+  h->d_seam = h->h_seam = h->d_map = nullptr;
+  h->map_cap = 0;
   h->d_table = nullptr;
   h->table_cap = 0;
   h->allocated = false;
@@ -530,6 +612,10 @@ int allocate(wdpm_ponds *h) {
   if (e == hipSuccess) e = guarded_malloc(h, (void **)&h->d_busum, (size_t)h->nb * 2 * sizeof(unsigned long long));
   if (e == hipSuccess) e = hipMalloc(&h->d_status, sizeof(Status));
   if (e == hipSuccess) e = hipHostMalloc(&h->h_status, sizeof(Status));
+  if (h->seams) {
+    if (e == hipSuccess) e = guarded_malloc(h, (void **)&h->d_seam, (size_t)2 * h->g.ncp * sizeof(int));
+    if (e == hipSuccess) e = hipHostMalloc(&h->h_seam, (size_t)2 * h->g.ncp * sizeof(int));
+  }
   if (e != hipSuccess) {
     release(h);                     /* what was taken so far: the next call starts from nothing again */
     return wdpm_fail("wdpm_ponds_label: device allocation failed: %s", hipGetErrorString(e));
@@ -540,21 +626,16 @@ int allocate(wdpm_ponds *h) {
 
 inline unsigned blocks_for(long long items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
 
-}  // namespace
-
-extern "C" int wdpm_ponds_create(wdpm_ponds **out, wdpm_ctx *ctx) {
-  if (!out || !ctx) return wdpm_fail("wdpm_ponds_create: null argument");
-  const SlabGeom &sg = ctx->g;
-  if (sg.row0 != 0 || sg.rows != sg.R + 2)
-    return wdpm_fail("wdpm_ponds_create: a slab context (rows %d..%d of %d) cannot take an inventory: ponds cross row blocks; "
-                     "use a context that holds the whole raster", sg.row0, sg.row0 + sg.rows, sg.R + 2);
-  if (wdpm_synchronize(ctx)) return 1;          /* binds the device */
+/* a handle on rows [row_off, row_off + rows) of ctx; reads the environment as include/wdpm_ponds.h says */
+wdpm_ponds *make_handle(wdpm_ctx *ctx, int row_off, int rows, bool seams) {
   wdpm_ponds *h = new wdpm_ponds();
   h->x = ctx;
-  h->g.rows = sg.rows;
-  h->g.ncp = sg.ncp;
-  h->g.nsc = (sg.ncp + kSeg - 1) / kSeg;
-  h->g.nseg = h->g.rows * h->g.nsc;             /* <= cells / 64 + rows: an int with 2e9 cells */
+  h->row_off = row_off;
+  h->seams = seams;
+  h->g.rows = rows;
+  h->g.ncp = ctx->g.ncp;
+  h->g.nsc = (ctx->g.ncp + kSeg - 1) / kSeg;
+  h->g.nseg = h->g.rows * h->g.nsc;             /* <= cells / 64 + rows: an int with 2^31 - 1 cells */
   const char *e = getenv("WDPM_GUARD_KB");
   const long kb = e ? atol(e) : 0;
   h->guard = kb > 0 ? (size_t)kb * 1024 : 0;
@@ -563,10 +644,17 @@ extern "C" int wdpm_ponds_create(wdpm_ponds **out, wdpm_ctx *ctx) {
   h->d_parent = h->d_labels = h->d_cnt = h->d_bsum = nullptr;
   h->d_ucnt = nullptr;
   h->d_status = h->h_status = nullptr;
+  h->d_seam = h->h_seam = h->d_map = nullptr;
+  h->map_cap = 0;
+  h->h_map = nullptr;
+  h->h_table = nullptr;
+  h->stage_cap = 0;
   h->d_table = nullptr;
   h->table_cap = 0;
   h->nb = 0;
   { const char *re = getenv("WDPM_PONDS_ROWS_PER_WAVE"); h->forced_rpw = re ? atoi(re) : 0; }
+  h->rpw = 1;
+  memset(&h->last, 0, sizeof h->last);
   h->valid = false;
   memset(&h->stats, 0, sizeof h->stats);
   const char *te = getenv("WDPM_PONDS_TIMING");
@@ -576,22 +664,16 @@ extern "C" int wdpm_ponds_create(wdpm_ponds **out, wdpm_ctx *ctx) {
   if (h->timing)
     for (int i = 0; i < WDPM_PONDS_PHASES + 2; i++)
       if (hipEventCreate(&h->ev[i]) != hipSuccess) { h->timing = false; break; }
-  *out = h;
-  return 0;
+  return h;
 }
 
-extern "C" void wdpm_ponds_destroy(wdpm_ponds *h) {
-  if (!h) return;
-  (void)wdpm_synchronize(h->x);
-  release(h);
-  for (int i = 0; i < WDPM_PONDS_PHASES + 2; i++)
-    if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-  delete h;
-}
+#define PONDS_MARK(i) do { if (h->timing) HIP_TRY(hipEventRecord(h->ev[i], sm)); } while (0)
 
-extern "C" int wdpm_ponds_label(wdpm_ponds *h, double min_depth, int64_t *nponds) {
-  if (!h) return wdpm_fail("wdpm_ponds_label: null handle");
-  if (!(min_depth >= 0.0) || std::isinf(min_depth)) return wdpm_fail("wdpm_ponds_label: min_depth must be finite and >= 0 (got %g)", min_depth);
+/* ---- a label call in four steps: the two that queue work never wait for it, so a group queues every rank before it waits for
+ * the first.  wdpm_ponds_label runs them back to back. ---- */
+
+/* 1: mask, merge, flatten, scan (and the seam rows of a row block), status words on their way to the host */
+int label_queue(wdpm_ponds *h, double min_depth) {
   wdpm_ctx *x = h->x;
   h->valid = false;
   /* the raster as a reader sees it: side stream joined, owed drain() and threshold flush applied (what wdpm_count_stats asks for) */
@@ -600,13 +682,13 @@ extern "C" int wdpm_ponds_label(wdpm_ponds *h, double min_depth, int64_t *nponds
   if (allocate(h)) return 1;
   const Geom g = h->g;
   const hipStream_t sm = x->stream;
-  const double *w = x->d_w[x->cur];
+  const size_t off = (size_t)h->row_off * g.ncp;
+  const double *w = x->d_w[x->cur] + off;
   const unsigned seg_blocks = blocks_for(g.nseg, kWaves);
 
   HIP_TRY(hipMemsetAsync(h->d_status, 0, sizeof(Status), sm));
-#define PONDS_MARK(i) do { if (h->timing) HIP_TRY(hipEventRecord(h->ev[i], sm)); } while (0)
   PONDS_MARK(0);
-  hipLaunchKernelGGL(ponds_mask_kernel, dim3(seg_blocks), dim3(kBlock), 0, sm, w, x->d_dem, g, min_depth, h->d_masks, h->d_parent, h->d_status);
+  hipLaunchKernelGGL(ponds_mask_kernel, dim3(seg_blocks), dim3(kBlock), 0, sm, w, x->d_dem + off, g, min_depth, h->d_masks, h->d_parent, h->d_status);
   PONDS_MARK(1);
   hipLaunchKernelGGL(ponds_merge_kernel, dim3(seg_blocks), dim3(kBlock), 0, sm, h->d_masks, h->d_parent, g, h->d_ucnt);
   PONDS_MARK(2);
@@ -615,16 +697,38 @@ extern "C" int wdpm_ponds_label(wdpm_ponds *h, double min_depth, int64_t *nponds
   hipLaunchKernelGGL(ponds_scan_reduce_kernel, dim3(h->nb), dim3(kBlock), 0, sm, h->d_cnt, h->d_ucnt, g.nseg, h->d_bsum, h->d_busum);
   hipLaunchKernelGGL(ponds_scan_sums_kernel, dim3(1), dim3(kBlock), 0, sm, h->d_bsum, h->d_busum, h->nb, h->d_status);
   hipLaunchKernelGGL(ponds_scan_down_kernel, dim3(h->nb), dim3(kBlock), 0, sm, h->d_cnt, g.nseg, h->d_bsum);
+  if (h->seams)
+    hipLaunchKernelGGL(ponds_seam_kernel, dim3(blocks_for(2 * g.nsc, kWaves)), dim3(kBlock), 0, sm, h->d_masks, h->d_parent, h->d_cnt,
+                       h->d_rootmask, g, h->d_seam);
   PONDS_MARK(4);
   HIP_TRY(hipGetLastError());
+  if (h->seams) HIP_TRY(hipMemcpyAsync(h->h_seam, h->d_seam, (size_t)2 * g.ncp * sizeof(int), hipMemcpyDeviceToHost, sm));
   HIP_TRY(hipMemcpyAsync(h->h_status, h->d_status, sizeof(Status), hipMemcpyDeviceToHost, sm));
-  if (wdpm_stream_sync(x, sm)) return 1;
-  const Status st = *h->h_status;
-  if (st.deep)
+  return 0;
+}
+
+/* 2: wait for 1; N of the view */
+int label_status(wdpm_ponds *h, long long *n) {
+  HIP_TRY(hipSetDevice(h->x->p.device));
+  if (wdpm_stream_sync(h->x, h->x->stream)) return 1;
+  h->last = *h->h_status;
+  if (h->last.deep)
     return wdpm_fail("wdpm_ponds_label: a pond cell holds 512 m of water or more: volume_q (a 64-bit sum of depths in units of "
                      "2^-24 m) is only safe below that depth");
-  const long long n = st.ponds;
+  *n = h->last.ponds;
+  return 0;
+}
 
+/* 3: the table kernels.  With `mapped` (row blocks; `map` holds n ints, copied here) the label raster takes map[label - 1] and the
+ * finished table follows to h->h_table.  Map and table travel through pinned memory, so every transfer is queued like the
+ * kernels and the call returns without waiting for any of them; the pinned buffers grow only when N outgrows them. */
+int table_queue(wdpm_ponds *h, bool mapped, const int *map) {
+  wdpm_ctx *x = h->x;
+  const Geom g = h->g;
+  const hipStream_t sm = x->stream;
+  const long long n = h->last.ponds;
+  const double *w = x->d_w[x->cur] + (size_t)h->row_off * g.ncp;
+  HIP_TRY(hipSetDevice(x->p.device));
   if (n > h->table_cap) {                       /* sized from N, now that N is known */
     guarded_free(h, h->d_table);
     h->d_table = nullptr;
@@ -633,18 +737,52 @@ extern "C" int wdpm_ponds_label(wdpm_ponds *h, double min_depth, int64_t *nponds
     if (e != hipSuccess) return wdpm_fail("wdpm_ponds_label: no device memory for a table of %lld ponds: %s", n, hipGetErrorString(e));
     h->table_cap = n;
   }
-  const int rpw = ponds_rows_per_wave(g.nseg, g.rows, h->forced_rpw);
+  if (mapped && n > h->map_cap) {
+    guarded_free(h, h->d_map);
+    h->d_map = nullptr;
+    h->map_cap = 0;
+    const hipError_t e = guarded_malloc(h, (void **)&h->d_map, (size_t)n * sizeof(int));
+    if (e != hipSuccess) return wdpm_fail("wdpm_group_ponds_label: no device memory for the numbers of %lld ponds: %s", n, hipGetErrorString(e));
+    h->map_cap = n;
+  }
+  if (mapped && n > h->stage_cap) {
+    if (h->h_map) (void)hipHostFree(h->h_map);
+    if (h->h_table) (void)hipHostFree(h->h_table);
+    h->h_map = nullptr;
+    h->h_table = nullptr;
+    h->stage_cap = 0;
+    hipError_t e = hipHostMalloc(&h->h_map, (size_t)n * sizeof(int));
+    if (e == hipSuccess) e = hipHostMalloc(&h->h_table, (size_t)n * sizeof(wdpm_pond));
+    if (e != hipSuccess) return wdpm_fail("wdpm_group_ponds_label: no pinned host memory for %lld ponds: %s", n, hipGetErrorString(e));
+    h->stage_cap = n;
+  }
+  if (mapped && n > 0) {
+    memcpy(h->h_map, map, (size_t)n * sizeof(int));
+    HIP_TRY(hipMemcpyAsync(h->d_map, h->h_map, (size_t)n * sizeof(int), hipMemcpyHostToDevice, sm));
+  }
+  const int rpw = h->rpw = ponds_rows_per_wave(g.nseg, g.rows, h->forced_rpw);
   const int nwaves = ((g.rows + rpw - 1) / rpw) * g.nsc;
   PONDS_MARK(5);
   if (n > 0) hipLaunchKernelGGL(ponds_table_init_kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, sm, h->d_table, n);
-  hipLaunchKernelGGL(ponds_table_kernel, dim3(blocks_for(nwaves, kWaves)), dim3(kBlock), 0, sm, w, h->d_masks, h->d_parent, h->d_cnt,
-                     h->d_rootmask, g, rpw, nwaves, h->d_labels, h->d_table);
+  if (mapped)
+    hipLaunchKernelGGL(ponds_table_mapped_kernel, dim3(blocks_for(nwaves, kWaves)), dim3(kBlock), 0, sm, w, h->d_masks, h->d_parent,
+                       h->d_cnt, h->d_rootmask, g, rpw, nwaves, h->d_labels, h->d_table, h->d_map);
+  else
+    hipLaunchKernelGGL(ponds_table_kernel, dim3(blocks_for(nwaves, kWaves)), dim3(kBlock), 0, sm, w, h->d_masks, h->d_parent, h->d_cnt,
+                       h->d_rootmask, g, rpw, nwaves, h->d_labels, h->d_table);
   PONDS_MARK(6);
   if (n > 0) hipLaunchKernelGGL(ponds_table_finish_kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, sm, h->d_table, n);
   PONDS_MARK(7);
-#undef PONDS_MARK
   HIP_TRY(hipGetLastError());
-  if (wdpm_stream_sync(x, sm)) return 1;
+  if (mapped && n > 0) HIP_TRY(hipMemcpyAsync(h->h_table, h->d_table, (size_t)n * sizeof(wdpm_pond), hipMemcpyDeviceToHost, sm));
+  return 0;
+}
+#undef PONDS_MARK
+
+/* 4: wait for 3; the handle has an inventory */
+int table_wait(wdpm_ponds *h) {
+  HIP_TRY(hipSetDevice(h->x->p.device));
+  if (wdpm_stream_sync(h->x, h->x->stream)) return 1;
   if (h->timing) {
     /* mask, merge, flatten, scan, (host: status, table allocation), table init + table, finish */
     static const int from[WDPM_PONDS_PHASES] = {0, 1, 2, 3, 5, 6}, to[WDPM_PONDS_PHASES] = {1, 2, 3, 4, 6, 7};
@@ -654,14 +792,57 @@ extern "C" int wdpm_ponds_label(wdpm_ponds *h, double min_depth, int64_t *nponds
       h->phase_ms[i] = ms;
     }
   }
-
-  h->stats.segments = g.nseg;
-  h->stats.unions = (int64_t)st.unions;
-  h->stats.seam_unions = (int64_t)st.seam_unions;
+  h->stats.segments = h->g.nseg;
+  h->stats.unions = (int64_t)h->last.unions;
+  h->stats.seam_unions = (int64_t)h->last.seam_unions;
   h->stats.passes = 0;
-  h->stats.rows_per_wave = rpw;
-  h->stats.ponds = n;
+  h->stats.rows_per_wave = h->rpw;
+  h->stats.ponds = h->last.ponds;
   h->valid = true;
+  return 0;
+}
+
+int count_guard_bad(wdpm_ponds *h, int64_t *bytes) {
+  if (!h->guard || h->guards.empty()) return 0;
+  if (wdpm_synchronize(h->x)) return 1;
+  std::vector<unsigned char> buf(h->guard);
+  for (const Guarded &gb : h->guards)
+    for (int side = 0; side < 2; side++) {
+      HIP_TRY(hipMemcpy(buf.data(), gb.base + (side ? h->guard + gb.bytes : 0), h->guard, hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < h->guard; i++) *bytes += buf[i] != 0xA5;
+    }
+  return 0;
+}
+
+void destroy_handle(wdpm_ponds *h) {
+  if (!h) return;
+  (void)wdpm_synchronize(h->x);
+  release(h);
+  for (int i = 0; i < WDPM_PONDS_PHASES + 2; i++)
+    if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
+  delete h;
+}
+
+}  // namespace
+
+extern "C" int wdpm_ponds_create(wdpm_ponds **out, wdpm_ctx *ctx) {
+  if (!out || !ctx) return wdpm_fail("wdpm_ponds_create: null argument");
+  const SlabGeom &sg = ctx->g;
+  if (sg.row0 != 0 || sg.rows != sg.R + 2)
+    return wdpm_fail("wdpm_ponds_create: a slab context (rows %d..%d of %d) cannot take an inventory: ponds cross row blocks; "
+                     "use a context that holds the whole raster", sg.row0, sg.row0 + sg.rows, sg.R + 2);
+  if (wdpm_synchronize(ctx)) return 1;          /* binds the device */
+  *out = make_handle(ctx, 0, sg.rows, false);
+  return 0;
+}
+
+extern "C" void wdpm_ponds_destroy(wdpm_ponds *h) { destroy_handle(h); }
+
+extern "C" int wdpm_ponds_label(wdpm_ponds *h, double min_depth, int64_t *nponds) {
+  if (!h) return wdpm_fail("wdpm_ponds_label: null handle");
+  if (!(min_depth >= 0.0) || std::isinf(min_depth)) return wdpm_fail("wdpm_ponds_label: min_depth must be finite and >= 0 (got %g)", min_depth);
+  long long n = 0;
+  if (label_queue(h, min_depth) || label_status(h, &n) || table_queue(h, false, nullptr) || table_wait(h)) return 1;
   if (nponds) *nponds = n;
   return 0;
 }
@@ -689,15 +870,7 @@ extern "C" int wdpm_ponds_labels(wdpm_ponds *h, int32_t *padded) {
 extern "C" int wdpm_ponds_guard_bad(wdpm_ponds *h, int64_t *bytes) {
   if (!h || !bytes) return wdpm_fail("wdpm_ponds_guard_bad: null argument");
   *bytes = 0;
-  if (!h->guard || h->guards.empty()) return 0;
-  if (wdpm_synchronize(h->x)) return 1;
-  std::vector<unsigned char> buf(h->guard);
-  for (const Guarded &gb : h->guards)
-    for (int side = 0; side < 2; side++) {
-      HIP_TRY(hipMemcpy(buf.data(), gb.base + (side ? h->guard + gb.bytes : 0), h->guard, hipMemcpyDeviceToHost));
-      for (size_t i = 0; i < h->guard; i++) *bytes += buf[i] != 0xA5;
-    }
-  return 0;
+  return count_guard_bad(h, bytes);
 }
 
 extern "C" int wdpm_ponds_stats(wdpm_ponds *h, wdpm_pond_stats *out) {
@@ -712,6 +885,197 @@ extern "C" int wdpm_ponds_phase_ms(wdpm_ponds *h, double *ms) {
   if (!h->timing) return wdpm_fail("wdpm_ponds_phase_ms: the handle records no events (set WDPM_PONDS_TIMING=1 before it is made)");
   if (!h->valid) return wdpm_fail("wdpm_ponds_phase_ms: no inventory: wdpm_ponds_label has not succeeded on this handle");
   for (int i = 0; i < WDPM_PONDS_PHASES; i++) ms[i] = h->phase_ms[i];
+  return 0;
+}
+
+/* ---- row blocks (include/wdpm_group_ponds.h) --------------------------------------------------------------------------------- */
+struct wdpm_group_ponds {
+  wdpm_group *grp;
+  int n;                                   /* ranks */
+  int rows, ncp;                           /* the whole raster, padded */
+  std::vector<wdpm_ponds *> r;             /* one handle per rank, on its owned rows with one row either side */
+  std::vector<int> own_lo, own_rows, view0;   /* whole-raster rows: first owned, how many owned, the view's row 0 */
+  std::vector<wdpm_pond> table;            /* the merged table of the last label call */
+  bool timing, valid;
+  wdpm_group_pond_stats stats;
+};
+
+extern "C" int wdpm_group_ponds_create(wdpm_group_ponds **out, wdpm_group *grp) {
+  if (!out || !grp) return wdpm_fail("wdpm_group_ponds_create: null argument");
+  const int n = wdpm_group_size(grp);
+  if (n < 1) return wdpm_fail("wdpm_group_ponds_create: the group has no rank");
+  wdpm_group_ponds *h = new wdpm_group_ponds();
+  h->grp = grp;
+  h->n = n;
+  h->valid = false;
+  h->timing = true;
+  memset(&h->stats, 0, sizeof h->stats);
+  for (int i = 0; i < n; i++) {
+    wdpm_rank *rk = wdpm_group_rank(grp, i);
+    wdpm_ctx *x = rk ? wdpm_rank_ctx(rk) : nullptr;
+    wdpm_slab s;
+    if (!x || (n > 1 && wdpm_rank_slab(rk, -1, &s))) {
+      wdpm_group_ponds_destroy(h);
+      return wdpm_fail("wdpm_group_ponds_create: rank %d of the group cannot be read", i);
+    }
+    const int P = x->g.R + 2;
+    if (n == 1) { s.own_lo = 0; s.own_hi = P - 1; s.row0 = 0; }
+    /* owned rows and one row either side (the halos hold them); the raster's own border row at either end */
+    const int v0 = s.own_lo > 0 ? s.own_lo - 1 : 0, v1 = s.own_hi < P - 1 ? s.own_hi + 1 : P - 1;
+    if (v0 < x->g.row0 || v1 >= x->g.row0 + x->g.rows || v1 - v0 + 1 < 3) {
+      wdpm_group_ponds_destroy(h);
+      return wdpm_fail("wdpm_group_ponds_create: rank %d holds rows %d..%d, its owned rows %d..%d want one more either side", i,
+                       x->g.row0, x->g.row0 + x->g.rows - 1, s.own_lo, s.own_hi);
+    }
+    if ((long long)(v1 - v0 + 1) * x->g.ncp > (long long)INT_MAX) {
+      wdpm_group_ponds_destroy(h);
+      return wdpm_fail("wdpm_group_ponds_create: rank %d would label %lld cells, more than 2^31 - 1: use more row blocks", i,
+                       (long long)(v1 - v0 + 1) * x->g.ncp);
+    }
+    if (wdpm_synchronize(x)) { wdpm_group_ponds_destroy(h); return 1; }   /* binds the device */
+    wdpm_ponds *p = make_handle(x, v0 - x->g.row0, v1 - v0 + 1, true);
+    h->r.push_back(p);
+    h->own_lo.push_back(s.own_lo);
+    h->own_rows.push_back(s.own_hi - s.own_lo + 1);
+    h->view0.push_back(v0);
+    h->timing = h->timing && p->timing;
+    h->rows = P;
+    h->ncp = x->g.ncp;
+  }
+  *out = h;
+  return 0;
+}
+
+extern "C" void wdpm_group_ponds_destroy(wdpm_group_ponds *h) {
+  if (!h) return;
+  for (wdpm_ponds *p : h->r) destroy_handle(p);
+  delete h;
+}
+
+namespace {
+/* after a failure with work queued: let every rank's stream run dry, so that nothing still reads what the caller may free */
+int drain_and_fail(wdpm_group_ponds *h) {
+  std::string msg = wdpm_last_error();
+  for (wdpm_ponds *p : h->r)
+    if (hipSetDevice(p->x->p.device) == hipSuccess) (void)hipStreamSynchronize(p->x->stream);
+  return wdpm_fail("%s", msg.c_str());
+}
+}  // namespace
+
+extern "C" int wdpm_group_ponds_label(wdpm_group_ponds *h, double min_depth, int64_t *nponds) {
+  if (!h) return wdpm_fail("wdpm_group_ponds_label: null handle");
+  if (!(min_depth >= 0.0) || std::isinf(min_depth))
+    return wdpm_fail("wdpm_group_ponds_label: min_depth must be finite and >= 0 (got %g)", min_depth);
+  h->valid = false;
+  const int n = h->n;
+  /* every rank up to its scan, on its own stream and device, before the first wait */
+  for (int i = 0; i < n; i++)
+    if (label_queue(h->r[i], min_depth)) return drain_and_fail(h);
+  std::vector<wdpm_stitch::RankSeams> seams((size_t)n);
+  bool bad = false;
+  std::string first_msg;
+  for (int i = 0; i < n; i++) {
+    long long ni = 0;
+    if (label_status(h->r[i], &ni)) {           /* go on waiting for the others: nothing stays queued behind a failure */
+      if (!bad) first_msg = wdpm_last_error();
+      bad = true;
+      continue;
+    }
+    seams[i].n = ni;
+    seams[i].top = h->r[i]->h_seam;
+    seams[i].bottom = h->r[i]->h_seam + h->ncp;
+  }
+  if (bad) return wdpm_fail("%s", first_msg.c_str());
+
+  timespec t0, t1;
+  clock_gettime(CLOCK_MONOTONIC, &t0);
+  wdpm_stitch::Result res;
+  std::string err;
+  if (wdpm_stitch::stitch(seams, h->ncp, res, err)) return wdpm_fail("wdpm_group_ponds_label: %s", err.c_str());
+  clock_gettime(CLOCK_MONOTONIC, &t1);
+
+  /* every rank's table kernel, its labels written once as whole-raster numbers, and its own table on the way to the host:
+   * all of it queued (pinned staging on both ways) before the first wait */
+  for (int i = 0; i < n; i++)
+    if (table_queue(h->r[i], true, res.map[i].data())) return drain_and_fail(h);
+  for (int i = 0; i < n; i++)
+    if (table_wait(h->r[i])) {
+      if (!bad) first_msg = wdpm_last_error();
+      bad = true;
+    }
+  if (bad) return wdpm_fail("%s", first_msg.c_str());
+
+  h->table.assign((size_t)res.ponds, wdpm_pond());
+  for (int i = 0; i < n; i++)
+    if (wdpm_stitch::fold_table(h->r[i]->h_table, res.map[i], h->view0[i], h->table.data(), err))
+      return wdpm_fail("wdpm_group_ponds_label: %s", err.c_str());
+
+  h->stats.ranks = n;
+  h->stats.ponds = res.ponds;
+  h->stats.local_ponds = res.local_ponds;
+  h->stats.stitch_unions = res.unions;
+  h->stats.merged = res.merged;
+  h->stats.stitch_ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
+  h->valid = true;
+  if (nponds) *nponds = res.ponds;
+  return 0;
+}
+
+extern "C" int wdpm_group_ponds_table(wdpm_group_ponds *h, wdpm_pond *out, int64_t capacity) {
+  if (!h) return wdpm_fail("wdpm_group_ponds_table: null handle");
+  if (!h->valid) return wdpm_fail("wdpm_group_ponds_table: no inventory: wdpm_group_ponds_label has not succeeded on this handle");
+  const long long n = h->stats.ponds;
+  if (capacity < n) return wdpm_fail("wdpm_group_ponds_table: capacity %lld is too small for %lld ponds", (long long)capacity, n);
+  if (n == 0) return 0;
+  if (!out) return wdpm_fail("wdpm_group_ponds_table: null output");
+  memcpy(out, h->table.data(), (size_t)n * sizeof(wdpm_pond));
+  return 0;
+}
+
+extern "C" int wdpm_group_ponds_labels(wdpm_group_ponds *h, int32_t *padded) {
+  if (!h || !padded) return wdpm_fail("wdpm_group_ponds_labels: null argument");
+  if (!h->valid) return wdpm_fail("wdpm_group_ponds_labels: no inventory: wdpm_group_ponds_label has not succeeded on this handle");
+  /* Every rank's owned rows, to where they lie in the whole raster.  The caller's raster is pageable memory, to which a copy is
+   * synchronous whatever it is called: the ranks' rows come down one after another, as wdpm_group_download_water's do. */
+  for (int i = 0; i < h->n; i++) {
+    wdpm_ponds *p = h->r[i];
+    if (wdpm_synchronize(p->x)) return 1;
+    HIP_TRY(hipMemcpyAsync(padded + (size_t)h->own_lo[i] * h->ncp, p->d_labels + (size_t)(h->own_lo[i] - h->view0[i]) * h->ncp,
+                           (size_t)h->own_rows[i] * h->ncp * sizeof(int32_t), hipMemcpyDeviceToHost, p->x->stream));
+    if (wdpm_stream_sync(p->x, p->x->stream)) return 1;
+  }
+  return 0;
+}
+
+extern "C" int wdpm_group_ponds_guard_bad(wdpm_group_ponds *h, int64_t *bytes) {
+  if (!h || !bytes) return wdpm_fail("wdpm_group_ponds_guard_bad: null argument");
+  *bytes = 0;
+  for (wdpm_ponds *p : h->r)
+    if (count_guard_bad(p, bytes)) return 1;
+  return 0;
+}
+
+extern "C" int wdpm_group_ponds_stats(wdpm_group_ponds *h, wdpm_group_pond_stats *out) {
+  if (!h || !out) return wdpm_fail("wdpm_group_ponds_stats: null argument");
+  if (!h->valid) return wdpm_fail("wdpm_group_ponds_stats: no inventory: wdpm_group_ponds_label has not succeeded on this handle");
+  *out = h->stats;
+  return 0;
+}
+
+extern "C" int wdpm_group_ponds_rank_stats(wdpm_group_ponds *h, int32_t rank, wdpm_pond_stats *out) {
+  if (!h || !out) return wdpm_fail("wdpm_group_ponds_rank_stats: null argument");
+  if (rank < 0 || rank >= h->n) return wdpm_fail("wdpm_group_ponds_rank_stats: rank %d of %d", rank, h->n);
+  if (!h->valid) return wdpm_fail("wdpm_group_ponds_rank_stats: no inventory: wdpm_group_ponds_label has not succeeded on this handle");
+  *out = h->r[rank]->stats;
+  return 0;
+}
+
+extern "C" int wdpm_group_ponds_phase_ms(wdpm_group_ponds *h, int32_t rank, double *ms) {
+  if (!h || !ms) return wdpm_fail("wdpm_group_ponds_phase_ms: null argument");
+  if (rank < 0 || rank >= h->n) return wdpm_fail("wdpm_group_ponds_phase_ms: rank %d of %d", rank, h->n);
+  if (!h->timing) return wdpm_fail("wdpm_group_ponds_phase_ms: the handle records no events (set WDPM_PONDS_TIMING=1 before it is made)");
+  if (!h->valid) return wdpm_fail("wdpm_group_ponds_phase_ms: no inventory: wdpm_group_ponds_label has not succeeded on this handle");
+  for (int i = 0; i < WDPM_PONDS_PHASES; i++) ms[i] = h->r[rank]->phase_ms[i];
   return 0;
 }
 #endif  /* WDPM_PONDS_EMULATION */

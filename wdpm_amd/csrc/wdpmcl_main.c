@@ -37,7 +37,7 @@
 #include <unistd.h>
 
 #include "../../include/wdpm.h"
-#include "../../include/wdpm_ponds.h"
+#include "../../include/wdpm_group_ponds.h"
 /* the pond inventory is the HIP library's alone: weak references, so that this file also links against a back-end that
  * exports include/wdpm.h and nothing else (WDPM_PONDS then says so and writes no file) */
 #pragma weak wdpm_ponds_create
@@ -45,6 +45,12 @@
 #pragma weak wdpm_ponds_label
 #pragma weak wdpm_ponds_table
 #pragma weak wdpm_ponds_guard_bad
+#pragma weak wdpm_group_ponds_create
+#pragma weak wdpm_group_ponds_destroy
+#pragma weak wdpm_group_ponds_label
+#pragma weak wdpm_group_ponds_table
+#pragma weak wdpm_group_ponds_guard_bad
+#pragma weak wdpm_group_ponds_stats
 #include "arcascii.h"
 
 #define ITER_PER_BLOCK 1000 /* IterationNum, WDPMCL.c:597 */
@@ -633,13 +639,15 @@ static void relief_finish(relief_helper *h) {
  * WDPM_PONDS=<path>: the 8-connected water bodies of the final water, one CSV line per pond, numbered by first cell.  A pond
  * cell holds more than WDPM_PONDS_MIN_DEPTH_MM of water (default 1.0: the reference's own wet threshold, water > 0.001,
  * WDPMCL.c:1397-1404, so the cells column sums to the wet count of the final statistics).  Nothing of it goes to stdout. */
-typedef struct { wdpm_pond *rows; int64_t n; int64_t guard_bad; } pond_inventory;
+typedef struct { wdpm_pond *rows; int64_t n; int64_t guard_bad; int64_t blocks, joined; } pond_inventory;
 
 static int take_inventory(wdpm_ctx *c, double min_depth, pond_inventory *inv) {
   wdpm_ponds *h = NULL;
   inv->rows = NULL;
   inv->n = 0;
   inv->guard_bad = 0;
+  inv->blocks = 1;
+  inv->joined = 0;
   if (!wdpm_ponds_create || !wdpm_ponds_destroy || !wdpm_ponds_label || !wdpm_ponds_table || !wdpm_ponds_guard_bad) {
     fprintf(stderr, "WDPMCL: pond inventory: back-end %s has none, no file written\n", wdpm_backend_name());
     return 1;
@@ -658,6 +666,40 @@ static int take_inventory(wdpm_ctx *c, double min_depth, pond_inventory *inv) {
     inv->rows = NULL;
   }
   wdpm_ponds_destroy(h);
+  return rc;
+}
+
+/* the same of a raster in several row blocks: every block is labelled where it lies (include/wdpm_group_ponds.h) */
+static int take_group_inventory(wdpm_group *grp, double min_depth, pond_inventory *inv) {
+  wdpm_group_ponds *h = NULL;
+  wdpm_group_pond_stats gs;
+  inv->rows = NULL;
+  inv->n = 0;
+  inv->guard_bad = 0;
+  inv->blocks = 1;
+  inv->joined = 0;
+  if (!wdpm_group_ponds_create || !wdpm_group_ponds_destroy || !wdpm_group_ponds_label || !wdpm_group_ponds_table ||
+      !wdpm_group_ponds_guard_bad || !wdpm_group_ponds_stats) {
+    fprintf(stderr, "WDPMCL: pond inventory: back-end %s has none, no file written\n", wdpm_backend_name());
+    return 1;
+  }
+  int rc = wdpm_group_ponds_create(&h, grp);
+  if (!rc) rc = wdpm_group_ponds_label(h, min_depth, &inv->n);
+  if (!rc) rc = wdpm_group_ponds_stats(h, &gs);
+  if (!rc) {
+    inv->blocks = gs.ranks;
+    inv->joined = gs.merged;
+    inv->rows = (wdpm_pond *)malloc((size_t)(inv->n > 0 ? inv->n : 1) * sizeof(wdpm_pond));
+    if (!inv->rows) { wdpm_set_last_error("out of host memory for the pond table"); rc = 1; }
+  }
+  if (!rc) rc = wdpm_group_ponds_table(h, inv->rows, inv->n);
+  if (!rc && getenv("WDPM_GUARD_KB")) rc = wdpm_group_ponds_guard_bad(h, &inv->guard_bad);
+  if (rc) {
+    fprintf(stderr, "WDPMCL: pond inventory failed, no file written: %s\n", wdpm_last_error());
+    free(inv->rows);
+    inv->rows = NULL;
+  }
+  if (h) wdpm_group_ponds_destroy(h);
   return rc;
 }
 
@@ -681,7 +723,9 @@ static int write_inventory(const char *path, const pond_inventory *inv, double c
     fprintf(stderr, "WDPMCL: error writing pond inventory %s\n", path);
     return 1;
   }
-  fprintf(stderr, "WDPMCL: pond inventory: %lld pond%s written to %s\n", (long long)inv->n, inv->n == 1 ? "" : "s", path);
+  fprintf(stderr, "WDPMCL: pond inventory: %lld pond%s written to %s", (long long)inv->n, inv->n == 1 ? "" : "s", path);
+  if (inv->blocks > 1) fprintf(stderr, " (%lld row blocks, %lld joined across them)", (long long)inv->blocks, (long long)inv->joined);
+  fprintf(stderr, "\n");
   return 0;
 }
 
@@ -909,34 +953,21 @@ int main(int argc, char **argv) {
   ABI_TRY(wdpm_group_count_stats(ctx, NULL, &wet, &dev_max));
   ABI_TRY(wdpm_group_download_unpadded(ctx, 1, st.water));
   if (cfg.module == WDPM_DRAIN) ABI_TRY(wdpm_group_get_totaldrain(ctx, &totaldrain));
-  /* the pond inventory of the final water (WDPM_PONDS): on the one context of the default group here; a raster in several row
-   * blocks keeps its unmasked depths on the host and is labelled in one piece once the group is gone (below) */
+  /* the pond inventory of the final water (WDPM_PONDS), taken on the group before it goes: on its one context, or over its row
+   * blocks with every block labelled where it lies */
   const char *ponds_path = getenv("WDPM_PONDS");
   if (ponds_path && !*ponds_path) ponds_path = NULL;
   const double ponds_min_depth = (getenv("WDPM_PONDS_MIN_DEPTH_MM") ? atof(getenv("WDPM_PONDS_MIN_DEPTH_MM")) : 1.0) / 1000.0;
   pond_inventory inv;
   memset(&inv, 0, sizeof inv);
   int ponds_failed = 0;
-  double *ponds_water = NULL;
   if (ponds_path) {
     phase("statistics + download");
-    if (ndev == 1) {
-      ponds_failed = take_inventory(wdpm_rank_ctx(wdpm_group_rank(ctx, 0)), ponds_min_depth, &inv);
-      if (!ponds_failed) ponds_failed = write_inventory(ponds_path, &inv, st.cellarea);
-      free(inv.rows);
-      phase("pond inventory");
-    } else if (((double)st.R + 2) * ((double)st.C + 2) > 2.0e9) {
-      fprintf(stderr, "WDPMCL: pond inventory: the raster is larger than one context (2e9 cells): no file written\n");
-      ponds_path = NULL;
-    } else {
-      ponds_water = (double *)malloc(ncell * sizeof(double));
-      if (!ponds_water) {
-        fprintf(stderr, "WDPMCL: pond inventory: out of host memory, no file written\n");
-        ponds_failed = 1;
-      } else {
-        ABI_TRY(wdpm_group_download_unpadded(ctx, 0, ponds_water));   /* unmasked: the output raster carries NODATA marks */
-      }
-    }
+    ponds_failed = ndev == 1 ? take_inventory(wdpm_rank_ctx(wdpm_group_rank(ctx, 0)), ponds_min_depth, &inv)
+                             : take_group_inventory(ctx, ponds_min_depth, &inv);
+    if (!ponds_failed) ponds_failed = write_inventory(ponds_path, &inv, st.cellarea);
+    free(inv.rows);
+    phase("pond inventory");
   }
   int64_t guard_bad = inv.guard_bad;
   if (getenv("WDPM_GUARD_KB")) {   /* debugging aid (include/wdpm.h: WDPM_OPT_GUARD_BAD): did any kernel write outside its buffer? */
@@ -950,34 +981,6 @@ int main(int argc, char **argv) {
   wdpm_group_destroy(ctx);
   if (guard_bad) return 3;
   phase("statistics + download + destroy");
-  if (ponds_water) {
-    /* several row blocks: one whole-raster context on the first device, made from the host rasters, only to be labelled */
-    wdpm_params pp = p;
-    pp.module = WDPM_ADD;
-    pp.drainrow = pp.draincol = 0;
-    pp.slab_row0 = pp.slab_rows = 0;
-    pp.device = devices[0];
-    wdpm_setup none;
-    memset(&none, 0, sizeof none);
-    wdpm_ctx *whole = NULL;
-    int64_t bad = 0;
-    if (wdpm_create(&whole, &pp) != 0 || wdpm_upload_unpadded(whole, st.dem, ponds_water, &none) != 0) {
-      fprintf(stderr, "WDPMCL: pond inventory failed, no file written: %s\n", wdpm_last_error());
-      ponds_failed = 1;
-    } else {
-      ponds_failed = take_inventory(whole, ponds_min_depth, &inv);
-      if (!ponds_failed) ponds_failed = write_inventory(ponds_path, &inv, st.cellarea);
-      free(inv.rows);
-      if (getenv("WDPM_GUARD_KB")) ABI_TRY(wdpm_get_option(whole, WDPM_OPT_GUARD_BAD, &bad));
-    }
-    if (whole) wdpm_destroy(whole);
-    free(ponds_water);
-    if (bad + inv.guard_bad) {
-      fprintf(stderr, "WDPMCL: guard bands of the pond inventory: %lld bytes overwritten\n", (long long)(bad + inv.guard_bad));
-      return 3;
-    }
-    phase("pond inventory");
-  }
 
   const int watercount = (int)wet;
   const double final_vol = watertotal * st.cellarea;

@@ -1,4 +1,5 @@
-"""ctypes binding of include/wdpm_ponds.h: the pond inventory of a context's current water raster.
+"""ctypes binding of include/wdpm_ponds.h and include/wdpm_group_ponds.h: the pond inventory of a context's current water
+raster, and of a raster spread over the row blocks of a rowblock.Group.
 
 Product library only (the symbols are not part of the ABI of include/wdpm.h, and ``capi.SYMBOLS`` does not list them).
 
@@ -6,6 +7,9 @@ Product library only (the symbols are not part of the ABI of include/wdpm.h, and
         n = ponds.label(0.001)
         table = ponds.table()       # structured array, one row per pond, numbered by first cell
         labels = ponds.labels()     # int32, padded layout like the water raster
+
+    with rowblock.Group(...) as grp, GroupPonds(grp) as ponds:     # the same calls, the same answer, every rank labelled in place
+        n = ponds.label(0.001)
 """
 from __future__ import annotations
 
@@ -51,11 +55,31 @@ SYMBOLS = {
 }
 
 
+class GroupStatsStruct(C.Structure):
+    """struct wdpm_group_pond_stats"""
+    _fields_ = [("ranks", C.c_int64), ("ponds", C.c_int64), ("local_ponds", C.c_int64), ("stitch_unions", C.c_int64),
+                ("merged", C.c_int64), ("stitch_ms", C.c_double)]
+
+
+# every symbol include/wdpm_group_ponds.h declares
+GROUP_SYMBOLS = {
+    "wdpm_group_ponds_create": (C.c_int, [C.POINTER(_vp), _vp]),
+    "wdpm_group_ponds_destroy": (None, [_vp]),
+    "wdpm_group_ponds_label": (C.c_int, [_vp, C.c_double, C.POINTER(C.c_int64)]),
+    "wdpm_group_ponds_table": (C.c_int, [_vp, _vp, C.c_int64]),
+    "wdpm_group_ponds_labels": (C.c_int, [_vp, _vp]),
+    "wdpm_group_ponds_guard_bad": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "wdpm_group_ponds_stats": (C.c_int, [_vp, C.POINTER(GroupStatsStruct)]),
+    "wdpm_group_ponds_rank_stats": (C.c_int, [_vp, C.c_int32, C.POINTER(StatsStruct)]),
+    "wdpm_group_ponds_phase_ms": (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_double)]),
+}
+
+
 def bind(lib: capi.Lib):
     """Set the prototypes on a loaded product library; a library without the symbols is an error (no fallback)."""
     if getattr(lib, "_ponds_bound", False):
         return lib.dll
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(GROUP_SYMBOLS.items()):
         try:
             fn = getattr(lib.dll, name)
         except AttributeError:
@@ -137,4 +161,86 @@ class Ponds:
     def guard_bad(self) -> int:
         v = C.c_int64()
         self.lib.check(self.dll.wdpm_ponds_guard_bad(self._h, C.byref(v)))
+        return v.value
+
+
+class GroupPonds:
+    """The inventory handle of a rowblock.Group - wraps wdpm_group_ponds.  Labels the water Group.download_water returns, every
+    rank's rows where they lie, and answers as Ponds does on a whole-raster context holding the same water.  The C handle must
+    go before its group: the object keeps its Group alive, and a Group that is closed first closes the handles that live on it."""
+
+    def __init__(self, group):
+        self.group = group
+        self.lib = group.lib
+        self.dll = bind(group.lib)
+        self.shape = group.shape
+        self.n = None
+        self._h = None
+        h = C.c_void_p()
+        self.lib.check(self.dll.wdpm_group_ponds_create(C.byref(h), group._h))
+        self._h = h
+        self.ranks = group.size
+        deps = getattr(group, "_dependents", None)
+        if deps is not None:
+            deps.append(weakref.ref(self))
+
+    def close(self):
+        if self._h:
+            self.dll.wdpm_group_ponds_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def label(self, min_depth: float) -> int:
+        """Label the ponds deeper than min_depth (metres, strict) on the group's current water; returns their number."""
+        n = C.c_int64()
+        self.n = None
+        self.lib.check(self.dll.wdpm_group_ponds_label(self._h, float(min_depth), C.byref(n)))
+        self.n = n.value
+        return n.value
+
+    def table(self, capacity: int | None = None) -> np.ndarray:
+        """One row per pond (POND_DTYPE), coordinates of the whole raster."""
+        if self.n is None:
+            raise capi.WdpmError("GroupPonds.table: label() has not succeeded on this handle")
+        cap = self.n if capacity is None else int(capacity)
+        out = np.zeros(max(cap, 0), dtype=POND_DTYPE)
+        self.lib.check(self.dll.wdpm_group_ponds_table(self._h, out.ctypes.data, cap))
+        return out[:self.n]
+
+    def labels(self) -> np.ndarray:
+        out = np.empty(self.shape, dtype=np.int32)
+        self.lib.check(self.dll.wdpm_group_ponds_labels(self._h, out.ctypes.data))
+        return out
+
+    def stats(self) -> dict:
+        s = GroupStatsStruct()
+        self.lib.check(self.dll.wdpm_group_ponds_stats(self._h, C.byref(s)))
+        return {name: (float if name == "stitch_ms" else int)(getattr(s, name)) for name, _ in GroupStatsStruct._fields_}
+
+    def rank_stats(self, rank: int) -> dict:
+        """what Ponds.stats says, of one rank's own labelling"""
+        s = StatsStruct()
+        self.lib.check(self.dll.wdpm_group_ponds_rank_stats(self._h, int(rank), C.byref(s)))
+        return {name: int(getattr(s, name)) for name, _ in StatsStruct._fields_}
+
+    def phase_ms(self, rank: int) -> dict:
+        """milliseconds per kernel phase of one rank in the last label call (handles made with WDPM_PONDS_TIMING=1)"""
+        ms = (C.c_double * len(PHASES))()
+        self.lib.check(self.dll.wdpm_group_ponds_phase_ms(self._h, int(rank), ms))
+        return dict(zip(PHASES, (float(v) for v in ms)))
+
+    def guard_bad(self) -> int:
+        v = C.c_int64()
+        self.lib.check(self.dll.wdpm_group_ponds_guard_bad(self._h, C.byref(v)))
         return v.value

@@ -294,8 +294,14 @@ class Group:
         self._h, self.shape = h, (nrows + 2, ncols + 2)
         self.size = lib.dll.wdpm_group_size(h)
         self.halo_kind = lib.dll.wdpm_group_halo(h)
+        self._dependents = []   # weak references to handles that live on this group (wdpm_amd.ponds.GroupPonds): closed before it
 
     def close(self):
+        for ref in reversed(getattr(self, "_dependents", [])):
+            dep = ref()
+            if dep is not None:
+                dep.close()
+        self._dependents = []
         if self._h:
             self.lib.dll.wdpm_group_destroy(self._h)
             self._h = None
