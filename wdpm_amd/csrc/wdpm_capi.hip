@@ -316,11 +316,8 @@ int wdpm_create(wdpm_ctx **out, const wdpm_params *p) {
   x->signed_zero_safe = false;
   x->w_negative = false;
   x->w_odd = true;                /* nothing known about the rasters before the first upload */
-  x->launches = 0;
-  x->ms = 0.0;
-  x->steady_launches = 0;
-  x->steady_ms = 0.0;
-  x->timing = false; x->xch_count = 0; x->xch_ms = 0.0;
+  x->timing = false;
+  for (auto *t : x->timers()) { t->count = 0; t->ms = 0.0; }
   x->comm = nullptr;
   x->leak = false;
   x->d_dem = x->d_w[0] = x->d_w[1] = x->d_w[2] = nullptr;
@@ -416,8 +413,7 @@ void wdpm_destroy(wdpm_ctx *x) {
   for (int i = 0; i < 2; i++)
     if (x->ev_copy[i]) (void)hipEventDestroy(x->ev_copy[i]);
   for (auto &ge : x->graphs) (void)hipGraphExecDestroy(ge.exec);
-  for (auto &ep : x->pending) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
-  for (auto &ep : x->pending_steady) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
+  for (auto *t : x->timers()) x->pool.insert(x->pool.end(), t->pending.begin(), t->pending.end());   /* recorded, never read */
   for (auto &ep : x->pool) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
   guarded_free(x->d_dem); guarded_free(x->d_w[0]); guarded_free(x->d_w[1]); guarded_free(x->d_w[2]);
   (void)hipFree(x->d_scal); (void)hipFree(x->d_bits); guarded_free(x->d_dem32); (void)hipFree(x->d_stat);
@@ -511,7 +507,7 @@ static LaunchRequest iteration_request(const wdpm_ctx *x, int A0, int out_last, 
   return q;
 }
 
-/* captured launches carry what they were given by value (wdpm_ctx::GraphEntry): a new DEM, other codes or another outlet end them */
+/* captured launches carry what they were given by value (wdpm_ctx::GraphKey): a new DEM, other codes or another outlet end them */
 static void drop_graphs(wdpm_ctx *x) {
   if (x->graphs.empty()) return;
   (void)hipStreamSynchronize(x->stream);             /* a replay may still be running */
@@ -929,49 +925,47 @@ int wdpm_begin_block(wdpm_ctx *x, double thres) {
   return 0;
 }
 
+/* the recorded pairs of every timer: their milliseconds to the timer, their events back to the pool.  A pair leaves its list as it
+ * enters the pool, so that an error on the way leaves none in both. */
 static int fold_timing(wdpm_ctx *x) {
-  for (auto &ep : x->pending) {
-    HIP_TRY(hipEventSynchronize(ep.b));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ep.a, ep.b));
-    x->ms += ms;
-    x->pool.push_back(ep);
-  }
-  x->pending.clear();
-  for (auto &ep : x->pending_steady) {
-    HIP_TRY(hipEventSynchronize(ep.b));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ep.a, ep.b));
-    x->steady_ms += ms;
-    x->pool.push_back(ep);
-  }
-  x->pending_steady.clear();
-  for (auto &ep : x->pending_xch) {
-    HIP_TRY(hipEventSynchronize(ep.b));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ep.a, ep.b));
-    x->xch_ms += ms;
-    x->xch_count += 1;
-    x->pool.push_back(ep);
-  }
-  x->pending_xch.clear();
+  for (auto *t : x->timers())
+    while (!t->pending.empty()) {
+      const EventPair ep = t->pending.back();
+      HIP_TRY(hipEventSynchronize(ep.b));
+      float ms = 0.f;
+      HIP_TRY(hipEventElapsedTime(&ms, ep.a, ep.b));
+      t->ms += ms;
+      t->pending.pop_back();
+      x->pool.push_back(ep);
+    }
+  return 0;
+}
+
+/* an event pair from the pool, or a new one */
+static int take_pair(wdpm_ctx *x, EventPair *ep) {
+  if (!x->pool.empty()) { *ep = x->pool.back(); x->pool.pop_back(); }
+  else { HIP_TRY(hipEventCreate(&ep->a)); HIP_TRY(hipEventCreate(&ep->b)); }
+  return 0;
+}
+
+/* the first event of a pair for timer `t`, recorded on the context's stream (a pending list grown long is folded first) */
+static int start_pair(wdpm_ctx *x, const wdpm_ctx::Timer &t, EventPair *ep) {
+  if (t.pending.size() >= 256 && fold_timing(x)) return 1;
+  if (take_pair(x, ep)) return 1;
+  HIP_TRY(hipEventRecord(ep->a, x->stream));
   return 0;
 }
 
 int wdpm_xch_timing_begin(wdpm_ctx *x, EventPair *ep) {
   ep->a = ep->b = nullptr;
-  if (!x->timing) return 0;
-  if (x->pending_xch.size() >= 256 && fold_timing(x)) return 1;
-  if (!x->pool.empty()) { *ep = x->pool.back(); x->pool.pop_back(); }
-  else { HIP_TRY(hipEventCreate(&ep->a)); HIP_TRY(hipEventCreate(&ep->b)); }
-  HIP_TRY(hipEventRecord(ep->a, x->stream));
-  return 0;
+  return x->timing ? start_pair(x, x->t_xch, ep) : 0;
 }
 
 int wdpm_xch_timing_end(wdpm_ctx *x, const EventPair *ep) {
   if (!ep->a) return 0;
   HIP_TRY(hipEventRecord(ep->b, x->stream));
-  x->pending_xch.push_back(*ep);
+  x->t_xch.pending.push_back(*ep);
+  x->t_xch.count += 1;
   return 0;
 }
 
@@ -995,165 +989,192 @@ int wdpm_drain_outlet(wdpm_ctx *x) {
   return 0;
 }
 
+/* what a call of wdpm_iterate decides before its first launch */
+struct IterateCall {
+  int n_iter;
+  bool fold;        /* the last launch folds the max diff the caller announced (wdpm_expect_max_diff) */
+  bool steady;      /* the launches between the first and the last are timed by `st`, the whole call by `ep` where timing is on */
+  EventPair ep, st;
+};
+
+static int begin_call(wdpm_ctx *x, int n_iter, IterateCall *call) {
+  *call = IterateCall{n_iter, x->md_hint && x->kernel == WDPM_KERNEL_FUSED && x->p.module != WDPM_DRAIN && !x->signed_zero_safe,
+                      x->timing && n_iter >= 3 && x->kernel == WDPM_KERNEL_FUSED, {nullptr, nullptr}, {nullptr, nullptr}};
+  x->md_hint = x->md_valid = false;
+  /* stencil timing is opt-in (wdpm_timing_reset switches it on): two event records per call are a
+   * measurable share of a small raster's iteration */
+  if (x->timing && start_pair(x, x->t_call, &call->ep)) return 1;
+  return call->steady ? take_pair(x, &call->st) : 0;
+}
+
+static int end_call(wdpm_ctx *x, const IterateCall &call) {
+  if (x->timing) {
+    HIP_TRY(hipEventRecord(call.ep.b, x->stream));
+    x->t_call.pending.push_back(call.ep);
+  }
+  if (call.steady) {
+    x->t_steady.pending.push_back(call.st);
+    x->t_steady.count += call.n_iter - 2;
+  }
+  return 0;
+}
+
+/* whether a whole-slab launch of this context keeps the dry-tile flags, and its chunk height (0: the planner's) */
+struct SlabPolicy { bool track; int chunk_rows; };
+static SlabPolicy whole_slab_policy(const wdpm_ctx *x) {
+  /* A mostly wet raster (the last block that kept flags found most tiles working) drops the dry-tile flags for chunk heights
+   * that follow the XCDs' speeds (wdpm_kernels.h::XcdBalance): a tiling of its own.  The flags are looked at again every 16 blocks. */
+  const bool balanced = x->bal.mode == 2 || (x->bal.mode == 1 && x->wide_tri_ok);
+  const bool track = x->tiles_mode != 0 && !x->signed_zero_safe && !balanced;
+  /* sparse rasters march short chunks: the launch takes as long as its wettest tile */
+  return {track, x->p.chunk_rows >= 3 ? x->p.chunk_rows : (track && x->sparse ? kSparseChunkRows : 0)};
+}
+
+/* what a launch that may reduce max |w - oldw| over the rows the caller announced is given; with `fold` it does, into a cell zeroed here */
+static int max_diff_args(wdpm_ctx *x, bool fold, MaxDiffArgs *md) {
+  *md = MaxDiffArgs{fold ? x->d_w[x->old] : nullptr, x->flush_thres, x->md_lo, x->md_hi, x->d_md};
+  if (fold) HIP_TRY(hipMemsetAsync(x->d_md, 0, sizeof(unsigned long long), x->stream));
+  return 0;
+}
+
+/* The host's state after an iteration launch that read d_w[cur] whole and wrote d_w[t], `advanced` iterations on; `tp`: the tile
+ * plan of a launch that maintained t's dry-tile flags, else nullptr. */
+static int launched(wdpm_ctx *x, int t, int advanced, const TilePlan *tp) {
+  if (x->flush_pending) flushed_whole(x, x->flush_thres);   /* the launch flushed every value it loaded, and it loaded them all */
+  if (tp) {
+    if (tp->nstrips != x->tile_nstrips || tp->H != x->tile_H || tp->nchunks != x->tile_nchunks) {
+      /* another tiling from here on: nothing known about any raster, and the flag arrays get their border of
+       * 1s for the new pitch (queued behind the launch, which wrote t's interior flags: only the other two) */
+      x->zero_valid[0] = x->zero_valid[1] = x->zero_valid[2] = false;
+      x->tile_nstrips = tp->nstrips; x->tile_H = tp->H; x->tile_nchunks = tp->nchunks;
+      for (int i = 0; i < 3; i++)
+        if (i != t) HIP_TRY(hipMemsetAsync(x->d_zero[i], 1, (size_t)x->tile_cap, x->stream));
+    }
+    x->tiles_launched += (int64_t)tp->nstrips * tp->nchunks;
+  }
+  x->zero_valid[t] = tp != nullptr;
+  x->cur = t;
+  x->flush_pending = false;
+  x->drain_owed = x->p.module == WDPM_DRAIN;     /* this iteration's drain(): owed to the next launch or reader */
+  x->t_call.count += advanced;
+  return 0;
+}
+
+/* One launch of the fused kernels over the whole slab, as iteration `it` of the call.  *did: iterations it advanced the raster by -
+ * two where the dispatch offers both in one launch (plan_iter2); did == nullptr: one, never two (launches before and inside a graph) */
+static int fused_step(wdpm_ctx *x, const IterateCall &call, const int it, int *did) {
+  if (call.steady && it == 1) HIP_TRY(hipEventRecord(call.st.a, x->stream));
+  if (call.steady && it == call.n_iter - 1) HIP_TRY(hipEventRecord(call.st.b, x->stream));
+  if (x->flush_pending && x->signed_zero_safe && ensure_flushed(x)) return 1;   /* no flush-on-load variant of that kernel */
+  const int t = free_slot(x);
+  TilePlan tp{x->d_zero[x->cur], x->d_zero[t], x->zero_valid[x->cur] ? 1 : 0, x->zero_valid[t] ? 1 : 0, x->d_active,
+              x->tile_cap, x->tile_nstrips, x->tile_H, x->tile_nchunks, 0, x->wide_tri_ok ? 1 : 0};
+  const SlabPolicy pol = whole_slab_policy(x);
+  /* the block's last iteration also reduces max |w - oldw| over the rows the caller announced */
+  MaxDiffArgs md;
+  if (max_diff_args(x, call.fold && it == call.n_iter - 1, &md)) return 1;
+  const LaunchRequest q = iteration_request(x, 0, x->g.rows - 1, pol.chunk_rows, md.old != nullptr, 0, pol.track ? &tp : nullptr, x->bal.mode != 0);
+  const IterationBuffers buf{x->d_w[x->cur], x->d_w[t], x->d_dem, &x->code, x->flush_pending ? x->flush_thres : 0.0, x->drain_owed ? 1 : 0,
+                             x->d_scal, x->stream, pol.track ? &tp : nullptr, &md, &x->bal, x->d_iter2_err};
+  /* iterations from this one on that are launches like it: not the block's last where that folds the max diff - and, where the
+   * steady launches are timed, neither the call's first nor its last */
+  int alike = 0;
+  if (did && !x->flush_pending && !md.old && !(call.steady && it == 0))
+    alike = call.n_iter - it - ((call.fold || call.steady) ? 1 : 0);
+  const LaunchPlan plan = alike >= 2 ? plan_iter2(q, *x->facts, wdpm_switches(), alike) : plan_iteration(q, *x->facts, wdpm_switches());
+  const int advanced = plan.iter2 ? 2 : 1;
+  if (did) *did = advanced;
+  HIP_TRY(wdpm_launch_iteration(q, plan, buf));
+  if (md.old) x->md_valid = true;
+  return launched(x, t, advanced, pol.track && tp.maintained ? &tp : nullptr);
+}
+
+/* one iteration as the pass kernel's nine colour passes, each a launch, and the drain module's drain() */
+static int pass_step(wdpm_ctx *x) {
+  for (int oi = 1; oi <= 3; oi++)
+    for (int oj = 1; oj <= 3; oj++)
+      if (one_pass(x, oi, oj)) return 1;
+  x->t_call.count += 9;
+  if (x->p.module == WDPM_DRAIN)
+    HIP_TRY(wdpm_launch_drain_outlet(x->d_w[x->cur], x->d_dem, x->g, x->d_scal, x->stream));
+  return 0;
+}
+
+/* Small rasters are launch-bound (482 x 471: 5.2 us of kernel, 6.3 us from launch to launch when the host queues them one by one):
+ * the iterations between a block's first (threshold flush on load) and last (max diff) are replayed as HIP graphs of kGraphIters
+ * launches each, captured from wdpm_iterate's own steps (round 5; `tools/graph_probe.py` measured +21 % for add at that size, +3 % for
+ * drain, nothing from 2048^2 up).  Only where a launch keeps no state on the host (the relay / triangle kernels: no tile flags, no
+ * balance table) and nobody times the launches; the rasters ping-pong between two buffers within a block, so an even count returns
+ * to the state it was captured in.  WDPM_GRAPH=0: never. */
+constexpr int kGraphIters = 32;
+
+static bool graphs_apply(wdpm_ctx *x, const IterateCall &call) {
+  if (x->kernel != WDPM_KERNEL_FUSED || x->timing || call.n_iter < kGraphIters + 2 || x->graph_mode == 0) return false;
+  if (x->graph_mode < 0) { const char *e = getenv("WDPM_GRAPH"); x->graph_mode = (e && atoi(e) == 0) ? 0 : 1; }
+  const SlabPolicy pol = whole_slab_policy(x);
+  TilePlan tq{nullptr, nullptr, 0, 0, nullptr, 0, 0, 0, 0, 0, x->wide_tri_ok ? 1 : 0};
+  /* would a whole-slab steady launch (no flush, no folded max diff) of this context go to the relay / triangle kernels of small
+   * rasters?  Asks the dispatch itself. */
+  LaunchRequest steady = iteration_request(x, 0, x->g.rows - 1, pol.chunk_rows, false, 0, pol.track ? &tq : nullptr, false);
+  steady.flush = false;
+  const LaunchPlan sp = plan_iteration(steady, *x->facts, wdpm_switches());
+  return x->graph_mode == 1 && !sp.error && sp.family != WDPM_FAMILY_MARCHING;
+}
+
+/* iterations *it ... of the call, kGraphIters at a time, while that leaves the call its last launch */
+static int replay_steady(wdpm_ctx *x, const IterateCall &call, int *it) {
+  while (call.n_iter - 1 - *it >= kGraphIters && x->graph_mode == 1) {
+    const wdpm_ctx::GraphKey key{x->code.q, x->code.h, x->cur, x->old, launch_flags(x), x->drain_owed ? 1 : 0, whole_slab_policy(x).chunk_rows,
+                                 x->g.dr, x->g.dc, x->wide_tri_ok ? 1 : 0, x->code.force, 0};
+    hipGraphExec_t exec = nullptr;
+    for (const auto &ge : x->graphs)
+      if (!memcmp(&ge.key, &key, sizeof key)) { exec = ge.exec; break; }
+    if (!exec) {
+      /* capture kGraphIters launches of wdpm_iterate's (nothing runs yet; the host's bookkeeping moves on as if they had) */
+      hipGraph_t graph = nullptr;
+      if (hipStreamBeginCapture(x->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); x->graph_mode = 0; break; }
+      int bad = 0;
+      for (int k = 0; k < kGraphIters && !bad; k++) bad = fused_step(x, call, *it + k, nullptr);
+      const hipError_t ec = hipStreamEndCapture(x->stream, &graph);
+      if (bad || ec != hipSuccess || !graph || hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
+        if (graph) (void)hipGraphDestroy(graph);
+        (void)hipGetLastError();
+        x->graph_mode = 0;
+        return fail("wdpm_iterate: capturing %d iterations as a HIP graph failed (set WDPM_GRAPH=0 to launch them one by one)", kGraphIters);
+      }
+      (void)hipGraphDestroy(graph);
+      if (x->graphs.size() >= 12) drop_graphs(x);
+      x->graphs.push_back({key, exec});
+    } else {
+      /* what kGraphIters steps leave on the host: the same current raster (an even count), nothing known about dry tiles of the
+       * two rasters written, drain() owed by the last launch */
+      for (int k = 0; k < kGraphIters; k++)
+        if (launched(x, free_slot(x), 1, nullptr)) return 1;
+    }
+    HIP_TRY(hipGraphLaunch(exec, x->stream));
+    x->graph_launches++;
+    *it += kGraphIters;
+  }
+  return 0;
+}
+
 int wdpm_iterate(wdpm_ctx *x, int32_t n_iter) {
   if (n_iter < 0) return fail("wdpm_iterate: negative iteration count");
   if (n_iter == 0) return 0;
   if (bind(x)) return 1;
-  const bool fold = x->md_hint && x->kernel == WDPM_KERNEL_FUSED && x->p.module != WDPM_DRAIN && !x->signed_zero_safe;
-  x->md_hint = x->md_valid = false;
-  /* stencil timing is opt-in (wdpm_timing_reset switches it on): two event records per call are a
-   * measurable share of a small raster's iteration */
-  EventPair ep{nullptr, nullptr};
-  if (x->timing) {
-    if (x->pending.size() >= 256 && fold_timing(x)) return 1;
-    if (!x->pool.empty()) { ep = x->pool.back(); x->pool.pop_back(); }
-    else { HIP_TRY(hipEventCreate(&ep.a)); HIP_TRY(hipEventCreate(&ep.b)); }
-    HIP_TRY(hipEventRecord(ep.a, x->stream));
-  }
-  EventPair st{nullptr, nullptr};
-  const bool steady = x->timing && n_iter >= 3 && x->kernel == WDPM_KERNEL_FUSED;
-  if (steady) {
-    if (!x->pool.empty()) { st = x->pool.back(); x->pool.pop_back(); }
-    else { HIP_TRY(hipEventCreate(&st.a)); HIP_TRY(hipEventCreate(&st.b)); }
-  }
-  /* *did: iterations this call advanced the raster by - two where the dispatch offers both in one launch (plan_iter2) */
-  auto one_iteration = [&](const int it, int *did = nullptr) -> int {
-    if (steady && it == 1) HIP_TRY(hipEventRecord(st.a, x->stream));
-    if (steady && it == n_iter - 1) HIP_TRY(hipEventRecord(st.b, x->stream));
-    if (x->kernel == WDPM_KERNEL_FUSED) {
-      if (x->flush_pending && x->signed_zero_safe && ensure_flushed(x)) return 1;   /* no flush-on-load variant of that kernel */
-      const int t = free_slot(x);
-      TilePlan tp{x->d_zero[x->cur], x->d_zero[t], x->zero_valid[x->cur] ? 1 : 0, x->zero_valid[t] ? 1 : 0, x->d_active,
-                  x->tile_cap, x->tile_nstrips, x->tile_H, x->tile_nchunks, 0, x->wide_tri_ok ? 1 : 0};
-      /* A mostly wet raster (the last block that kept flags found most tiles working) drops the dry-tile flags for chunk heights
-       * that follow the XCDs' speeds (wdpm_kernels.h::XcdBalance): a tiling of its own.  The flags are looked at again every 16 blocks. */
-      const bool balanced = x->bal.mode == 2 || (x->bal.mode == 1 && x->wide_tri_ok);
-      const bool track = x->tiles_mode != 0 && !x->signed_zero_safe && !balanced;
-      /* sparse rasters march short chunks: the launch takes as long as its wettest tile */
-      const int chunk_rows = x->p.chunk_rows >= 3 ? x->p.chunk_rows : (track && x->sparse ? kSparseChunkRows : 0);
-      /* the block's last iteration also reduces max |w - oldw| over the rows the caller announced */
-      MaxDiffArgs md{nullptr, x->flush_thres, x->md_lo, x->md_hi, x->d_md};
-      if (fold && it == n_iter - 1) {
-        md.old = x->d_w[x->old];
-        HIP_TRY(hipMemsetAsync(x->d_md, 0, sizeof(unsigned long long), x->stream));
-      }
-      const LaunchRequest q = iteration_request(x, 0, x->g.rows - 1, chunk_rows, md.old != nullptr, 0, track ? &tp : nullptr, x->bal.mode != 0);
-      const IterationBuffers buf{x->d_w[x->cur], x->d_w[t], x->d_dem, &x->code, x->flush_pending ? x->flush_thres : 0.0, x->drain_owed ? 1 : 0,
-                                 x->d_scal, x->stream, track ? &tp : nullptr, &md, &x->bal, x->d_iter2_err};
-      /* iterations from this one on that are launches like it: not the block's last where that folds the max diff - and, where the
-       * steady launches are timed, neither the call's first nor its last */
-      int alike = 0;
-      if (did && !x->flush_pending && !md.old && !(steady && it == 0))
-        alike = n_iter - it - ((fold || steady) ? 1 : 0);
-      const LaunchPlan plan = alike >= 2 ? plan_iter2(q, *x->facts, wdpm_switches(), alike) : plan_iteration(q, *x->facts, wdpm_switches());
-      const int advanced = plan.iter2 ? 2 : 1;
-      if (did) *did = advanced;
-      HIP_TRY(wdpm_launch_iteration(q, plan, buf));
-      if (x->flush_pending) flushed_whole(x, x->flush_thres);   /* the launch flushed every value it loaded, and it loaded them all */
-      if (md.old) x->md_valid = true;
-      if (track && tp.maintained) {
-        if (tp.nstrips != x->tile_nstrips || tp.H != x->tile_H || tp.nchunks != x->tile_nchunks) {
-          /* another tiling from here on: nothing known about any raster, and the flag arrays get their border of
-           * 1s for the new pitch (queued behind the launch, which wrote t's interior flags: only the other two) */
-          x->zero_valid[0] = x->zero_valid[1] = x->zero_valid[2] = false;
-          x->tile_nstrips = tp.nstrips; x->tile_H = tp.H; x->tile_nchunks = tp.nchunks;
-          for (int i = 0; i < 3; i++)
-            if (i != t) HIP_TRY(hipMemsetAsync(x->d_zero[i], 1, (size_t)x->tile_cap, x->stream));
-        }
-        x->zero_valid[t] = true;
-        x->tiles_launched += (int64_t)tp.nstrips * tp.nchunks;
-      } else {
-        x->zero_valid[t] = false;
-      }
-      x->cur = t;
-      x->flush_pending = false;
-      x->drain_owed = x->p.module == WDPM_DRAIN;     /* this iteration's drain(): owed to the next launch or reader */
-      x->launches += advanced;
-      return 0;
-    } else {
-      for (int oi = 1; oi <= 3; oi++)
-        for (int oj = 1; oj <= 3; oj++)
-          if (one_pass(x, oi, oj)) return 1;
-      x->launches += 9;
-    }
-    if (x->p.module == WDPM_DRAIN)
-      HIP_TRY(wdpm_launch_drain_outlet(x->d_w[x->cur], x->d_dem, x->g, x->d_scal, x->stream));
-    return 0;
-  };
+  IterateCall call;
+  if (begin_call(x, n_iter, &call)) return 1;
   int it = 0;
-  /* Small rasters are launch-bound (482 x 471: 5.2 us of kernel, 6.3 us from launch to launch when the host queues them one by one):
-   * the iterations between a block's first (threshold flush on load) and last (max diff) are replayed as HIP graphs of kGraphIters
-   * launches each, captured from this very loop (round 5; `tools/graph_probe.py` measured +21 % for add at that size, +3 % for drain,
-   * nothing from 2048^2 up).  Only where a launch keeps no state on the host (the relay / triangle kernels: no tile flags, no balance
-   * table) and nobody times the launches; the rasters ping-pong between two buffers within a block, so an even count returns to
-   * the state it was captured in.  WDPM_GRAPH=0: never. */
-  constexpr int kGraphIters = 32;
-  if (x->kernel == WDPM_KERNEL_FUSED && !x->timing && n_iter >= kGraphIters + 2 && x->graph_mode != 0) {
-    if (x->graph_mode < 0) { const char *e = getenv("WDPM_GRAPH"); x->graph_mode = (e && atoi(e) == 0) ? 0 : 1; }
-    const bool balanced = x->bal.mode == 2 || (x->bal.mode == 1 && x->wide_tri_ok);
-    const bool track = x->tiles_mode != 0 && !x->signed_zero_safe && !balanced;
-    const int chunk_rows = x->p.chunk_rows >= 3 ? x->p.chunk_rows : (track && x->sparse ? kSparseChunkRows : 0);
-    TilePlan tq{nullptr, nullptr, 0, 0, nullptr, 0, 0, 0, 0, 0, x->wide_tri_ok ? 1 : 0};
-    /* would a whole-slab steady launch (no flush, no folded max diff) of this context go to the relay / triangle kernels of small
-     * rasters?  Asks the dispatch itself. */
-    LaunchRequest steady = iteration_request(x, 0, x->g.rows - 1, chunk_rows, false, 0, track ? &tq : nullptr, false);
-    steady.flush = false;
-    const LaunchPlan sp = plan_iteration(steady, *x->facts, wdpm_switches());
-    if (x->graph_mode == 1 && !sp.error && sp.family != WDPM_FAMILY_MARCHING) {
-      if (one_iteration(it++)) return 1;                   /* the block's first launch: as ever */
-      while (n_iter - 1 - it >= kGraphIters && x->graph_mode == 1) {
-        wdpm_ctx::GraphEntry key{x->cur, x->old, launch_flags(x), x->drain_owed ? 1 : 0, chunk_rows, x->g.dr, x->g.dc, x->wide_tri_ok ? 1 : 0,
-                                 x->code.force, x->code.q, x->code.h, nullptr};
-        hipGraphExec_t exec = nullptr;
-        for (const auto &ge : x->graphs)
-          if (ge.cur == key.cur && ge.old == key.old && ge.flags == key.flags && ge.drain_owed == key.drain_owed && ge.chunk_rows == key.chunk_rows &&
-              ge.dr == key.dr && ge.dc == key.dc && ge.wide == key.wide && ge.force == key.force && ge.q == key.q && ge.h == key.h) { exec = ge.exec; break; }
-        if (!exec) {
-          /* capture kGraphIters launches of this loop (nothing runs yet; the host's bookkeeping moves on as if they had) */
-          hipGraph_t graph = nullptr;
-          if (hipStreamBeginCapture(x->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); x->graph_mode = 0; break; }
-          int bad = 0;
-          for (int k = 0; k < kGraphIters && !bad; k++) bad = one_iteration(it + k);
-          const hipError_t ec = hipStreamEndCapture(x->stream, &graph);
-          if (bad || ec != hipSuccess || !graph || hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-            if (graph) (void)hipGraphDestroy(graph);
-            (void)hipGetLastError();
-            x->graph_mode = 0;
-            return fail("wdpm_iterate: capturing %d iterations as a HIP graph failed (set WDPM_GRAPH=0 to launch them one by one)", kGraphIters);
-          }
-          (void)hipGraphDestroy(graph);
-          if (x->graphs.size() >= 12) drop_graphs(x);
-          key.exec = exec;
-          x->graphs.push_back(key);
-          HIP_TRY(hipGraphLaunch(exec, x->stream));
-          x->graph_launches++;
-        } else {
-          HIP_TRY(hipGraphLaunch(exec, x->stream));
-          x->graph_launches++;
-          /* what kGraphIters passes through one_iteration() leave on the host: the same current raster (an even count), nothing known
-           * about dry tiles of the two rasters written, drain() owed by the last launch */
-          x->zero_valid[x->cur] = x->zero_valid[free_slot(x)] = false;
-          x->drain_owed = x->p.module == WDPM_DRAIN;
-          x->launches += kGraphIters;
-        }
-        it += kGraphIters;
-      }
-    }
+  if (graphs_apply(x, call)) {
+    if (fused_step(x, call, it++, nullptr)) return 1;      /* the block's first launch: as ever */
+    if (replay_steady(x, call, &it)) return 1;
   }
   while (it < n_iter) {
     int did = 1;
-    if (one_iteration(it, &did)) return 1;
+    if (x->kernel == WDPM_KERNEL_FUSED ? fused_step(x, call, it, &did) : pass_step(x)) return 1;
     it += did;
   }
-  if (x->timing) {
-    HIP_TRY(hipEventRecord(ep.b, x->stream));
-    x->pending.push_back(ep);
-  }
-  if (steady) {
-    x->pending_steady.push_back(st);
-    x->steady_launches += n_iter - 2;
-  }
-  return 0;
+  return end_call(x, call);
 }
 
 int wdpm_iterate_overlapped(wdpm_ctx *x, int32_t n_iter, int32_t top_rows, int32_t bottom_rows) {
@@ -1179,17 +1200,12 @@ int wdpm_iterate_overlapped(wdpm_ctx *x, int32_t n_iter, int32_t top_rows, int32
   double *w_out = x->d_w[t_slot];
   const bool fold = x->md_hint && !x->signed_zero_safe;     /* (usable: fused kernel, not the drain module) */
   x->md_hint = x->md_valid = false;
-  MaxDiffArgs md{fold ? x->d_w[x->old] : nullptr, x->flush_thres, x->md_lo, x->md_hi, x->d_md};
-  if (fold) HIP_TRY(hipMemsetAsync(x->d_md, 0, sizeof(unsigned long long), x->stream));
+  MaxDiffArgs md;
+  if (max_diff_args(x, fold, &md)) return 1;
   /* stencil timing of this iteration: from here on the main stream to the end of the interior launch
    * on the side stream (the longest of the three) */
   EventPair ep{nullptr, nullptr};
-  if (x->timing) {
-    if (x->pending.size() >= 256 && fold_timing(x)) return 1;
-    if (!x->pool.empty()) { ep = x->pool.back(); x->pool.pop_back(); }
-    else { HIP_TRY(hipEventCreate(&ep.a)); HIP_TRY(hipEventCreate(&ep.b)); }
-    HIP_TRY(hipEventRecord(ep.a, x->stream));
-  }
+  if (x->timing && start_pair(x, x->t_call, &ep)) return 1;
   HIP_TRY(hipEventRecord(x->ev_fork, x->stream));               /* w_in is complete here */
   /* one window of the three: no tile flags (not the tiling they are kept for), no balance table */
   auto window = [&](const int A0, const int out_last, const int leave_cus, hipStream_t s) -> hipError_t {
@@ -1204,17 +1220,13 @@ int wdpm_iterate_overlapped(wdpm_ctx *x, int32_t n_iter, int32_t top_rows, int32
   HIP_TRY(window(t_last >= 0 ? t_last - 1 : 0, b_first < rows ? b_first - 1 : rows - 1, x->comm ? 8 : 0, x->side));
   if (x->timing) {
     HIP_TRY(hipEventRecord(ep.b, x->side));
-    x->pending.push_back(ep);
+    x->t_call.pending.push_back(ep);
   }
   HIP_TRY(hipEventRecord(x->ev_join, x->side));
   x->pending_join = true;
-  x->zero_valid[t_slot] = false;   /* three windows, not the tiling the flags are kept for */
   if (fold) x->md_valid = true;
-  x->cur = t_slot;
-  if (x->flush_pending) flushed_whole(x, x->flush_thres);
-  x->flush_pending = false;
-  x->launches += 3;
-  return 0;
+  x->t_call.count += 3;
+  return launched(x, t_slot, 0, nullptr);   /* no flags kept: three windows, not the tiling they are for; the launches are counted above */
 }
 
 int wdpm_expect_max_diff(wdpm_ctx *x, int32_t row_lo, int32_t row_hi) {
@@ -1368,12 +1380,7 @@ int wdpm_run_block(wdpm_ctx *x, int32_t n_iter, double thres, double *max_diff) 
 int wdpm_timing_reset(wdpm_ctx *x) {
   if (bind(x)) return 1;
   if (fold_timing(x)) return 1;
-  x->launches = 0;
-  x->ms = 0.0;
-  x->steady_launches = 0;
-  x->steady_ms = 0.0;
-  x->xch_count = 0;
-  x->xch_ms = 0.0;
+  for (auto *t : x->timers()) { t->count = 0; t->ms = 0.0; }
   x->timing = true;
   return 0;
 }
@@ -1400,28 +1407,16 @@ int wdpm_balance_info(wdpm_ctx *x, int32_t *updates, double *weights9) {
   return 0;
 }
 
-int wdpm_timing_get_exchange(wdpm_ctx *x, int64_t *refreshes, double *ms) {
+static int timing_get(wdpm_ctx *x, const wdpm_ctx::Timer &t, int64_t *count, double *ms) {
   if (bind(x)) return 1;
   if (fold_timing(x)) return 1;
-  if (refreshes) *refreshes = x->xch_count;
-  if (ms) *ms = x->xch_ms;
+  if (count) *count = t.count;
+  if (ms) *ms = t.ms;
   return 0;
 }
 
-int wdpm_timing_get_steady(wdpm_ctx *x, int64_t *launches, double *ms) {
-  if (bind(x)) return 1;
-  if (fold_timing(x)) return 1;
-  if (launches) *launches = x->steady_launches;
-  if (ms) *ms = x->steady_ms;
-  return 0;
-}
-
-int wdpm_timing_get(wdpm_ctx *x, int64_t *launches, double *ms) {
-  if (bind(x)) return 1;
-  if (fold_timing(x)) return 1;
-  if (launches) *launches = x->launches;
-  if (ms) *ms = x->ms;
-  return 0;
-}
+int wdpm_timing_get_exchange(wdpm_ctx *x, int64_t *refreshes, double *ms) { return timing_get(x, x->t_xch, refreshes, ms); }
+int wdpm_timing_get_steady(wdpm_ctx *x, int64_t *launches, double *ms) { return timing_get(x, x->t_steady, launches, ms); }
+int wdpm_timing_get(wdpm_ctx *x, int64_t *launches, double *ms) { return timing_get(x, x->t_call, launches, ms); }
 
 } /* extern "C" */

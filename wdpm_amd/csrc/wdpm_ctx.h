@@ -7,6 +7,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <array>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/wdpm.h"
@@ -82,32 +84,31 @@ struct wdpm_ctx {
   hipEvent_t ev_fork, ev_join;
   bool pending_join;
   hipEvent_t ev_copy[2];        /* wdpm_copy_rows: [0] "my rows are produced" as source, [1] "the copy has read them" as destination */
-  /* stencil timing */
   /* HIP graphs of steady small-raster iterations (wdpm_capi.hip: wdpm_iterate).  A launch of the relay / triangle kernels keeps no state
    * on the host, and within a block the water rasters ping-pong between two buffers: an even number of iterations captured once from
-   * the context's own launches replays any number of times from the same pair.  What a captured launch was given is the key. */
-  struct GraphEntry {
-    int cur, old, flags, drain_owed, chunk_rows, dr, dc, wide, force;
+   * the context's own launches replays any number of times from the same pair.  What a captured launch was given is the key:
+   * compared with memcmp, so it has no padding bytes (`pad` is always 0) and a field added to it is compared without further ado. */
+  struct GraphKey {
     const void *q, *h;
-    hipGraphExec_t exec;
+    int cur, old, flags, drain_owed, chunk_rows, dr, dc, wide, force, pad;
   };
+  static_assert(std::has_unique_object_representations_v<GraphKey>, "GraphKey is compared with memcmp: no padding");
+  struct GraphEntry { GraphKey key; hipGraphExec_t exec; };
   std::vector<GraphEntry> graphs;
   int graph_mode;               /* -1 unknown, 0 off (WDPM_GRAPH=0, or a capture failed on this context), 1 on */
   int64_t graph_launches;       /* graphs launched so far (WDPM_OPT_GRAPH_LAUNCHES) */
-  std::vector<EventPair> pending;
-  std::vector<EventPair> pool;
+  /* stencil timing, three kinds of it: what was counted, the event pairs recorded and not yet read, the milliseconds of those that
+   * were (fold_timing); the events of a pair that was read wait in `pool` for their next use */
+  struct Timer { int64_t count; double ms; std::vector<EventPair> pending; };
+  Timer t_call;                 /* whole calls of wdpm_iterate; count: an iteration of the fused kernels 1, of the pass kernel 9, an overlapped one 3 */
   /* the same for the launches of a call between its first and its last (those two may be the flush-on-load and the
    * max-diff variants of the kernel): what rocprofv3 lists as the dominant kernel */
-  std::vector<EventPair> pending_steady;
+  Timer t_steady;
   /* halo refreshes (wdpm_comm_exchange, wdpm_copy_rows into this context): from the point of the stream where the transfer is
    * queued to the point where the rows have arrived - what an N-GPU bench line needs to explain its scaling */
-  std::vector<EventPair> pending_xch;
-  int64_t xch_count;
-  double xch_ms;
-  int64_t steady_launches;
-  double steady_ms;
-  int64_t launches;
-  double ms;
+  Timer t_xch;
+  std::array<Timer *, 3> timers() { return {&t_call, &t_steady, &t_xch}; }
+  std::vector<EventPair> pool;
   bool timing;                  /* record the event pairs at all (off until wdpm_timing_reset asks) */
   wdpm_comm *comm;              /* wdpm_comm_init_rank / wdpm_comm_init_all, or nullptr */
   bool leak;                    /* a guarded RCCL call or a stream wait ran past its deadline: somebody may still be using this
