@@ -6,6 +6,13 @@
     python tools/ponds_bench.py ponds N [--out FILE]   the mostly dry raster of tests/test_settled_golden.py: 12 m on one
                                                        256 x 256 block in eight, 100 iterations - many ponds
 
+    python tools/ponds_bench.py noise N [--out FILE]   no iterations: water on 41 % of the cells, independently (the 8-connected
+                                                       percolation region: one giant pond among very many small ones), 3 % NODATA
+
+    ... --rims        the rims of the ponds as well (include/wdpm_pond_rims.h): five more timed calls of label_rims, the two rim
+                      phases beside the table phase of the SAME calls, and their ratio (default --out profiles/r12/pond_rims.json)
+    ... --iterations K   instead of the job's own number of iterations before the inventory
+
 Per job: one untimed label call, then five timed ones (wall clock around the call, which ends with the stream idle; HIP events
 around every kernel with WDPM_PONDS_TIMING=1), medians; one steady iteration launch of the same context as the unit; the bytes
 each phase has to move, against what tools/hbm_yardstick.hip streams on the same box (--yardstick FILE, the output of
@@ -31,7 +38,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 import wdpm_amd  # noqa: E402
-from wdpm_amd.ponds import PHASES, GroupPonds, Ponds  # noqa: E402
+from wdpm_amd.ponds import PHASES, RIM_PHASES, GroupPonds, Ponds  # noqa: E402
 
 MISS = -99999.0
 
@@ -47,6 +54,41 @@ def bytes_model(rows, ncp, wet_cells, n):
         "table": 8 * wet_cells + 4 * cells + 8 * segs + 48 * n,   # wet water in, labels out, masks in, table
         "finish": 16 * n,
     }
+
+
+def rims_bytes_model(rows, ncp, wet_cells, rim_lanes, n):
+    """what the two rim phases must move at least: dem and w of pond cells and of their dry neighbours, the labels of the pond
+    cells (a wet lane's label is read, a dry lane's is 0 by its mask), masks; the locate pass the dry neighbours again"""
+    segs = rows * ((ncp + 63) // 64)
+    return {"rims": 16 * (wet_cells + rim_lanes) + 4 * wet_cells + 3 * 8 * segs + 48 * n,
+            "locate": 16 * rim_lanes + 3 * 8 * segs + 48 * n}
+
+
+def rims_job(ctx, p, rec, n):
+    """after the label calls: one untimed label_rims (allocates the rim table), five timed ones"""
+    p.label_rims(0.001)
+    wall, phases, table_ms = [], {k: [] for k in RIM_PHASES}, []
+    for _ in range(5):
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        p.label_rims(0.001)
+        wall.append((time.perf_counter() - t0) * 1e3)
+        for k, v in p.rims_phase_ms().items():
+            phases[k].append(v)
+        table_ms.append(p.phase_ms()["table"])
+    rims = p.rims()
+    med = {k: statistics.median(v) for k, v in phases.items()}
+    rec["rims"] = dict(label_rims_wall_ms=statistics.median(wall), label_rims_wall_ms_all=wall, phase_ms=med, phase_ms_all=phases,
+                       table_ms_same_calls=statistics.median(table_ms),
+                       rims_plus_locate_over_table=(med["rims"] + med["locate"]) / statistics.median(table_ms),
+                       rim_memberships=int(rims["rim_cells"].sum()), wall_memberships=int(rims["wall_cells"].sum()),
+                       longest_shoreline=int(rims["rim_cells"].max()) if len(rims) else 0,
+                       ponds_without_rim=int((rims["rim_cells"] == 0).sum()),
+                       spilling=int((rims["rim_level"] - rims["surface_max"] <= 0).sum()), guard_bad=p.guard_bad())
+    # every membership is a lane at most, and at least a quarter of one: bytes from the upper bound of lanes
+    model = rims_bytes_model(n + 2, n + 2, rec["wet_cells"], rec["rims"]["rim_memberships"] + rec["rims"]["wall_memberships"], len(rims))
+    rec["rims"]["bytes_model_upper"] = model
+    rec["rims"]["gbps_upper"] = {k: model[k] / (med[k] * 1e6) if med[k] > 0 else None for k in RIM_PHASES}
 
 
 def yardstick_gbps(path):
@@ -87,24 +129,35 @@ def group_job(hip, a, bd, bw, iters, rec):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("job", choices=["wet", "ponds"])
+    ap.add_argument("job", choices=["wet", "ponds", "noise"])
     ap.add_argument("n", type=int)
     ap.add_argument("--out", help="default: profiles/r10/ponds.json, with --devices profiles/r11/ponds_group.json")
     ap.add_argument("--no-scipy", action="store_true")
     ap.add_argument("--yardstick", metavar="FILE",
                     help="output of tools/_build/hbm_yardstick from the same box: its best streaming rate goes into the record")
     ap.add_argument("--devices", metavar="a,b,...", help="label over row blocks, one per device named (wdpm_amd.ponds.GroupPonds)")
+    ap.add_argument("--rims", action="store_true", help="time label_rims as well: the rim and locate phases beside the table phase")
+    ap.add_argument("--iterations", type=int, help="iterations before the inventory, instead of the job's own")
     a = ap.parse_args()
+    if a.rims and a.devices:
+        raise SystemExit("--rims: rims are taken on whole rasters only")
     if not a.out:
-        a.out = os.path.join(ROOT, "profiles", *(("r11", "ponds_group.json") if a.devices else ("r10", "ponds.json")))
+        a.out = os.path.join(ROOT, "profiles", *(("r11", "ponds_group.json") if a.devices else ("r12", "pond_rims.json") if a.rims
+                                                  else ("r10", "ponds.json")))
     hip = wdpm_amd.load_hip()
     n = a.n
     dem = hip.synth_dem(n, n)
     if a.job == "wet":
         water, iters = np.full((n, n), 0.1), 1000
+    elif a.job == "noise":
+        rng = np.random.default_rng(41)
+        water, iters = np.where(rng.random((n, n)) < 0.41, 0.002 + 2.0 * rng.random((n, n)), 0.0), 0
+        dem[rng.random((n, n)) < 0.03] = MISS
     else:
         bi, bj = np.mgrid[0:n, 0:n] // 256
         water, iters = np.where((3 * bi + 5 * bj) % 8 == 0, 12.0, 0.0), 100
+    if a.iterations is not None:
+        iters = a.iterations
     bd = np.full((n + 2, n + 2), MISS)
     bd[1:-1, 1:-1] = dem
     bw = np.zeros((n + 2, n + 2))
@@ -123,11 +176,13 @@ def main():
         return
     with hip.context(module="add", nrows=n, ncols=n, missingvalue=MISS) as ctx:
         ctx.upload(bd, bw)
-        ctx.run_block(iters, 0.005 / 1000)
-        ctx.timing_reset()
-        ctx.run_block(20, 0.005 / 1000)
-        launches, ms = ctx.timing_steady()
-        rec["iteration_launch_ms"] = ms / max(launches, 1)
+        rec["iteration_launch_ms"] = None
+        if iters > 0:
+            ctx.run_block(iters, 0.005 / 1000)
+            ctx.timing_reset()
+            ctx.run_block(20, 0.005 / 1000)
+            launches, ms = ctx.timing_steady()
+            rec["iteration_launch_ms"] = ms / max(launches, 1)
         with Ponds(ctx) as p:
             npond = p.label(0.001)                             # untimed: allocates
             wall, phases = [], {k: [] for k in PHASES}
@@ -142,7 +197,7 @@ def main():
             rec.update(ponds=npond, stats=stats, label_wall_ms=statistics.median(wall), label_wall_ms_all=wall,
                        phase_ms={k: statistics.median(v) for k, v in phases.items()}, guard_bad=p.guard_bad())
             rec["kernels_ms"] = sum(rec["phase_ms"].values())
-            rec["in_iteration_launches"] = rec["kernels_ms"] / rec["iteration_launch_ms"]
+            rec["in_iteration_launches"] = rec["kernels_ms"] / rec["iteration_launch_ms"] if rec["iteration_launch_ms"] else None
             wet = int(table["cells"].sum())
             rec["wet_cells"], rec["largest_pond_cells"] = wet, int(table["cells"].max()) if npond else 0
             model = bytes_model(n + 2, n + 2, wet, npond)
@@ -151,6 +206,8 @@ def main():
             rec["gbps"] = {k: model[k] / (rec["phase_ms"][k] * 1e6) if rec["phase_ms"][k] > 0 else None for k in PHASES}
             if rec.get("hbm_yardstick_gbps"):
                 rec["of_yardstick"] = {k: v / rec["hbm_yardstick_gbps"] if v else None for k, v in rec["gbps"].items()}
+            if a.rims:
+                rims_job(ctx, p, rec, n)
         if not a.no_scipy:
             try:
                 import scipy.ndimage as ndi

@@ -20,85 +20,27 @@
  */
 /* tests/ponds_emu_main.cpp compiles the kernels below for the host (256 threads per block in lockstep at the cross-lane operations,
  * address and undefined-behaviour sanitizers on) with WDPM_PONDS_EMULATION defined: it brings its own stand-ins for the HIP
- * device language and leaves the host half of this file out. */
+ * device language and leaves the host half of this file out.  What this unit shares with wdpm_pond_rims.hip (geometry, depth keys,
+ * the handle) lives in wdpm_ponds_priv.h. */
+#include "wdpm_ponds_priv.h"
 #ifndef WDPM_PONDS_EMULATION
-#include <hip/hip_runtime.h>
-
-#include <climits>
-#include <cmath>
-#include <cstdlib>
-#include <cstring>
 #include <ctime>
 #include <string>
-#include <vector>
 
-#include "wdpm_ctx.h"
 #include "wdpm_ponds_stitch.h"
-
-#define HIP_TRY(expr)                                                                                  \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) return wdpm_fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
 #endif
-#include "../../include/wdpm_group_ponds.h"
+
+using namespace wdpm_pond_detail;   /* Geom, the depth keys, the table row and the handle's parts: shared with wdpm_pond_rims.hip */
 
 namespace {
 
-constexpr int kSeg = 64;             /* columns per segment = lanes per wave */
-constexpr int kBlock = 256;          /* threads per block: four waves, four segments */
-constexpr int kWaves = kBlock / kSeg;
 constexpr int kScanItems = 4;        /* segments per thread of the scan kernels */
 constexpr int kScanTile = kBlock * kScanItems;
-constexpr int kTableWaves = 32768;   /* the table kernel aims at this many waves: bounds the atomics on one table row */
-
-/* Rows one wave of the table kernel owns: about kTableWaves waves whatever the raster's size, or what the caller forces
- * (WDPM_PONDS_ROWS_PER_WAVE when the handle is made: tests and tuning).  The host and the host emulation both ask here. */
-constexpr int ponds_rows_per_wave(long long nseg, int rows, int forced) {
-  long long rpw = forced > 0 ? forced : (nseg + kTableWaves - 1) / kTableWaves;
-  if (rpw < 1) rpw = 1;
-  if (rpw > rows) rpw = rows;
-  return (int)rpw;
-}
-
-/* the table as the device accumulates it: wdpm_pond with the depth as its order-preserving image */
-struct PondRow {
-  int first_row, first_col;
-  unsigned long long cells;
-  unsigned long long volume_q;
-  unsigned long long depth_key;
-  int row_min, row_max, col_min, col_max;
-};
-static_assert(sizeof(PondRow) == sizeof(wdpm_pond), "the device table is copied out as wdpm_pond");
-
-/* status words the host reads after the scan */
-struct Status {
-  long long ponds;
-  unsigned long long unions, seam_unions;
-  unsigned deep;           /* a pond cell of >= 512 m */
-  unsigned pad;
-};
-
-struct Geom {
-  int rows, ncp, nsc;      /* padded rows, padded columns, segments per row */
-  int nseg;                /* rows * nsc */
-};
-
-__device__ __forceinline__ unsigned long long depth_key(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double depth_from_key(unsigned long long k) {
-  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
-
 /* first bit of the run of `m` that holds bit `pos` (which is set) */
 __device__ __forceinline__ int run_start(unsigned long long m, int pos) {
   const unsigned long long z = ~m & ((1ull << pos) - 1ull);
   return z ? 64 - __clzll((long long)z) : 0;
 }
-__device__ __forceinline__ int bit(unsigned long long m, int pos) { return (int)((m >> pos) & 1ull); }
-
 __device__ __forceinline__ int load_parent(const int *p, int x) {
   return __hip_atomic_load(p + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -510,47 +452,8 @@ __global__ __launch_bounds__(kBlock) void ponds_seam_kernel(const unsigned long 
 }  // namespace
 
 #ifndef WDPM_PONDS_EMULATION
-namespace {
 /* ---- host ------------------------------------------------------------------------------------------------------------------ */
-struct Guarded { char *base; size_t bytes; };
-
-}  // namespace
-
-/* The handle labels a VIEW of its context: rows [row_off, row_off + g.rows) of the context's rasters, whose first and last row the
- * kernels take for the dry border.  wdpm_ponds_create views a whole-raster context; a row block of a group (wdpm_group_ponds_*) is
- * viewed as its owned rows with one row either side. */
-struct wdpm_ponds {
-  wdpm_ctx *x;
-  Geom g;
-  int row_off;                      /* context row of the view's row 0 */
-  bool seams;                       /* a row block: the labels of rows 1 and g.rows - 2 come to the host with the status */
-  size_t guard;                     /* bytes of each guard band (WDPM_GUARD_KB when the handle was made) */
-  std::vector<Guarded> guards;
-  bool allocated;
-  unsigned long long *d_masks, *d_rootmask, *d_busum;
-  int *d_parent, *d_labels, *d_cnt, *d_bsum;
-  unsigned *d_ucnt;
-  Status *d_status, *h_status;      /* h_status pinned */
-  int *d_seam, *h_seam;             /* 2 x g.ncp labels (seams); h_seam pinned */
-  int *d_map;                       /* local label - 1 -> label in the whole raster (seams) */
-  long long map_cap;
-  int *h_map;                       /* pinned staging (seams): the map on its way up, the finished table on its way down - */
-  wdpm_pond *h_table;               /* a copy to or from pageable memory would make the host wait inside the queueing step */
-  long long stage_cap;
-  PondRow *d_table;
-  long long table_cap;
-  int nb;                           /* blocks of the scan */
-  int forced_rpw;                   /* WDPM_PONDS_ROWS_PER_WAVE when the handle was made, 0: the library chooses */
-  int rpw;                          /* of the call under way */
-  Status last;                      /* status words of the call under way */
-  bool valid;                       /* the last label call succeeded */
-  bool timing;                      /* WDPM_PONDS_TIMING=1 when the handle was made: HIP events around every kernel */
-  hipEvent_t ev[WDPM_PONDS_PHASES + 2];   /* the host reads the status between scan and table: two marks there */
-  double phase_ms[WDPM_PONDS_PHASES];
-  wdpm_pond_stats stats;
-};
-
-namespace {
+namespace wdpm_pond_detail {
 
 hipError_t guarded_malloc(wdpm_ponds *h, void **p, size_t bytes) {
   char *base = nullptr;
@@ -574,11 +477,15 @@ void guarded_free(wdpm_ponds *h, void *p) {
   (void)hipFree(base);
 }
 
+}  // namespace wdpm_pond_detail
+
+namespace {
+
 /* frees every buffer and leaves the handle as it was made */
 void release(wdpm_ponds *h) {
   guarded_free(h, h->d_masks); guarded_free(h, h->d_rootmask); guarded_free(h, h->d_parent); guarded_free(h, h->d_labels);
   guarded_free(h, h->d_cnt); guarded_free(h, h->d_ucnt); guarded_free(h, h->d_bsum); guarded_free(h, h->d_busum);
-  guarded_free(h, h->d_table); guarded_free(h, h->d_seam); guarded_free(h, h->d_map);
+  guarded_free(h, h->d_table); guarded_free(h, h->d_seam); guarded_free(h, h->d_map); guarded_free(h, h->d_rims);
   (void)hipFree(h->d_status);
   if (h->h_status) (void)hipHostFree(h->h_status);
   if (h->h_seam) (void)hipHostFree(h->h_seam);
@@ -595,6 +502,9 @@ void release(wdpm_ponds *h) {
   h->map_cap = 0;
   h->d_table = nullptr;
   h->table_cap = 0;
+  h->d_rims = nullptr;
+  h->rims_cap = 0;
+  h->rims_valid = false;
   h->allocated = false;
 }
 
@@ -651,6 +561,9 @@ wdpm_ponds *make_handle(wdpm_ctx *ctx, int row_off, int rows, bool seams) {
   h->stage_cap = 0;
   h->d_table = nullptr;
   h->table_cap = 0;
+  h->d_rims = nullptr;
+  h->rims_cap = 0;
+  h->rims_valid = false;
   h->nb = 0;
   { const char *re = getenv("WDPM_PONDS_ROWS_PER_WAVE"); h->forced_rpw = re ? atoi(re) : 0; }
   h->rpw = 1;
@@ -664,6 +577,11 @@ wdpm_ponds *make_handle(wdpm_ctx *ctx, int row_off, int rows, bool seams) {
   if (h->timing)
     for (int i = 0; i < WDPM_PONDS_PHASES + 2; i++)
       if (hipEventCreate(&h->ev[i]) != hipSuccess) { h->timing = false; break; }
+  for (int i = 0; i < WDPM_RIMS_PHASES + 1; i++) h->rim_ev[i] = nullptr;
+  for (int i = 0; i < WDPM_RIMS_PHASES; i++) h->rim_ms[i] = 0.0;
+  if (h->timing)
+    for (int i = 0; i < WDPM_RIMS_PHASES + 1; i++)
+      if (hipEventCreate(&h->rim_ev[i]) != hipSuccess) { h->timing = false; break; }
   return h;
 }
 
@@ -676,6 +594,7 @@ wdpm_ponds *make_handle(wdpm_ctx *ctx, int row_off, int rows, bool seams) {
 int label_queue(wdpm_ponds *h, double min_depth) {
   wdpm_ctx *x = h->x;
   h->valid = false;
+  h->rims_valid = false;            /* a rim table belongs to the label call that made it (wdpm_pond_rims.hip) */
   /* the raster as a reader sees it: side stream joined, owed drain() and threshold flush applied (what wdpm_count_stats asks for) */
   if (wdpm_synchronize(x)) return 1;
   if (wdpm_apply_owed_flush(x)) return 1;
@@ -820,6 +739,8 @@ void destroy_handle(wdpm_ponds *h) {
   release(h);
   for (int i = 0; i < WDPM_PONDS_PHASES + 2; i++)
     if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
+  for (int i = 0; i < WDPM_RIMS_PHASES + 1; i++)
+    if (h->rim_ev[i]) (void)hipEventDestroy(h->rim_ev[i]);
   delete h;
 }
 

@@ -1,0 +1,142 @@
+/*
+ * wdpm_ponds_priv.h — what the two units of the pond inventory share: wdpm_ponds.hip (labels and table) and wdpm_pond_rims.hip
+ * (rims).  Geometry, the order-preserving image of a double, the table row as the device accumulates it, and - outside the host
+ * emulations of the tests, which define WDPM_PONDS_EMULATION and bring stand-ins for the HIP device language - the handle itself
+ * with its guarded allocator.  Private: nothing here is exported, and no header under include/ knows it.
+ */
+#ifndef WDPM_PONDS_PRIV_H
+#define WDPM_PONDS_PRIV_H
+
+#ifndef WDPM_PONDS_EMULATION
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "wdpm_ctx.h"
+
+#define HIP_TRY(expr)                                                                                  \
+  do {                                                                                                 \
+    hipError_t e_ = (expr);                                                                            \
+    if (e_ != hipSuccess) return wdpm_fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+  } while (0)
+#endif
+#include "../../include/wdpm_group_ponds.h"
+#include "../../include/wdpm_pond_rims.h"
+
+namespace wdpm_pond_detail {
+
+constexpr int kSeg = 64;             /* columns per segment = lanes per wave */
+constexpr int kBlock = 256;          /* threads per block: four waves, four segments */
+constexpr int kWaves = kBlock / kSeg;
+constexpr int kTableWaves = 32768;   /* the table kernel aims at this many waves: bounds the atomics on one table row */
+
+/* Rows one wave of the table kernel (and of the rim kernels) owns: about kTableWaves waves whatever the raster's size, or what
+ * the caller forces (WDPM_PONDS_ROWS_PER_WAVE when the handle is made: tests and tuning).  The host and the host emulations both
+ * ask here. */
+constexpr int ponds_rows_per_wave(long long nseg, int rows, int forced) {
+  long long rpw = forced > 0 ? forced : (nseg + kTableWaves - 1) / kTableWaves;
+  if (rpw < 1) rpw = 1;
+  if (rpw > rows) rpw = rows;
+  return (int)rpw;
+}
+
+/* the table as the device accumulates it: wdpm_pond with the depth as its order-preserving image */
+struct PondRow {
+  int first_row, first_col;
+  unsigned long long cells;
+  unsigned long long volume_q;
+  unsigned long long depth_key;
+  int row_min, row_max, col_min, col_max;
+};
+static_assert(sizeof(PondRow) == sizeof(wdpm_pond), "the device table is copied out as wdpm_pond");
+
+/* the rim table as the device accumulates it: wdpm_pond_rim with its three doubles as their order-preserving images and the rim
+ * cell as a view-local padded index (INT_MAX: none yet) */
+struct RimRow {
+  unsigned long long smin_key, smax_key, rim_key;
+  int rim_idx, pad;
+  unsigned long long rim_cells, wall_cells;
+};
+static_assert(sizeof(RimRow) == sizeof(wdpm_pond_rim), "the device rim table is copied out as wdpm_pond_rim");
+
+/* status words the host reads after the scan */
+struct Status {
+  long long ponds;
+  unsigned long long unions, seam_unions;
+  unsigned deep;           /* a pond cell of >= 512 m */
+  unsigned pad;
+};
+
+struct Geom {
+  int rows, ncp, nsc;      /* padded rows, padded columns, segments per row */
+  int nseg;                /* rows * nsc */
+};
+
+__device__ __forceinline__ unsigned long long depth_key(double v) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double depth_from_key(unsigned long long k) {
+  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
+__device__ __forceinline__ int bit(unsigned long long m, int pos) { return (int)((m >> pos) & 1ull); }
+
+#ifndef WDPM_PONDS_EMULATION
+struct Guarded { char *base; size_t bytes; };
+#endif
+
+}  // namespace wdpm_pond_detail
+
+#ifndef WDPM_PONDS_EMULATION
+/* The handle labels a VIEW of its context: rows [row_off, row_off + g.rows) of the context's rasters, whose first and last row the
+ * kernels take for the dry border.  wdpm_ponds_create views a whole-raster context; a row block of a group (wdpm_group_ponds_*) is
+ * viewed as its owned rows with one row either side. */
+struct wdpm_ponds {
+  wdpm_ctx *x;
+  wdpm_pond_detail::Geom g;
+  int row_off;                      /* context row of the view's row 0 */
+  bool seams;                       /* a row block: the labels of rows 1 and g.rows - 2 come to the host with the status */
+  size_t guard;                     /* bytes of each guard band (WDPM_GUARD_KB when the handle was made) */
+  std::vector<wdpm_pond_detail::Guarded> guards;
+  bool allocated;
+  unsigned long long *d_masks, *d_rootmask, *d_busum;
+  int *d_parent, *d_labels, *d_cnt, *d_bsum;
+  unsigned *d_ucnt;
+  wdpm_pond_detail::Status *d_status, *h_status;      /* h_status pinned */
+  int *d_seam, *h_seam;             /* 2 x g.ncp labels (seams); h_seam pinned */
+  int *d_map;                       /* local label - 1 -> label in the whole raster (seams) */
+  long long map_cap;
+  int *h_map;                       /* pinned staging (seams): the map on its way up, the finished table on its way down - */
+  wdpm_pond *h_table;               /* a copy to or from pageable memory would make the host wait inside the queueing step */
+  long long stage_cap;
+  wdpm_pond_detail::PondRow *d_table;
+  long long table_cap;
+  int nb;                           /* blocks of the scan */
+  int forced_rpw;                   /* WDPM_PONDS_ROWS_PER_WAVE when the handle was made, 0: the library chooses */
+  int rpw;                          /* of the call under way */
+  wdpm_pond_detail::Status last;    /* status words of the call under way */
+  bool valid;                       /* the last label call succeeded */
+  bool timing;                      /* WDPM_PONDS_TIMING=1 when the handle was made: HIP events around every kernel */
+  hipEvent_t ev[WDPM_PONDS_PHASES + 2];   /* the host reads the status between scan and table: two marks there */
+  double phase_ms[WDPM_PONDS_PHASES];
+  wdpm_pond_stats stats;
+  /* rims (wdpm_pond_rims.hip): the table of the last wdpm_rims_label; every label call takes rims_valid away first */
+  wdpm_pond_detail::RimRow *d_rims;
+  long long rims_cap;
+  bool rims_valid;
+  hipEvent_t rim_ev[WDPM_RIMS_PHASES + 1];   /* made with the others when the handle records events */
+  double rim_ms[WDPM_RIMS_PHASES];
+};
+
+namespace wdpm_pond_detail {
+/* device memory of the handle between two guard bands (when it carries any): wdpm_ponds_guard_bad looks at every band */
+__attribute__((visibility("hidden"))) hipError_t guarded_malloc(wdpm_ponds *h, void **p, size_t bytes);
+__attribute__((visibility("hidden"))) void guarded_free(wdpm_ponds *h, void *p);
+}  // namespace wdpm_pond_detail
+#endif
+
+#endif

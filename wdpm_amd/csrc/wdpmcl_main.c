@@ -38,6 +38,7 @@
 
 #include "../../include/wdpm.h"
 #include "../../include/wdpm_group_ponds.h"
+#include "../../include/wdpm_pond_rims.h"
 /* the pond inventory is the HIP library's alone: weak references, so that this file also links against a back-end that
  * exports include/wdpm.h and nothing else (WDPM_PONDS then says so and writes no file) */
 #pragma weak wdpm_ponds_create
@@ -51,6 +52,8 @@
 #pragma weak wdpm_group_ponds_table
 #pragma weak wdpm_group_ponds_guard_bad
 #pragma weak wdpm_group_ponds_stats
+#pragma weak wdpm_rims_label
+#pragma weak wdpm_rims_table
 #include "arcascii.h"
 
 #define ITER_PER_BLOCK 1000 /* IterationNum, WDPMCL.c:597 */
@@ -639,11 +642,14 @@ static void relief_finish(relief_helper *h) {
  * WDPM_PONDS=<path>: the 8-connected water bodies of the final water, one CSV line per pond, numbered by first cell.  A pond
  * cell holds more than WDPM_PONDS_MIN_DEPTH_MM of water (default 1.0: the reference's own wet threshold, water > 0.001,
  * WDPMCL.c:1397-1404, so the cells column sums to the wet count of the final statistics).  Nothing of it goes to stdout. */
-typedef struct { wdpm_pond *rows; int64_t n; int64_t guard_bad; int64_t blocks, joined; } pond_inventory;
+typedef struct { wdpm_pond *rows; int64_t n; int64_t guard_bad; int64_t blocks, joined; wdpm_pond_rim *rims; } pond_inventory;
 
-static int take_inventory(wdpm_ctx *c, double min_depth, pond_inventory *inv) {
+/* with_rims (WDPM_POND_RIMS, include/wdpm_pond_rims.h; the caller has seen that the back-end has them): one wdpm_rims_label serves
+ * the pond table and the rim table */
+static int take_inventory(wdpm_ctx *c, double min_depth, pond_inventory *inv, int with_rims) {
   wdpm_ponds *h = NULL;
   inv->rows = NULL;
+  inv->rims = NULL;
   inv->n = 0;
   inv->guard_bad = 0;
   inv->blocks = 1;
@@ -653,17 +659,21 @@ static int take_inventory(wdpm_ctx *c, double min_depth, pond_inventory *inv) {
     return 1;
   }
   int rc = wdpm_ponds_create(&h, c);
-  if (!rc) rc = wdpm_ponds_label(h, min_depth, &inv->n);
+  if (!rc) rc = with_rims ? wdpm_rims_label(h, min_depth, &inv->n) : wdpm_ponds_label(h, min_depth, &inv->n);
   if (!rc) {
     inv->rows = (wdpm_pond *)malloc((size_t)(inv->n > 0 ? inv->n : 1) * sizeof(wdpm_pond));
-    if (!inv->rows) { wdpm_set_last_error("out of host memory for the pond table"); rc = 1; }
+    if (with_rims) inv->rims = (wdpm_pond_rim *)malloc((size_t)(inv->n > 0 ? inv->n : 1) * sizeof(wdpm_pond_rim));
+    if (!inv->rows || (with_rims && !inv->rims)) { wdpm_set_last_error("out of host memory for the pond table"); rc = 1; }
   }
   if (!rc) rc = wdpm_ponds_table(h, inv->rows, inv->n);
+  if (!rc && with_rims) rc = wdpm_rims_table(h, inv->rims, inv->n);
   if (!rc && getenv("WDPM_GUARD_KB")) rc = wdpm_ponds_guard_bad(h, &inv->guard_bad);
   if (rc) {
     fprintf(stderr, "WDPMCL: pond inventory failed, no file written: %s\n", wdpm_last_error());
     free(inv->rows);
+    free(inv->rims);
     inv->rows = NULL;
+    inv->rims = NULL;
   }
   wdpm_ponds_destroy(h);
   return rc;
@@ -674,6 +684,7 @@ static int take_group_inventory(wdpm_group *grp, double min_depth, pond_inventor
   wdpm_group_ponds *h = NULL;
   wdpm_group_pond_stats gs;
   inv->rows = NULL;
+  inv->rims = NULL;
   inv->n = 0;
   inv->guard_bad = 0;
   inv->blocks = 1;
@@ -726,6 +737,32 @@ static int write_inventory(const char *path, const pond_inventory *inv, double c
   fprintf(stderr, "WDPMCL: pond inventory: %lld pond%s written to %s", (long long)inv->n, inv->n == 1 ? "" : "s", path);
   if (inv->blocks > 1) fprintf(stderr, " (%lld row blocks, %lld joined across them)", (long long)inv->blocks, (long long)inv->joined);
   fprintf(stderr, "\n");
+  return 0;
+}
+
+/* WDPM_POND_RIMS=<path>: one CSV line per pond of the same inventory: the spread of its water surface, its spill level and where
+ * that lies (file coordinates, 0-based; -1 without a rim cell), its freeboard = rim level - highest surface, its shoreline and
+ * its walls (include/wdpm_pond_rims.h).  Doubles as %.17g. */
+static int write_rims(const char *path, const pond_inventory *inv) {
+  FILE *f = fopen(path, "w");
+  if (!f) {
+    fprintf(stderr, "WDPMCL: cannot write pond rims %s\n", path);
+    return 1;
+  }
+  fprintf(f, "label,surface_min_m,surface_max_m,rim_level_m,freeboard_m,rim_row,rim_col,rim_cells,wall_cells\n");
+  for (int64_t k = 0; k < inv->n; k++) {
+    const wdpm_pond_rim *q = &inv->rims[k];
+    const int none = q->rim_row < 0;
+    fprintf(f, "%lld,%.17g,%.17g,%.17g,%.17g,%d,%d,%lld,%lld\n", (long long)(k + 1), q->surface_min, q->surface_max, q->rim_level,
+            q->rim_level - q->surface_max, none ? -1 : q->rim_row - 1, none ? -1 : q->rim_col - 1, (long long)q->rim_cells,
+            (long long)q->wall_cells);
+  }
+  const int bad = ferror(f);
+  if (fclose(f) != 0 || bad) {
+    fprintf(stderr, "WDPMCL: error writing pond rims %s\n", path);
+    return 1;
+  }
+  fprintf(stderr, "WDPMCL: pond rims: %lld pond%s written to %s\n", (long long)inv->n, inv->n == 1 ? "" : "s", path);
   return 0;
 }
 
@@ -958,15 +995,32 @@ int main(int argc, char **argv) {
   const char *ponds_path = getenv("WDPM_PONDS");
   if (ponds_path && !*ponds_path) ponds_path = NULL;
   const double ponds_min_depth = (getenv("WDPM_PONDS_MIN_DEPTH_MM") ? atof(getenv("WDPM_PONDS_MIN_DEPTH_MM")) : 1.0) / 1000.0;
+  /* ... and the rims of the same ponds (WDPM_POND_RIMS), alone or beside it: whole rasters only */
+  const char *rims_path = getenv("WDPM_POND_RIMS");
+  if (rims_path && !*rims_path) rims_path = NULL;
   pond_inventory inv;
   memset(&inv, 0, sizeof inv);
   int ponds_failed = 0;
-  if (ponds_path) {
+  if (rims_path && ndev > 1) {
+    fprintf(stderr, "WDPMCL: pond rims: the raster lies in %d row blocks and rims are taken on a whole raster only, no file written to %s\n",
+            ndev, rims_path);
+    ponds_failed = 1;
+    rims_path = NULL;
+  }
+  if (rims_path && (!wdpm_rims_label || !wdpm_rims_table)) {
+    fprintf(stderr, "WDPMCL: pond rims: back-end %s has none, no file written\n", wdpm_backend_name());
+    ponds_failed = 1;
+    rims_path = NULL;
+  }
+  if (ponds_path || rims_path) {
     phase("statistics + download");
-    ponds_failed = ndev == 1 ? take_inventory(wdpm_rank_ctx(wdpm_group_rank(ctx, 0)), ponds_min_depth, &inv)
-                             : take_group_inventory(ctx, ponds_min_depth, &inv);
-    if (!ponds_failed) ponds_failed = write_inventory(ponds_path, &inv, st.cellarea);
+    const int failed = ndev == 1 ? take_inventory(wdpm_rank_ctx(wdpm_group_rank(ctx, 0)), ponds_min_depth, &inv, rims_path != NULL)
+                                 : take_group_inventory(ctx, ponds_min_depth, &inv);
+    if (failed) ponds_failed = 1;
+    if (!failed && ponds_path && write_inventory(ponds_path, &inv, st.cellarea)) ponds_failed = 1;
+    if (!failed && rims_path && write_rims(rims_path, &inv)) ponds_failed = 1;
     free(inv.rows);
+    free(inv.rims);
     phase("pond inventory");
   }
   int64_t guard_bad = inv.guard_bad;

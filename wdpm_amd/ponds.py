@@ -1,5 +1,5 @@
-"""ctypes binding of include/wdpm_ponds.h and include/wdpm_group_ponds.h: the pond inventory of a context's current water
-raster, and of a raster spread over the row blocks of a rowblock.Group.
+"""ctypes binding of include/wdpm_ponds.h, include/wdpm_group_ponds.h and include/wdpm_pond_rims.h: the pond inventory of a
+context's current water raster, of a raster spread over the row blocks of a rowblock.Group, and the rim of every pond.
 
 Product library only (the symbols are not part of the ABI of include/wdpm.h, and ``capi.SYMBOLS`` does not list them).
 
@@ -7,6 +7,9 @@ Product library only (the symbols are not part of the ABI of include/wdpm.h, and
         n = ponds.label(0.001)
         table = ponds.table()       # structured array, one row per pond, numbered by first cell
         labels = ponds.labels()     # int32, padded layout like the water raster
+        n = ponds.label_rims(0.001) # the same inventory, and one rim row per pond
+        rims = ponds.rims()         # spill level and where it lies, shoreline, walls, surface spread (RIM_DTYPE)
+        freeboard = rims["rim_level"] - rims["surface_max"]
 
     with rowblock.Group(...) as grp, GroupPonds(grp) as ponds:     # the same calls, the same answer, every rank labelled in place
         n = ponds.label(0.001)
@@ -22,6 +25,7 @@ from . import capi
 
 VOLUME_QUANTUM = 2.0 ** -24   # metres per unit of volume_q
 PHASES = ("mask", "merge", "flatten", "scan", "table", "finish")   # wdpm_ponds_phase_ms
+RIM_PHASES = ("rims", "locate")                                    # wdpm_rims_phase_ms
 
 
 class PondStruct(C.Structure):
@@ -55,6 +59,24 @@ SYMBOLS = {
 }
 
 
+class RimStruct(C.Structure):
+    """struct wdpm_pond_rim"""
+    _fields_ = [("surface_min", C.c_double), ("surface_max", C.c_double), ("rim_level", C.c_double), ("rim_row", C.c_int32),
+                ("rim_col", C.c_int32), ("rim_cells", C.c_int64), ("wall_cells", C.c_int64)]
+
+
+RIM_DTYPE = np.dtype([("surface_min", "<f8"), ("surface_max", "<f8"), ("rim_level", "<f8"), ("rim_row", "<i4"), ("rim_col", "<i4"),
+                      ("rim_cells", "<i8"), ("wall_cells", "<i8")])
+assert RIM_DTYPE.itemsize == C.sizeof(RimStruct) == 48
+
+# every symbol include/wdpm_pond_rims.h declares
+RIM_SYMBOLS = {
+    "wdpm_rims_label": (C.c_int, [_vp, C.c_double, C.POINTER(C.c_int64)]),
+    "wdpm_rims_table": (C.c_int, [_vp, _vp, C.c_int64]),
+    "wdpm_rims_phase_ms": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+}
+
+
 class GroupStatsStruct(C.Structure):
     """struct wdpm_group_pond_stats"""
     _fields_ = [("ranks", C.c_int64), ("ponds", C.c_int64), ("local_ponds", C.c_int64), ("stitch_unions", C.c_int64),
@@ -79,7 +101,7 @@ def bind(lib: capi.Lib):
     """Set the prototypes on a loaded product library; a library without the symbols is an error (no fallback)."""
     if getattr(lib, "_ponds_bound", False):
         return lib.dll
-    for name, (res, args) in list(SYMBOLS.items()) + list(GROUP_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(GROUP_SYMBOLS.items()) + list(RIM_SYMBOLS.items()):
         try:
             fn = getattr(lib.dll, name)
         except AttributeError:
@@ -162,6 +184,30 @@ class Ponds:
         v = C.c_int64()
         self.lib.check(self.dll.wdpm_ponds_guard_bad(self._h, C.byref(v)))
         return v.value
+
+    def label_rims(self, min_depth: float) -> int:
+        """label(min_depth), then the rim pass on the same water; table(), labels() and stats() answer as after label()."""
+        n = C.c_int64()
+        self.n = None
+        self.lib.check(self.dll.wdpm_rims_label(self._h, float(min_depth), C.byref(n)))
+        self.n = n.value
+        return n.value
+
+    def rims(self, capacity: int | None = None) -> np.ndarray:
+        """One row per pond (RIM_DTYPE) of the last label_rims(); fails after a plain label().  Coordinates are padded, -1 where a
+        pond has no rim cell; freeboard is rim_level - surface_max."""
+        if self.n is None:
+            raise capi.WdpmError("Ponds.rims: label_rims() has not succeeded on this handle")
+        cap = self.n if capacity is None else int(capacity)
+        out = np.zeros(max(cap, 0), dtype=RIM_DTYPE)
+        self.lib.check(self.dll.wdpm_rims_table(self._h, out.ctypes.data, cap))
+        return out[:self.n]
+
+    def rims_phase_ms(self) -> dict:
+        """milliseconds of the rim pass and of the locate pass of the last label_rims() (handles made with WDPM_PONDS_TIMING=1)"""
+        ms = (C.c_double * len(RIM_PHASES))()
+        self.lib.check(self.dll.wdpm_rims_phase_ms(self._h, ms))
+        return dict(zip(RIM_PHASES, (float(v) for v in ms)))
 
 
 class GroupPonds:
