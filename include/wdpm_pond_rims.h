@@ -34,7 +34,8 @@ typedef struct wdpm_pond_rim {
 
 /* wdpm_ponds_label, then the rim pass on the same water, queued on the context's stream with nothing in between: label raster
  * and water belong together.  Afterwards wdpm_ponds_table, wdpm_ponds_labels and wdpm_ponds_stats answer as after
- * wdpm_ponds_label.  Handles of wdpm_ponds_create (whole rasters) only. */
+ * wdpm_ponds_label.  Handles of wdpm_ponds_create; a raster spread over row blocks has wdpm_group_rims_label
+ * (wdpm_group_pond_rims.h). */
 int wdpm_rims_label(wdpm_ponds *h, double min_depth, int64_t *nponds);
 /* the rim table of the last wdpm_rims_label: N rows; capacity < N fails and writes nothing.  Fails after a plain
  * wdpm_ponds_label, which leaves no rim table. */

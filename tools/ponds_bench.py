@@ -11,6 +11,8 @@
 
     ... --rims        the rims of the ponds as well (include/wdpm_pond_rims.h): five more timed calls of label_rims, the two rim
                       phases beside the table phase of the SAME calls, and their ratio (default --out profiles/r12/pond_rims.json)
+                      With --devices: GroupPonds.label_rims (include/wdpm_group_pond_rims.h) - per-rank rim phases, their sum over
+                      the ranks, the host's merge_ms beside stitch_ms, foreign (default --out profiles/r13/pond_rims_group.json)
     ... --iterations K   instead of the job's own number of iterations before the inventory
 
 Per job: one untimed label call, then five timed ones (wall clock around the call, which ends with the stream idle; HIP events
@@ -125,6 +127,38 @@ def group_job(hip, a, bd, bw, iters, rec):
                        rank_phase_ms=[{k: statistics.median(v) for k, v in ph.items()} for ph in phases], guard_bad=p.guard_bad())
             rec["rank_kernels_ms"] = [sum(ph.values()) for ph in rec["rank_phase_ms"]]
             rec["wet_cells"] = int(p.table()["cells"].sum())
+            if a.rims:
+                group_rims_job(p, rec, len(devices))
+
+
+def group_rims_job(p, rec, nranks):
+    """after the label calls: one untimed label_rims (allocates every rank's rim rows and slots), five timed ones"""
+    p.label_rims(0.001)
+    wall, merge, stitch = [], [], []
+    phases = [{k: [] for k in RIM_PHASES} for _ in range(nranks)]
+    table_ms = [[] for _ in range(nranks)]
+    for _ in range(5):
+        t0 = time.perf_counter()
+        p.label_rims(0.001)
+        wall.append((time.perf_counter() - t0) * 1e3)
+        merge.append(p.rims_stats()["merge_ms"])
+        stitch.append(p.stats()["stitch_ms"])
+        for i in range(nranks):
+            for k, v in p.rims_phase_ms(i).items():
+                phases[i][k].append(v)
+            table_ms[i].append(p.phase_ms(i)["table"])
+    rims, rstats = p.rims(), p.rims_stats()
+    sums = [sum(phases[i][k][j] for i in range(nranks) for k in RIM_PHASES) for j in range(5)]     # per call, over ranks
+    rec["rims"] = dict(label_rims_wall_ms=statistics.median(wall), label_rims_wall_ms_all=wall,
+                       rank_phase_ms=[{k: statistics.median(v) for k, v in ph.items()} for ph in phases], rank_phase_ms_all=phases,
+                       rims_plus_locate_sum_over_ranks_ms=statistics.median(sums), rims_plus_locate_sum_over_ranks_ms_all=sums,
+                       rank_table_ms_same_calls=[statistics.median(v) for v in table_ms],
+                       merge_ms=statistics.median(merge), merge_ms_all=merge, stitch_ms_same_calls=statistics.median(stitch),
+                       foreign=rstats["foreign"], slots=rstats["slots"],
+                       rim_memberships=int(rims["rim_cells"].sum()), wall_memberships=int(rims["wall_cells"].sum()),
+                       longest_shoreline=int(rims["rim_cells"].max()) if len(rims) else 0,
+                       ponds_without_rim=int((rims["rim_cells"] == 0).sum()),
+                       spilling=int((rims["rim_level"] - rims["surface_max"] <= 0).sum()), guard_bad=p.guard_bad())
 
 
 def main():
@@ -139,11 +173,10 @@ def main():
     ap.add_argument("--rims", action="store_true", help="time label_rims as well: the rim and locate phases beside the table phase")
     ap.add_argument("--iterations", type=int, help="iterations before the inventory, instead of the job's own")
     a = ap.parse_args()
-    if a.rims and a.devices:
-        raise SystemExit("--rims: rims are taken on whole rasters only")
     if not a.out:
-        a.out = os.path.join(ROOT, "profiles", *(("r11", "ponds_group.json") if a.devices else ("r12", "pond_rims.json") if a.rims
-                                                  else ("r10", "ponds.json")))
+        a.out = os.path.join(ROOT, "profiles", *(("r13", "pond_rims_group.json") if a.devices and a.rims else
+                                                  ("r11", "ponds_group.json") if a.devices else
+                                                  ("r12", "pond_rims.json") if a.rims else ("r10", "ponds.json")))
     hip = wdpm_amd.load_hip()
     n = a.n
     dem = hip.synth_dem(n, n)

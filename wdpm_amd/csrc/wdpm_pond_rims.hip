@@ -18,8 +18,12 @@
  *            offers its padded index (atomicMin on an int32: a view holds fewer than 2^31 cells)
  *   finish   keys back to doubles, the index to row and column; +inf, -1, -1 for a pond without rim cells
  *
- * tests/rims_emu_main.cpp compiles the kernels for the host under sanitizers with WDPM_PONDS_EMULATION defined, as
- * tests/ponds_emu_main.cpp does with wdpm_ponds.hip, and leaves the host half out.
+ * Over row blocks (include/wdpm_group_pond_rims.h) every rank runs the same body over its owned rows, with the whole-raster labels
+ * of the one row beyond either end uploaded beside them and its table indexed through a flat label -> slot table (rim_slot,
+ * rims_slots_kernel); the host merges the ranks' rows (wdpm_rims_merge.h).
+ *
+ * tests/rims_emu_main.cpp and tests/group_rims_emu_main.cpp compile the kernels for the host under sanitizers with
+ * WDPM_PONDS_EMULATION defined, as tests/ponds_emu_main.cpp does with wdpm_ponds.hip, and leave the host half out.
  */
 #include "wdpm_ponds_priv.h"
 
@@ -112,10 +116,18 @@ __device__ __forceinline__ void rim_carry_reset(RimCarry &c, int label) {
   c.rim_cells = c.wall_cells = 0ull;
 }
 
+/* The table row of label L: row L - 1 of a whole raster's table.  kSlots (row blocks): the labels are whole-raster numbers and the
+ * table holds one row per pond the rank touches, so slot_of[L] says which (wdpm_group_rims_label fills it). */
+template <bool kSlots>
+__device__ __forceinline__ int rim_slot(const int *__restrict__ slot_of, int L) {
+  return kSlots ? slot_of[L] : L - 1;
+}
+
 /* one lane sends a carry.  The extrema only move one way, so a look first spares the atomic that would change nothing; what a
  * carry never gathered still holds its start value and passes no look. */
-__device__ __forceinline__ void rim_send(RimRow *table, const RimCarry &c) {
-  RimRow *t = table + (c.label - 1);
+template <bool kSlots>
+__device__ __forceinline__ void rim_send(RimRow *table, const int *__restrict__ slot_of, const RimCarry &c) {
+  RimRow *t = table + rim_slot<kSlots>(slot_of, c.label);
   if (__hip_atomic_load(&t->smin_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > c.smin) atomicMin(&t->smin_key, c.smin);
   if (__hip_atomic_load(&t->smax_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < c.smax) atomicMax(&t->smax_key, c.smax);
   if (__hip_atomic_load(&t->rim_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > c.rmin) atomicMin(&t->rim_key, c.rmin);
@@ -124,16 +136,19 @@ __device__ __forceinline__ void rim_send(RimRow *table, const RimCarry &c) {
 }
 
 /* kLocate false: the rim pass.  kLocate true: the locate pass, after every rim key is final.  Everything that steers the loops
- * is wave-uniform. */
-template <bool kLocate>
+ * is wave-uniform.  The strips are cut over rows [ra, rb) of the view: all of a whole raster; the owned rows of a row block, whose
+ * view rows 0 and g.rows - 1 then only ever stand above or below a strip, with the masks and labels of the neighbouring rank's
+ * row (nothing of their dem or water is read).  kSlots: see rim_slot. */
+template <bool kLocate, bool kSlots>
 __device__ __forceinline__ void rims_body(const double *__restrict__ w, const double *__restrict__ dem,
                                           const unsigned long long *__restrict__ masks, const int *__restrict__ labels, const Geom g,
-                                          const int rpw, const int nwaves, RimRow *table) {
+                                          const int rpw, const int nwaves, RimRow *table, const int ra, const int rb,
+                                          const int *__restrict__ slot_of) {
   const int wid = blockIdx.x * kWaves + (threadIdx.x >> 6);
   if (wid >= nwaves) return;
   const int lane = threadIdx.x & 63;
-  const int rb = wid / g.nsc, s = wid - rb * g.nsc;
-  const int r0 = rb * rpw, r1 = min(r0 + rpw, g.rows);
+  const int strip = wid / g.nsc, s = wid - strip * g.nsc;
+  const int r0 = ra + strip * rpw, r1 = min(r0 + rpw, rb);
   const int c = s * kSeg + lane;
   RimCarry cy;
   rim_carry_reset(cy, 0);
@@ -186,9 +201,10 @@ __device__ __forceinline__ void rims_body(const double *__restrict__ w, const do
 #pragma unroll
         for (int i = 0; i < 4; i++) {
           const int L = i == 0 ? q0 : i == 1 ? q1 : i == 2 ? q2 : q3;
-          if (L != 0 && table[L - 1].rim_key == key &&
-              __hip_atomic_load(&table[L - 1].rim_idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > idx)
-            atomicMin(&table[L - 1].rim_idx, idx);
+          if (L == 0) continue;
+          RimRow *t = table + rim_slot<kSlots>(slot_of, L);
+          if (t->rim_key == key && __hip_atomic_load(&t->rim_idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > idx)
+            atomicMin(&t->rim_idx, idx);
         }
       }
       continue;
@@ -205,7 +221,7 @@ __device__ __forceinline__ void rims_body(const double *__restrict__ w, const do
       const unsigned long long rimm = __ballot(hit && !wet && !wall);
       const unsigned long long wallm = __ballot(hit && !wet && wall);
       if (cy.label != L) {                  /* down the rows: the same label goes on gathering, another one sends first */
-        if (cy.label != 0 && lane == 0) rim_send(table, cy);
+        if (cy.label != 0 && lane == 0) rim_send<kSlots>(table, slot_of, cy);
         rim_carry_reset(cy, L);
       }
       if (pondm) {
@@ -225,21 +241,46 @@ __device__ __forceinline__ void rims_body(const double *__restrict__ w, const do
       if (q3 == L) q3 = 0;
     }
   }
-  if (!kLocate && cy.label != 0 && lane == 0) rim_send(table, cy);
+  if (!kLocate && cy.label != 0 && lane == 0) rim_send<kSlots>(table, slot_of, cy);
 }
 
 __global__ __launch_bounds__(kBlock) void rims_pass_kernel(const double *__restrict__ w, const double *__restrict__ dem,
                                                            const unsigned long long *__restrict__ masks,
                                                            const int *__restrict__ labels, Geom g, int rpw, int nwaves,
                                                            RimRow *table) {
-  rims_body<false>(w, dem, masks, labels, g, rpw, nwaves, table);
+  rims_body<false, false>(w, dem, masks, labels, g, rpw, nwaves, table, 0, g.rows, nullptr);
 }
 
 __global__ __launch_bounds__(kBlock) void rims_locate_kernel(const double *__restrict__ w, const double *__restrict__ dem,
                                                              const unsigned long long *__restrict__ masks,
                                                              const int *__restrict__ labels, Geom g, int rpw, int nwaves,
                                                              RimRow *table) {
-  rims_body<true>(w, dem, masks, labels, g, rpw, nwaves, table);
+  rims_body<true, false>(w, dem, masks, labels, g, rpw, nwaves, table, 0, g.rows, nullptr);
+}
+
+/* the same two passes over the owned rows [ra, rb) of a row block's view, the table indexed through slot_of */
+__global__ __launch_bounds__(kBlock) void rims_pass_rows_kernel(const double *__restrict__ w, const double *__restrict__ dem,
+                                                                const unsigned long long *__restrict__ masks,
+                                                                const int *__restrict__ labels, Geom g, int rpw, int nwaves,
+                                                                RimRow *table, int ra, int rb, const int *__restrict__ slot_of) {
+  rims_body<false, true>(w, dem, masks, labels, g, rpw, nwaves, table, ra, rb, slot_of);
+}
+
+__global__ __launch_bounds__(kBlock) void rims_locate_rows_kernel(const double *__restrict__ w, const double *__restrict__ dem,
+                                                                  const unsigned long long *__restrict__ masks,
+                                                                  const int *__restrict__ labels, Geom g, int rpw, int nwaves,
+                                                                  RimRow *table, int ra, int rb, const int *__restrict__ slot_of) {
+  rims_body<true, true>(w, dem, masks, labels, g, rpw, nwaves, table, ra, rb, slot_of);
+}
+
+/* slot_of for one rank (every entry INT_MAX before): local pond l (map[l - 1] in the whole raster) has slot l - 1, and local ponds
+ * that are one pond of the whole raster share the slot of the first of them; foreign pond j, which the host found in the rows
+ * beside the rank's own and in none of its cells, has slot nlocal + j.  The two kinds never meet in one entry. */
+__global__ __launch_bounds__(kBlock) void rims_slots_kernel(const int *__restrict__ map, int nlocal, const int *__restrict__ foreign,
+                                                            int nforeign, int *slot_of) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < nlocal) atomicMin(&slot_of[map[i]], i);
+  else if (i - nlocal < nforeign) slot_of[foreign[i - nlocal]] = i;
 }
 
 __global__ __launch_bounds__(kBlock) void rims_init_kernel(RimRow *t, long long n) {
@@ -342,6 +383,195 @@ extern "C" int wdpm_rims_phase_ms(wdpm_ponds *h, double *ms) {
   if (!h->valid || !h->rims_valid)
     return wdpm_fail("wdpm_rims_phase_ms: no rim table: the last label call on this handle was not a wdpm_rims_label that succeeded");
   for (int i = 0; i < WDPM_RIMS_PHASES; i++) ms[i] = h->rim_ms[i];
+  return 0;
+}
+/* ---- row blocks (include/wdpm_group_pond_rims.h) ----------------------------------------------------------------------------- */
+#include <ctime>
+#include <string>
+
+#include "wdpm_rims_merge.h"
+
+namespace {
+
+/* Rank i's rim work behind its table kernels, on its stream, nothing waited for (group_label calls this for every rank before the
+ * first wait).  The rows beside the rank's own come from the neighbours' seam rows through the stitch's numbers. */
+int group_rims_rank(wdpm_group_ponds *gh, int i, const std::vector<std::vector<int>> &map, long long ponds) {
+  wdpm_ponds *h = gh->r[i];
+  wdpm_ctx *x = h->x;
+  const Geom g = h->g;
+  const hipStream_t sm = x->stream;
+  const int ncp = g.ncp, nsc = g.nsc;
+  const bool up = i > 0, dn = i + 1 < gh->n;
+  h->rim_ms[0] = h->rim_ms[1] = 0.0;
+  h->rim_slots = h->rim_foreign = 0;
+  h->slot_label.clear();
+  if (ponds == 0) return 0;
+  HIP_TRY(hipSetDevice(x->p.device));
+  if (!h->h_beside) {
+    const hipError_t e = hipHostMalloc(&h->h_beside, (size_t)2 * nsc * sizeof(unsigned long long) + (size_t)4 * ncp * sizeof(int));
+    if (e != hipSuccess) { h->h_beside = nullptr; return wdpm_fail("wdpm_group_rims_label: no pinned host memory for two rows: %s", hipGetErrorString(e)); }
+  }
+  if (!h->d_foreign) {
+    const hipError_t e = guarded_malloc(h, (void **)&h->d_foreign, (size_t)2 * ncp * sizeof(int));
+    if (e != hipSuccess) { h->d_foreign = nullptr; return wdpm_fail("wdpm_group_rims_label: no device memory for two rows of labels: %s", hipGetErrorString(e)); }
+  }
+  unsigned long long *bm = h->h_beside;             /* [2][nsc] */
+  int *bl = (int *)(bm + (size_t)2 * nsc);          /* [2][ncp] */
+  int *bf = bl + (size_t)2 * ncp;                   /* up to 2 * ncp foreign labels */
+  memset(bm, 0, (size_t)2 * nsc * sizeof(unsigned long long));
+  memset(bl, 0, (size_t)2 * ncp * sizeof(int));
+  for (int side = 0; side < 2; side++) {
+    if (side ? !dn : !up) continue;
+    const int j = side ? i + 1 : i - 1;
+    const int *src = gh->r[j]->h_seam + (side ? 0 : ncp);     /* the lower rank's first owned row, the upper rank's last */
+    for (int c = 0; c < ncp; c++)
+      if (src[c]) {
+        bl[side * ncp + c] = map[j][(size_t)src[c] - 1];
+        bm[side * nsc + c / kSeg] |= 1ull << (c % kSeg);
+      }
+  }
+  std::vector<int> own, foreign;
+  for (int side = 0; side < 2; side++) {
+    if (side ? !dn : !up) continue;
+    const int *src = h->h_seam + side * ncp;
+    for (int c = 0; c < ncp; c++)
+      if (src[c]) own.push_back(map[i][(size_t)src[c] - 1]);
+  }
+  wdpm_rims_merge::foreign_labels(bl, (size_t)2 * ncp, own.data(), own.size(), foreign);
+  const long long nlocal = (long long)map[i].size(), nforeign = (long long)foreign.size(), slots = nlocal + nforeign;
+  if (slots == 0) return 0;                         /* no pond in the rank's rows, none beside them */
+  if (slots > (long long)0x7f7f7f7f) return wdpm_fail("wdpm_group_rims_label: rank %d would hold %lld rim rows", i, slots);
+  for (long long k = 0; k < nforeign; k++) bf[k] = foreign[(size_t)k];
+  h->slot_label = map[i];
+  h->slot_label.insert(h->slot_label.end(), foreign.begin(), foreign.end());
+
+  if (slots > h->rims_cap) {
+    guarded_free(h, h->d_rims);
+    h->d_rims = nullptr;
+    h->rims_cap = 0;
+    const hipError_t e = guarded_malloc(h, (void **)&h->d_rims, (size_t)slots * sizeof(RimRow));
+    if (e != hipSuccess) return wdpm_fail("wdpm_group_rims_label: no device memory for the rims of %lld ponds: %s", slots, hipGetErrorString(e));
+    h->rims_cap = slots;
+  }
+  if (ponds + 1 > h->slot_cap) {
+    guarded_free(h, h->d_slot_of);
+    h->d_slot_of = nullptr;
+    h->slot_cap = 0;
+    const hipError_t e = guarded_malloc(h, (void **)&h->d_slot_of, (size_t)(ponds + 1) * sizeof(int));
+    if (e != hipSuccess) return wdpm_fail("wdpm_group_rims_label: no device memory for the slots of %lld ponds: %s", ponds, hipGetErrorString(e));
+    h->slot_cap = ponds + 1;
+  }
+  if (slots > h->h_rims_cap) {
+    if (h->h_rims) (void)hipHostFree(h->h_rims);
+    h->h_rims = nullptr;
+    h->h_rims_cap = 0;
+    const hipError_t e = hipHostMalloc(&h->h_rims, (size_t)slots * sizeof(wdpm_pond_rim));
+    if (e != hipSuccess) { h->h_rims = nullptr; return wdpm_fail("wdpm_group_rims_label: no pinned host memory for %lld rim rows: %s", slots, hipGetErrorString(e)); }
+    h->h_rims_cap = slots;
+  }
+
+  /* the rows beside the rank's own, into view rows 0 and g.rows - 1, which the label path left dry and unlabelled */
+  for (int side = 0; side < 2; side++) {
+    if (side ? !dn : !up) continue;
+    const size_t row = side ? (size_t)g.rows - 1 : 0;
+    HIP_TRY(hipMemcpyAsync(h->d_labels + row * ncp, bl + (size_t)side * ncp, (size_t)ncp * sizeof(int), hipMemcpyHostToDevice, sm));
+    HIP_TRY(hipMemcpyAsync(h->d_masks + row * nsc, bm + (size_t)side * nsc, (size_t)nsc * sizeof(unsigned long long), hipMemcpyHostToDevice, sm));
+  }
+  if (nforeign) HIP_TRY(hipMemcpyAsync(h->d_foreign, bf, (size_t)nforeign * sizeof(int), hipMemcpyHostToDevice, sm));
+
+  const size_t off = (size_t)h->row_off * ncp;
+  const double *w = x->d_w[x->cur] + off, *dem = x->d_dem + off;
+  const int ra = gh->own_lo[i] - gh->view0[i], rb = ra + gh->own_rows[i];      /* the owned rows, in rows of the view */
+  const int rpw = ponds_rows_per_wave(g.nseg, g.rows, h->forced_rpw);
+  const int nwaves = ((rb - ra + rpw - 1) / rpw) * nsc;
+  const unsigned sblocks = blocks_for(slots, kBlock), wblocks = blocks_for(nwaves, kWaves);
+  if (h->timing) HIP_TRY(hipEventRecord(h->rim_ev[0], sm));
+  /* every entry above any slot (slots <= 0x7f7f7f7f); only the entries of the rank's own and foreign ponds are ever read */
+  HIP_TRY(hipMemsetAsync(h->d_slot_of, 0x7f, (size_t)(ponds + 1) * sizeof(int), sm));
+  hipLaunchKernelGGL(rims_slots_kernel, dim3(sblocks), dim3(kBlock), 0, sm, h->d_map, (int)nlocal, h->d_foreign, (int)nforeign, h->d_slot_of);
+  hipLaunchKernelGGL(rims_init_kernel, dim3(sblocks), dim3(kBlock), 0, sm, h->d_rims, slots);
+  hipLaunchKernelGGL(rims_pass_rows_kernel, dim3(wblocks), dim3(kBlock), 0, sm, w, dem, h->d_masks, h->d_labels, g, rpw, nwaves, h->d_rims,
+                     ra, rb, h->d_slot_of);
+  if (h->timing) HIP_TRY(hipEventRecord(h->rim_ev[1], sm));
+  hipLaunchKernelGGL(rims_locate_rows_kernel, dim3(wblocks), dim3(kBlock), 0, sm, w, dem, h->d_masks, h->d_labels, g, rpw, nwaves, h->d_rims,
+                     ra, rb, h->d_slot_of);
+  hipLaunchKernelGGL(rims_finish_kernel, dim3(sblocks), dim3(kBlock), 0, sm, h->d_rims, slots, ncp);
+  if (h->timing) HIP_TRY(hipEventRecord(h->rim_ev[2], sm));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h->h_rims, h->d_rims, (size_t)slots * sizeof(wdpm_pond_rim), hipMemcpyDeviceToHost, sm));
+  h->rim_slots = slots;
+  h->rim_foreign = nforeign;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int wdpm_group_rims_label(wdpm_group_ponds *h, double min_depth, int64_t *nponds) {
+  if (!h) return wdpm_fail("wdpm_group_rims_label: null handle");
+  if (!(min_depth >= 0.0) || std::isinf(min_depth))
+    return wdpm_fail("wdpm_group_rims_label: min_depth must be finite and >= 0 (got %g)", min_depth);
+  int64_t n = 0;
+  if (group_label(h, min_depth, &n, group_rims_rank)) return 1;       /* every stream has run dry: one wait per rank ended both tables */
+  h->valid = false;                                                     /* until the rims are merged as well */
+  std::vector<wdpm_rims_merge::RankRims> ranks((size_t)h->n);
+  long long slots = 0, foreign = 0;
+  for (int i = 0; i < h->n; i++) {
+    wdpm_ponds *p = h->r[i];
+    if (h->timing && p->rim_slots > 0) {
+      HIP_TRY(hipSetDevice(p->x->p.device));
+      for (int k = 0; k < WDPM_RIMS_PHASES; k++) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, p->rim_ev[k], p->rim_ev[k + 1]));
+        p->rim_ms[k] = ms;
+      }
+    }
+    ranks[(size_t)i] = {p->h_rims, p->slot_label.data(), p->rim_slots, h->view0[i]};
+    slots += p->rim_slots;
+    foreign += p->rim_foreign;
+  }
+  timespec t0, t1;
+  clock_gettime(CLOCK_MONOTONIC, &t0);
+  h->rims.resize((size_t)n);
+  std::string err;
+  if (wdpm_rims_merge::merge(ranks, n, h->rims.data(), err)) return wdpm_fail("wdpm_group_rims_label: %s", err.c_str());
+  clock_gettime(CLOCK_MONOTONIC, &t1);
+  h->rim_stats.ranks = h->n;
+  h->rim_stats.slots = slots;
+  h->rim_stats.foreign = foreign;
+  h->rim_stats.merge_ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
+  h->valid = true;
+  h->rims_valid = true;
+  if (nponds) *nponds = n;
+  return 0;
+}
+
+extern "C" int wdpm_group_rims_table(wdpm_group_ponds *h, wdpm_pond_rim *out, int64_t capacity) {
+  if (!h) return wdpm_fail("wdpm_group_rims_table: null handle");
+  if (!h->valid || !h->rims_valid)
+    return wdpm_fail("wdpm_group_rims_table: no rim table: the last label call on this handle was not a wdpm_group_rims_label that succeeded");
+  const long long n = h->stats.ponds;
+  if (capacity < n) return wdpm_fail("wdpm_group_rims_table: capacity %lld is too small for %lld ponds", (long long)capacity, n);
+  if (n == 0) return 0;
+  if (!out) return wdpm_fail("wdpm_group_rims_table: null output");
+  memcpy(out, h->rims.data(), (size_t)n * sizeof(wdpm_pond_rim));
+  return 0;
+}
+
+extern "C" int wdpm_group_rims_stats(wdpm_group_ponds *h, wdpm_group_rim_stats *out) {
+  if (!h || !out) return wdpm_fail("wdpm_group_rims_stats: null argument");
+  if (!h->valid || !h->rims_valid)
+    return wdpm_fail("wdpm_group_rims_stats: no rim table: the last label call on this handle was not a wdpm_group_rims_label that succeeded");
+  *out = h->rim_stats;
+  return 0;
+}
+
+extern "C" int wdpm_group_rims_phase_ms(wdpm_group_ponds *h, int32_t rank, double *ms) {
+  if (!h || !ms) return wdpm_fail("wdpm_group_rims_phase_ms: null argument");
+  if (rank < 0 || rank >= h->n) return wdpm_fail("wdpm_group_rims_phase_ms: rank %d of %d", rank, h->n);
+  if (!h->timing) return wdpm_fail("wdpm_group_rims_phase_ms: the handle records no events (set WDPM_PONDS_TIMING=1 before it is made)");
+  if (!h->valid || !h->rims_valid)
+    return wdpm_fail("wdpm_group_rims_phase_ms: no rim table: the last label call on this handle was not a wdpm_group_rims_label that succeeded");
+  for (int i = 0; i < WDPM_RIMS_PHASES; i++) ms[i] = h->r[rank]->rim_ms[i];
   return 0;
 }
 #endif  /* WDPM_PONDS_EMULATION */

@@ -486,6 +486,14 @@ void release(wdpm_ponds *h) {
   guarded_free(h, h->d_masks); guarded_free(h, h->d_rootmask); guarded_free(h, h->d_parent); guarded_free(h, h->d_labels);
   guarded_free(h, h->d_cnt); guarded_free(h, h->d_ucnt); guarded_free(h, h->d_bsum); guarded_free(h, h->d_busum);
   guarded_free(h, h->d_table); guarded_free(h, h->d_seam); guarded_free(h, h->d_map); guarded_free(h, h->d_rims);
+  guarded_free(h, h->d_slot_of); guarded_free(h, h->d_foreign);
+  if (h->h_beside) (void)hipHostFree(h->h_beside);
+  if (h->h_rims) (void)hipHostFree(h->h_rims);
+  h->d_slot_of = h->d_foreign = nullptr;
+  h->slot_cap = 0;
+  h->h_beside = nullptr;
+  h->h_rims = nullptr;
+  h->h_rims_cap = 0;
   (void)hipFree(h->d_status);
   if (h->h_status) (void)hipHostFree(h->h_status);
   if (h->h_seam) (void)hipHostFree(h->h_seam);
@@ -564,6 +572,12 @@ wdpm_ponds *make_handle(wdpm_ctx *ctx, int row_off, int rows, bool seams) {
   h->d_rims = nullptr;
   h->rims_cap = 0;
   h->rims_valid = false;
+  h->d_slot_of = h->d_foreign = nullptr;
+  h->slot_cap = 0;
+  h->h_beside = nullptr;
+  h->h_rims = nullptr;
+  h->h_rims_cap = 0;
+  h->rim_slots = h->rim_foreign = 0;
   h->nb = 0;
   { const char *re = getenv("WDPM_PONDS_ROWS_PER_WAVE"); h->forced_rpw = re ? atoi(re) : 0; }
   h->rpw = 1;
@@ -810,17 +824,7 @@ extern "C" int wdpm_ponds_phase_ms(wdpm_ponds *h, double *ms) {
 }
 
 /* ---- row blocks (include/wdpm_group_ponds.h) --------------------------------------------------------------------------------- */
-struct wdpm_group_ponds {
-  wdpm_group *grp;
-  int n;                                   /* ranks */
-  int rows, ncp;                           /* the whole raster, padded */
-  std::vector<wdpm_ponds *> r;             /* one handle per rank, on its owned rows with one row either side */
-  std::vector<int> own_lo, own_rows, view0;   /* whole-raster rows: first owned, how many owned, the view's row 0 */
-  std::vector<wdpm_pond> table;            /* the merged table of the last label call */
-  bool timing, valid;
-  wdpm_group_pond_stats stats;
-};
-
+/* (struct wdpm_group_ponds: wdpm_ponds_priv.h) */
 extern "C" int wdpm_group_ponds_create(wdpm_group_ponds **out, wdpm_group *grp) {
   if (!out || !grp) return wdpm_fail("wdpm_group_ponds_create: null argument");
   const int n = wdpm_group_size(grp);
@@ -829,8 +833,10 @@ extern "C" int wdpm_group_ponds_create(wdpm_group_ponds **out, wdpm_group *grp) 
   h->grp = grp;
   h->n = n;
   h->valid = false;
+  h->rims_valid = false;
   h->timing = true;
   memset(&h->stats, 0, sizeof h->stats);
+  memset(&h->rim_stats, 0, sizeof h->rim_stats);
   for (int i = 0; i < n; i++) {
     wdpm_rank *rk = wdpm_group_rank(grp, i);
     wdpm_ctx *x = rk ? wdpm_rank_ctx(rk) : nullptr;
@@ -887,7 +893,12 @@ extern "C" int wdpm_group_ponds_label(wdpm_group_ponds *h, double min_depth, int
   if (!h) return wdpm_fail("wdpm_group_ponds_label: null handle");
   if (!(min_depth >= 0.0) || std::isinf(min_depth))
     return wdpm_fail("wdpm_group_ponds_label: min_depth must be finite and >= 0 (got %g)", min_depth);
+  return group_label(h, min_depth, nponds, nullptr);
+}
+
+int wdpm_pond_detail::group_label(wdpm_group_ponds *h, double min_depth, int64_t *nponds, group_rims_queue rims) {
   h->valid = false;
+  h->rims_valid = false;            /* a rim table belongs to the label call that made it */
   const int n = h->n;
   /* every rank up to its scan, on its own stream and device, before the first wait */
   for (int i = 0; i < n; i++)
@@ -917,8 +928,10 @@ extern "C" int wdpm_group_ponds_label(wdpm_group_ponds *h, double min_depth, int
 
   /* every rank's table kernel, its labels written once as whole-raster numbers, and its own table on the way to the host:
    * all of it queued (pinned staging on both ways) before the first wait */
-  for (int i = 0; i < n; i++)
+  for (int i = 0; i < n; i++) {
     if (table_queue(h->r[i], true, res.map[i].data())) return drain_and_fail(h);
+    if (rims && rims(h, i, res.map, res.ponds)) return drain_and_fail(h);
+  }
   for (int i = 0; i < n; i++)
     if (table_wait(h->r[i])) {
       if (!bad) first_msg = wdpm_last_error();

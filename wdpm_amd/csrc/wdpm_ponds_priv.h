@@ -26,6 +26,7 @@
 #endif
 #include "../../include/wdpm_group_ponds.h"
 #include "../../include/wdpm_pond_rims.h"
+#include "../../include/wdpm_group_pond_rims.h"
 
 namespace wdpm_pond_detail {
 
@@ -130,12 +131,45 @@ struct wdpm_ponds {
   bool rims_valid;
   hipEvent_t rim_ev[WDPM_RIMS_PHASES + 1];   /* made with the others when the handle records events */
   double rim_ms[WDPM_RIMS_PHASES];
+  /* rims of a row block (wdpm_group_rims_label): d_rims then holds one row per SLOT - the rank's local ponds, then its foreign
+   * ponds - and d_slot_of[label in the whole raster] says which */
+  int *d_slot_of;
+  long long slot_cap;               /* entries of d_slot_of */
+  int *d_foreign;                   /* 2 x g.ncp: the foreign ponds' labels */
+  unsigned long long *h_beside;     /* pinned staging: 2 x g.nsc wet masks, 2 x g.ncp labels of the rows beside the rank's own, */
+                                    /* 2 x g.ncp foreign labels */
+  wdpm_pond_rim *h_rims;            /* pinned: the finished rim rows on their way down */
+  long long h_rims_cap;
+  long long rim_slots;              /* of the call under way */
+  long long rim_foreign;
+  std::vector<int> slot_label;      /* slot -> label in the whole raster */
+};
+
+/* the handle of include/wdpm_group_ponds.h and include/wdpm_group_pond_rims.h */
+struct wdpm_group_ponds {
+  wdpm_group *grp;
+  int n;                                   /* ranks */
+  int rows, ncp;                           /* the whole raster, padded */
+  std::vector<wdpm_ponds *> r;             /* one handle per rank, on its owned rows with one row either side */
+  std::vector<int> own_lo, own_rows, view0;   /* whole-raster rows: first owned, how many owned, the view's row 0 */
+  std::vector<wdpm_pond> table;            /* the merged table of the last label call */
+  bool timing, valid;
+  wdpm_group_pond_stats stats;
+  /* rims: the merged table of the last wdpm_group_rims_label; every label call takes rims_valid away first */
+  std::vector<wdpm_pond_rim> rims;
+  bool rims_valid;
+  wdpm_group_rim_stats rim_stats;
 };
 
 namespace wdpm_pond_detail {
 /* device memory of the handle between two guard bands (when it carries any): wdpm_ponds_guard_bad looks at every band */
 __attribute__((visibility("hidden"))) hipError_t guarded_malloc(wdpm_ponds *h, void **p, size_t bytes);
 __attribute__((visibility("hidden"))) void guarded_free(wdpm_ponds *h, void *p);
+/* wdpm_group_ponds_label, and with `rims` what wdpm_group_rims_label adds to it: after rank i's table kernels are queued and
+ * before any rank is waited for, rims(h, i, map) queues that rank's rim work, map[rank][local label - 1] being the stitch's
+ * numbers.  One wait per rank then ends both. */
+typedef int (*group_rims_queue)(wdpm_group_ponds *h, int rank, const std::vector<std::vector<int>> &map, long long ponds);
+__attribute__((visibility("hidden"))) int group_label(wdpm_group_ponds *h, double min_depth, int64_t *nponds, group_rims_queue rims);
 }  // namespace wdpm_pond_detail
 #endif
 

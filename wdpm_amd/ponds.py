@@ -1,5 +1,6 @@
-"""ctypes binding of include/wdpm_ponds.h, include/wdpm_group_ponds.h and include/wdpm_pond_rims.h: the pond inventory of a
-context's current water raster, of a raster spread over the row blocks of a rowblock.Group, and the rim of every pond.
+"""ctypes binding of include/wdpm_ponds.h, include/wdpm_group_ponds.h, include/wdpm_pond_rims.h and
+include/wdpm_group_pond_rims.h: the pond inventory of a context's current water raster, of a raster spread over the row blocks of
+a rowblock.Group, and the rim of every pond of either.
 
 Product library only (the symbols are not part of the ABI of include/wdpm.h, and ``capi.SYMBOLS`` does not list them).
 
@@ -13,6 +14,8 @@ Product library only (the symbols are not part of the ABI of include/wdpm.h, and
 
     with rowblock.Group(...) as grp, GroupPonds(grp) as ponds:     # the same calls, the same answer, every rank labelled in place
         n = ponds.label(0.001)
+        n = ponds.label_rims(0.001) # every rank takes the rims of its own rows; the host merges them
+        rims = ponds.rims()         # RIM_DTYPE, coordinates of the whole raster
 """
 from __future__ import annotations
 
@@ -97,11 +100,26 @@ GROUP_SYMBOLS = {
 }
 
 
+class GroupRimStatsStruct(C.Structure):
+    """struct wdpm_group_rim_stats"""
+    _fields_ = [("ranks", C.c_int64), ("slots", C.c_int64), ("foreign", C.c_int64), ("merge_ms", C.c_double)]
+
+
+# every symbol include/wdpm_group_pond_rims.h declares
+GROUP_RIM_SYMBOLS = {
+    "wdpm_group_rims_label": (C.c_int, [_vp, C.c_double, C.POINTER(C.c_int64)]),
+    "wdpm_group_rims_table": (C.c_int, [_vp, _vp, C.c_int64]),
+    "wdpm_group_rims_stats": (C.c_int, [_vp, C.POINTER(GroupRimStatsStruct)]),
+    "wdpm_group_rims_phase_ms": (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_double)]),
+}
+
+
 def bind(lib: capi.Lib):
     """Set the prototypes on a loaded product library; a library without the symbols is an error (no fallback)."""
     if getattr(lib, "_ponds_bound", False):
         return lib.dll
-    for name, (res, args) in list(SYMBOLS.items()) + list(GROUP_SYMBOLS.items()) + list(RIM_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(GROUP_SYMBOLS.items()) + list(RIM_SYMBOLS.items()) + \
+            list(GROUP_RIM_SYMBOLS.items()):
         try:
             fn = getattr(lib.dll, name)
         except AttributeError:
@@ -290,3 +308,32 @@ class GroupPonds:
         v = C.c_int64()
         self.lib.check(self.dll.wdpm_group_ponds_guard_bad(self._h, C.byref(v)))
         return v.value
+
+    def label_rims(self, min_depth: float) -> int:
+        """label(min_depth), and every rank's rim pass on the same water; table(), labels(), stats() and rank_stats() answer as
+        after label()."""
+        n = C.c_int64()
+        self.n = None
+        self.lib.check(self.dll.wdpm_group_rims_label(self._h, float(min_depth), C.byref(n)))
+        self.n = n.value
+        return n.value
+
+    def rims(self, capacity: int | None = None) -> np.ndarray:
+        """One row per pond (RIM_DTYPE) of the last label_rims(), coordinates of the whole raster; fails after a plain label()."""
+        if self.n is None:
+            raise capi.WdpmError("GroupPonds.rims: label_rims() has not succeeded on this handle")
+        cap = self.n if capacity is None else int(capacity)
+        out = np.zeros(max(cap, 0), dtype=RIM_DTYPE)
+        self.lib.check(self.dll.wdpm_group_rims_table(self._h, out.ctypes.data, cap))
+        return out[:self.n]
+
+    def rims_stats(self) -> dict:
+        s = GroupRimStatsStruct()
+        self.lib.check(self.dll.wdpm_group_rims_stats(self._h, C.byref(s)))
+        return {name: (float if name == "merge_ms" else int)(getattr(s, name)) for name, _ in GroupRimStatsStruct._fields_}
+
+    def rims_phase_ms(self, rank: int) -> dict:
+        """milliseconds of one rank's rim pass and locate pass in the last label_rims() (handles made with WDPM_PONDS_TIMING=1)"""
+        ms = (C.c_double * len(RIM_PHASES))()
+        self.lib.check(self.dll.wdpm_group_rims_phase_ms(self._h, int(rank), ms))
+        return dict(zip(RIM_PHASES, (float(v) for v in ms)))
