@@ -13,6 +13,10 @@
                       phases beside the table phase of the SAME calls, and their ratio (default --out profiles/r12/pond_rims.json)
                       With --devices: GroupPonds.label_rims (include/wdpm_group_pond_rims.h) - per-rank rim phases, their sum over
                       the ranks, the host's merge_ms beside stitch_ms, foreign (default --out profiles/r13/pond_rims_group.json)
+    ... --catchments  the catchments of the ponds as well (include/wdpm_pond_catchments.h): five timed pairs of label_rims and
+                      label_catchments, interleaved - the three catchment phases beside the table phase of the SAME calls, their
+                      ratios and rounds, and the label, table and rim phases of either call side by side (default --out
+                      profiles/r14/pond_catchments.json)
     ... --iterations K   instead of the job's own number of iterations before the inventory
 
 Per job: one untimed label call, then five timed ones (wall clock around the call, which ends with the stream idle; HIP events
@@ -40,7 +44,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 import wdpm_amd  # noqa: E402
-from wdpm_amd.ponds import PHASES, RIM_PHASES, GroupPonds, Ponds  # noqa: E402
+from wdpm_amd.ponds import CATCH_PHASES, PHASES, RIM_PHASES, GroupPonds, Ponds  # noqa: E402
 
 MISS = -99999.0
 
@@ -91,6 +95,49 @@ def rims_job(ctx, p, rec, n):
     model = rims_bytes_model(n + 2, n + 2, rec["wet_cells"], rec["rims"]["rim_memberships"] + rec["rims"]["wall_memberships"], len(rims))
     rec["rims"]["bytes_model_upper"] = model
     rec["rims"]["gbps_upper"] = {k: model[k] / (med[k] * 1e6) if med[k] > 0 else None for k in RIM_PHASES}
+
+
+def catchments_bytes_model(rows, ncp, caught):
+    """the algorithmic traffic of the catchment phases: receivers dem 8, w 8, label 4, link 4 per cell (rows of pond cells alone
+    read neither dem nor w: the model is an upper bound there); a jump round at least one link per cell; the tally a link in and a
+    basin out per cell, and dem and w of the slope cells that drain to a pond"""
+    cells = rows * ncp
+    return {"receivers": 24 * cells, "jump_per_round": 4 * cells, "tally": 8 * cells + 16 * caught}
+
+
+def catchments_job(ctx, p, rec, n):
+    """after the label calls: one untimed label_catchments (allocates links and table), then five pairs of label_rims and
+    label_catchments, interleaved: what the new pass costs, and whether the phases it sits beside notice it"""
+    p.label_catchments(0.001)
+    shared = list(PHASES) + list(RIM_PHASES)
+    wall = {"rims": [], "catchments": []}
+    beside = {"rims": {k: [] for k in shared}, "catchments": {k: [] for k in shared}}
+    phases, rounds = {k: [] for k in CATCH_PHASES}, []
+    for _ in range(5):
+        for which, call in (("rims", p.label_rims), ("catchments", p.label_catchments)):
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            call(0.001)
+            wall[which].append((time.perf_counter() - t0) * 1e3)
+            for k, v in list(p.phase_ms().items()) + list(p.rims_phase_ms().items()):
+                beside[which][k].append(v)
+        for k, v in p.catchment_phase_ms().items():
+            phases[k].append(v)
+        rounds.append(p.catchment_stats()["rounds"])
+    catch, stats = p.catchments(), p.catchment_stats()
+    med = {k: statistics.median(v) for k, v in phases.items()}
+    table_ms = statistics.median(beside["catchments"]["table"])
+    model = catchments_bytes_model(n + 2, n + 2, int(catch["catch_cells"].sum()))
+    c = rec["catchments"] = dict(
+        wall_ms={k: statistics.median(v) for k, v in wall.items()}, wall_ms_all=wall, phase_ms=med, phase_ms_all=phases,
+        table_ms_same_calls=table_ms, over_table={k: med[k] / table_ms for k in CATCH_PHASES}, rounds=rounds, stats=stats,
+        beside_ms={w: {k: statistics.median(v) for k, v in ph.items()} for w, ph in beside.items()}, beside_ms_all=beside,
+        caught_cells=int(catch["catch_cells"].sum()), inflow_cells=int(catch["inflow_cells"].sum()),
+        largest_catchment=int(catch["catch_cells"].max()) if len(catch) else 0, bytes_model=model, guard_bad=p.guard_bad())
+    c["gbps"] = {"receivers": model["receivers"] / (med["receivers"] * 1e6), "tally": model["tally"] / (med["tally"] * 1e6),
+                 "jump": model["jump_per_round"] * rounds[-1] / (med["jump"] * 1e6)}
+    if rec.get("hbm_yardstick_gbps"):
+        c["of_yardstick"] = {k: v / rec["hbm_yardstick_gbps"] for k, v in c["gbps"].items()}
 
 
 def yardstick_gbps(path):
@@ -171,12 +218,17 @@ def main():
                     help="output of tools/_build/hbm_yardstick from the same box: its best streaming rate goes into the record")
     ap.add_argument("--devices", metavar="a,b,...", help="label over row blocks, one per device named (wdpm_amd.ponds.GroupPonds)")
     ap.add_argument("--rims", action="store_true", help="time label_rims as well: the rim and locate phases beside the table phase")
+    ap.add_argument("--catchments", action="store_true",
+                    help="time label_catchments as well, interleaved with label_rims: the receiver, jump and tally phases")
     ap.add_argument("--iterations", type=int, help="iterations before the inventory, instead of the job's own")
     a = ap.parse_args()
     if not a.out:
         a.out = os.path.join(ROOT, "profiles", *(("r13", "pond_rims_group.json") if a.devices and a.rims else
                                                   ("r11", "ponds_group.json") if a.devices else
+                                                  ("r14", "pond_catchments.json") if a.catchments else
                                                   ("r12", "pond_rims.json") if a.rims else ("r10", "ponds.json")))
+    if a.catchments and a.devices:
+        raise SystemExit("--catchments: catchments are taken on whole rasters only (include/wdpm_pond_catchments.h)")
     hip = wdpm_amd.load_hip()
     n = a.n
     dem = hip.synth_dem(n, n)
@@ -241,6 +293,8 @@ def main():
                 rec["of_yardstick"] = {k: v / rec["hbm_yardstick_gbps"] if v else None for k, v in rec["gbps"].items()}
             if a.rims:
                 rims_job(ctx, p, rec, n)
+            if a.catchments:
+                catchments_job(ctx, p, rec, n)
         if not a.no_scipy:
             try:
                 import scipy.ndimage as ndi

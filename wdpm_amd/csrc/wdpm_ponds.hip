@@ -486,7 +486,14 @@ void release(wdpm_ponds *h) {
   guarded_free(h, h->d_masks); guarded_free(h, h->d_rootmask); guarded_free(h, h->d_parent); guarded_free(h, h->d_labels);
   guarded_free(h, h->d_cnt); guarded_free(h, h->d_ucnt); guarded_free(h, h->d_bsum); guarded_free(h, h->d_busum);
   guarded_free(h, h->d_table); guarded_free(h, h->d_seam); guarded_free(h, h->d_map); guarded_free(h, h->d_rims);
-  guarded_free(h, h->d_slot_of); guarded_free(h, h->d_foreign);
+  guarded_free(h, h->d_slot_of); guarded_free(h, h->d_foreign); guarded_free(h, h->d_link); guarded_free(h, h->d_catch);
+  if (h->d_cstat) (void)hipFree(h->d_cstat);
+  if (h->h_cstat) (void)hipHostFree(h->h_cstat);
+  h->d_link = nullptr;
+  h->d_catch = nullptr;
+  h->catch_cap = 0;
+  h->d_cstat = h->h_cstat = nullptr;
+  h->catch_valid = false;
   if (h->h_beside) (void)hipHostFree(h->h_beside);
   if (h->h_rims) (void)hipHostFree(h->h_rims);
   h->d_slot_of = h->d_foreign = nullptr;
@@ -578,6 +585,12 @@ wdpm_ponds *make_handle(wdpm_ctx *ctx, int row_off, int rows, bool seams) {
   h->h_rims = nullptr;
   h->h_rims_cap = 0;
   h->rim_slots = h->rim_foreign = 0;
+  h->d_link = nullptr;
+  h->d_catch = nullptr;
+  h->catch_cap = 0;
+  h->d_cstat = h->h_cstat = nullptr;
+  h->catch_valid = false;
+  memset(&h->catch_stats, 0, sizeof h->catch_stats);
   h->nb = 0;
   { const char *re = getenv("WDPM_PONDS_ROWS_PER_WAVE"); h->forced_rpw = re ? atoi(re) : 0; }
   h->rpw = 1;
@@ -596,6 +609,11 @@ wdpm_ponds *make_handle(wdpm_ctx *ctx, int row_off, int rows, bool seams) {
   if (h->timing)
     for (int i = 0; i < WDPM_RIMS_PHASES + 1; i++)
       if (hipEventCreate(&h->rim_ev[i]) != hipSuccess) { h->timing = false; break; }
+  for (int i = 0; i < 5; i++) h->catch_ev[i] = nullptr;
+  for (int i = 0; i < WDPM_CATCH_PHASES; i++) h->catch_ms[i] = 0.0;
+  if (h->timing)
+    for (int i = 0; i < 5; i++)
+      if (hipEventCreate(&h->catch_ev[i]) != hipSuccess) { h->timing = false; break; }
   return h;
 }
 
@@ -609,6 +627,7 @@ int label_queue(wdpm_ponds *h, double min_depth) {
   wdpm_ctx *x = h->x;
   h->valid = false;
   h->rims_valid = false;            /* a rim table belongs to the label call that made it (wdpm_pond_rims.hip) */
+  h->catch_valid = false;           /* and so does a catchment table (wdpm_pond_catchments.hip) */
   /* the raster as a reader sees it: side stream joined, owed drain() and threshold flush applied (what wdpm_count_stats asks for) */
   if (wdpm_synchronize(x)) return 1;
   if (wdpm_apply_owed_flush(x)) return 1;
@@ -755,6 +774,8 @@ void destroy_handle(wdpm_ponds *h) {
     if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
   for (int i = 0; i < WDPM_RIMS_PHASES + 1; i++)
     if (h->rim_ev[i]) (void)hipEventDestroy(h->rim_ev[i]);
+  for (int i = 0; i < 5; i++)
+    if (h->catch_ev[i]) (void)hipEventDestroy(h->catch_ev[i]);
   delete h;
 }
 

@@ -1,6 +1,6 @@
 /*
- * wdpm_ponds_priv.h — what the two units of the pond inventory share: wdpm_ponds.hip (labels and table) and wdpm_pond_rims.hip
- * (rims).  Geometry, the order-preserving image of a double, the table row as the device accumulates it, and - outside the host
+ * wdpm_ponds_priv.h — what the units of the pond inventory share: wdpm_ponds.hip (labels and table), wdpm_pond_rims.hip
+ * (rims) and wdpm_pond_catchments.hip (catchments).  Geometry, the order-preserving image of a double, the table row as the device accumulates it, and - outside the host
  * emulations of the tests, which define WDPM_PONDS_EMULATION and bring stand-ins for the HIP device language - the handle itself
  * with its guarded allocator.  Private: nothing here is exported, and no header under include/ knows it.
  */
@@ -27,6 +27,7 @@
 #include "../../include/wdpm_group_ponds.h"
 #include "../../include/wdpm_pond_rims.h"
 #include "../../include/wdpm_group_pond_rims.h"
+#include "../../include/wdpm_pond_catchments.h"
 
 namespace wdpm_pond_detail {
 
@@ -63,6 +64,26 @@ struct RimRow {
   unsigned long long rim_cells, wall_cells;
 };
 static_assert(sizeof(RimRow) == sizeof(wdpm_pond_rim), "the device rim table is copied out as wdpm_pond_rim");
+
+/* the catchment table as the device accumulates it: wdpm_pond_catchment with the head level as its order-preserving image */
+struct CatchRow {
+  unsigned long long catch_cells, inflow_cells, head_key;
+  int row_min, row_max, col_min, col_max;
+};
+static_assert(sizeof(CatchRow) == sizeof(wdpm_pond_catchment) && sizeof(CatchRow) == 40, "the device catchment table is copied out as wdpm_pond_catchment");
+
+/* Pointer jumping over the link raster runs in rounds, each of which at least halves every descent: 32 would do for fewer than
+ * 2^31 cells.  Past kCatchRoundCap the call fails; the host looks at the count of unresolved cells once per kCatchBatch rounds. */
+constexpr int kCatchRoundCap = 40;
+constexpr int kCatchBatch = 4;
+constexpr int kCatchHops = 4;        /* links one thread follows in one round */
+static_assert(kCatchRoundCap % kCatchBatch == 0, "whole batches up to the cap");
+
+/* what the catchment kernels count for the host: unres[k] is the number of cells round k left with a link that is no terminal */
+struct CatchStatus {
+  unsigned long long slope, pit, unponded;
+  unsigned unres[kCatchRoundCap];
+};
 
 /* status words the host reads after the scan */
 struct Status {
@@ -143,6 +164,16 @@ struct wdpm_ponds {
   long long rim_slots;              /* of the call under way */
   long long rim_foreign;
   std::vector<int> slot_label;      /* slot -> label in the whole raster */
+  /* catchments (wdpm_pond_catchments.hip): link raster (the basin raster once a call has ended) and table of the last
+   * wdpm_catch_label; every label call takes catch_valid away first */
+  int *d_link;                      /* g.rows x g.ncp, allocated at the first wdpm_catch_label */
+  wdpm_pond_detail::CatchRow *d_catch;
+  long long catch_cap;
+  wdpm_pond_detail::CatchStatus *d_cstat, *h_cstat;   /* h_cstat pinned */
+  bool catch_valid;
+  hipEvent_t catch_ev[5];           /* init | receivers | jump rounds | tally, finish */
+  double catch_ms[WDPM_CATCH_PHASES];
+  wdpm_pond_catchment_stats catch_stats;
 };
 
 /* the handle of include/wdpm_group_ponds.h and include/wdpm_group_pond_rims.h */

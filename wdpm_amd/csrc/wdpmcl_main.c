@@ -39,6 +39,7 @@
 #include "../../include/wdpm.h"
 #include "../../include/wdpm_group_ponds.h"
 #include "../../include/wdpm_pond_rims.h"
+#include "../../include/wdpm_pond_catchments.h"
 /* the pond inventory is the HIP library's alone: weak references, so that this file also links against a back-end that
  * exports include/wdpm.h and nothing else (WDPM_PONDS then says so and writes no file) */
 #pragma weak wdpm_ponds_create
@@ -54,6 +55,9 @@
 #pragma weak wdpm_group_ponds_stats
 #pragma weak wdpm_rims_label
 #pragma weak wdpm_rims_table
+#pragma weak wdpm_catch_label
+#pragma weak wdpm_catch_table
+#pragma weak wdpm_catch_stats
 #include "arcascii.h"
 
 #define ITER_PER_BLOCK 1000 /* IterationNum, WDPMCL.c:597 */
@@ -642,14 +646,19 @@ static void relief_finish(relief_helper *h) {
  * WDPM_PONDS=<path>: the 8-connected water bodies of the final water, one CSV line per pond, numbered by first cell.  A pond
  * cell holds more than WDPM_PONDS_MIN_DEPTH_MM of water (default 1.0: the reference's own wet threshold, water > 0.001,
  * WDPMCL.c:1397-1404, so the cells column sums to the wet count of the final statistics).  Nothing of it goes to stdout. */
-typedef struct { wdpm_pond *rows; int64_t n; int64_t guard_bad; int64_t blocks, joined; wdpm_pond_rim *rims; } pond_inventory;
+typedef struct {
+  wdpm_pond *rows; int64_t n; int64_t guard_bad; int64_t blocks, joined; wdpm_pond_rim *rims;
+  wdpm_pond_catchment *catch; wdpm_pond_catchment_stats catch_stats;
+} pond_inventory;
 
 /* with_rims (WDPM_POND_RIMS, include/wdpm_pond_rims.h; the caller has seen that the back-end has them): one wdpm_rims_label serves
- * the pond table and the rim table */
-static int take_inventory(wdpm_ctx *c, double min_depth, pond_inventory *inv, int with_rims) {
+ * the pond table and the rim table.  with_catch (WDPM_POND_CATCHMENTS, include/wdpm_pond_catchments.h; likewise): one
+ * wdpm_catch_label serves all three, whichever of the files are asked for. */
+static int take_inventory(wdpm_ctx *c, double min_depth, pond_inventory *inv, int with_rims, int with_catch) {
   wdpm_ponds *h = NULL;
   inv->rows = NULL;
   inv->rims = NULL;
+  inv->catch = NULL;
   inv->n = 0;
   inv->guard_bad = 0;
   inv->blocks = 1;
@@ -659,21 +668,32 @@ static int take_inventory(wdpm_ctx *c, double min_depth, pond_inventory *inv, in
     return 1;
   }
   int rc = wdpm_ponds_create(&h, c);
-  if (!rc) rc = with_rims ? wdpm_rims_label(h, min_depth, &inv->n) : wdpm_ponds_label(h, min_depth, &inv->n);
+  if (!rc)
+    rc = with_catch  ? wdpm_catch_label(h, min_depth, &inv->n)
+         : with_rims ? wdpm_rims_label(h, min_depth, &inv->n)
+                     : wdpm_ponds_label(h, min_depth, &inv->n);
   if (!rc) {
     inv->rows = (wdpm_pond *)malloc((size_t)(inv->n > 0 ? inv->n : 1) * sizeof(wdpm_pond));
     if (with_rims) inv->rims = (wdpm_pond_rim *)malloc((size_t)(inv->n > 0 ? inv->n : 1) * sizeof(wdpm_pond_rim));
-    if (!inv->rows || (with_rims && !inv->rims)) { wdpm_set_last_error("out of host memory for the pond table"); rc = 1; }
+    if (with_catch) inv->catch = (wdpm_pond_catchment *)malloc((size_t)(inv->n > 0 ? inv->n : 1) * sizeof(wdpm_pond_catchment));
+    if (!inv->rows || (with_rims && !inv->rims) || (with_catch && !inv->catch)) {
+      wdpm_set_last_error("out of host memory for the pond table");
+      rc = 1;
+    }
   }
   if (!rc) rc = wdpm_ponds_table(h, inv->rows, inv->n);
   if (!rc && with_rims) rc = wdpm_rims_table(h, inv->rims, inv->n);
+  if (!rc && with_catch) rc = wdpm_catch_table(h, inv->catch, inv->n);
+  if (!rc && with_catch) rc = wdpm_catch_stats(h, &inv->catch_stats);
   if (!rc && getenv("WDPM_GUARD_KB")) rc = wdpm_ponds_guard_bad(h, &inv->guard_bad);
   if (rc) {
     fprintf(stderr, "WDPMCL: pond inventory failed, no file written: %s\n", wdpm_last_error());
     free(inv->rows);
     free(inv->rims);
+    free(inv->catch);
     inv->rows = NULL;
     inv->rims = NULL;
+    inv->catch = NULL;
   }
   wdpm_ponds_destroy(h);
   return rc;
@@ -685,6 +705,7 @@ static int take_group_inventory(wdpm_group *grp, double min_depth, pond_inventor
   wdpm_group_pond_stats gs;
   inv->rows = NULL;
   inv->rims = NULL;
+  inv->catch = NULL;
   inv->n = 0;
   inv->guard_bad = 0;
   inv->blocks = 1;
@@ -763,6 +784,34 @@ static int write_rims(const char *path, const pond_inventory *inv) {
     return 1;
   }
   fprintf(stderr, "WDPMCL: pond rims: %lld pond%s written to %s\n", (long long)inv->n, inv->n == 1 ? "" : "s", path);
+  return 0;
+}
+
+/* WDPM_POND_CATCHMENTS=<path>: one CSV line per pond of the same inventory: the dry cells that drain to it and their area, the cells
+ * through which the land's water enters it, the highest level among the cells that drain to it (-inf: none does) and the box of
+ * pond and catchment together (file coordinates, 0-based) (include/wdpm_pond_catchments.h).  Doubles as %.17g. */
+static int write_catchments(const char *path, const pond_inventory *inv, double cellarea) {
+  FILE *f = fopen(path, "w");
+  if (!f) {
+    fprintf(stderr, "WDPMCL: cannot write pond catchments %s\n", path);
+    return 1;
+  }
+  fprintf(f, "label,catch_cells,catch_area_m2,inflow_cells,head_level_m,row_min,row_max,col_min,col_max\n");
+  for (int64_t k = 0; k < inv->n; k++) {
+    const wdpm_pond_catchment *q = &inv->catch[k];
+    fprintf(f, "%lld,%lld,%.17g,%lld,%.17g,%d,%d,%d,%d\n", (long long)(k + 1), (long long)q->catch_cells,
+            (double)q->catch_cells * cellarea, (long long)q->inflow_cells, q->head_level, q->row_min - 1, q->row_max - 1,
+            q->col_min - 1, q->col_max - 1);
+  }
+  const int bad = ferror(f);
+  if (fclose(f) != 0 || bad) {
+    fprintf(stderr, "WDPMCL: error writing pond catchments %s\n", path);
+    return 1;
+  }
+  const wdpm_pond_catchment_stats *cs = &inv->catch_stats;
+  fprintf(stderr, "WDPMCL: pond catchments: %lld pond%s written to %s (%lld slope cells, %lld pits, %lld cells drain to no pond, %lld rounds)\n",
+          (long long)inv->n, inv->n == 1 ? "" : "s", path, (long long)cs->slope_cells, (long long)cs->pit_cells,
+          (long long)cs->unponded_cells, (long long)cs->rounds);
   return 0;
 }
 
@@ -1012,15 +1061,32 @@ int main(int argc, char **argv) {
     ponds_failed = 1;
     rims_path = NULL;
   }
-  if (ponds_path || rims_path) {
+  /* ... and their catchments (WDPM_POND_CATCHMENTS), alone or beside either: whole rasters only as well */
+  const char *catch_path = getenv("WDPM_POND_CATCHMENTS");
+  if (catch_path && !*catch_path) catch_path = NULL;
+  if (catch_path && ndev > 1) {
+    fprintf(stderr, "WDPMCL: pond catchments: the raster lies in %d row blocks and catchments are taken on a whole raster only, no file written to %s\n",
+            ndev, catch_path);
+    ponds_failed = 1;
+    catch_path = NULL;
+  }
+  if (catch_path && (!wdpm_catch_label || !wdpm_catch_table || !wdpm_catch_stats || !wdpm_rims_table)) {
+    fprintf(stderr, "WDPMCL: pond catchments: back-end %s has none, no file written\n", wdpm_backend_name());
+    ponds_failed = 1;
+    catch_path = NULL;
+  }
+  if (ponds_path || rims_path || catch_path) {
     phase("statistics + download");
-    const int failed = ndev == 1 ? take_inventory(wdpm_rank_ctx(wdpm_group_rank(ctx, 0)), ponds_min_depth, &inv, rims_path != NULL)
+    const int failed = ndev == 1 ? take_inventory(wdpm_rank_ctx(wdpm_group_rank(ctx, 0)), ponds_min_depth, &inv,
+                                                  rims_path != NULL || catch_path != NULL, catch_path != NULL)
                                  : take_group_inventory(ctx, ponds_min_depth, &inv);
     if (failed) ponds_failed = 1;
     if (!failed && ponds_path && write_inventory(ponds_path, &inv, st.cellarea)) ponds_failed = 1;
     if (!failed && rims_path && write_rims(rims_path, &inv)) ponds_failed = 1;
+    if (!failed && catch_path && write_catchments(catch_path, &inv, st.cellarea)) ponds_failed = 1;
     free(inv.rows);
     free(inv.rims);
+    free(inv.catch);
     phase("pond inventory");
   }
   int64_t guard_bad = inv.guard_bad;

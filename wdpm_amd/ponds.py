@@ -1,6 +1,6 @@
-"""ctypes binding of include/wdpm_ponds.h, include/wdpm_group_ponds.h, include/wdpm_pond_rims.h and
-include/wdpm_group_pond_rims.h: the pond inventory of a context's current water raster, of a raster spread over the row blocks of
-a rowblock.Group, and the rim of every pond of either.
+"""ctypes binding of include/wdpm_ponds.h, include/wdpm_group_ponds.h, include/wdpm_pond_rims.h, include/wdpm_group_pond_rims.h
+and include/wdpm_pond_catchments.h: the pond inventory of a context's current water raster, of a raster spread over the row blocks
+of a rowblock.Group, the rim of every pond of either, and the catchment of every pond of a whole raster.
 
 Product library only (the symbols are not part of the ABI of include/wdpm.h, and ``capi.SYMBOLS`` does not list them).
 
@@ -11,6 +11,9 @@ Product library only (the symbols are not part of the ABI of include/wdpm.h, and
         n = ponds.label_rims(0.001) # the same inventory, and one rim row per pond
         rims = ponds.rims()         # spill level and where it lies, shoreline, walls, surface spread (RIM_DTYPE)
         freeboard = rims["rim_level"] - rims["surface_max"]
+        n = ponds.label_catchments(0.001)   # all of the above, and which pond every dry cell drains to
+        basins = ponds.basins()     # int32, padded: k > 0 pond k or its catchment, 0 drains to a pit, -1 no level
+        catch = ponds.catchments()  # contributing cells, inflow cells, head level, bounding box (CATCH_DTYPE)
 
     with rowblock.Group(...) as grp, GroupPonds(grp) as ponds:     # the same calls, the same answer, every rank labelled in place
         n = ponds.label(0.001)
@@ -29,6 +32,7 @@ from . import capi
 VOLUME_QUANTUM = 2.0 ** -24   # metres per unit of volume_q
 PHASES = ("mask", "merge", "flatten", "scan", "table", "finish")   # wdpm_ponds_phase_ms
 RIM_PHASES = ("rims", "locate")                                    # wdpm_rims_phase_ms
+CATCH_PHASES = ("receivers", "jump", "tally")                      # wdpm_catch_phase_ms
 
 
 class PondStruct(C.Structure):
@@ -80,6 +84,32 @@ RIM_SYMBOLS = {
 }
 
 
+class CatchStruct(C.Structure):
+    """struct wdpm_pond_catchment"""
+    _fields_ = [("catch_cells", C.c_int64), ("inflow_cells", C.c_int64), ("head_level", C.c_double), ("row_min", C.c_int32),
+                ("row_max", C.c_int32), ("col_min", C.c_int32), ("col_max", C.c_int32)]
+
+
+class CatchStatsStruct(C.Structure):
+    """struct wdpm_pond_catchment_stats"""
+    _fields_ = [("slope_cells", C.c_int64), ("pit_cells", C.c_int64), ("unponded_cells", C.c_int64), ("rounds", C.c_int64),
+                ("ponds", C.c_int64)]
+
+
+CATCH_DTYPE = np.dtype([("catch_cells", "<i8"), ("inflow_cells", "<i8"), ("head_level", "<f8"), ("row_min", "<i4"),
+                        ("row_max", "<i4"), ("col_min", "<i4"), ("col_max", "<i4")])
+assert CATCH_DTYPE.itemsize == C.sizeof(CatchStruct) == 40
+
+# every symbol include/wdpm_pond_catchments.h declares
+CATCH_SYMBOLS = {
+    "wdpm_catch_label": (C.c_int, [_vp, C.c_double, C.POINTER(C.c_int64)]),
+    "wdpm_catch_table": (C.c_int, [_vp, _vp, C.c_int64]),
+    "wdpm_catch_basins": (C.c_int, [_vp, _vp]),
+    "wdpm_catch_stats": (C.c_int, [_vp, C.POINTER(CatchStatsStruct)]),
+    "wdpm_catch_phase_ms": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+}
+
+
 class GroupStatsStruct(C.Structure):
     """struct wdpm_group_pond_stats"""
     _fields_ = [("ranks", C.c_int64), ("ponds", C.c_int64), ("local_ponds", C.c_int64), ("stitch_unions", C.c_int64),
@@ -119,7 +149,7 @@ def bind(lib: capi.Lib):
     if getattr(lib, "_ponds_bound", False):
         return lib.dll
     for name, (res, args) in list(SYMBOLS.items()) + list(GROUP_SYMBOLS.items()) + list(RIM_SYMBOLS.items()) + \
-            list(GROUP_RIM_SYMBOLS.items()):
+            list(GROUP_RIM_SYMBOLS.items()) + list(CATCH_SYMBOLS.items()):
         try:
             fn = getattr(lib.dll, name)
         except AttributeError:
@@ -226,6 +256,44 @@ class Ponds:
         ms = (C.c_double * len(RIM_PHASES))()
         self.lib.check(self.dll.wdpm_rims_phase_ms(self._h, ms))
         return dict(zip(RIM_PHASES, (float(v) for v in ms)))
+
+    def label_catchments(self, min_depth: float) -> int:
+        """label_rims(min_depth), then the catchment pass on the same water; table(), labels(), stats() and rims() answer as
+        after label_rims()."""
+        n = C.c_int64()
+        self.n = None
+        self.lib.check(self.dll.wdpm_catch_label(self._h, float(min_depth), C.byref(n)))
+        self.n = n.value
+        return n.value
+
+    def catchments(self, capacity: int | None = None) -> np.ndarray:
+        """One row per pond (CATCH_DTYPE) of the last label_catchments(); fails after label() or label_rims().  The box is padded
+        and holds the pond and its catchment; head_level is -inf where no cell drains to the pond."""
+        if self.n is None:
+            raise capi.WdpmError("Ponds.catchments: label_catchments() has not succeeded on this handle")
+        cap = self.n if capacity is None else int(capacity)
+        out = np.zeros(max(cap, 0), dtype=CATCH_DTYPE)
+        self.lib.check(self.dll.wdpm_catch_table(self._h, out.ctypes.data, cap))
+        return out[:self.n]
+
+    def basins(self) -> np.ndarray:
+        """int32, padded like labels(): k > 0 for pond k and the cells that drain to it, 0 for cells that drain to a pit, -1 for
+        cells without a level (border, NODATA)"""
+        out = np.empty(self.shape, dtype=np.int32)
+        self.lib.check(self.dll.wdpm_catch_basins(self._h, out.ctypes.data))
+        return out
+
+    def catchment_stats(self) -> dict:
+        s = CatchStatsStruct()
+        self.lib.check(self.dll.wdpm_catch_stats(self._h, C.byref(s)))
+        return {name: int(getattr(s, name)) for name, _ in CatchStatsStruct._fields_}
+
+    def catchment_phase_ms(self) -> dict:
+        """milliseconds of the receiver pass, the jump rounds and the tally of the last label_catchments() (handles made with
+        WDPM_PONDS_TIMING=1)"""
+        ms = (C.c_double * len(CATCH_PHASES))()
+        self.lib.check(self.dll.wdpm_catch_phase_ms(self._h, ms))
+        return dict(zip(CATCH_PHASES, (float(v) for v in ms)))
 
 
 class GroupPonds:
