@@ -8,136 +8,11 @@
  *   catch_emu ROWS COLS DENSITY SEED [ROWS_PER_WAVE]     (file rows and columns; odd seeds label at 0.001 m, even ones at 0;
  *                                                         seed 0: a serpentine channel into one pond cell, DENSITY unused)
  */
-#include <pthread.h>
-
-#include <algorithm>
-#include <climits>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <queue>
-#include <thread>
-#include <vector>
-
-/* ---- stand-ins for the HIP device language (those of tests/rims_emu_main.cpp, and the relaxed store of a link) ----------- */
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(x)
-#define __restrict__
-#define __shared__ static
-#define __HIP_MEMORY_SCOPE_AGENT 0
-
-struct Dim { unsigned x; };
-static thread_local Dim threadIdx, blockIdx;
-static pthread_barrier_t wave_bar[4], block_bar;
-static unsigned long long slots[4][64];          /* what the lanes of a wave show each other */
-
-static inline int wave_of_thread() { return threadIdx.x >> 6; }
-static inline int lane_of_thread() { return threadIdx.x & 63; }
-static void wave_sync() { pthread_barrier_wait(&wave_bar[wave_of_thread()]); }
-
-static unsigned long long __ballot(bool pred) {
-  unsigned long long *slot = slots[wave_of_thread()];
-  slot[lane_of_thread()] = pred;
-  wave_sync();
-  unsigned long long mask = 0;
-  for (int i = 0; i < 64; i++) mask |= (slot[i] & 1ull) << i;
-  wave_sync();
-  return mask;
-}
-
-/* every lane shows its value, then takes lane src's (its own when src is no lane) */
-template <class T>
-static T exchange(T v, int src) {
-  unsigned long long *slot = slots[wave_of_thread()];
-  unsigned long long raw = 0;
-  memcpy(&raw, &v, sizeof(T));
-  slot[lane_of_thread()] = raw;
-  wave_sync();
-  T out = v;
-  if (src >= 0 && src < 64) memcpy(&out, &slot[src], sizeof(T));
-  wave_sync();
-  return out;
-}
-template <class T> static T __shfl(T v, int src) { return exchange(v, src & 63); }
-template <class T> static T __shfl_up(T v, int d) { return exchange(v, lane_of_thread() - d); }
-template <class T> static T __shfl_down(T v, int d) { return exchange(v, lane_of_thread() + d); }
-template <class T> static T __shfl_xor(T v, int d) { return exchange(v, lane_of_thread() ^ d); }
-
-static inline int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
-static inline long long __double_as_longlong(double d) { long long r; memcpy(&r, &d, 8); return r; }
-static inline double __longlong_as_double(long long d) { double r; memcpy(&r, &d, 8); return r; }
-
-static inline int __clzll(long long v) { return __builtin_clzll((unsigned long long)v); }
-template <class T> static T __hip_atomic_load(const T *p, int, int) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
-template <class T> static void __hip_atomic_store(T *p, T v, int, int) { __atomic_store_n(p, v, __ATOMIC_RELAXED); }
-template <class T> static T atomicAdd(T *p, T v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
-template <class T>
-static T atomicMin(T *p, T v) {
-  T old = __atomic_load_n(p, __ATOMIC_RELAXED);
-  while (v < old && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
-  return old;
-}
-template <class T>
-static T atomicMax(T *p, T v) {
-  T old = __atomic_load_n(p, __ATOMIC_RELAXED);
-  while (v > old && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
-  return old;
-}
-using std::max;
-using std::min;
-
-#define WDPM_PONDS_EMULATION
+#include "hip_emu.h"
 #include "../wdpm_amd/csrc/wdpm_pond_catchments.hip"
-
-/* one launch: 256 threads walk the blocks together */
-template <class F>
-static void launch(unsigned blocks, F kernel) {
-  std::vector<std::thread> threads;
-  for (unsigned t = 0; t < 256; t++)
-    threads.emplace_back([=] {
-      threadIdx.x = t;
-      for (unsigned b = 0; b < blocks; b++) {
-        blockIdx.x = b;
-        kernel();
-        pthread_barrier_wait(&block_bar);
-      }
-    });
-  for (auto &t : threads) t.join();
-}
-static unsigned blocks_for(long long items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
+#include "pond_emu.h"
 
 /* ---- the raster, the reference ------------------------------------------------------------------------------------------- */
-struct Raster {
-  int R, C;                        /* file rows and columns */
-  Geom g;
-  std::vector<double> w, dem;      /* padded; NODATA and the border are +inf in dem */
-  double min_depth;
-  size_t at(int r, int c) const { return (size_t)r * g.ncp + c; }
-  bool inside(int r, int c) const { return r >= 0 && r < g.rows && c >= 0 && c < g.ncp; }
-  bool pond_cell(int r, int c) const {
-    return r >= 1 && r <= R && c >= 1 && c <= C && dem[at(r, c)] < INFINITY && w[at(r, c)] > min_depth;
-  }
-};
-
-static double unit_random() { return rand() / (double)RAND_MAX; }
-
-static Raster blank(int R, int C, int seed) {
-  Raster a;
-  a.R = R;
-  a.C = C;
-  a.g.rows = R + 2;
-  a.g.ncp = C + 2;
-  a.g.nsc = (a.g.ncp + 63) / 64;
-  a.g.nseg = a.g.rows * a.g.nsc;
-  a.min_depth = 0.001 * (seed % 2);
-  a.w.assign((size_t)a.g.rows * a.g.ncp, 0.0);
-  a.dem.assign(a.w.size(), INFINITY);
-  return a;
-}
-
 static Raster make_raster(int R, int C, double density, int seed) {
   Raster a = blank(R, C, seed);
   srand(seed);
@@ -177,36 +52,6 @@ static Raster make_serpentine(int R, int C) {
   a.dem[a.at(r, c)] -= 1.0;                         /* the pond's surface stays below the channel's last cell */
   a.w[a.at(r, c)] = 0.5;
   return a;
-}
-
-static void flood_fill(const Raster &a, std::vector<int> &labels, int &n) {
-  labels.assign(a.w.size(), 0);
-  n = 0;
-  for (int r = 0; r < a.g.rows; r++)
-    for (int c = 0; c < a.g.ncp; c++) {
-      if (!a.pond_cell(r, c) || labels[a.at(r, c)]) continue;
-      const int label = ++n;
-      std::queue<std::pair<int, int>> todo;
-      todo.push({r, c});
-      labels[a.at(r, c)] = label;
-      while (!todo.empty()) {
-        const auto [i, j] = todo.front();
-        todo.pop();
-        for (int di = -1; di <= 1; di++)
-          for (int dj = -1; dj <= 1; dj++)
-            if (a.pond_cell(i + di, j + dj) && !labels[a.at(i + di, j + dj)]) {
-              labels[a.at(i + di, j + dj)] = label;
-              todo.push({i + di, j + dj});
-            }
-      }
-    }
-}
-
-
-static unsigned long long key_of(double v) {
-  unsigned long long b;
-  memcpy(&b, &v, 8);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 
 struct Reference {
@@ -285,14 +130,13 @@ int main(int argc, char **argv) {
   const int seed = atoi(argv[4]);
   const Raster a = seed ? make_raster(atoi(argv[1]), atoi(argv[2]), atof(argv[3]), seed) : make_serpentine(atoi(argv[1]), atoi(argv[2]));
   const int forced_rpw = argc > 5 ? atoi(argv[5]) : 0;
-  for (int i = 0; i < 4; i++) pthread_barrier_init(&wave_bar[i], nullptr, 64);
-  pthread_barrier_init(&block_bar, nullptr, 256);
+  emu_init();
 
   const Geom g = a.g;
   std::vector<int> labels;
   int n = 0;
   flood_fill(a, labels, n);
-  std::vector<unsigned long long> masks((size_t)g.nseg, 0ull);         /* exact sizes: the sanitizer sees a stray index */
+  const std::vector<unsigned long long> masks = wet_masks(g, labels);  /* exact sizes: the sanitizer sees a stray index */
   std::vector<PondRow> ponds((size_t)n);
   for (auto &p : ponds) { p.row_min = p.col_min = INT_MAX; p.row_max = p.col_max = -1; }
   long long pond_cells = 0, levelled = 0;
@@ -302,7 +146,6 @@ int main(int argc, char **argv) {
       const int L = labels[a.at(r, c)];
       if (!L) continue;
       pond_cells++;
-      masks[(size_t)r * g.nsc + c / 64] |= 1ull << (c % 64);
       PondRow &p = ponds[(size_t)L - 1];
       p.row_min = std::min(p.row_min, r); p.row_max = std::max(p.row_max, r);
       p.col_min = std::min(p.col_min, c); p.col_max = std::max(p.col_max, c);
@@ -313,8 +156,8 @@ int main(int argc, char **argv) {
   std::vector<CatchRow> table((size_t)n);
   CatchStatus st;
   memset(&st, 0, sizeof st);
-  const int rpw = ponds_rows_per_wave(g.nseg, g.rows, forced_rpw);
-  const int nwaves = ((g.rows + rpw - 1) / rpw) * g.nsc;
+  const Waves wv = waves_over(g, g.rows, forced_rpw);
+  const int rpw = wv.rpw, nwaves = wv.n;
   if (n) launch(blocks_for(n, kBlock), [&] { catch_init_kernel(table.data(), ponds.data(), n); });
   launch(blocks_for(nwaves, kWaves), [&] {
     catch_receivers_kernel(a.w.data(), a.dem.data(), masks.data(), labels.data(), g, rpw, nwaves, link.data(), table.data(), &st);

@@ -1,6 +1,6 @@
 /* The pond inventory over row blocks on the host (include/wdpm_group_ponds.h), under the sanitizers of
- * tests/test_group_ponds_stitch.py.  Reuses the emulation of tests/ponds_emu_main.cpp - its stand-ins for the HIP device language,
- * its raster and its flood fill - by including that file with its main() renamed.
+ * tests/test_group_ponds_stitch.py, over what tests/ponds_emu_main.cpp runs on: the stand-ins for the HIP device language, the
+ * raster, the flood fill and the launches of a label call (tests/ponds_label_emu.h).
  *
  *   group_ponds_emu stitch                                   the product's stitch (wdpm_amd/csrc/wdpm_ponds_stitch.h) alone: strips of
  *                                                            a raster are labelled by the flood fill, joined by the stitch and held
@@ -9,16 +9,9 @@
  *                                                            the kernels' own source per strip: the seven existing kernels, the seam
  *                                                            kernel, the stitch, the mapping table kernel
  */
-/* tests/ponds_emu_main.cpp is a yardstick and has to compile unchanged, so it is included rather than copied.  The define renames
- * every `main` it meets: keep that file the first include here, before any header of this file could be caught by it (the headers
- * it pulls in itself declare no `main`). */
-#define main ponds_emu_single_raster_main
-#include "ponds_emu_main.cpp"
-#undef main
-
 #include <functional>
-#include <string>
 
+#include "ponds_label_emu.h"
 #include "../wdpm_amd/csrc/wdpm_ponds_stitch.h"
 
 static_assert(sizeof(PondRow) == sizeof(wdpm_pond), "the finished device table is a wdpm_pond table");
@@ -52,7 +45,7 @@ static std::vector<Strip> cut(const Raster &whole, int n) {
 }
 
 static Raster raster_from(int R, int C, const std::function<double(int, int)> &depth) {
-  Raster a = make_raster(R, C, 0.0, 0);
+  Raster a = blank(R, C, 0);
   for (int r = 1; r <= R; r++)
     for (int c = 1; c <= C; c++) {
       a.dem[a.at(r, c)] = 100.0;
@@ -148,54 +141,29 @@ static int stitch_main() {
 }
 
 /* ---- the kernels per strip ----------------------------------------------------------------------------------------------- */
-struct StripRun {
-  std::vector<unsigned long long> masks, rootmask, busum;
-  std::vector<int> parent, labels, cnt, bsum, seam, map;
-  std::vector<unsigned> ucnt;
-  std::vector<PondRow> table;
-  Status st;
-};
-
 static int kernels_main(int argc, char **argv) {
   if (argc < 7) return 2;
   const Raster whole = make_raster(atoi(argv[2]), atoi(argv[3]), atof(argv[5]), atoi(argv[6]));
   const int n = atoi(argv[4]), forced_rpw = argc > 7 ? atoi(argv[7]) : 0;
-  for (int i = 0; i < 4; i++) pthread_barrier_init(&wave_bar[i], nullptr, 64);
-  pthread_barrier_init(&block_bar, nullptr, 256);
+  emu_init();
   const std::vector<Strip> strips = cut(whole, n);
   const int ncp = whole.g.ncp;
-  std::vector<StripRun> run(n);
+  std::vector<LabelRun> run(n);
+  std::vector<std::vector<int>> seam(n);
   std::vector<wdpm_stitch::RankSeams> seams(n);
 
   /* every strip up to its scan and its seam rows: what wdpm_group_ponds_label queues first */
   for (int k = 0; k < n; k++) {
-    const Raster &a = strips[k].a;
-    const Geom g = a.g;
-    StripRun &s = run[k];
-    s.masks.resize(g.nseg);
-    s.rootmask.resize(g.nseg);
-    s.parent.assign(a.w.size(), -7);          /* exact sizes: the sanitizer sees a stray index */
-    s.labels.assign(a.w.size(), -1);
-    s.cnt.resize(g.nseg);
-    s.ucnt.resize(g.nseg);
-    const int nb = (g.nseg + kScanTile - 1) / kScanTile;
-    s.bsum.resize(nb);
-    s.busum.resize(2 * nb);
-    s.seam.assign((size_t)2 * ncp, -1);
-    memset(&s.st, 0, sizeof s.st);
-    const unsigned seg_blocks = blocks_for(g.nseg, kWaves);
-    launch(seg_blocks, [&] { ponds_mask_kernel(a.w.data(), a.dem.data(), g, a.min_depth, s.masks.data(), s.parent.data(), &s.st); });
-    launch(seg_blocks, [&] { ponds_merge_kernel(s.masks.data(), s.parent.data(), g, s.ucnt.data()); });
-    launch(seg_blocks, [&] { ponds_flatten_kernel(s.masks.data(), s.parent.data(), g, s.cnt.data(), s.rootmask.data()); });
-    launch(nb, [&] { ponds_scan_reduce_kernel(s.cnt.data(), s.ucnt.data(), g.nseg, s.bsum.data(), s.busum.data()); });
-    launch(1, [&] { ponds_scan_sums_kernel(s.bsum.data(), s.busum.data(), nb, &s.st); });
-    launch(nb, [&] { ponds_scan_down_kernel(s.cnt.data(), g.nseg, s.bsum.data()); });
+    const Geom g = strips[k].a.g;
+    LabelRun &s = run[k];
+    label_scan(strips[k].a, s);
+    seam[k].assign((size_t)2 * ncp, -1);
     launch(blocks_for(2 * g.nsc, kWaves), [&] {
-      ponds_seam_kernel(s.masks.data(), s.parent.data(), s.cnt.data(), s.rootmask.data(), g, s.seam.data());
+      ponds_seam_kernel(s.masks.data(), s.parent.data(), s.cnt.data(), s.rootmask.data(), g, seam[k].data());
     });
     seams[k].n = s.st.ponds;
-    seams[k].top = s.seam.data();
-    seams[k].bottom = s.seam.data() + ncp;
+    seams[k].top = seam[k].data();
+    seams[k].bottom = seam[k].data() + ncp;
   }
   wdpm_stitch::Result res;
   std::string err;
@@ -205,22 +173,10 @@ static int kernels_main(int argc, char **argv) {
   std::vector<std::vector<int>> labels(n);
   std::vector<std::vector<PondRow>> tables(n);
   for (int k = 0; k < n; k++) {
-    const Raster &a = strips[k].a;
-    const Geom g = a.g;
-    StripRun &s = run[k];
-    const long long np = s.st.ponds;
-    s.table.resize(np);
-    s.map = res.map[k];                       /* exactly n entries */
-    const int rpw = ponds_rows_per_wave(g.nseg, g.rows, forced_rpw);
-    const int nwaves = ((g.rows + rpw - 1) / rpw) * g.nsc;
-    if (np) launch(blocks_for(np, kBlock), [&] { ponds_table_init_kernel(s.table.data(), np); });
-    launch(blocks_for(nwaves, kWaves), [&] {
-      ponds_table_mapped_kernel(a.w.data(), s.masks.data(), s.parent.data(), s.cnt.data(), s.rootmask.data(), g, rpw, nwaves,
-                                s.labels.data(), s.table.data(), s.map.data());
-    });
-    if (np) launch(blocks_for(np, kBlock), [&] { ponds_table_finish_kernel(s.table.data(), np); });
-    labels[k] = s.labels;
-    tables[k] = s.table;
+    const std::vector<int> map = res.map[k];      /* a copy: exactly st.ponds entries */
+    label_table(strips[k].a, run[k], forced_rpw, map.data());
+    labels[k] = run[k].labels;
+    tables[k] = run[k].table;
   }
   return compare(whole, strips, labels, tables, res, false, "kernels") != 0;
 }

@@ -11,133 +11,14 @@
  *   group_rims_emu cases STRIP [ROWS_PER_WAVE]     hand-made ponds on the boundaries of strips of 4: foreign, counted once, ties
  *   group_rims_emu merge                           wdpm_rims_merge::merge alone on hand-written rank tables
  */
-#include <pthread.h>
-
-#include <algorithm>
-#include <climits>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <queue>
-#include <string>
-#include <thread>
-#include <vector>
-
-/* ---- stand-ins for the HIP device language (those of tests/ponds_emu_main.cpp, and __shfl_down) -------------------------- */
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(x)
-#define __restrict__
-#define __shared__ static
-#define __HIP_MEMORY_SCOPE_AGENT 0
-
-struct Dim { unsigned x; };
-static thread_local Dim threadIdx, blockIdx;
-static pthread_barrier_t wave_bar[4], block_bar;
-static unsigned long long slots[4][64];          /* what the lanes of a wave show each other */
-
-static inline int wave_of_thread() { return threadIdx.x >> 6; }
-static inline int lane_of_thread() { return threadIdx.x & 63; }
-static void wave_sync() { pthread_barrier_wait(&wave_bar[wave_of_thread()]); }
-
-static unsigned long long __ballot(bool pred) {
-  unsigned long long *slot = slots[wave_of_thread()];
-  slot[lane_of_thread()] = pred;
-  wave_sync();
-  unsigned long long mask = 0;
-  for (int i = 0; i < 64; i++) mask |= (slot[i] & 1ull) << i;
-  wave_sync();
-  return mask;
-}
-
-/* every lane shows its value, then takes lane src's (its own when src is no lane) */
-template <class T>
-static T exchange(T v, int src) {
-  unsigned long long *slot = slots[wave_of_thread()];
-  unsigned long long raw = 0;
-  memcpy(&raw, &v, sizeof(T));
-  slot[lane_of_thread()] = raw;
-  wave_sync();
-  T out = v;
-  if (src >= 0 && src < 64) memcpy(&out, &slot[src], sizeof(T));
-  wave_sync();
-  return out;
-}
-template <class T> static T __shfl(T v, int src) { return exchange(v, src & 63); }
-template <class T> static T __shfl_up(T v, int d) { return exchange(v, lane_of_thread() - d); }
-template <class T> static T __shfl_down(T v, int d) { return exchange(v, lane_of_thread() + d); }
-template <class T> static T __shfl_xor(T v, int d) { return exchange(v, lane_of_thread() ^ d); }
-
-static inline int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
-static inline long long __double_as_longlong(double d) { long long r; memcpy(&r, &d, 8); return r; }
-static inline double __longlong_as_double(long long d) { double r; memcpy(&r, &d, 8); return r; }
-
-template <class T> static T __hip_atomic_load(const T *p, int, int) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
-template <class T> static T atomicAdd(T *p, T v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
-template <class T>
-static T atomicMin(T *p, T v) {
-  T old = __atomic_load_n(p, __ATOMIC_RELAXED);
-  while (v < old && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
-  return old;
-}
-template <class T>
-static T atomicMax(T *p, T v) {
-  T old = __atomic_load_n(p, __ATOMIC_RELAXED);
-  while (v > old && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
-  return old;
-}
-using std::max;
-using std::min;
-
-#define WDPM_PONDS_EMULATION
+#include "hip_emu.h"
 #include "../wdpm_amd/csrc/wdpm_pond_rims.hip"
 #include "../wdpm_amd/csrc/wdpm_rims_merge.h"
-
-/* one launch: 256 threads walk the blocks together */
-template <class F>
-static void launch(unsigned blocks, F kernel) {
-  std::vector<std::thread> threads;
-  for (unsigned t = 0; t < 256; t++)
-    threads.emplace_back([=] {
-      threadIdx.x = t;
-      for (unsigned b = 0; b < blocks; b++) {
-        blockIdx.x = b;
-        kernel();
-        pthread_barrier_wait(&block_bar);
-      }
-    });
-  for (auto &t : threads) t.join();
-}
-static unsigned blocks_for(long long items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
+#include "pond_emu.h"
 
 /* ---- the raster, the reference ------------------------------------------------------------------------------------------- */
-struct Raster {
-  int R, C;                        /* file rows and columns */
-  Geom g;
-  std::vector<double> w, dem;      /* padded; NODATA and the border are +inf in dem */
-  double min_depth;
-  size_t at(int r, int c) const { return (size_t)r * g.ncp + c; }
-  bool inside(int r, int c) const { return r >= 0 && r < g.rows && c >= 0 && c < g.ncp; }
-  bool pond_cell(int r, int c) const {
-    return r >= 1 && r <= R && c >= 1 && c <= C && dem[at(r, c)] < INFINITY && w[at(r, c)] > min_depth;
-  }
-};
-
-static double unit_random() { return rand() / (double)RAND_MAX; }
-
 static Raster make_raster(int R, int C, double density, int seed) {
-  Raster a;
-  a.R = R;
-  a.C = C;
-  a.g.rows = R + 2;
-  a.g.ncp = C + 2;
-  a.g.nsc = (a.g.ncp + 63) / 64;
-  a.g.nseg = a.g.rows * a.g.nsc;
-  a.min_depth = 0.001 * (seed % 2);
-  a.w.assign((size_t)a.g.rows * a.g.ncp, 0.0);
-  a.dem.assign(a.w.size(), INFINITY);
+  Raster a = blank(R, C, seed);
   srand(seed);
   for (int r = 1; r <= R; r++)
     for (int c = 1; c <= C; c++) {
@@ -152,35 +33,6 @@ static Raster make_raster(int R, int C, double density, int seed) {
       if (rand() % 100 == 0) a.w[i] = NAN;                                      /* never a pond cell, never added */
     }
   return a;
-}
-
-static void flood_fill(const Raster &a, std::vector<int> &labels, int &n) {
-  labels.assign(a.w.size(), 0);
-  n = 0;
-  for (int r = 0; r < a.g.rows; r++)
-    for (int c = 0; c < a.g.ncp; c++) {
-      if (!a.pond_cell(r, c) || labels[a.at(r, c)]) continue;
-      const int label = ++n;
-      std::queue<std::pair<int, int>> todo;
-      todo.push({r, c});
-      labels[a.at(r, c)] = label;
-      while (!todo.empty()) {
-        const auto [i, j] = todo.front();
-        todo.pop();
-        for (int di = -1; di <= 1; di++)
-          for (int dj = -1; dj <= 1; dj++)
-            if (a.pond_cell(i + di, j + dj) && !labels[a.at(i + di, j + dj)]) {
-              labels[a.at(i + di, j + dj)] = label;
-              todo.push({i + di, j + dj});
-            }
-      }
-    }
-}
-
-static unsigned long long key_of(double v) {
-  unsigned long long b;
-  memcpy(&b, &v, 8);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 
 /* every cell, its eight neighbours: the definitions of include/wdpm_pond_rims.h as they are written */
@@ -229,16 +81,7 @@ static std::vector<wdpm_pond_rim> reference(const Raster &a, const std::vector<i
 
 /* ---- the hand-made raster: 14 x 130, padded 16 x 132; with strips of 4 the boundaries lie under rows 3, 7 and 11 ------------- */
 static Raster make_cases() {
-  Raster a;
-  a.R = 14;
-  a.C = 130;
-  a.g.rows = a.R + 2;
-  a.g.ncp = a.C + 2;
-  a.g.nsc = (a.g.ncp + 63) / 64;
-  a.g.nseg = a.g.rows * a.g.nsc;
-  a.min_depth = 0.001;
-  a.w.assign((size_t)a.g.rows * a.g.ncp, 0.0);
-  a.dem.assign(a.w.size(), INFINITY);
+  Raster a = blank(14, 130, 1);      /* labels at 0.001 m */
   for (int r = 1; r <= a.R; r++)
     for (int c = 1; c <= a.C; c++) a.dem[a.at(r, c)] = 200.0 + r * 0.5 + c * 0.01;      /* a ramp: no two dry levels alike */
   auto wet = [&](int r, int c, double d) { a.w[a.at(r, c)] = d; a.dem[a.at(r, c)] = 100.0; };
@@ -304,7 +147,6 @@ static RankOut run_rank(const Raster &a, const std::vector<int> &whole, int nwho
   const int ra = st.lo - v0, rb = ra + (st.hi - st.lo + 1);
   std::vector<double> w((size_t)g.rows * ncp), dem(w.size());
   std::vector<int> labels(w.size());
-  std::vector<unsigned long long> masks((size_t)g.nseg, 0ull);
   for (int r = 0; r < g.rows; r++)
     for (int c = 0; c < ncp; c++) {
       const size_t i = (size_t)r * ncp + c, j = a.at(v0 + r, c);
@@ -312,8 +154,8 @@ static RankOut run_rank(const Raster &a, const std::vector<int> &whole, int nwho
       w[i] = own ? a.w[j] : 1e300;            /* a halo row's water and DEM are not current between exchanges: never read */
       dem[i] = own ? a.dem[j] : -1e300;
       labels[i] = whole[j];
-      if (whole[j]) masks[(size_t)r * g.nsc + c / 64] |= 1ull << (c % 64);
     }
+  const std::vector<unsigned long long> masks = wet_masks(g, labels);
   /* the rank's own numbering: a flood fill of its owned rows alone, first-cell order; map[local - 1] = the whole raster's number */
   std::vector<int> local(w.size(), 0), map;
   for (int r = ra; r < rb; r++)
@@ -361,8 +203,8 @@ static RankOut run_rank(const Raster &a, const std::vector<int> &whole, int nwho
   const int nlocal = (int)map.size(), nforeign = (int)foreign.size();
   std::vector<int> slot_of((size_t)nwhole + 1, 0x7f7f7f7f);
   std::vector<RimRow> table((size_t)slots);
-  const int rpw = ponds_rows_per_wave(g.nseg, g.rows, forced_rpw);
-  const int nwaves = ((rb - ra + rpw - 1) / rpw) * g.nsc;
+  const Waves wv = waves_over(g, rb - ra, forced_rpw);
+  const int rpw = wv.rpw, nwaves = wv.n;
   launch(blocks_for(slots, kBlock), [&] { rims_slots_kernel(map.data(), nlocal, foreign.data(), nforeign, slot_of.data()); });
   launch(blocks_for(slots, kBlock), [&] { rims_init_kernel(table.data(), slots); });
   launch(blocks_for(nwaves, kWaves), [&] {
@@ -458,8 +300,7 @@ static int run_merge_checks() {
 }
 
 int main(int argc, char **argv) {
-  for (int i = 0; i < 4; i++) pthread_barrier_init(&wave_bar[i], nullptr, 64);
-  pthread_barrier_init(&block_bar, nullptr, 256);
+  emu_init();
   if (argc == 2 && !strcmp(argv[1], "merge")) return run_merge_checks();
   if (argc >= 3 && !strcmp(argv[1], "cases")) return run_raster(make_cases(), atoi(argv[2]), argc > 3 ? atoi(argv[3]) : 0, "cases");
   if (argc >= 7 && !strcmp(argv[1], "noise"))

@@ -3,12 +3,9 @@ of rows, gives each strip the labels of its neighbours' rows (and rubbish for th
 (wdpm_amd/csrc/wdpm_pond_rims.hip) per strip as host threads on buffers of exact size, merges the strips' rim rows with
 wdpm_amd/csrc/wdpm_rims_merge.h and holds the table against a plain loop over the whole raster - all under the address and
 undefined-behaviour sanitizers, in a program of its own.  The merge is also called alone on hand-written rank tables."""
-import os
-import subprocess
-
 import pytest
 
-from conftest import ROOT
+import emu_build
 
 # file rows, columns, density, seed, owned rows per strip, rows per wave (0: as the library chooses)
 NOISE = [(20, 70, 0.41, 1, 2, 0),         # strips of two rows: every owned row has a neighbour's row beside it
@@ -22,23 +19,12 @@ NOISE = [(20, 70, 0.41, 1, 2, 0),         # strips of two rows: every owned row 
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("group_rims_emu") / "group_rims_emu")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-pthread", os.path.join(ROOT, "tests", "group_rims_emu_main.cpp"),
-                           "-o", exe])
-    return exe
-
-
-def run(emu, *args):
-    p = subprocess.run([emu] + [str(a) for a in args], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stdout + p.stderr[-3000:]
-    assert "ERROR" not in p.stderr, p.stdout + p.stderr[-3000:]
-    return p.stdout
+    return emu_build.build(tmp_path_factory, "group_rims_emu")
 
 
 @pytest.mark.parametrize("case", NOISE, ids=lambda c: "x".join(map(str, c[:2])) + f"-strips-of-{c[4]}")
 def test_noise_in_strips_on_the_host_under_sanitizers(emu, case):
-    out = run(emu, "noise", *case)
+    out = emu_build.run(emu, "noise", *case)
     assert "rim mismatches 0" in out and " N 0 " not in out, out
     if case[2] < 0.5:                             # many small ponds: some lie beside a strip without entering it
         assert " foreign 0 " not in out, out
@@ -49,7 +35,7 @@ def test_hand_made_ponds_on_the_boundaries(emu, strip, rpw):
     """a foreign pond whose lowest rim cell lies across the boundary (and mirrored upward), a dry cell that touches one pond from
     both sides of a boundary, ties of the rim level across strips with both zeros, walls only, two arms joined in the next strip,
     ponds on the raster's first and last row"""
-    out = run(emu, "cases", strip, rpw)
+    out = emu_build.run(emu, "cases", strip, rpw)
     assert "rim mismatches 0" in out and " N 10 " in out and "without a rim 1 " in out, out
     if strip == 4:
         assert " foreign 3 " in out, out          # the two foreign ponds of the pattern, and the walled cell's ring from above
@@ -57,4 +43,4 @@ def test_hand_made_ponds_on_the_boundaries(emu, strip, rpw):
 
 def test_the_merge_alone_on_hand_written_rank_tables(emu):
     """a tie, signed zeros on either side, no rim anywhere, a foreign row, an empty slot, counts that overflow (a message)"""
-    assert "merge checks ok" in run(emu, "merge")
+    assert "merge checks ok" in emu_build.run(emu, "merge")

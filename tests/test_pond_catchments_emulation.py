@@ -2,12 +2,9 @@
 host threads per block under the address and undefined-behaviour sanitizers - a stand-alone program, nothing is loaded into
 Python - on labels and masks from a flood fill and buffers of exact size, with the links of the jump rounds raced as relaxed host
 atomics, and holds basin raster, table and counts against a plain loop that walks every cell's descent one step at a time."""
-import os
-import subprocess
-
 import pytest
 
-from conftest import ROOT
+import emu_build
 
 # file rows, columns, density, seed, rows per wave (0: as the library chooses, 1000: all rows in one strip); the shapes of
 # tests/test_pond_rims_emulation.py
@@ -25,18 +22,13 @@ SERPENTINE = [(33, 200, 0, 0, rpw) for rpw in (1, 2, 7, 64, 1000)]
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("catch_emu") / "catch_emu")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-pthread", os.path.join(ROOT, "tests", "catch_emu_main.cpp"), "-o", exe])
-    return exe
+    return emu_build.build(tmp_path_factory, "catch_emu")
 
 
 def run(emu, case):
-    p = subprocess.run([emu] + [str(v) for v in case], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stdout + p.stderr[-3000:]
-    assert "basin mismatches 0 table mismatches 0 counts agree identity holds" in p.stdout and "ERROR" not in p.stderr, \
-        p.stdout + p.stderr[-3000:]
-    return p.stdout
+    out = emu_build.run(emu, *case)
+    assert "basin mismatches 0 table mismatches 0 counts agree identity holds" in out, out
+    return out
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "x".join(map(str, c[:2])))

@@ -2,12 +2,9 @@
 per block under the address and undefined-behaviour sanitizers, on labels and masks from a flood fill and buffers of exact size, and
 holds the rim table against a plain loop over every cell's eight neighbours.  The halo reads - the rows above and below a wave's
 strip, the cells beside a segment, column 0 and ncp - 1, row 0 and rows - 1 - are checked here, where a stray index harms nobody."""
-import os
-import subprocess
-
 import pytest
 
-from conftest import ROOT
+import emu_build
 
 # file rows, columns, density, seed, rows per wave (0: as the library chooses, 1000: all rows in one strip)
 CASES = [(20, 70, 0.40, 1, 0),        # two segments, the second nearly empty; threshold 0.001 with 0.0005 m on rim cells
@@ -22,15 +19,11 @@ CASES = [(20, 70, 0.40, 1, 0),        # two segments, the second nearly empty; t
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("rims_emu") / "rims_emu")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-pthread", os.path.join(ROOT, "tests", "rims_emu_main.cpp"), "-o", exe])
-    return exe
+    return emu_build.build(tmp_path_factory, "rims_emu")
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "x".join(map(str, c[:2])))
 def test_kernels_on_the_host_under_sanitizers(emu, case):
-    p = subprocess.run([emu] + [str(v) for v in case], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stdout + p.stderr[-3000:]
-    assert "rim mismatches 0" in p.stdout and "ERROR" not in p.stderr, p.stdout + p.stderr[-3000:]
-    assert " N 0 " not in p.stdout, p.stdout
+    out = emu_build.run(emu, *case)
+    assert "rim mismatches 0" in out, out
+    assert " N 0 " not in out, out

@@ -1,12 +1,9 @@
 """The pond kernels' own source (wdpm_amd/csrc/wdpm_ponds.hip) on the CPU: tests/ponds_emu_main.cpp runs every kernel as 256 host
 threads per block under the address and undefined-behaviour sanitizers and holds labels and table against a flood fill.  What the
 GPU tests cannot say - that no lane reads or writes outside a buffer - is said here, where a stray index harms nobody."""
-import os
-import subprocess
-
 import pytest
 
-from conftest import ROOT
+import emu_build
 
 # file rows, columns, density, seed, rows per wave of the table kernel (0: as the library chooses)
 CASES = [(20, 70, 0.40, 1, 0),        # two segments, the second nearly empty
@@ -20,14 +17,10 @@ CASES = [(20, 70, 0.40, 1, 0),        # two segments, the second nearly empty
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("ponds_emu") / "ponds_emu")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-pthread", os.path.join(ROOT, "tests", "ponds_emu_main.cpp"), "-o", exe])
-    return exe
+    return emu_build.build(tmp_path_factory, "ponds_emu")
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "x".join(map(str, c[:2])))
 def test_kernels_on_the_host_under_sanitizers(emu, case):
-    p = subprocess.run([emu] + [str(v) for v in case], capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stdout + p.stderr[-3000:]
-    assert "label mismatches 0  table mismatches 0" in p.stdout and "ERROR" not in p.stderr, p.stdout + p.stderr[-3000:]
+    out = emu_build.run(emu, *case)
+    assert "label mismatches 0  table mismatches 0" in out, out

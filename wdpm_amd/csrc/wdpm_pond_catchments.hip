@@ -92,32 +92,6 @@ __device__ __forceinline__ void catch_fill(CatchWin &x, const double *__restrict
   x.ek = level_key(ee, de);
 }
 
-__device__ __forceinline__ unsigned long long key_from_left(unsigned long long v, unsigned long long edge, int lane) {
-  const unsigned long long t = __shfl_up(v, 1);
-  return lane > 0 ? t : edge;
-}
-__device__ __forceinline__ unsigned long long key_from_right(unsigned long long v, unsigned long long edge, int lane) {
-  const unsigned long long t = __shfl_down(v, 1);
-  return lane < 63 ? t : edge;
-}
-__device__ __forceinline__ int lbl_from_left(int v, int edge, int lane) {
-  const int t = __shfl_up(v, 1);
-  return lane > 0 ? t : edge;
-}
-__device__ __forceinline__ int lbl_from_right(int v, int edge, int lane) {
-  const int t = __shfl_down(v, 1);
-  return lane < 63 ? t : edge;
-}
-
-__device__ __forceinline__ unsigned long long catch_wave_max(unsigned long long v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const unsigned long long t = __shfl_xor(v, d);
-    v = t > v ? t : v;
-  }
-  return v;
-}
-
 /* ---- receivers ------------------------------------------------------------------------------------------------------------- */
 /* Everything that steers the loops is wave-uniform. */
 __global__ __launch_bounds__(kBlock) void catch_receivers_kernel(const double *__restrict__ w, const double *__restrict__ dem,
@@ -148,12 +122,12 @@ __global__ __launch_bounds__(kBlock) void catch_receivers_kernel(const double *_
     catch_fill(cur, w, dem, labels, g, r, c, lane);
     catch_fill(dn, w, dem, labels, g, r + 1, c, lane);
     /* the eight neighbours in the order of their padded index */
-    const unsigned long long nk[8] = {key_from_left(up.key, up.ek, lane),   up.key, key_from_right(up.key, up.ek, lane),
-                                      key_from_left(cur.key, cur.ek, lane),         key_from_right(cur.key, cur.ek, lane),
-                                      key_from_left(dn.key, dn.ek, lane),   dn.key, key_from_right(dn.key, dn.ek, lane)};
-    const int nl[8] = {lbl_from_left(up.lbl, up.el, lane),   up.lbl, lbl_from_right(up.lbl, up.el, lane),
-                       lbl_from_left(cur.lbl, cur.el, lane),         lbl_from_right(cur.lbl, cur.el, lane),
-                       lbl_from_left(dn.lbl, dn.el, lane),   dn.lbl, lbl_from_right(dn.lbl, dn.el, lane)};
+    const unsigned long long nk[8] = {lane_from_left(up.key, up.ek, lane),   up.key, lane_from_right(up.key, up.ek, lane),
+                                      lane_from_left(cur.key, cur.ek, lane),         lane_from_right(cur.key, cur.ek, lane),
+                                      lane_from_left(dn.key, dn.ek, lane),   dn.key, lane_from_right(dn.key, dn.ek, lane)};
+    const int nl[8] = {lane_from_left(up.lbl, up.el, lane),   up.lbl, lane_from_right(up.lbl, up.el, lane),
+                       lane_from_left(cur.lbl, cur.el, lane),         lane_from_right(cur.lbl, cur.el, lane),
+                       lane_from_left(dn.lbl, dn.el, lane),   dn.lbl, lane_from_right(dn.lbl, dn.el, lane)};
     const bool slope = inside && !wet && cur.key != kNoLevel;
     unsigned long long best = cur.key;     /* strictly below the cell's own, the first of equals */
     int to = 0, to_label = 0;
@@ -242,15 +216,15 @@ struct CatchCarry {
   int row_min, row_max, col_min, col_max;
 };
 
-/* one lane sends a carry.  The extrema only move one way, so a look first spares the atomic that would change nothing. */
+/* one lane sends a carry: the extrema through atomic_min_if / atomic_max_if */
 __device__ __forceinline__ void catch_send(CatchRow *table, const CatchCarry &c) {
   CatchRow *t = table + (c.label - 1);
   atomicAdd(&t->catch_cells, c.cells);
-  if (__hip_atomic_load(&t->head_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < c.key) atomicMax(&t->head_key, c.key);
-  if (__hip_atomic_load(&t->row_min, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > c.row_min) atomicMin(&t->row_min, c.row_min);
-  if (__hip_atomic_load(&t->row_max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < c.row_max) atomicMax(&t->row_max, c.row_max);
-  if (__hip_atomic_load(&t->col_min, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > c.col_min) atomicMin(&t->col_min, c.col_min);
-  if (__hip_atomic_load(&t->col_max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < c.col_max) atomicMax(&t->col_max, c.col_max);
+  atomic_max_if(&t->head_key, c.key);
+  atomic_min_if(&t->row_min, c.row_min);
+  atomic_max_if(&t->row_max, c.row_max);
+  atomic_min_if(&t->col_min, c.col_min);
+  atomic_max_if(&t->col_max, c.col_max);
 }
 
 __global__ __launch_bounds__(kBlock) void catch_tally_kernel(const double *__restrict__ w, const double *__restrict__ dem,
@@ -285,7 +259,7 @@ __global__ __launch_bounds__(kBlock) void catch_tally_kernel(const double *__res
       if (pending == 0ull) break;
       const int L = __shfl(cand, __builtin_ctzll(pending));
       const unsigned long long hitm = __ballot(cand == L);
-      const unsigned long long hi = catch_wave_max(cand == L ? key : 0ull);
+      const unsigned long long hi = wave_max(cand == L ? key : 0ull);
       const int cmin = s * kSeg + __builtin_ctzll(hitm), cmax = s * kSeg + 63 - __clzll((long long)hitm);
       if (cy.label != L) {                  /* down the rows: the same label goes on gathering, another one sends first */
         if (cy.label != 0 && lane == 0) catch_send(table, cy);
@@ -311,7 +285,6 @@ __global__ __launch_bounds__(kBlock) void catch_tally_kernel(const double *__res
 #ifndef WDPM_PONDS_EMULATION
 /* ---- host ------------------------------------------------------------------------------------------------------------------ */
 namespace {
-inline unsigned blocks_for(long long items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
 const char kNoTable[] = "no catchment table: the last label call on this handle was not a wdpm_catch_label that succeeded";
 }  // namespace
 

@@ -77,32 +77,6 @@ __device__ __forceinline__ void win_edges(RimWin &w, const int *__restrict__ lab
   w.has_edges = true;
 }
 
-__device__ __forceinline__ int from_left(int v, int edge, int lane) {
-  const int t = __shfl_up(v, 1);
-  return lane > 0 ? t : edge;
-}
-__device__ __forceinline__ int from_right(int v, int edge, int lane) {
-  const int t = __shfl_down(v, 1);
-  return lane < 63 ? t : edge;
-}
-
-__device__ __forceinline__ unsigned long long wave_min(unsigned long long v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const unsigned long long t = __shfl_xor(v, d);
-    v = t < v ? t : v;
-  }
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const unsigned long long t = __shfl_xor(v, d);
-    v = t > v ? t : v;
-  }
-  return v;
-}
-
 /* what a wave has gathered for one label and not yet sent */
 struct RimCarry {
   int label;               /* 0: nothing held */
@@ -123,14 +97,13 @@ __device__ __forceinline__ int rim_slot(const int *__restrict__ slot_of, int L) 
   return kSlots ? slot_of[L] : L - 1;
 }
 
-/* one lane sends a carry.  The extrema only move one way, so a look first spares the atomic that would change nothing; what a
- * carry never gathered still holds its start value and passes no look. */
+/* one lane sends a carry: the extrema through atomic_min_if / atomic_max_if */
 template <bool kSlots>
 __device__ __forceinline__ void rim_send(RimRow *table, const int *__restrict__ slot_of, const RimCarry &c) {
   RimRow *t = table + rim_slot<kSlots>(slot_of, c.label);
-  if (__hip_atomic_load(&t->smin_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > c.smin) atomicMin(&t->smin_key, c.smin);
-  if (__hip_atomic_load(&t->smax_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < c.smax) atomicMax(&t->smax_key, c.smax);
-  if (__hip_atomic_load(&t->rim_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > c.rmin) atomicMin(&t->rim_key, c.rmin);
+  atomic_min_if(&t->smin_key, c.smin);
+  atomic_max_if(&t->smax_key, c.smax);
+  atomic_min_if(&t->rim_key, c.rmin);
   if (c.rim_cells) atomicAdd(&t->rim_cells, c.rim_cells);
   if (c.wall_cells) atomicAdd(&t->wall_cells, c.wall_cells);
 }
@@ -170,9 +143,9 @@ __device__ __forceinline__ void rims_body(const double *__restrict__ w, const do
       win_edges(up, labels, g, r - 1, s);
       win_edges(cur, labels, g, r, s);
       win_edges(dn, labels, g, r + 1, s);
-      const int around[8] = {from_left(up.lbl, up.el, lane),  up.lbl,  from_right(up.lbl, up.er, lane),
-                             from_left(cur.lbl, cur.el, lane),         from_right(cur.lbl, cur.er, lane),
-                             from_left(dn.lbl, dn.el, lane),  dn.lbl,  from_right(dn.lbl, dn.er, lane)};
+      const int around[8] = {lane_from_left(up.lbl, up.el, lane),  up.lbl,  lane_from_right(up.lbl, up.er, lane),
+                             lane_from_left(cur.lbl, cur.el, lane),         lane_from_right(cur.lbl, cur.er, lane),
+                             lane_from_left(dn.lbl, dn.el, lane),  dn.lbl,  lane_from_right(dn.lbl, dn.er, lane)};
       if (nb) {
 #pragma unroll
         for (int i = 0; i < 8; i++) {
@@ -314,10 +287,6 @@ __global__ __launch_bounds__(kBlock) void rims_finish_kernel(RimRow *t, long lon
 
 #ifndef WDPM_PONDS_EMULATION
 /* ---- host ------------------------------------------------------------------------------------------------------------------ */
-namespace {
-inline unsigned blocks_for(long long items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
-}  // namespace
-
 extern "C" int wdpm_rims_label(wdpm_ponds *h, double min_depth, int64_t *nponds) {
   if (!h) return wdpm_fail("wdpm_rims_label: null handle");
   if (!(min_depth >= 0.0) || std::isinf(min_depth)) return wdpm_fail("wdpm_rims_label: min_depth must be finite and >= 0 (got %g)", min_depth);

@@ -19,9 +19,9 @@
  *            carried down the rows a wave owns, before one set of atomics per (wave, label change) goes to the table
  */
 /* tests/ponds_emu_main.cpp compiles the kernels below for the host (256 threads per block in lockstep at the cross-lane operations,
- * address and undefined-behaviour sanitizers on) with WDPM_PONDS_EMULATION defined: it brings its own stand-ins for the HIP
+ * address and undefined-behaviour sanitizers on) with WDPM_PONDS_EMULATION defined: tests/hip_emu.h brings the stand-ins for the HIP
  * device language and leaves the host half of this file out.  What this unit shares with wdpm_pond_rims.hip (geometry, depth keys,
- * the handle) lives in wdpm_ponds_priv.h. */
+ * wave helpers, the handle) lives in wdpm_ponds_priv.h. */
 #include "wdpm_ponds_priv.h"
 #ifndef WDPM_PONDS_EMULATION
 #include <ctime>
@@ -291,18 +291,12 @@ struct Carry {
   int row_min, row_max, col_min, col_max;
 };
 
-__device__ __forceinline__ void atomic_min_if(int *p, int v) {
-  if (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > v) atomicMin(p, v);
-}
-__device__ __forceinline__ void atomic_max_if(int *p, int v) {
-  if (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < v) atomicMax(p, v);
-}
-/* one lane sends a carry.  The extrema only move one way, so a look first spares the atomic that would change nothing. */
+/* one lane sends a carry: the extrema through atomic_min_if / atomic_max_if */
 __device__ __forceinline__ void send(PondRow *table, const Carry &c) {
   PondRow *t = table + (c.label - 1);
   atomicAdd(&t->cells, c.cells);
   atomicAdd(&t->volume_q, c.vol);
-  if (__hip_atomic_load(&t->depth_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < c.key) atomicMax(&t->depth_key, c.key);
+  atomic_max_if(&t->depth_key, c.key);
   atomic_min_if(&t->row_min, c.row_min);
   atomic_max_if(&t->row_max, c.row_max);
   atomic_min_if(&t->col_min, c.col_min);
@@ -549,7 +543,6 @@ int allocate(wdpm_ponds *h) {
   return 0;
 }
 
-inline unsigned blocks_for(long long items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
 
 /* a handle on rows [row_off, row_off + rows) of ctx; reads the environment as include/wdpm_ponds.h says */
 wdpm_ponds *make_handle(wdpm_ctx *ctx, int row_off, int rows, bool seams) {

@@ -1,8 +1,9 @@
 /*
  * wdpm_ponds_priv.h — what the units of the pond inventory share: wdpm_ponds.hip (labels and table), wdpm_pond_rims.hip
- * (rims) and wdpm_pond_catchments.hip (catchments).  Geometry, the order-preserving image of a double, the table row as the device accumulates it, and - outside the host
- * emulations of the tests, which define WDPM_PONDS_EMULATION and bring stand-ins for the HIP device language - the handle itself
- * with its guarded allocator.  Private: nothing here is exported, and no header under include/ knows it.
+ * (rims) and wdpm_pond_catchments.hip (catchments).  Geometry, the order-preserving image of a double, the table rows as the device
+ * accumulates them, the wave helpers of the kernels (a lane's neighbour, the wave's extremum, the look before an atomic) and -
+ * outside the host emulations of the tests, which define WDPM_PONDS_EMULATION and bring stand-ins for the HIP device language
+ * (tests/hip_emu.h) - the handle itself with its guarded allocator.  Private: nothing here is exported, and no header under include/ knows it.
  */
 #ifndef WDPM_PONDS_PRIV_H
 #define WDPM_PONDS_PRIV_H
@@ -107,8 +108,51 @@ __device__ __forceinline__ double depth_from_key(unsigned long long k) {
 }
 __device__ __forceinline__ int bit(unsigned long long m, int pos) { return (int)((m >> pos) & 1ull); }
 
+/* the value of the lane to the left (right); lane 0 (63) takes `edge`, the cell beside the segment */
+template <class T>
+__device__ __forceinline__ T lane_from_left(T v, T edge, int lane) {
+  const T t = __shfl_up(v, 1);
+  return lane > 0 ? t : edge;
+}
+template <class T>
+__device__ __forceinline__ T lane_from_right(T v, T edge, int lane) {
+  const T t = __shfl_down(v, 1);
+  return lane < 63 ? t : edge;
+}
+
+/* butterflies: every lane ends with the wave's extremum */
+__device__ __forceinline__ unsigned long long wave_min(unsigned long long v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const unsigned long long t = __shfl_xor(v, d);
+    v = t < v ? t : v;
+  }
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const unsigned long long t = __shfl_xor(v, d);
+    v = t > v ? t : v;
+  }
+  return v;
+}
+
+/* A table's extrema only move one way, so a look first spares the atomic that would change nothing; what a carry never gathered
+ * still holds its start value and passes no look. */
+template <class T>
+__device__ __forceinline__ void atomic_min_if(T *p, T v) {
+  if (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > v) atomicMin(p, v);
+}
+template <class T>
+__device__ __forceinline__ void atomic_max_if(T *p, T v) {
+  if (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < v) atomicMax(p, v);
+}
+
 #ifndef WDPM_PONDS_EMULATION
 struct Guarded { char *base; size_t bytes; };
+/* blocks of a launch with per_block items each (the host emulations bring their own with their launch) */
+inline unsigned blocks_for(long long items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
 #endif
 
 }  // namespace wdpm_pond_detail

@@ -160,27 +160,30 @@ def bind(lib: capi.Lib):
     return lib.dll
 
 
-class Ponds:
-    """The inventory handle of one whole-raster context — wraps wdpm_ponds.  The C handle must go before its context: the
-    object keeps its Context alive, and a Context that is closed first closes the handles that live on it."""
+_LABELLED_BY = {"table": "label", "rims": "label_rims", "catchments": "label_catchments"}   # the call a table method reads
 
-    def __init__(self, ctx: capi.Context):
-        self.ctx = ctx
-        self.lib = ctx.lib
-        self.dll = bind(ctx.lib)
-        self.shape = ctx.shape
+
+class _Handle:
+    """What Ponds and GroupPonds share: a C handle made on an owner (a Context, a Group) and destroyed before it, and the four
+    shapes of call the headers repeat."""
+
+    def __init__(self, owner, create: str, destroy: str):
+        self.lib = owner.lib
+        self.dll = bind(owner.lib)
+        self.shape = owner.shape
         self.n = None
         self._h = None
+        self._destroy = destroy
         h = C.c_void_p()
-        self.lib.check(self.dll.wdpm_ponds_create(C.byref(h), ctx._h))
+        self.lib.check(getattr(self.dll, create)(C.byref(h), owner._h))
         self._h = h
-        deps = getattr(ctx, "_dependents", None)
+        deps = getattr(owner, "_dependents", None)
         if deps is not None:
             deps.append(weakref.ref(self))
 
     def close(self):
         if self._h:
-            self.dll.wdpm_ponds_destroy(self._h)
+            getattr(self.dll, self._destroy)(self._h)
             self._h = None
 
     def __enter__(self):
@@ -195,22 +198,47 @@ class Ponds:
         except Exception:
             pass
 
-    def label(self, min_depth: float) -> int:
-        """Label the ponds deeper than min_depth (metres, strict) on the context's current water; returns their number."""
+    def _label(self, fn, min_depth) -> int:
         n = C.c_int64()
         self.n = None
-        self.lib.check(self.dll.wdpm_ponds_label(self._h, float(min_depth), C.byref(n)))
+        self.lib.check(fn(self._h, float(min_depth), C.byref(n)))
         self.n = n.value
         return n.value
 
+    def _table(self, fn, dtype, method, capacity) -> np.ndarray:
+        if self.n is None:
+            raise capi.WdpmError(f"{type(self).__name__}.{method}: {_LABELLED_BY[method]}() has not succeeded on this handle")
+        cap = self.n if capacity is None else int(capacity)
+        out = np.zeros(max(cap, 0), dtype=dtype)
+        self.lib.check(fn(self._h, out.ctypes.data, cap))
+        return out[:self.n]
+
+    def _stats(self, fn, struct, *lead) -> dict:
+        s = struct()
+        self.lib.check(fn(self._h, *lead, C.byref(s)))
+        return {name: (float if ctype is C.c_double else int)(getattr(s, name)) for name, ctype in struct._fields_}
+
+    def _phase_ms(self, fn, names, *lead) -> dict:
+        ms = (C.c_double * len(names))()
+        self.lib.check(fn(self._h, *lead, ms))
+        return dict(zip(names, (float(v) for v in ms)))
+
+
+class Ponds(_Handle):
+    """The inventory handle of one whole-raster context — wraps wdpm_ponds.  The C handle must go before its context: the
+    object keeps its Context alive, and a Context that is closed first closes the handles that live on it."""
+
+    def __init__(self, ctx: capi.Context):
+        self.ctx = ctx
+        super().__init__(ctx, "wdpm_ponds_create", "wdpm_ponds_destroy")
+
+    def label(self, min_depth: float) -> int:
+        """Label the ponds deeper than min_depth (metres, strict) on the context's current water; returns their number."""
+        return self._label(self.dll.wdpm_ponds_label, min_depth)
+
     def table(self, capacity: int | None = None) -> np.ndarray:
         """One row per pond (POND_DTYPE).  `capacity` is what the C call is told the buffer holds (default: exactly N)."""
-        if self.n is None:
-            raise capi.WdpmError("Ponds.table: label() has not succeeded on this handle")
-        cap = self.n if capacity is None else int(capacity)
-        out = np.zeros(max(cap, 0), dtype=POND_DTYPE)
-        self.lib.check(self.dll.wdpm_ponds_table(self._h, out.ctypes.data, cap))
-        return out[:self.n]
+        return self._table(self.dll.wdpm_ponds_table, POND_DTYPE, "table", capacity)
 
     def labels(self) -> np.ndarray:
         out = np.empty(self.shape, dtype=np.int32)
@@ -218,15 +246,11 @@ class Ponds:
         return out
 
     def stats(self) -> dict:
-        s = StatsStruct()
-        self.lib.check(self.dll.wdpm_ponds_stats(self._h, C.byref(s)))
-        return {name: int(getattr(s, name)) for name, _ in StatsStruct._fields_}
+        return self._stats(self.dll.wdpm_ponds_stats, StatsStruct)
 
     def phase_ms(self) -> dict:
         """milliseconds per kernel phase of the last label call (handles made with WDPM_PONDS_TIMING=1 in the environment)"""
-        ms = (C.c_double * len(PHASES))()
-        self.lib.check(self.dll.wdpm_ponds_phase_ms(self._h, ms))
-        return dict(zip(PHASES, (float(v) for v in ms)))
+        return self._phase_ms(self.dll.wdpm_ponds_phase_ms, PHASES)
 
     def guard_bad(self) -> int:
         v = C.c_int64()
@@ -235,46 +259,26 @@ class Ponds:
 
     def label_rims(self, min_depth: float) -> int:
         """label(min_depth), then the rim pass on the same water; table(), labels() and stats() answer as after label()."""
-        n = C.c_int64()
-        self.n = None
-        self.lib.check(self.dll.wdpm_rims_label(self._h, float(min_depth), C.byref(n)))
-        self.n = n.value
-        return n.value
+        return self._label(self.dll.wdpm_rims_label, min_depth)
 
     def rims(self, capacity: int | None = None) -> np.ndarray:
         """One row per pond (RIM_DTYPE) of the last label_rims(); fails after a plain label().  Coordinates are padded, -1 where a
         pond has no rim cell; freeboard is rim_level - surface_max."""
-        if self.n is None:
-            raise capi.WdpmError("Ponds.rims: label_rims() has not succeeded on this handle")
-        cap = self.n if capacity is None else int(capacity)
-        out = np.zeros(max(cap, 0), dtype=RIM_DTYPE)
-        self.lib.check(self.dll.wdpm_rims_table(self._h, out.ctypes.data, cap))
-        return out[:self.n]
+        return self._table(self.dll.wdpm_rims_table, RIM_DTYPE, "rims", capacity)
 
     def rims_phase_ms(self) -> dict:
         """milliseconds of the rim pass and of the locate pass of the last label_rims() (handles made with WDPM_PONDS_TIMING=1)"""
-        ms = (C.c_double * len(RIM_PHASES))()
-        self.lib.check(self.dll.wdpm_rims_phase_ms(self._h, ms))
-        return dict(zip(RIM_PHASES, (float(v) for v in ms)))
+        return self._phase_ms(self.dll.wdpm_rims_phase_ms, RIM_PHASES)
 
     def label_catchments(self, min_depth: float) -> int:
         """label_rims(min_depth), then the catchment pass on the same water; table(), labels(), stats() and rims() answer as
         after label_rims()."""
-        n = C.c_int64()
-        self.n = None
-        self.lib.check(self.dll.wdpm_catch_label(self._h, float(min_depth), C.byref(n)))
-        self.n = n.value
-        return n.value
+        return self._label(self.dll.wdpm_catch_label, min_depth)
 
     def catchments(self, capacity: int | None = None) -> np.ndarray:
         """One row per pond (CATCH_DTYPE) of the last label_catchments(); fails after label() or label_rims().  The box is padded
         and holds the pond and its catchment; head_level is -inf where no cell drains to the pond."""
-        if self.n is None:
-            raise capi.WdpmError("Ponds.catchments: label_catchments() has not succeeded on this handle")
-        cap = self.n if capacity is None else int(capacity)
-        out = np.zeros(max(cap, 0), dtype=CATCH_DTYPE)
-        self.lib.check(self.dll.wdpm_catch_table(self._h, out.ctypes.data, cap))
-        return out[:self.n]
+        return self._table(self.dll.wdpm_catch_table, CATCH_DTYPE, "catchments", capacity)
 
     def basins(self) -> np.ndarray:
         """int32, padded like labels(): k > 0 for pond k and the cells that drain to it, 0 for cells that drain to a pit, -1 for
@@ -284,71 +288,31 @@ class Ponds:
         return out
 
     def catchment_stats(self) -> dict:
-        s = CatchStatsStruct()
-        self.lib.check(self.dll.wdpm_catch_stats(self._h, C.byref(s)))
-        return {name: int(getattr(s, name)) for name, _ in CatchStatsStruct._fields_}
+        return self._stats(self.dll.wdpm_catch_stats, CatchStatsStruct)
 
     def catchment_phase_ms(self) -> dict:
         """milliseconds of the receiver pass, the jump rounds and the tally of the last label_catchments() (handles made with
         WDPM_PONDS_TIMING=1)"""
-        ms = (C.c_double * len(CATCH_PHASES))()
-        self.lib.check(self.dll.wdpm_catch_phase_ms(self._h, ms))
-        return dict(zip(CATCH_PHASES, (float(v) for v in ms)))
+        return self._phase_ms(self.dll.wdpm_catch_phase_ms, CATCH_PHASES)
 
 
-class GroupPonds:
+class GroupPonds(_Handle):
     """The inventory handle of a rowblock.Group - wraps wdpm_group_ponds.  Labels the water Group.download_water returns, every
     rank's rows where they lie, and answers as Ponds does on a whole-raster context holding the same water.  The C handle must
     go before its group: the object keeps its Group alive, and a Group that is closed first closes the handles that live on it."""
 
     def __init__(self, group):
         self.group = group
-        self.lib = group.lib
-        self.dll = bind(group.lib)
-        self.shape = group.shape
-        self.n = None
-        self._h = None
-        h = C.c_void_p()
-        self.lib.check(self.dll.wdpm_group_ponds_create(C.byref(h), group._h))
-        self._h = h
+        super().__init__(group, "wdpm_group_ponds_create", "wdpm_group_ponds_destroy")
         self.ranks = group.size
-        deps = getattr(group, "_dependents", None)
-        if deps is not None:
-            deps.append(weakref.ref(self))
-
-    def close(self):
-        if self._h:
-            self.dll.wdpm_group_ponds_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def label(self, min_depth: float) -> int:
         """Label the ponds deeper than min_depth (metres, strict) on the group's current water; returns their number."""
-        n = C.c_int64()
-        self.n = None
-        self.lib.check(self.dll.wdpm_group_ponds_label(self._h, float(min_depth), C.byref(n)))
-        self.n = n.value
-        return n.value
+        return self._label(self.dll.wdpm_group_ponds_label, min_depth)
 
     def table(self, capacity: int | None = None) -> np.ndarray:
         """One row per pond (POND_DTYPE), coordinates of the whole raster."""
-        if self.n is None:
-            raise capi.WdpmError("GroupPonds.table: label() has not succeeded on this handle")
-        cap = self.n if capacity is None else int(capacity)
-        out = np.zeros(max(cap, 0), dtype=POND_DTYPE)
-        self.lib.check(self.dll.wdpm_group_ponds_table(self._h, out.ctypes.data, cap))
-        return out[:self.n]
+        return self._table(self.dll.wdpm_group_ponds_table, POND_DTYPE, "table", capacity)
 
     def labels(self) -> np.ndarray:
         out = np.empty(self.shape, dtype=np.int32)
@@ -356,21 +320,15 @@ class GroupPonds:
         return out
 
     def stats(self) -> dict:
-        s = GroupStatsStruct()
-        self.lib.check(self.dll.wdpm_group_ponds_stats(self._h, C.byref(s)))
-        return {name: (float if name == "stitch_ms" else int)(getattr(s, name)) for name, _ in GroupStatsStruct._fields_}
+        return self._stats(self.dll.wdpm_group_ponds_stats, GroupStatsStruct)
 
     def rank_stats(self, rank: int) -> dict:
         """what Ponds.stats says, of one rank's own labelling"""
-        s = StatsStruct()
-        self.lib.check(self.dll.wdpm_group_ponds_rank_stats(self._h, int(rank), C.byref(s)))
-        return {name: int(getattr(s, name)) for name, _ in StatsStruct._fields_}
+        return self._stats(self.dll.wdpm_group_ponds_rank_stats, StatsStruct, int(rank))
 
     def phase_ms(self, rank: int) -> dict:
         """milliseconds per kernel phase of one rank in the last label call (handles made with WDPM_PONDS_TIMING=1)"""
-        ms = (C.c_double * len(PHASES))()
-        self.lib.check(self.dll.wdpm_group_ponds_phase_ms(self._h, int(rank), ms))
-        return dict(zip(PHASES, (float(v) for v in ms)))
+        return self._phase_ms(self.dll.wdpm_group_ponds_phase_ms, PHASES, int(rank))
 
     def guard_bad(self) -> int:
         v = C.c_int64()
@@ -380,28 +338,15 @@ class GroupPonds:
     def label_rims(self, min_depth: float) -> int:
         """label(min_depth), and every rank's rim pass on the same water; table(), labels(), stats() and rank_stats() answer as
         after label()."""
-        n = C.c_int64()
-        self.n = None
-        self.lib.check(self.dll.wdpm_group_rims_label(self._h, float(min_depth), C.byref(n)))
-        self.n = n.value
-        return n.value
+        return self._label(self.dll.wdpm_group_rims_label, min_depth)
 
     def rims(self, capacity: int | None = None) -> np.ndarray:
         """One row per pond (RIM_DTYPE) of the last label_rims(), coordinates of the whole raster; fails after a plain label()."""
-        if self.n is None:
-            raise capi.WdpmError("GroupPonds.rims: label_rims() has not succeeded on this handle")
-        cap = self.n if capacity is None else int(capacity)
-        out = np.zeros(max(cap, 0), dtype=RIM_DTYPE)
-        self.lib.check(self.dll.wdpm_group_rims_table(self._h, out.ctypes.data, cap))
-        return out[:self.n]
+        return self._table(self.dll.wdpm_group_rims_table, RIM_DTYPE, "rims", capacity)
 
     def rims_stats(self) -> dict:
-        s = GroupRimStatsStruct()
-        self.lib.check(self.dll.wdpm_group_rims_stats(self._h, C.byref(s)))
-        return {name: (float if name == "merge_ms" else int)(getattr(s, name)) for name, _ in GroupRimStatsStruct._fields_}
+        return self._stats(self.dll.wdpm_group_rims_stats, GroupRimStatsStruct)
 
     def rims_phase_ms(self, rank: int) -> dict:
         """milliseconds of one rank's rim pass and locate pass in the last label_rims() (handles made with WDPM_PONDS_TIMING=1)"""
-        ms = (C.c_double * len(RIM_PHASES))()
-        self.lib.check(self.dll.wdpm_group_rims_phase_ms(self._h, int(rank), ms))
-        return dict(zip(RIM_PHASES, (float(v) for v in ms)))
+        return self._phase_ms(self.dll.wdpm_group_rims_phase_ms, RIM_PHASES, int(rank))
