@@ -17,6 +17,10 @@
                       label_catchments, interleaved - the three catchment phases beside the table phase of the SAME calls, their
                       ratios and rounds, and the label, table and rim phases of either call side by side (default --out
                       profiles/r14/pond_catchments.json)
+    ... --outlets     the outlets of the ponds as well (include/wdpm_pond_outlets.h): five more timed calls of label_outlets, the two
+                      outlet phases beside the table phase of the SAME calls, their ratios, and their rates under the byte model
+                      of 20 B per cell and pass (basin, dem, w) and of 4 B per cell (a row that holds no pass reads its basins
+                      alone) against the yardstick (default --out profiles/r15/pond_outlets.json)
     ... --iterations K   instead of the job's own number of iterations before the inventory
 
 Per job: one untimed label call, then five timed ones (wall clock around the call, which ends with the stream idle; HIP events
@@ -44,7 +48,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 import wdpm_amd  # noqa: E402
-from wdpm_amd.ponds import CATCH_PHASES, PHASES, RIM_PHASES, GroupPonds, Ponds  # noqa: E402
+from wdpm_amd.ponds import CATCH_PHASES, OUTLET_PHASES, PHASES, RIM_PHASES, GroupPonds, Ponds  # noqa: E402
 
 MISS = -99999.0
 
@@ -140,6 +144,32 @@ def catchments_job(ctx, p, rec, n):
         c["of_yardstick"] = {k: v / rec["hbm_yardstick_gbps"] for k, v in c["gbps"].items()}
 
 
+def outlets_job(ctx, p, rec, n):
+    """after the label calls: one untimed label_outlets (allocates the basin raster and every table), five timed ones"""
+    p.label_outlets(0.001)
+    wall, phases, table_ms = [], {k: [] for k in OUTLET_PHASES}, []
+    for _ in range(5):
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        p.label_outlets(0.001)
+        wall.append((time.perf_counter() - t0) * 1e3)
+        for k, v in p.outlet_phase_ms().items():
+            phases[k].append(v)
+        table_ms.append(p.phase_ms()["table"])
+    table, stats = p.outlets(), p.outlet_stats()
+    med = {k: statistics.median(v) for k, v in phases.items()}
+    tms = statistics.median(table_ms)
+    cells = (n + 2) * (n + 2)
+    o = rec["outlets"] = dict(
+        label_outlets_wall_ms=statistics.median(wall), label_outlets_wall_ms_all=wall, phase_ms=med, phase_ms_all=phases,
+        table_ms_same_calls=tms, over_table={k: med[k] / tms for k in OUTLET_PHASES}, stats=stats,
+        fill_cells=int(table["fill_cells"].sum()), largest_divide=int(table["divide_cells"].max()) if len(table) else 0,
+        bytes_model={"per_pass_20B": 20 * cells, "per_pass_4B": 4 * cells}, guard_bad=p.guard_bad())
+    o["gbps"] = {k: {"20B": 20 * cells / (med[k] * 1e6), "4B": 4 * cells / (med[k] * 1e6)} if med[k] > 0 else None for k in OUTLET_PHASES}
+    if rec.get("hbm_yardstick_gbps"):
+        o["of_yardstick"] = {k: {m: r / rec["hbm_yardstick_gbps"] for m, r in v.items()} if v else None for k, v in o["gbps"].items()}
+
+
 def yardstick_gbps(path):
     """the best rate tools/hbm_yardstick.hip reached on this box (its lines end in `<ms> ms  <rate> GB/s`)"""
     rates = [float(m.group(1)) for m in re.finditer(r"([0-9.]+) GB/s\s*$", open(path).read(), flags=re.M)]
@@ -220,15 +250,19 @@ def main():
     ap.add_argument("--rims", action="store_true", help="time label_rims as well: the rim and locate phases beside the table phase")
     ap.add_argument("--catchments", action="store_true",
                     help="time label_catchments as well, interleaved with label_rims: the receiver, jump and tally phases")
+    ap.add_argument("--outlets", action="store_true", help="time label_outlets as well: the passes and locate phases beside the table phase")
     ap.add_argument("--iterations", type=int, help="iterations before the inventory, instead of the job's own")
     a = ap.parse_args()
     if not a.out:
         a.out = os.path.join(ROOT, "profiles", *(("r13", "pond_rims_group.json") if a.devices and a.rims else
                                                   ("r11", "ponds_group.json") if a.devices else
+                                                  ("r15", "pond_outlets.json") if a.outlets else
                                                   ("r14", "pond_catchments.json") if a.catchments else
                                                   ("r12", "pond_rims.json") if a.rims else ("r10", "ponds.json")))
     if a.catchments and a.devices:
         raise SystemExit("--catchments: catchments are taken on whole rasters only (include/wdpm_pond_catchments.h)")
+    if a.outlets and a.devices:
+        raise SystemExit("--outlets: outlets are taken on whole rasters only (include/wdpm_pond_outlets.h)")
     hip = wdpm_amd.load_hip()
     n = a.n
     dem = hip.synth_dem(n, n)
@@ -295,6 +329,8 @@ def main():
                 rims_job(ctx, p, rec, n)
             if a.catchments:
                 catchments_job(ctx, p, rec, n)
+            if a.outlets:
+                outlets_job(ctx, p, rec, n)
         if not a.no_scipy:
             try:
                 import scipy.ndimage as ndi

@@ -1,0 +1,414 @@
+/*
+ * wdpm_pond_outlets.hip — the outlet of every pond (include/wdpm_pond_outlets.h): the lowest pass between a pond's basin and any
+ * other, the cells on the divide, and what the basin floods and holds until it spills there; from the basin raster, the DEM and the
+ * water a wdpm_catch_label leaves on the device.  gfx950.  A unit of its own beside wdpm_ponds.hip, wdpm_pond_rims.hip and
+ * wdpm_pond_catchments.hip: not in the launch ledger, not among the sources wdpm_build_info() hashes.
+ *
+ * Shaped like the rim pair: a wave owns one 64-column segment over rows_per_wave rows (ponds_rows_per_wave) and keeps a sliding
+ * three-row window in registers - the basins first, the level keys only when a row wants them; column neighbours come from the
+ * lanes next door, those of lanes 0 and 63 from memory.
+ *
+ *   passes   A lane of basin k > 0 takes the minimum over its eight neighbours of max(own key, neighbour's key), over neighbours
+ *            whose basin is >= 0 and another.  Then per wave BY LABEL: a ballot of the lanes that hold a pass of basin L, a popcount
+ *            for the divide, a butterfly minimum; carried down the rows while the label stays, and one atomic_min_if on the pour
+ *            key and one add of the divide count per (wave, label change).  A row whose own lanes hold no basin > 0, or whose three
+ *            window rows - the cells beside the segment included - hold one basin >= 0 and no other, holds no pass and reads
+ *            neither dem nor w: the settled all-wet raster, the inside of every large catchment
+ *   locate   the same window, after every pour key is final (read once per (wave, label change)): a lane whose own minimum equals
+ *            its pond's pour key offers from_index * 8 + direction to a 64-bit atomic_min_if, which is the tie rule.  In the same
+ *            pass the lanes of basin L whose key lies below the pour key are counted and their rint((pour - level) * 2^24) summed
+ *            by label, carried like the tally.  A row without a pass whose one pond has no outlet at all is skipped as above; a
+ *            term of 512 m or more, or one that is not finite, sets a status word
+ *   finish   index and direction to the four coordinates, to_basin from the basin raster, the key back to a double; +inf, -1 and
+ *            zeros for a pond without a pass; the counts for wdpm_outlets_stats
+ *
+ * Everything that steers a loop is wave-uniform.  tests/outlets_emu_main.cpp compiles the kernels for the host under sanitizers
+ * with WDPM_PONDS_EMULATION defined, as tests/catch_emu_main.cpp does with wdpm_pond_catchments.hip, and leaves the host half out.
+ */
+#include "wdpm_ponds_priv.h"
+
+using namespace wdpm_pond_detail;
+
+namespace {
+
+constexpr unsigned long long kNone = ~0ull;        /* no pour key, no pair yet */
+
+/* the key of the level of a cell that has one (basin >= 0): dem + w where there is water to add, dem where there is none */
+__device__ __forceinline__ unsigned long long level_key(double e, double d) { return depth_key(d > 0.0 ? e + d : e); }
+
+/* butterfly: every lane ends with the wave's sum */
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  return v;
+}
+
+/* One row of the window.  eb and ek belong to the cell beside the segment: lane 0 holds the one on the left, lane 63 the one on
+ * the right, every other lane -1.  val, mixed and pond are wave-uniform. */
+struct OutWin {
+  int b, eb;
+  unsigned long long key, ek;
+  int val;                 /* a basin >= 0 of the row or beside it, -1: there is none */
+  bool mixed;              /* ... and another one */
+  bool pond;               /* a lane of the segment holds a basin > 0 */
+  bool has;                /* the keys are filled */
+};
+
+/* The basins of row r (-1 outside the raster) and what the wave-uniform tests want of them; nothing of the levels yet.  Both loads
+ * are issued before either is used. */
+__device__ __forceinline__ OutWin out_open(const int *__restrict__ basins, const Geom &g, int r, int c, int lane) {
+  OutWin x;
+  x.b = x.eb = -1;
+  x.key = x.ek = 0ull;
+  x.has = false;
+  if (r >= 0 && r < g.rows) {
+    const int ce = lane == 0 ? c - 1 : c + 1;
+    const bool own = c < g.ncp, beside = (lane == 0 || lane == 63) && ce >= 0 && ce < g.ncp;
+    if (own) x.b = basins[r * g.ncp + c];
+    if (beside) x.eb = basins[r * g.ncp + ce];
+  }
+  const unsigned long long in = __ballot(x.b >= 0), ein = __ballot(x.eb >= 0);
+  x.val = in ? __shfl(x.b, __builtin_ctzll(in)) : ein ? __shfl(x.eb, __builtin_ctzll(ein)) : -1;
+  x.mixed = __ballot((x.b >= 0 && x.b != x.val) || (x.eb >= 0 && x.eb != x.val)) != 0ull;
+  x.pond = __ballot(x.b > 0) != 0ull;
+  return x;
+}
+
+/* no pass starts in the row `cur` */
+__device__ __forceinline__ bool out_quiet(const OutWin &up, const OutWin &cur, const OutWin &dn) {
+  if (!cur.pond) return true;
+  if (up.mixed || cur.mixed || dn.mixed) return false;
+  return (up.val < 0 || up.val == cur.val) && (dn.val < 0 || dn.val == cur.val);
+}
+
+/* Level keys of row r's cells that have a basin (those alone have a level and lie inside the raster).  Every load is issued before
+ * the first is used: dem and w of a cell do not wait for each other. */
+__device__ __forceinline__ void out_fill(OutWin &x, const double *__restrict__ w, const double *__restrict__ dem, const Geom &g, int r,
+                                         int c, int lane) {
+  if (x.has) return;
+  x.has = true;
+  if (x.val < 0) return;
+  const int ce = lane == 0 ? c - 1 : c + 1;
+  double e = 0.0, d = 0.0, ee = 0.0, de = 0.0;
+  if (x.b >= 0) {
+    e = dem[r * g.ncp + c];
+    d = w[r * g.ncp + c];
+  }
+  if (x.eb >= 0) {
+    ee = dem[r * g.ncp + ce];
+    de = w[r * g.ncp + ce];
+  }
+  x.key = level_key(e, d);
+  x.ek = level_key(ee, de);
+}
+
+/* This lane's lowest pass: over the eight neighbours in the order of their padded index, those of another basin >= 0; the first of
+ * equals stays.  Every lane takes part in the exchanges. */
+__device__ __forceinline__ bool out_lowest(const OutWin &up, const OutWin &cur, const OutWin &dn, int lane, unsigned long long &height,
+                                           int &dir) {
+  const unsigned long long nk[8] = {lane_from_left(up.key, up.ek, lane),   up.key, lane_from_right(up.key, up.ek, lane),
+                                    lane_from_left(cur.key, cur.ek, lane),         lane_from_right(cur.key, cur.ek, lane),
+                                    lane_from_left(dn.key, dn.ek, lane),   dn.key, lane_from_right(dn.key, dn.ek, lane)};
+  const int nb[8] = {lane_from_left(up.b, up.eb, lane),   up.b, lane_from_right(up.b, up.eb, lane),
+                     lane_from_left(cur.b, cur.eb, lane),       lane_from_right(cur.b, cur.eb, lane),
+                     lane_from_left(dn.b, dn.eb, lane),   dn.b, lane_from_right(dn.b, dn.eb, lane)};
+  bool found = false;
+  height = kNone;
+  dir = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const unsigned long long hi = nk[i] > cur.key ? nk[i] : cur.key;
+    if (cur.b > 0 && nb[i] >= 0 && nb[i] != cur.b && (!found || hi < height)) {
+      height = hi;
+      dir = i;
+      found = true;
+    }
+  }
+  return found;
+}
+
+/* ---- passes ---------------------------------------------------------------------------------------------------------------- */
+__global__ __launch_bounds__(kBlock) void outlet_passes_kernel(const double *__restrict__ w, const double *__restrict__ dem,
+                                                               const int *__restrict__ basins, Geom g, int rpw, int nwaves,
+                                                               OutletRow *table) {
+  const int wid = blockIdx.x * kWaves + (threadIdx.x >> 6);
+  if (wid >= nwaves) return;
+  const int lane = threadIdx.x & 63;
+  const int strip = wid / g.nsc, s = wid - strip * g.nsc;
+  const int r0 = strip * rpw, r1 = min(r0 + rpw, g.rows);
+  const int c = s * kSeg + lane;
+  int cy_label = 0;                        /* what the wave holds for one label and has not yet sent */
+  unsigned long long cy_min = kNone, cy_divide = 0ull;
+
+  OutWin up = out_open(basins, g, r0 - 1, c, lane), cur = out_open(basins, g, r0, c, lane), dn;
+  for (int r = r0; r < r1; r++, up = cur, cur = dn) {
+    dn = out_open(basins, g, r + 1, c, lane);
+    if (out_quiet(up, cur, dn)) continue;
+    out_fill(up, w, dem, g, r - 1, c, lane);
+    out_fill(cur, w, dem, g, r, c, lane);
+    out_fill(dn, w, dem, g, r + 1, c, lane);
+    unsigned long long height;
+    int dir;
+    const bool found = out_lowest(up, cur, dn, lane, height, dir);
+
+    /* per wave, by label */
+    int cand = found ? cur.b : 0;
+    for (;;) {
+      const unsigned long long pending = __ballot(cand != 0);
+      if (pending == 0ull) break;
+      const int L = __shfl(cand, __builtin_ctzll(pending));
+      const unsigned long long hitm = __ballot(cand == L);
+      const unsigned long long lo = wave_min(cand == L ? height : kNone);
+      if (cy_label != L) {                 /* down the rows: the same label goes on gathering, another one sends first */
+        if (cy_label != 0 && lane == 0) {
+          atomic_min_if(&table[cy_label - 1].pour_key, cy_min);
+          atomicAdd(&table[cy_label - 1].divide_cells, cy_divide);
+        }
+        cy_label = L;
+        cy_min = kNone;
+        cy_divide = 0ull;
+      }
+      cy_min = lo < cy_min ? lo : cy_min;
+      cy_divide += (unsigned long long)__popcll(hitm);
+      if (cand == L) cand = 0;
+    }
+  }
+  if (cy_label != 0 && lane == 0) {
+    atomic_min_if(&table[cy_label - 1].pour_key, cy_min);
+    atomicAdd(&table[cy_label - 1].divide_cells, cy_divide);
+  }
+}
+
+/* ---- locate ---------------------------------------------------------------------------------------------------------------- */
+/* what a wave of the locate pass holds for one label */
+struct FillCarry {
+  int label;               /* 0: nothing held */
+  unsigned long long pour, cells, q;
+};
+
+/* the carry turns to label L: what it held goes out, and L's final pour key comes in */
+__device__ __forceinline__ void fill_turn(FillCarry &cy, OutletRow *table, int L, int lane) {
+  if (cy.label == L) return;
+  if (cy.label != 0 && cy.cells != 0ull && lane == 0) {
+    atomicAdd(&table[cy.label - 1].fill_cells, cy.cells);
+    atomicAdd(&table[cy.label - 1].fill_q, cy.q);
+  }
+  cy.label = L;
+  cy.pour = L ? table[L - 1].pour_key : kNone;
+  cy.cells = cy.q = 0ull;
+}
+
+__global__ __launch_bounds__(kBlock) void outlet_locate_kernel(const double *__restrict__ w, const double *__restrict__ dem,
+                                                               const int *__restrict__ basins, Geom g, int rpw, int nwaves,
+                                                               OutletRow *table, OutletStatus *st) {
+  const int wid = blockIdx.x * kWaves + (threadIdx.x >> 6);
+  if (wid >= nwaves) return;
+  const int lane = threadIdx.x & 63;
+  const int strip = wid / g.nsc, s = wid - strip * g.nsc;
+  const int r0 = strip * rpw, r1 = min(r0 + rpw, g.rows);
+  const int c = s * kSeg + lane;
+  FillCarry cy;
+  cy.label = 0;
+  cy.pour = kNone;
+  cy.cells = cy.q = 0ull;
+
+  OutWin up = out_open(basins, g, r0 - 1, c, lane), cur = out_open(basins, g, r0, c, lane), dn;
+  for (int r = r0; r < r1; r++, up = cur, cur = dn) {
+    dn = out_open(basins, g, r + 1, c, lane);
+    if (!cur.pond) continue;
+    const bool quiet = out_quiet(up, cur, dn);
+    if (quiet) {                           /* one basin, cur.val > 0, and no pass here: without an outlet there is nothing to fill */
+      fill_turn(cy, table, cur.val, lane);
+      if (cy.pour == kNone) continue;
+    }
+    out_fill(cur, w, dem, g, r, c, lane);
+    unsigned long long height = kNone;
+    int dir = 0;
+    bool found = false;
+    if (!quiet) {
+      out_fill(up, w, dem, g, r - 1, c, lane);
+      out_fill(dn, w, dem, g, r + 1, c, lane);
+      found = out_lowest(up, cur, dn, lane, height, dir);
+    }
+
+    int cand = cur.b > 0 ? cur.b : 0;
+    for (;;) {
+      const unsigned long long pending = __ballot(cand != 0);
+      if (pending == 0ull) break;
+      const int L = __shfl(cand, __builtin_ctzll(pending));
+      fill_turn(cy, table, L, lane);
+      const bool mine = cand == L;
+      if (mine && found && height == cy.pour)
+        atomic_min_if(&table[L - 1].pair, (unsigned long long)(r * g.ncp + c) * 8ull + (unsigned long long)dir);
+      const bool below = mine && cy.pour != kNone && cur.key < cy.pour;
+      const unsigned long long belowm = __ballot(below);
+      if (belowm != 0ull) {
+        const double depth = depth_from_key(cy.pour) - depth_from_key(cur.key);
+        const bool bad = below && !(depth < 512.0);          /* 512 m or more, +inf, NaN */
+        if (bad) st->deep = 1u;
+        cy.cells += (unsigned long long)__popcll(__ballot(below && !bad));
+        cy.q += wave_sum(below && !bad ? (unsigned long long)rint(depth * 16777216.0) : 0ull);
+      }
+      if (mine) cand = 0;
+    }
+  }
+  fill_turn(cy, table, 0, lane);
+}
+
+/* ---- init, finish ---------------------------------------------------------------------------------------------------------- */
+__global__ __launch_bounds__(kBlock) void outlet_init_kernel(OutletRow *t, long long n) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  OutletRow r;
+  r.pour_key = r.pair = kNone;
+  r.spare = 0ull;
+  r.to_basin = -1;
+  r.reserved = 0;
+  r.divide_cells = r.fill_cells = r.fill_q = 0ull;
+  t[i] = r;
+}
+
+/* two int32 as they lie in memory, the first at the lower address */
+__device__ __forceinline__ unsigned long long two_ints(int first, int second) {
+  return (unsigned long long)(unsigned)first | ((unsigned long long)(unsigned)second << 32);
+}
+
+/* the accumulated row becomes a wdpm_pond_outlet in place; every lane stays for the counts */
+__global__ __launch_bounds__(kBlock) void outlet_finish_kernel(OutletRow *t, long long n, const int *__restrict__ basins, int ncp,
+                                                               OutletStatus *st) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  const bool live = i < n;
+  bool none = false, land = false;
+  unsigned long long divide = 0ull;
+  if (live) {
+    OutletRow r = t[i];
+    none = r.pair == kNone || r.pour_key == kNone;
+    if (none) {
+      r.pour_key = (unsigned long long)__double_as_longlong(__builtin_inf());
+      r.pair = r.spare = two_ints(-1, -1);
+      r.to_basin = -1;
+      r.divide_cells = r.fill_cells = r.fill_q = 0ull;
+    } else {
+      const int from = (int)(r.pair >> 3), i8 = (int)(r.pair & 7ull);
+      const int dr = (i8 < 3 ? -1 : i8 < 5 ? 0 : 1), dc = (i8 < 3 ? i8 - 1 : i8 == 3 ? -1 : i8 == 4 ? 1 : i8 - 6);
+      const int row = from / ncp, col = from - row * ncp;
+      r.pour_key = (unsigned long long)__double_as_longlong(depth_from_key(r.pour_key));
+      r.pair = two_ints(row, col);
+      r.spare = two_ints(row + dr, col + dc);
+      r.to_basin = basins[from + dr * ncp + dc];
+      land = r.to_basin == 0;
+      divide = r.divide_cells;
+    }
+    r.reserved = 0;
+    t[i] = r;
+  }
+  const unsigned long long nonem = __ballot(none), landm = __ballot(land);
+  divide = wave_sum(divide);
+  if ((threadIdx.x & 63) == 0) {
+    if (nonem) atomicAdd(&st->no_outlet, (unsigned long long)__popcll(nonem));
+    if (landm) atomicAdd(&st->to_land, (unsigned long long)__popcll(landm));
+    if (divide) atomicAdd(&st->divide, divide);
+  }
+}
+
+}  // namespace
+
+#ifndef WDPM_PONDS_EMULATION
+/* ---- host ------------------------------------------------------------------------------------------------------------------ */
+namespace {
+const char kNoTable[] = "no outlet table: the last label call on this handle was not a wdpm_outlets_label that succeeded";
+}  // namespace
+
+extern "C" int wdpm_outlets_label(wdpm_ponds *h, double min_depth, int64_t *nponds) {
+  if (!h) return wdpm_fail("wdpm_outlets_label: null handle");
+  if (!(min_depth >= 0.0) || std::isinf(min_depth)) return wdpm_fail("wdpm_outlets_label: min_depth must be finite and >= 0 (got %g)", min_depth);
+  if (h->seams) return wdpm_fail("wdpm_outlets_label: the handle views a row block: outlets are taken on whole rasters only");
+  int64_t n = 0;
+  if (wdpm_catch_label(h, min_depth, &n)) return 1;           /* leaves the basin raster and the stream as this pass wants them */
+  h->valid = false;                                           /* a wdpm_outlets_label that fails leaves no table of any kind */
+  wdpm_ctx *x = h->x;
+  const Geom g = h->g;
+  const hipStream_t sm = x->stream;
+  HIP_TRY(hipSetDevice(x->p.device));
+  if (!h->d_ostat) {
+    hipError_t e = hipMalloc(&h->d_ostat, sizeof(OutletStatus));
+    if (e != hipSuccess) { h->d_ostat = nullptr; return wdpm_fail("wdpm_outlets_label: no device memory for the status words: %s", hipGetErrorString(e)); }
+    e = hipHostMalloc(&h->h_ostat, sizeof(OutletStatus));
+    if (e != hipSuccess) { h->h_ostat = nullptr; (void)hipFree(h->d_ostat); h->d_ostat = nullptr; return wdpm_fail("wdpm_outlets_label: no pinned host memory for the status words: %s", hipGetErrorString(e)); }
+  }
+  if (n > h->outlets_cap) {                                   /* sized from N, like the pond table */
+    guarded_free(h, h->d_outlets);
+    h->d_outlets = nullptr;
+    h->outlets_cap = 0;
+    const hipError_t e = guarded_malloc(h, (void **)&h->d_outlets, (size_t)n * sizeof(OutletRow));
+    if (e != hipSuccess) return wdpm_fail("wdpm_outlets_label: no device memory for the outlets of %lld ponds: %s", (long long)n, hipGetErrorString(e));
+    h->outlets_cap = n;
+  }
+  h->outlet_ms[0] = h->outlet_ms[1] = 0.0;
+  memset(h->h_ostat, 0, sizeof(OutletStatus));
+  if (n > 0) {                                                /* no pond, no outlet: nothing to launch */
+    const size_t off = (size_t)h->row_off * g.ncp;
+    const double *w = x->d_w[x->cur] + off, *dem = x->d_dem + off;
+    const int rpw = ponds_rows_per_wave(g.nseg, g.rows, h->forced_rpw);
+    const int nwaves = ((g.rows + rpw - 1) / rpw) * g.nsc;
+    const unsigned nblocks = blocks_for(n, kBlock), wblocks = blocks_for(nwaves, kWaves);
+    HIP_TRY(hipMemsetAsync(h->d_ostat, 0, sizeof(OutletStatus), sm));
+    if (h->timing) HIP_TRY(hipEventRecord(h->outlet_ev[0], sm));
+    hipLaunchKernelGGL(outlet_init_kernel, dim3(nblocks), dim3(kBlock), 0, sm, h->d_outlets, (long long)n);
+    hipLaunchKernelGGL(outlet_passes_kernel, dim3(wblocks), dim3(kBlock), 0, sm, w, dem, h->d_link, g, rpw, nwaves, h->d_outlets);
+    if (h->timing) HIP_TRY(hipEventRecord(h->outlet_ev[1], sm));
+    hipLaunchKernelGGL(outlet_locate_kernel, dim3(wblocks), dim3(kBlock), 0, sm, w, dem, h->d_link, g, rpw, nwaves, h->d_outlets, h->d_ostat);
+    hipLaunchKernelGGL(outlet_finish_kernel, dim3(nblocks), dim3(kBlock), 0, sm, h->d_outlets, (long long)n, h->d_link, g.ncp, h->d_ostat);
+    if (h->timing) HIP_TRY(hipEventRecord(h->outlet_ev[2], sm));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h->h_ostat, h->d_ostat, sizeof(OutletStatus), hipMemcpyDeviceToHost, sm));
+    if (wdpm_stream_sync(x, sm)) return 1;
+    if (h->timing)
+      for (int i = 0; i < WDPM_OUTLETS_PHASES; i++) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, h->outlet_ev[i], h->outlet_ev[i + 1]));
+        h->outlet_ms[i] = ms;
+      }
+  }
+  if (h->h_ostat->deep)
+    return wdpm_fail("wdpm_outlets_label: a cell of a pond's basin lies 512 m or more below the pond's outlet, or not a finite depth "
+                     "below it: fill_q (a 64-bit sum of depths in units of 2^-24 m) is only safe below that depth");
+  h->outlet_stats.ponds = n;
+  h->outlet_stats.no_outlet = (int64_t)h->h_ostat->no_outlet;
+  h->outlet_stats.to_land = (int64_t)h->h_ostat->to_land;
+  h->outlet_stats.divide_cells = (int64_t)h->h_ostat->divide;
+  h->outlets_valid = true;
+  h->valid = true;
+  if (nponds) *nponds = n;
+  return 0;
+}
+
+extern "C" int wdpm_outlets_table(wdpm_ponds *h, wdpm_pond_outlet *out, int64_t capacity) {
+  if (!h) return wdpm_fail("wdpm_outlets_table: null handle");
+  if (!h->valid || !h->outlets_valid) return wdpm_fail("wdpm_outlets_table: %s", kNoTable);
+  const long long n = h->stats.ponds;
+  if (capacity < n) return wdpm_fail("wdpm_outlets_table: capacity %lld is too small for %lld ponds", (long long)capacity, n);
+  if (n == 0) return 0;
+  if (!out) return wdpm_fail("wdpm_outlets_table: null output");
+  if (wdpm_synchronize(h->x)) return 1;
+  HIP_TRY(hipMemcpyAsync(out, h->d_outlets, (size_t)n * sizeof(wdpm_pond_outlet), hipMemcpyDeviceToHost, h->x->stream));
+  return wdpm_stream_sync(h->x, h->x->stream);
+}
+
+extern "C" int wdpm_outlets_stats(wdpm_ponds *h, wdpm_pond_outlet_stats *out) {
+  if (!h) return wdpm_fail("wdpm_outlets_stats: null handle");
+  if (!out) return wdpm_fail("wdpm_outlets_stats: null output");
+  if (!h->valid || !h->outlets_valid) return wdpm_fail("wdpm_outlets_stats: %s", kNoTable);
+  *out = h->outlet_stats;
+  return 0;
+}
+
+extern "C" int wdpm_outlets_phase_ms(wdpm_ponds *h, double *ms) {
+  if (!h) return wdpm_fail("wdpm_outlets_phase_ms: null handle");
+  if (!ms) return wdpm_fail("wdpm_outlets_phase_ms: null output");
+  if (!h->timing) return wdpm_fail("wdpm_outlets_phase_ms: the handle records no events (set WDPM_PONDS_TIMING=1 before it is made)");
+  if (!h->valid || !h->outlets_valid) return wdpm_fail("wdpm_outlets_phase_ms: %s", kNoTable);
+  for (int i = 0; i < WDPM_OUTLETS_PHASES; i++) ms[i] = h->outlet_ms[i];
+  return 0;
+}
+#endif  /* WDPM_PONDS_EMULATION */

@@ -488,6 +488,13 @@ void release(wdpm_ponds *h) {
   h->catch_cap = 0;
   h->d_cstat = h->h_cstat = nullptr;
   h->catch_valid = false;
+  guarded_free(h, h->d_outlets);
+  if (h->d_ostat) (void)hipFree(h->d_ostat);
+  if (h->h_ostat) (void)hipHostFree(h->h_ostat);
+  h->d_outlets = nullptr;
+  h->outlets_cap = 0;
+  h->d_ostat = h->h_ostat = nullptr;
+  h->outlets_valid = false;
   if (h->h_beside) (void)hipHostFree(h->h_beside);
   if (h->h_rims) (void)hipHostFree(h->h_rims);
   h->d_slot_of = h->d_foreign = nullptr;
@@ -584,6 +591,11 @@ wdpm_ponds *make_handle(wdpm_ctx *ctx, int row_off, int rows, bool seams) {
   h->d_cstat = h->h_cstat = nullptr;
   h->catch_valid = false;
   memset(&h->catch_stats, 0, sizeof h->catch_stats);
+  h->d_outlets = nullptr;
+  h->outlets_cap = 0;
+  h->d_ostat = h->h_ostat = nullptr;
+  h->outlets_valid = false;
+  memset(&h->outlet_stats, 0, sizeof h->outlet_stats);
   h->nb = 0;
   { const char *re = getenv("WDPM_PONDS_ROWS_PER_WAVE"); h->forced_rpw = re ? atoi(re) : 0; }
   h->rpw = 1;
@@ -607,6 +619,11 @@ wdpm_ponds *make_handle(wdpm_ctx *ctx, int row_off, int rows, bool seams) {
   if (h->timing)
     for (int i = 0; i < 5; i++)
       if (hipEventCreate(&h->catch_ev[i]) != hipSuccess) { h->timing = false; break; }
+  for (int i = 0; i < WDPM_OUTLETS_PHASES + 1; i++) h->outlet_ev[i] = nullptr;
+  for (int i = 0; i < WDPM_OUTLETS_PHASES; i++) h->outlet_ms[i] = 0.0;
+  if (h->timing)
+    for (int i = 0; i < WDPM_OUTLETS_PHASES + 1; i++)
+      if (hipEventCreate(&h->outlet_ev[i]) != hipSuccess) { h->timing = false; break; }
   return h;
 }
 
@@ -621,6 +638,7 @@ int label_queue(wdpm_ponds *h, double min_depth) {
   h->valid = false;
   h->rims_valid = false;            /* a rim table belongs to the label call that made it (wdpm_pond_rims.hip) */
   h->catch_valid = false;           /* and so does a catchment table (wdpm_pond_catchments.hip) */
+  h->outlets_valid = false;         /* and an outlet table (wdpm_pond_outlets.hip) */
   /* the raster as a reader sees it: side stream joined, owed drain() and threshold flush applied (what wdpm_count_stats asks for) */
   if (wdpm_synchronize(x)) return 1;
   if (wdpm_apply_owed_flush(x)) return 1;
@@ -769,6 +787,8 @@ void destroy_handle(wdpm_ponds *h) {
     if (h->rim_ev[i]) (void)hipEventDestroy(h->rim_ev[i]);
   for (int i = 0; i < 5; i++)
     if (h->catch_ev[i]) (void)hipEventDestroy(h->catch_ev[i]);
+  for (int i = 0; i < WDPM_OUTLETS_PHASES + 1; i++)
+    if (h->outlet_ev[i]) (void)hipEventDestroy(h->outlet_ev[i]);
   delete h;
 }
 

@@ -1,9 +1,10 @@
 /*
  * wdpm_ponds_priv.h — what the units of the pond inventory share: wdpm_ponds.hip (labels and table), wdpm_pond_rims.hip
- * (rims) and wdpm_pond_catchments.hip (catchments).  Geometry, the order-preserving image of a double, the table rows as the device
- * accumulates them, the wave helpers of the kernels (a lane's neighbour, the wave's extremum, the look before an atomic) and -
- * outside the host emulations of the tests, which define WDPM_PONDS_EMULATION and bring stand-ins for the HIP device language
- * (tests/hip_emu.h) - the handle itself with its guarded allocator.  Private: nothing here is exported, and no header under include/ knows it.
+ * (rims), wdpm_pond_catchments.hip (catchments) and wdpm_pond_outlets.hip (outlets).  Geometry, the order-preserving image of a
+ * double, the table rows as the device accumulates them, the wave helpers of the kernels (a lane's neighbour, the wave's extremum,
+ * the look before an atomic) and - outside the host emulations of the tests, which define WDPM_PONDS_EMULATION and bring stand-ins
+ * for the HIP device language (tests/hip_emu.h) - the handle itself with its guarded allocator.  Private: nothing here is exported,
+ * and no header under include/ knows it.
  */
 #ifndef WDPM_PONDS_PRIV_H
 #define WDPM_PONDS_PRIV_H
@@ -25,10 +26,13 @@
     if (e_ != hipSuccess) return wdpm_fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 #endif
+#include <cstddef>
+
 #include "../../include/wdpm_group_ponds.h"
 #include "../../include/wdpm_pond_rims.h"
 #include "../../include/wdpm_group_pond_rims.h"
 #include "../../include/wdpm_pond_catchments.h"
+#include "../../include/wdpm_pond_outlets.h"
 
 namespace wdpm_pond_detail {
 
@@ -84,6 +88,25 @@ static_assert(kCatchRoundCap % kCatchBatch == 0, "whole batches up to the cap");
 struct CatchStatus {
   unsigned long long slope, pit, unponded;
   unsigned unres[kCatchRoundCap];
+};
+
+/* the outlet table as the device accumulates it: wdpm_pond_outlet with the pour level as its order-preserving image (~0: no pass
+ * yet) and the outlet pair as from_index * 8 + direction in the place of the four coordinates (~0: none yet) */
+struct OutletRow {
+  unsigned long long pour_key, pair, spare;
+  int to_basin, reserved;
+  unsigned long long divide_cells, fill_cells, fill_q;
+};
+static_assert(sizeof(OutletRow) == sizeof(wdpm_pond_outlet) && sizeof(OutletRow) == 56, "the device outlet table is copied out as wdpm_pond_outlet");
+static_assert(offsetof(wdpm_pond_outlet, from_row) == offsetof(OutletRow, pair) && offsetof(wdpm_pond_outlet, to_basin) == offsetof(OutletRow, to_basin) &&
+              offsetof(wdpm_pond_outlet, divide_cells) == offsetof(OutletRow, divide_cells) && offsetof(wdpm_pond_outlet, fill_q) == offsetof(OutletRow, fill_q),
+              "the finish kernel rewrites a row in place");
+
+/* what the outlet kernels count for the host */
+struct OutletStatus {
+  unsigned long long no_outlet, to_land, divide;
+  unsigned deep;           /* a fill term of >= 512 m, or one that is not finite */
+  unsigned pad;
 };
 
 /* status words the host reads after the scan */
@@ -218,6 +241,14 @@ struct wdpm_ponds {
   hipEvent_t catch_ev[5];           /* init | receivers | jump rounds | tally, finish */
   double catch_ms[WDPM_CATCH_PHASES];
   wdpm_pond_catchment_stats catch_stats;
+  /* outlets (wdpm_pond_outlets.hip): the table of the last wdpm_outlets_label; every label call takes outlets_valid away first */
+  wdpm_pond_detail::OutletRow *d_outlets;
+  long long outlets_cap;
+  wdpm_pond_detail::OutletStatus *d_ostat, *h_ostat;  /* h_ostat pinned */
+  bool outlets_valid;
+  hipEvent_t outlet_ev[WDPM_OUTLETS_PHASES + 1];      /* init, passes | locate, finish */
+  double outlet_ms[WDPM_OUTLETS_PHASES];
+  wdpm_pond_outlet_stats outlet_stats;
 };
 
 /* the handle of include/wdpm_group_ponds.h and include/wdpm_group_pond_rims.h */

@@ -40,6 +40,7 @@
 #include "../../include/wdpm_group_ponds.h"
 #include "../../include/wdpm_pond_rims.h"
 #include "../../include/wdpm_pond_catchments.h"
+#include "../../include/wdpm_pond_outlets.h"
 /* the pond inventory is the HIP library's alone: weak references, so that this file also links against a back-end that
  * exports include/wdpm.h and nothing else (WDPM_PONDS then says so and writes no file) */
 #pragma weak wdpm_ponds_create
@@ -58,6 +59,9 @@
 #pragma weak wdpm_catch_label
 #pragma weak wdpm_catch_table
 #pragma weak wdpm_catch_stats
+#pragma weak wdpm_outlets_label
+#pragma weak wdpm_outlets_table
+#pragma weak wdpm_outlets_stats
 #include "arcascii.h"
 
 #define ITER_PER_BLOCK 1000 /* IterationNum, WDPMCL.c:597 */
@@ -649,16 +653,20 @@ static void relief_finish(relief_helper *h) {
 typedef struct {
   wdpm_pond *rows; int64_t n; int64_t guard_bad; int64_t blocks, joined; wdpm_pond_rim *rims;
   wdpm_pond_catchment *catch; wdpm_pond_catchment_stats catch_stats;
+  wdpm_pond_outlet *outlets; wdpm_pond_outlet_stats outlet_stats;
 } pond_inventory;
 
 /* with_rims (WDPM_POND_RIMS, include/wdpm_pond_rims.h; the caller has seen that the back-end has them): one wdpm_rims_label serves
  * the pond table and the rim table.  with_catch (WDPM_POND_CATCHMENTS, include/wdpm_pond_catchments.h; likewise): one
- * wdpm_catch_label serves all three, whichever of the files are asked for. */
-static int take_inventory(wdpm_ctx *c, double min_depth, pond_inventory *inv, int with_rims, int with_catch) {
+ * wdpm_catch_label serves all three, whichever of the files are asked for.  with_outlets (WDPM_POND_OUTLETS,
+ * include/wdpm_pond_outlets.h; likewise, and the caller then sets with_rims too: the headroom wants the surface): one
+ * wdpm_outlets_label serves all four. */
+static int take_inventory(wdpm_ctx *c, double min_depth, pond_inventory *inv, int with_rims, int with_catch, int with_outlets) {
   wdpm_ponds *h = NULL;
   inv->rows = NULL;
   inv->rims = NULL;
   inv->catch = NULL;
+  inv->outlets = NULL;
   inv->n = 0;
   inv->guard_bad = 0;
   inv->blocks = 1;
@@ -669,14 +677,16 @@ static int take_inventory(wdpm_ctx *c, double min_depth, pond_inventory *inv, in
   }
   int rc = wdpm_ponds_create(&h, c);
   if (!rc)
-    rc = with_catch  ? wdpm_catch_label(h, min_depth, &inv->n)
-         : with_rims ? wdpm_rims_label(h, min_depth, &inv->n)
-                     : wdpm_ponds_label(h, min_depth, &inv->n);
+    rc = with_outlets ? wdpm_outlets_label(h, min_depth, &inv->n)
+         : with_catch ? wdpm_catch_label(h, min_depth, &inv->n)
+         : with_rims  ? wdpm_rims_label(h, min_depth, &inv->n)
+                      : wdpm_ponds_label(h, min_depth, &inv->n);
   if (!rc) {
     inv->rows = (wdpm_pond *)malloc((size_t)(inv->n > 0 ? inv->n : 1) * sizeof(wdpm_pond));
     if (with_rims) inv->rims = (wdpm_pond_rim *)malloc((size_t)(inv->n > 0 ? inv->n : 1) * sizeof(wdpm_pond_rim));
     if (with_catch) inv->catch = (wdpm_pond_catchment *)malloc((size_t)(inv->n > 0 ? inv->n : 1) * sizeof(wdpm_pond_catchment));
-    if (!inv->rows || (with_rims && !inv->rims) || (with_catch && !inv->catch)) {
+    if (with_outlets) inv->outlets = (wdpm_pond_outlet *)malloc((size_t)(inv->n > 0 ? inv->n : 1) * sizeof(wdpm_pond_outlet));
+    if (!inv->rows || (with_rims && !inv->rims) || (with_catch && !inv->catch) || (with_outlets && !inv->outlets)) {
       wdpm_set_last_error("out of host memory for the pond table");
       rc = 1;
     }
@@ -685,15 +695,19 @@ static int take_inventory(wdpm_ctx *c, double min_depth, pond_inventory *inv, in
   if (!rc && with_rims) rc = wdpm_rims_table(h, inv->rims, inv->n);
   if (!rc && with_catch) rc = wdpm_catch_table(h, inv->catch, inv->n);
   if (!rc && with_catch) rc = wdpm_catch_stats(h, &inv->catch_stats);
+  if (!rc && with_outlets) rc = wdpm_outlets_table(h, inv->outlets, inv->n);
+  if (!rc && with_outlets) rc = wdpm_outlets_stats(h, &inv->outlet_stats);
   if (!rc && getenv("WDPM_GUARD_KB")) rc = wdpm_ponds_guard_bad(h, &inv->guard_bad);
   if (rc) {
     fprintf(stderr, "WDPMCL: pond inventory failed, no file written: %s\n", wdpm_last_error());
     free(inv->rows);
     free(inv->rims);
     free(inv->catch);
+    free(inv->outlets);
     inv->rows = NULL;
     inv->rims = NULL;
     inv->catch = NULL;
+    inv->outlets = NULL;
   }
   wdpm_ponds_destroy(h);
   return rc;
@@ -706,6 +720,7 @@ static int take_group_inventory(wdpm_group *grp, double min_depth, pond_inventor
   inv->rows = NULL;
   inv->rims = NULL;
   inv->catch = NULL;
+  inv->outlets = NULL;
   inv->n = 0;
   inv->guard_bad = 0;
   inv->blocks = 1;
@@ -812,6 +827,36 @@ static int write_catchments(const char *path, const pond_inventory *inv, double 
   fprintf(stderr, "WDPMCL: pond catchments: %lld pond%s written to %s (%lld slope cells, %lld pits, %lld cells drain to no pond, %lld rounds)\n",
           (long long)inv->n, inv->n == 1 ? "" : "s", path, (long long)cs->slope_cells, (long long)cs->pit_cells,
           (long long)cs->unponded_cells, (long long)cs->rounds);
+  return 0;
+}
+
+/* WDPM_POND_OUTLETS=<path>: one CSV line per pond of the same inventory: the level at which its basin spills and how far the
+ * highest water surface is below it, the pass (file coordinates, 0-based; -1 without an outlet) and the basin beyond it (a label,
+ * 0: land that ends in a pit, -1: none), the cells on the divide, and the cells flooded and the storage left when it spills
+ * (include/wdpm_pond_outlets.h).  Doubles as %.17g. */
+static int write_outlets(const char *path, const pond_inventory *inv, double cellarea) {
+  FILE *f = fopen(path, "w");
+  if (!f) {
+    fprintf(stderr, "WDPMCL: cannot write pond outlets %s\n", path);
+    return 1;
+  }
+  fprintf(f, "label,pour_level_m,headroom_m,from_row,from_col,to_row,to_col,to_label,divide_cells,fill_cells,fill_area_m2,fill_q,fill_m3\n");
+  for (int64_t k = 0; k < inv->n; k++) {
+    const wdpm_pond_outlet *q = &inv->outlets[k];
+    const int none = q->from_row < 0;
+    fprintf(f, "%lld,%.17g,%.17g,%d,%d,%d,%d,%d,%lld,%lld,%.17g,%llu,%.17g\n", (long long)(k + 1), q->pour_level,
+            q->pour_level - inv->rims[k].surface_max, none ? -1 : q->from_row - 1, none ? -1 : q->from_col - 1,
+            none ? -1 : q->to_row - 1, none ? -1 : q->to_col - 1, q->to_basin, (long long)q->divide_cells, (long long)q->fill_cells,
+            (double)q->fill_cells * cellarea, (unsigned long long)q->fill_q, ldexp((double)q->fill_q, -24) * cellarea);
+  }
+  const int bad = ferror(f);
+  if (fclose(f) != 0 || bad) {
+    fprintf(stderr, "WDPMCL: error writing pond outlets %s\n", path);
+    return 1;
+  }
+  const wdpm_pond_outlet_stats *os = &inv->outlet_stats;
+  fprintf(stderr, "WDPMCL: pond outlets: %lld pond%s written to %s (%lld without an outlet, %lld spill onto land that ends in a pit, %lld cells on the divides)\n",
+          (long long)inv->n, inv->n == 1 ? "" : "s", path, (long long)os->no_outlet, (long long)os->to_land, (long long)os->divide_cells);
   return 0;
 }
 
@@ -1075,18 +1120,36 @@ int main(int argc, char **argv) {
     ponds_failed = 1;
     catch_path = NULL;
   }
-  if (ponds_path || rims_path || catch_path) {
+  /* ... and their outlets (WDPM_POND_OUTLETS), alone or beside any of them: whole rasters only */
+  const char *outlets_path = getenv("WDPM_POND_OUTLETS");
+  if (outlets_path && !*outlets_path) outlets_path = NULL;
+  if (outlets_path && ndev > 1) {
+    fprintf(stderr, "WDPMCL: pond outlets: the raster lies in %d row blocks and outlets are taken on a whole raster only, no file written to %s\n",
+            ndev, outlets_path);
+    ponds_failed = 1;
+    outlets_path = NULL;
+  }
+  if (outlets_path && (!wdpm_outlets_label || !wdpm_outlets_table || !wdpm_outlets_stats || !wdpm_rims_table || !wdpm_catch_table ||
+                       !wdpm_catch_stats)) {
+    fprintf(stderr, "WDPMCL: pond outlets: back-end %s has none, no file written\n", wdpm_backend_name());
+    ponds_failed = 1;
+    outlets_path = NULL;
+  }
+  if (ponds_path || rims_path || catch_path || outlets_path) {
     phase("statistics + download");
     const int failed = ndev == 1 ? take_inventory(wdpm_rank_ctx(wdpm_group_rank(ctx, 0)), ponds_min_depth, &inv,
-                                                  rims_path != NULL || catch_path != NULL, catch_path != NULL)
+                                                  rims_path != NULL || catch_path != NULL || outlets_path != NULL,
+                                                  catch_path != NULL || outlets_path != NULL, outlets_path != NULL)
                                  : take_group_inventory(ctx, ponds_min_depth, &inv);
     if (failed) ponds_failed = 1;
     if (!failed && ponds_path && write_inventory(ponds_path, &inv, st.cellarea)) ponds_failed = 1;
     if (!failed && rims_path && write_rims(rims_path, &inv)) ponds_failed = 1;
     if (!failed && catch_path && write_catchments(catch_path, &inv, st.cellarea)) ponds_failed = 1;
+    if (!failed && outlets_path && write_outlets(outlets_path, &inv, st.cellarea)) ponds_failed = 1;
     free(inv.rows);
     free(inv.rims);
     free(inv.catch);
+    free(inv.outlets);
     phase("pond inventory");
   }
   int64_t guard_bad = inv.guard_bad;

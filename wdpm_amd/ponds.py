@@ -1,6 +1,7 @@
-"""ctypes binding of include/wdpm_ponds.h, include/wdpm_group_ponds.h, include/wdpm_pond_rims.h, include/wdpm_group_pond_rims.h
-and include/wdpm_pond_catchments.h: the pond inventory of a context's current water raster, of a raster spread over the row blocks
-of a rowblock.Group, the rim of every pond of either, and the catchment of every pond of a whole raster.
+"""ctypes binding of include/wdpm_ponds.h, include/wdpm_group_ponds.h, include/wdpm_pond_rims.h, include/wdpm_group_pond_rims.h,
+include/wdpm_pond_catchments.h and include/wdpm_pond_outlets.h: the pond inventory of a context's current water raster, of a raster
+spread over the row blocks of a rowblock.Group, the rim of every pond of either, and the catchment and the outlet of every pond of a
+whole raster.
 
 Product library only (the symbols are not part of the ABI of include/wdpm.h, and ``capi.SYMBOLS`` does not list them).
 
@@ -14,6 +15,9 @@ Product library only (the symbols are not part of the ABI of include/wdpm.h, and
         n = ponds.label_catchments(0.001)   # all of the above, and which pond every dry cell drains to
         basins = ponds.basins()     # int32, padded: k > 0 pond k or its catchment, 0 drains to a pit, -1 no level
         catch = ponds.catchments()  # contributing cells, inflow cells, head level, bounding box (CATCH_DTYPE)
+        n = ponds.label_outlets(0.001)      # all of the above, and where every basin spills
+        outlets = ponds.outlets()   # pour level, the pass (from, to, into which basin), divide, flooded cells, storage left (OUTLET_DTYPE)
+        headroom = outlets["pour_level"] - rims["surface_max"]
 
     with rowblock.Group(...) as grp, GroupPonds(grp) as ponds:     # the same calls, the same answer, every rank labelled in place
         n = ponds.label(0.001)
@@ -33,6 +37,7 @@ VOLUME_QUANTUM = 2.0 ** -24   # metres per unit of volume_q
 PHASES = ("mask", "merge", "flatten", "scan", "table", "finish")   # wdpm_ponds_phase_ms
 RIM_PHASES = ("rims", "locate")                                    # wdpm_rims_phase_ms
 CATCH_PHASES = ("receivers", "jump", "tally")                      # wdpm_catch_phase_ms
+OUTLET_PHASES = ("passes", "locate")                               # wdpm_outlets_phase_ms
 
 
 class PondStruct(C.Structure):
@@ -110,6 +115,31 @@ CATCH_SYMBOLS = {
 }
 
 
+class OutletStruct(C.Structure):
+    """struct wdpm_pond_outlet"""
+    _fields_ = [("pour_level", C.c_double), ("from_row", C.c_int32), ("from_col", C.c_int32), ("to_row", C.c_int32),
+                ("to_col", C.c_int32), ("to_basin", C.c_int32), ("reserved", C.c_int32), ("divide_cells", C.c_int64),
+                ("fill_cells", C.c_int64), ("fill_q", C.c_uint64)]
+
+
+class OutletStatsStruct(C.Structure):
+    """struct wdpm_pond_outlet_stats"""
+    _fields_ = [("ponds", C.c_int64), ("no_outlet", C.c_int64), ("to_land", C.c_int64), ("divide_cells", C.c_int64)]
+
+
+OUTLET_DTYPE = np.dtype([("pour_level", "<f8"), ("from_row", "<i4"), ("from_col", "<i4"), ("to_row", "<i4"), ("to_col", "<i4"),
+                         ("to_basin", "<i4"), ("reserved", "<i4"), ("divide_cells", "<i8"), ("fill_cells", "<i8"), ("fill_q", "<u8")])
+assert OUTLET_DTYPE.itemsize == C.sizeof(OutletStruct) == 56
+
+# every symbol include/wdpm_pond_outlets.h declares
+OUTLET_SYMBOLS = {
+    "wdpm_outlets_label": (C.c_int, [_vp, C.c_double, C.POINTER(C.c_int64)]),
+    "wdpm_outlets_table": (C.c_int, [_vp, _vp, C.c_int64]),
+    "wdpm_outlets_stats": (C.c_int, [_vp, C.POINTER(OutletStatsStruct)]),
+    "wdpm_outlets_phase_ms": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+}
+
+
 class GroupStatsStruct(C.Structure):
     """struct wdpm_group_pond_stats"""
     _fields_ = [("ranks", C.c_int64), ("ponds", C.c_int64), ("local_ponds", C.c_int64), ("stitch_unions", C.c_int64),
@@ -149,7 +179,7 @@ def bind(lib: capi.Lib):
     if getattr(lib, "_ponds_bound", False):
         return lib.dll
     for name, (res, args) in list(SYMBOLS.items()) + list(GROUP_SYMBOLS.items()) + list(RIM_SYMBOLS.items()) + \
-            list(GROUP_RIM_SYMBOLS.items()) + list(CATCH_SYMBOLS.items()):
+            list(GROUP_RIM_SYMBOLS.items()) + list(CATCH_SYMBOLS.items()) + list(OUTLET_SYMBOLS.items()):
         try:
             fn = getattr(lib.dll, name)
         except AttributeError:
@@ -160,7 +190,8 @@ def bind(lib: capi.Lib):
     return lib.dll
 
 
-_LABELLED_BY = {"table": "label", "rims": "label_rims", "catchments": "label_catchments"}   # the call a table method reads
+# the call a table method reads
+_LABELLED_BY = {"table": "label", "rims": "label_rims", "catchments": "label_catchments", "outlets": "label_outlets"}
 
 
 class _Handle:
@@ -294,6 +325,25 @@ class Ponds(_Handle):
         """milliseconds of the receiver pass, the jump rounds and the tally of the last label_catchments() (handles made with
         WDPM_PONDS_TIMING=1)"""
         return self._phase_ms(self.dll.wdpm_catch_phase_ms, CATCH_PHASES)
+
+    def label_outlets(self, min_depth: float) -> int:
+        """label_catchments(min_depth), then the outlet pass on the same water; table(), labels(), stats(), rims(), basins() and
+        catchments() answer as after label_catchments()."""
+        return self._label(self.dll.wdpm_outlets_label, min_depth)
+
+    def outlets(self, capacity: int | None = None) -> np.ndarray:
+        """One row per pond (OUTLET_DTYPE) of the last label_outlets(); fails after any lesser label call.  Coordinates are padded;
+        a pond whose basin meets no other has pour_level +inf, coordinates -1, to_basin -1 and zeros.  fill_q counts in
+        VOLUME_QUANTUM metres, like volume_q."""
+        return self._table(self.dll.wdpm_outlets_table, OUTLET_DTYPE, "outlets", capacity)
+
+    def outlet_stats(self) -> dict:
+        return self._stats(self.dll.wdpm_outlets_stats, OutletStatsStruct)
+
+    def outlet_phase_ms(self) -> dict:
+        """milliseconds of the pass over the pairs and of the locate pass of the last label_outlets() (handles made with
+        WDPM_PONDS_TIMING=1)"""
+        return self._phase_ms(self.dll.wdpm_outlets_phase_ms, OUTLET_PHASES)
 
 
 class GroupPonds(_Handle):
