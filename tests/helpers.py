@@ -45,3 +45,11 @@ def random_case(seed, R, C, missing_frac=0.05, dry_frac=0.3, depth=0.3):
     water = np.where(rng.random((R, C)) < dry_frac, 0.0, depth * rng.random((R, C)))
     water = np.where(dem > missing, water, 0.0)
     return dem, water, missing
+
+
+def rough_dem(R, Cc, seed, step=0.0):
+    """hills a few cells across with noise on them; `step` quantises it, so that ties decide"""
+    rng = np.random.default_rng(seed)
+    y, x = np.mgrid[0:R, 0:Cc]
+    dem = 500.0 + 2.0 * np.sin(x / 5.1) * np.cos(y / 4.3) + rng.normal(0, 0.05, (R, Cc)) - 0.01 * (x + y)
+    return np.round(dem / step) * step if step else np.round(dem, 4)

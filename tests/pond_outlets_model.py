@@ -70,7 +70,7 @@ def outlets(labels, dem, w, pond_table, basin=None):
         table["to_row"][p] = a[first] // ncp + off[:, 0]
         table["to_col"][p] = a[first] % ncp + off[:, 1]
         table["to_basin"][p] = basin[table["to_row"][p], table["to_col"][p]]
-        divide = np.unique(np.stack([k, a], axis=1), axis=0)[:, 0]
+        divide = np.unique(k * (rows * ncp) + a) // (rows * ncp)      # distinct (pond, a) as one int64 each: below 2^62
         table["divide_cells"] = np.bincount(divide - 1, minlength=n)
     # the fill: cells of the basin strictly below the outlet
     inside = basin > 0

@@ -69,9 +69,9 @@ def rims(labels, dem, w, n):
                 continue
             other = big[dr:dr + rows, dc:dc + ncp]
             hit = (other > 0) & ~pond
-            pairs.append(np.stack([cell[hit], other[hit]], axis=1))
-    pairs = np.unique(np.concatenate(pairs), axis=0)
-    idx, k = pairs[:, 0], pairs[:, 1] - 1
+            pairs.append(cell[hit] * (n + 1) + other[hit])       # one int64 per pair: cells * (n + 1) < 2^62
+    pairs = np.unique(np.concatenate(pairs))
+    idx, k = pairs // (n + 1), pairs % (n + 1) - 1
     is_wall = wall.ravel()[idx]
     table["wall_cells"] = np.bincount(k[is_wall], minlength=n)
     idx, k = idx[~is_wall], k[~is_wall]

@@ -23,10 +23,12 @@ def pond_cells(dem_valid, w, min_depth):
     return wet
 
 
-def _row_runs(wet_row):
-    """[start, end) pairs of the set stretches of one row"""
-    d = np.diff(np.concatenate(([0], wet_row.astype(np.int8), [0])))
-    return np.flatnonzero(d == 1), np.flatnonzero(d == -1)
+def _runs(wet):
+    """row, start and end (exclusive) of the set stretches of every row, in row-major order"""
+    d = np.diff(wet.astype(np.int8), axis=1, prepend=0, append=0)
+    row, s = np.nonzero(d == 1)
+    _, e = np.nonzero(d == -1)          # the k-th end belongs to the k-th start: both come in row-major order
+    return row, s, e
 
 
 def _find(parent, x):
@@ -40,30 +42,23 @@ def inventory(dem_valid, w, min_depth):
     w = np.asarray(w, dtype=np.float64)
     wet = pond_cells(dem_valid, w, min_depth)
     rows, ncp = wet.shape
-    run_row, run_s, run_e = [], [], []
-    parent = []
-    prev = (0, 0)                       # run numbers [lo, hi) of the row above
-    for r in range(rows):
-        s, e = _row_runs(wet[r])
-        lo = len(run_row)
-        for a, b in zip(s.tolist(), e.tolist()):
-            run_row.append(r)
-            run_s.append(a)
-            run_e.append(b)
-            parent.append(len(parent))
-        hi = len(run_row)
+    run_row, run_s, run_e = _runs(wet)
+    parent = list(range(len(run_row)))
+    first_of = np.searchsorted(run_row, np.arange(rows + 1)).tolist()      # run numbers [first_of[r], first_of[r + 1]) lie in row r
+    has = np.diff(first_of) > 0
+    s_of, e_of = run_s.tolist(), run_e.tolist()
+    for r in (np.flatnonzero(has[1:] & has[:-1]) + 1).tolist():            # rows with runs under a row with runs
         # 8-connectivity: run [a, b) touches a run [c, d) of the row above when c < b + 1 and a < d + 1
-        i, j = prev[0], lo
-        while i < prev[1] and j < hi:
-            if run_s[i] <= run_e[j] and run_s[j] <= run_e[i]:
+        i, lo, j, hi = first_of[r - 1], first_of[r], first_of[r], first_of[r + 1]
+        while i < lo and j < hi:
+            if s_of[i] <= e_of[j] and s_of[j] <= e_of[i]:
                 ra, rb = _find(parent, i), _find(parent, j)
                 if ra != rb:
                     parent[max(ra, rb)] = min(ra, rb)
-            if run_e[i] < run_e[j]:
+            if e_of[i] < e_of[j]:
                 i += 1
             else:
                 j += 1
-        prev = (lo, hi)
     nruns = len(run_row)
     labels = np.zeros((rows, ncp), dtype=np.int32)
     if nruns == 0:
@@ -73,15 +68,14 @@ def inventory(dem_valid, w, min_depth):
     is_root = root == np.arange(nruns)
     number = np.cumsum(is_root)         # 1-based pond number at each root
     run_label = number[root].astype(np.int32)
-    for k in range(nruns):
-        labels[run_row[k], run_s[k]:run_e[k]] = run_label[k]
+    labels[wet] = np.repeat(run_label, run_e - run_s)        # pond cells and runs are both in row-major order
     n = int(is_root.sum())
     table = np.zeros(n, dtype=POND_DTYPE)
     rr, cc = np.nonzero(labels)
     lab = labels[rr, cc].astype(np.int64) - 1
     first = np.flatnonzero(is_root)
-    table["first_row"] = np.array(run_row)[first]
-    table["first_col"] = np.array(run_s)[first]
+    table["first_row"] = run_row[first]
+    table["first_col"] = run_s[first]
     table["cells"] = np.bincount(lab, minlength=n)
     q = np.rint(w[rr, cc] * 16777216.0)          # exact product, round half to even
     vol = np.zeros(n, dtype=np.uint64)

@@ -11,7 +11,7 @@ two blocks; a wave owns a 64-column segment, so padded column 63 is lane 63 and 
 import numpy as np
 import pytest
 
-from helpers import find_drain, n_bit_diff, pad
+from helpers import find_drain, n_bit_diff, pad, rough_dem
 from pond_catchments_model import assert_same_catchments, catchments, descent_length
 from pond_rims_model import device_dem
 from ponds_model import assert_same, inventory
@@ -180,14 +180,6 @@ def test_one_catchment_over_all_segments_and_strips(hip, monkeypatch, R, Cc):
 
 
 # ---- films, signed zeros, walls, NaN water ------------------------------------------------------------------------------------------
-def rough_dem(R, Cc, seed, step=0.0):
-    """hills a few cells across with noise on them; `step` quantises it, so that ties decide"""
-    rng = np.random.default_rng(seed)
-    y, x = np.mgrid[0:R, 0:Cc]
-    dem = 500.0 + 2.0 * np.sin(x / 5.1) * np.cos(y / 4.3) + rng.normal(0, 0.05, (R, Cc)) - 0.01 * (x + y)
-    return np.round(dem / step) * step if step else np.round(dem, 4)
-
-
 @pytest.mark.parametrize("R,Cc", SHAPES)
 def test_films_and_nan_water_on_the_slopes(hip, R, Cc):
     rng = np.random.default_rng(R)

@@ -11,7 +11,7 @@ owns a 64-column segment, so padded column 63 is lane 63 and padded column 64 la
 import numpy as np
 import pytest
 
-from helpers import find_drain, n_bit_diff, pad
+from helpers import find_drain, n_bit_diff, pad, rough_dem
 from pond_catchments_model import catchments
 from pond_outlets_model import TooDeep, assert_invariants, assert_same_outlets, outlets
 from pond_rims_model import device_dem
@@ -304,14 +304,6 @@ def test_a_600_m_pit_fails_and_the_handle_stays_usable(hip):
 
 
 # ---- rows that are skipped -----------------------------------------------------------------------------------------------------------
-def rough_dem(R, Cc, seed, step=0.0):
-    """hills a few cells across with noise on them; `step` quantises it, so that ties decide"""
-    rng = np.random.default_rng(seed)
-    y, x = np.mgrid[0:R, 0:Cc]
-    dem = 500.0 + 2.0 * np.sin(x / 5.1) * np.cos(y / 4.3) + rng.normal(0, 0.05, (R, Cc)) - 0.01 * (x + y)
-    return np.round(dem / step) * step if step else np.round(dem, 4)
-
-
 def ramp(R, Cc):
     """a plane that falls towards the last column, whose last two columns are one pond: one basin, every row skipped"""
     r, c = grid(R, Cc)

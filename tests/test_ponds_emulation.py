@@ -12,7 +12,9 @@ CASES = [(20, 70, 0.40, 1, 0),        # two segments, the second nearly empty
          (3, 700, 0.50, 5, 2),        # wide and flat
          (40, 1, 0.70, 6, 5),         # one column
          (20, 190, 1.00, 8, 7)]       # all wet but the NODATA cells: one table row takes everything
-# (more than 1024 segments - a second block of the scan - cost 20 s here; tests/test_ponds.py has them in most of its cases)
+# (more than 1024 segments - a second block of the scan - cost 20 s here as a whole label call.  The three scan kernels alone,
+# on made-up counts, run past their tile edges and past 262 144 segments - the second trip of ponds_scan_sums_kernel and its
+# carry - in tests/test_pond_scan_emulation.py; tests/test_pond_tall_rasters.py takes whole label calls there on the GPU.)
 
 
 @pytest.fixture(scope="module")
