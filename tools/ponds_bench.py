@@ -17,6 +17,10 @@
                       label_catchments, interleaved - the three catchment phases beside the table phase of the SAME calls, their
                       ratios and rounds, and the label, table and rim phases of either call side by side (default --out
                       profiles/r14/pond_catchments.json)
+                      With --devices: GroupPonds.label_catchments (include/wdpm_group_pond_catchments.h) - per-rank receiver, jump
+                      and tally phases and their sums over the ranks, the host's resolve_ms, exits, crossings and remote, beside the
+                      table phase; then the whole-raster call on the same water in the same process, the yardstick of those sums
+                      (default --out profiles/r16/pond_catchments_group.json)
     ... --outlets     the outlets of the ponds as well (include/wdpm_pond_outlets.h): five more timed calls of label_outlets, the two
                       outlet phases beside the table phase of the SAME calls, their ratios, and their rates under the byte model
                       of 20 B per cell and pass (basin, dem, w) and of 4 B per cell (a row that holds no pass reads its basins
@@ -206,6 +210,25 @@ def group_job(hip, a, bd, bw, iters, rec):
             rec["wet_cells"] = int(p.table()["cells"].sum())
             if a.rims:
                 group_rims_job(p, rec, len(devices))
+            if a.catchments:
+                group_catchments_job(p, rec, len(devices))
+    if a.catchments:                                           # the yardstick: the whole-raster call on the same water, same process
+        with hip.context(module="add", nrows=n, ncols=n, missingvalue=MISS) as ctx:
+            ctx.upload(bd, bw)
+            if iters > 0:
+                ctx.run_block(iters, 0.005 / 1000)
+            with Ponds(ctx) as p:
+                p.label_catchments(0.001)
+                phases = {k: [] for k in CATCH_PHASES}
+                for _ in range(5):
+                    p.label_catchments(0.001)
+                    for k, v in p.catchment_phase_ms().items():
+                        phases[k].append(v)
+                whole = {k: statistics.median(v) for k, v in phases.items()}
+                c = rec["catchments"]
+                c.update(whole_raster_phase_ms=whole, whole_raster_phase_ms_all=phases, whole_raster_stats=p.catchment_stats())
+                c["sum_over_ranks_over_whole_raster"] = {k: c["phase_sum_over_ranks_ms"][k] / whole[k] if whole[k] > 0 else None for k in CATCH_PHASES}
+                c["all_phases_sum_over_ranks_over_whole_raster"] = sum(c["phase_sum_over_ranks_ms"].values()) / sum(whole.values())
 
 
 def group_rims_job(p, rec, nranks):
@@ -238,6 +261,31 @@ def group_rims_job(p, rec, nranks):
                        spilling=int((rims["rim_level"] - rims["surface_max"] <= 0).sum()), guard_bad=p.guard_bad())
 
 
+def group_catchments_job(p, rec, nranks):
+    """after the label calls: one untimed label_catchments (allocates every rank's links, keys and rows), five timed ones"""
+    p.label_catchments(0.001)
+    wall, resolve = [], []
+    phases = [{k: [] for k in CATCH_PHASES} for _ in range(nranks)]
+    table_ms = [[] for _ in range(nranks)]
+    for _ in range(5):
+        t0 = time.perf_counter()
+        p.label_catchments(0.001)
+        wall.append((time.perf_counter() - t0) * 1e3)
+        resolve.append(p.catchment_stats()["resolve_ms"])
+        for i in range(nranks):
+            for k, v in p.catchment_phase_ms(i).items():
+                phases[i][k].append(v)
+            table_ms[i].append(p.phase_ms(i)["table"])
+    catch, stats = p.catchments(), p.catchment_stats()
+    sums = {k: statistics.median([sum(phases[i][k][j] for i in range(nranks)) for j in range(5)]) for k in CATCH_PHASES}   # per call, over ranks
+    rec["catchments"] = dict(label_catchments_wall_ms=statistics.median(wall), label_catchments_wall_ms_all=wall,
+                             rank_phase_ms=[{k: statistics.median(v) for k, v in ph.items()} for ph in phases], rank_phase_ms_all=phases,
+                             phase_sum_over_ranks_ms=sums, rank_table_ms_same_calls=[statistics.median(v) for v in table_ms],
+                             resolve_ms=statistics.median(resolve), resolve_ms_all=resolve, stats=stats, exits=stats["exits"],
+                             crossings=stats["crossings"], remote=stats["remote"], caught_cells=int(catch["catch_cells"].sum()),
+                             inflow_cells=int(catch["inflow_cells"].sum()), guard_bad=p.guard_bad())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("job", choices=["wet", "ponds", "noise"])
@@ -254,13 +302,12 @@ def main():
     ap.add_argument("--iterations", type=int, help="iterations before the inventory, instead of the job's own")
     a = ap.parse_args()
     if not a.out:
-        a.out = os.path.join(ROOT, "profiles", *(("r13", "pond_rims_group.json") if a.devices and a.rims else
+        a.out = os.path.join(ROOT, "profiles", *(("r16", "pond_catchments_group.json") if a.devices and a.catchments else
+                                                  ("r13", "pond_rims_group.json") if a.devices and a.rims else
                                                   ("r11", "ponds_group.json") if a.devices else
                                                   ("r15", "pond_outlets.json") if a.outlets else
                                                   ("r14", "pond_catchments.json") if a.catchments else
                                                   ("r12", "pond_rims.json") if a.rims else ("r10", "ponds.json")))
-    if a.catchments and a.devices:
-        raise SystemExit("--catchments: catchments are taken on whole rasters only (include/wdpm_pond_catchments.h)")
     if a.outlets and a.devices:
         raise SystemExit("--outlets: outlets are taken on whole rasters only (include/wdpm_pond_outlets.h)")
     hip = wdpm_amd.load_hip()

@@ -22,8 +22,13 @@
  *              rewrites the link raster in place into basin(c).  init takes each pond's box from its pond-table row, finish turns
  *              the head key into a double
  *
- * tests/catch_emu_main.cpp compiles the kernels for the host under sanitizers with WDPM_PONDS_EMULATION defined, as
- * tests/rims_emu_main.cpp does with wdpm_pond_rims.hip, and leaves the host half out.
+ * Over row blocks (include/wdpm_group_pond_catchments.h) every rank runs the same bodies over its owned rows (kRows): the one row
+ * beyond either end is known by its whole-raster labels (the rims' upload) and by the level keys its owner wrote
+ * (catch_seam_keys_kernel), a receiver that is a slope cell of such a row makes the link an EXIT, the table is indexed through the
+ * rims' label -> slot table, and the tally looks up where the host found each exit to end (wdpm_catch_stitch.h).
+ *
+ * tests/catch_emu_main.cpp and tests/group_catch_emu_main.cpp compile the kernels for the host under sanitizers with
+ * WDPM_PONDS_EMULATION defined, as tests/rims_emu_main.cpp does with wdpm_pond_rims.hip, and leave the host half out.
  */
 #include "wdpm_ponds_priv.h"
 
@@ -34,6 +39,24 @@ namespace {
 constexpr unsigned long long kNoLevel = ~0ull;     /* no level's key: the image of a NaN no addition makes */
 constexpr int kLinkPit = -1;                       /* pond k is -1 - k */
 constexpr int kLinkNone = INT_MIN;
+constexpr int kExitBase = INT_MIN + 1;             /* row blocks: the exit (side, column) is kExitBase + side * ncp + column */
+
+/* What a row block's kernels know beyond a whole raster's (kRows; wave-uniform all of it): the owned rows [ra, rb) of the view,
+ * over which the strips are cut; which of view rows 0 and g.rows - 1 belong to a neighbour (halo bit 0: the one above, bit 1: the
+ * one below) - of those the labels and masks are the rims' upload, the level keys come from nkeys (2 x ncp, written by their
+ * owners) and neither dem nor w is ever read; the table is indexed through slot_of; exit_basin (2 x ncp, the tally) says where
+ * each exit ends. */
+struct CatchRows {
+  int ra, rb, halo;
+  const unsigned long long *nkeys;
+  const int *slot_of;
+  const int *exit_basin;
+};
+
+template <bool kRows>
+__device__ __forceinline__ int catch_slot(const CatchRows &rw, int L) {
+  return kRows ? rw.slot_of[L] : L - 1;
+}
 
 __device__ __forceinline__ int load_link(const int *p, int i) {
   return __hip_atomic_load(p + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -69,14 +92,28 @@ __device__ __forceinline__ CatchWin catch_open(const unsigned long long *__restr
 
 /* Keys and labels of row r: a dry lane's label is 0 by its mask; border cells and cells beyond the raster have no level and are
  * not read.  Every load is issued before the first is used: dem and w of a cell do not wait for each other. */
+template <bool kRows>
 __device__ __forceinline__ void catch_fill(CatchWin &x, const double *__restrict__ w, const double *__restrict__ dem,
-                                           const int *__restrict__ labels, const Geom &g, int r, int c, int lane) {
+                                           const int *__restrict__ labels, const Geom &g, int r, int c, int lane, const CatchRows &rw) {
   if (x.has) return;
   x.has = true;
-  if (r < 1 || r > g.rows - 2) return;
+  const bool halo = kRows && ((r == 0 && (rw.halo & 1)) || (r == g.rows - 1 && (rw.halo & 2)));     /* a neighbour's row */
+  if (!halo && (r < 1 || r > g.rows - 2)) return;
   const int ce = lane == 0 ? c - 1 : c + 1;                  /* the cell beside the segment: lanes 0 and 63 */
   const bool own = c >= 1 && c <= g.ncp - 2, beside = (lane == 0 || lane == 63) && ce >= 1 && ce <= g.ncp - 2;
   const int idx = r * g.ncp + c, idxe = r * g.ncp + ce;
+  if (kRows && halo) {                                       /* its owner's keys; dem and w of a halo row are not current */
+    const unsigned long long *nk = rw.nkeys + (r == 0 ? 0 : g.ncp);
+    if (own) {
+      x.key = nk[c];
+      if (bit(x.m, lane)) x.lbl = labels[idx];
+    }
+    if (beside) {
+      x.ek = nk[ce];
+      x.el = labels[idxe];
+    }
+    return;
+  }
   double e = __builtin_inf(), d = 0.0, ee = __builtin_inf(), de = 0.0;
   if (own) {
     e = dem[idx];
@@ -94,15 +131,16 @@ __device__ __forceinline__ void catch_fill(CatchWin &x, const double *__restrict
 
 /* ---- receivers ------------------------------------------------------------------------------------------------------------- */
 /* Everything that steers the loops is wave-uniform. */
-__global__ __launch_bounds__(kBlock) void catch_receivers_kernel(const double *__restrict__ w, const double *__restrict__ dem,
-                                                                 const unsigned long long *__restrict__ masks,
-                                                                 const int *__restrict__ labels, Geom g, int rpw, int nwaves,
-                                                                 int *__restrict__ link, CatchRow *table, CatchStatus *st) {
+template <bool kRows>
+__device__ __forceinline__ void catch_receivers_body(const double *__restrict__ w, const double *__restrict__ dem,
+                                                     const unsigned long long *__restrict__ masks, const int *__restrict__ labels,
+                                                     const Geom &g, int rpw, int nwaves, int *__restrict__ link,
+                                                     CatchRow *table, CatchStatus *st, const CatchRows &rw) {
   const int wid = blockIdx.x * kWaves + (threadIdx.x >> 6);
   if (wid >= nwaves) return;
   const int lane = threadIdx.x & 63;
   const int strip = wid / g.nsc, s = wid - strip * g.nsc;
-  const int r0 = strip * rpw, r1 = min(r0 + rpw, g.rows);
+  const int r0 = (kRows ? rw.ra : 0) + strip * rpw, r1 = min(r0 + rpw, kRows ? rw.rb : g.rows);
   const int c = s * kSeg + lane;
   const bool inside = c < g.ncp;
   const unsigned long long edgem = __ballot(c < 1 || c > g.ncp - 2);     /* border columns and what lies beyond the raster */
@@ -118,9 +156,9 @@ __global__ __launch_bounds__(kBlock) void catch_receivers_kernel(const double *_
       if (inside) link[idx] = wet ? -1 - labels[idx] : kLinkNone;
       continue;
     }
-    catch_fill(up, w, dem, labels, g, r - 1, c, lane);
-    catch_fill(cur, w, dem, labels, g, r, c, lane);
-    catch_fill(dn, w, dem, labels, g, r + 1, c, lane);
+    catch_fill<kRows>(up, w, dem, labels, g, r - 1, c, lane, rw);
+    catch_fill<kRows>(cur, w, dem, labels, g, r, c, lane, rw);
+    catch_fill<kRows>(dn, w, dem, labels, g, r + 1, c, lane, rw);
     /* the eight neighbours in the order of their padded index */
     const unsigned long long nk[8] = {lane_from_left(up.key, up.ek, lane),   up.key, lane_from_right(up.key, up.ek, lane),
                                       lane_from_left(cur.key, cur.ek, lane),         lane_from_right(cur.key, cur.ek, lane),
@@ -130,7 +168,7 @@ __global__ __launch_bounds__(kBlock) void catch_receivers_kernel(const double *_
                        lane_from_left(dn.lbl, dn.el, lane),   dn.lbl, lane_from_right(dn.lbl, dn.el, lane)};
     const bool slope = inside && !wet && cur.key != kNoLevel;
     unsigned long long best = cur.key;     /* strictly below the cell's own, the first of equals */
-    int to = 0, to_label = 0;
+    int to = 0, to_label = 0, to_dr = 0, to_dc = 0;
     bool found = false;
 #pragma unroll
     for (int i = 0; i < 8; i++) {
@@ -140,10 +178,15 @@ __global__ __launch_bounds__(kBlock) void catch_receivers_kernel(const double *_
         to = idx + dr * g.ncp + dc;
         to_label = nl[i];
         found = true;
+        if (kRows) { to_dr = dr; to_dc = dc; }
       }
     }
     const bool pit = slope && !found;
     const int inflow = slope && found ? to_label : 0;      /* the pond this cell's water enters, 0: none */
+    if (kRows) {                                           /* a receiver in a neighbour's row that is no pond cell: the descent exits */
+      const bool up_out = r == 1 && (rw.halo & 1), dn_out = r == g.rows - 2 && (rw.halo & 2);
+      if ((to_dr < 0 && up_out) || (to_dr > 0 && dn_out)) to = kExitBase + (to_dr > 0 ? g.ncp : 0) + c + to_dc;
+    }
     if (inside) link[idx] = wet ? -1 - cur.lbl : !slope ? kLinkNone : pit ? kLinkPit : inflow ? -1 - inflow : to;
     n_slope += (unsigned long long)__popcll(__ballot(slope));
     n_pit += (unsigned long long)__popcll(__ballot(pit));
@@ -156,7 +199,7 @@ __global__ __launch_bounds__(kBlock) void catch_receivers_kernel(const double *_
       const int L = __shfl(cand, __builtin_ctzll(pending));
       const unsigned long long hitm = __ballot(cand == L);
       if (cy_label != L) {                 /* down the rows: the same label goes on gathering, another one sends first */
-        if (cy_label != 0 && lane == 0) atomicAdd(&table[cy_label - 1].inflow_cells, cy_n);
+        if (cy_label != 0 && lane == 0) atomicAdd(&table[catch_slot<kRows>(rw, cy_label)].inflow_cells, cy_n);
         cy_label = L;
         cy_n = 0ull;
       }
@@ -165,10 +208,55 @@ __global__ __launch_bounds__(kBlock) void catch_receivers_kernel(const double *_
     }
   }
   if (lane == 0) {
-    if (cy_label != 0) atomicAdd(&table[cy_label - 1].inflow_cells, cy_n);
+    if (cy_label != 0) atomicAdd(&table[catch_slot<kRows>(rw, cy_label)].inflow_cells, cy_n);
     if (n_slope) atomicAdd(&st->slope, n_slope);
     if (n_pit) atomicAdd(&st->pit, n_pit);
   }
+}
+
+__global__ __launch_bounds__(kBlock) void catch_receivers_kernel(const double *__restrict__ w, const double *__restrict__ dem,
+                                                                 const unsigned long long *__restrict__ masks,
+                                                                 const int *__restrict__ labels, Geom g, int rpw, int nwaves,
+                                                                 int *__restrict__ link, CatchRow *table, CatchStatus *st) {
+  catch_receivers_body<false>(w, dem, masks, labels, g, rpw, nwaves, link, table, st, CatchRows());
+}
+
+/* the same over the owned rows of a row block's view */
+__global__ __launch_bounds__(kBlock) void catch_receivers_rows_kernel(const double *__restrict__ w, const double *__restrict__ dem,
+                                                                      const unsigned long long *__restrict__ masks,
+                                                                      const int *__restrict__ labels, Geom g, int rpw, int nwaves,
+                                                                      int *__restrict__ link, CatchRow *table, CatchStatus *st,
+                                                                      CatchRows rw) {
+  catch_receivers_body<true>(w, dem, masks, labels, g, rpw, nwaves, link, table, st, rw);
+}
+
+/* Row blocks, before the receivers: the level keys of the rank's first and last owned row (view rows 1 and g.rows - 2, as the seam
+ * labels), 2 x ncp, for the neighbours - from the water that was labelled, which is on the device by now; and a terminal into the
+ * links of the neighbours' rows, which no descent of this rank enters but every jump round looks at. */
+__global__ __launch_bounds__(kBlock) void catch_seam_keys_kernel(const double *__restrict__ w, const double *__restrict__ dem, Geom g,
+                                                                 int halo, unsigned long long *__restrict__ keys, int *__restrict__ link) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= 2 * g.ncp) return;
+  const int side = i >= g.ncp, c = i - side * g.ncp, r = side ? g.rows - 2 : 1;
+  keys[i] = c >= 1 && c <= g.ncp - 2 ? level_of(w, dem, g, r, c) : kNoLevel;
+  if (halo & (1 << side)) link[(side ? g.rows - 1 : 0) * g.ncp + c] = kLinkNone;
+}
+
+/* row blocks: the table starts with empty boxes - the merge brings each pond's own */
+__global__ __launch_bounds__(kBlock) void catch_init_rows_kernel(CatchRow *t, long long n) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  CatchRow r;
+  r.catch_cells = r.inflow_cells = r.head_key = 0ull;
+  r.row_min = r.col_min = INT_MAX;
+  r.row_max = r.col_max = -1;
+  t[i] = r;
+}
+
+/* row blocks, before the tally: remote pond j takes slot base + j (its entry of slot_of held no slot before) */
+__global__ __launch_bounds__(kBlock) void catch_remote_slots_kernel(const int *__restrict__ remote, int nremote, int base, int *slot_of) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i < nremote) slot_of[remote[i]] = base + i;
 }
 
 /* ---- jump ------------------------------------------------------------------------------------------------------------------ */
@@ -217,8 +305,9 @@ struct CatchCarry {
 };
 
 /* one lane sends a carry: the extrema through atomic_min_if / atomic_max_if */
-__device__ __forceinline__ void catch_send(CatchRow *table, const CatchCarry &c) {
-  CatchRow *t = table + (c.label - 1);
+template <bool kRows>
+__device__ __forceinline__ void catch_send(CatchRow *table, const CatchCarry &c, const CatchRows &rw) {
+  CatchRow *t = table + catch_slot<kRows>(rw, c.label);
   atomicAdd(&t->catch_cells, c.cells);
   atomic_max_if(&t->head_key, c.key);
   atomic_min_if(&t->row_min, c.row_min);
@@ -227,17 +316,18 @@ __device__ __forceinline__ void catch_send(CatchRow *table, const CatchCarry &c)
   atomic_max_if(&t->col_max, c.col_max);
 }
 
-__global__ __launch_bounds__(kBlock) void catch_tally_kernel(const double *__restrict__ w, const double *__restrict__ dem,
-                                                             const unsigned long long *__restrict__ masks, Geom g, int rpw,
-                                                             int nwaves, int *link, CatchRow *table, CatchStatus *st) {
+template <bool kRows>
+__device__ __forceinline__ void catch_tally_body(const double *__restrict__ w, const double *__restrict__ dem,
+                                                 const unsigned long long *__restrict__ masks, const Geom &g, int rpw,
+                                                 int nwaves, int *link, CatchRow *table, CatchStatus *st, const CatchRows &rw) {
   const int wid = blockIdx.x * kWaves + (threadIdx.x >> 6);
   if (wid >= nwaves) return;
   const int lane = threadIdx.x & 63;
   const int strip = wid / g.nsc, s = wid - strip * g.nsc;
-  const int r0 = strip * rpw, r1 = min(r0 + rpw, g.rows);
+  const int r0 = (kRows ? rw.ra : 0) + strip * rpw, r1 = min(r0 + rpw, kRows ? rw.rb : g.rows);
   const int c = s * kSeg + lane;
   const bool inside = c < g.ncp;
-  unsigned long long n_unponded = 0ull;
+  unsigned long long n_unponded = 0ull, n_exits = 0ull;
   CatchCarry cy;
   cy.label = 0; cy.cells = cy.key = 0ull;
   cy.row_min = cy.col_min = INT_MAX; cy.row_max = cy.col_max = -1;
@@ -245,7 +335,12 @@ __global__ __launch_bounds__(kBlock) void catch_tally_kernel(const double *__res
   for (int r = r0; r < r1; r++) {
     const unsigned long long m = masks[(long long)r * g.nsc + s];
     const int idx = r * g.ncp + c;
-    const int v = inside ? link[idx] : kLinkNone;
+    int v = inside ? link[idx] : kLinkNone;
+    if (kRows) {                                           /* an exit: one look at where the host found it to end */
+      const bool exits = v != kLinkNone && v <= kExitBase + (2 * g.ncp - 1);
+      n_exits += (unsigned long long)__popcll(__ballot(exits));
+      if (exits) v = rw.exit_basin[v - kExitBase];
+    }
     const int basin = v == kLinkNone ? -1 : -1 - v;        /* a pit's -1 is 0, pond k's -1 - k is k */
     if (inside) link[idx] = basin;
     const bool slope = !bit(m, lane) && v != kLinkNone;
@@ -262,7 +357,7 @@ __global__ __launch_bounds__(kBlock) void catch_tally_kernel(const double *__res
       const unsigned long long hi = wave_max(cand == L ? key : 0ull);
       const int cmin = s * kSeg + __builtin_ctzll(hitm), cmax = s * kSeg + 63 - __clzll((long long)hitm);
       if (cy.label != L) {                  /* down the rows: the same label goes on gathering, another one sends first */
-        if (cy.label != 0 && lane == 0) catch_send(table, cy);
+        if (cy.label != 0 && lane == 0) catch_send<kRows>(table, cy, rw);
         cy.label = L; cy.cells = cy.key = 0ull;
         cy.row_min = r; cy.col_min = INT_MAX; cy.row_max = cy.col_max = -1;
       }
@@ -275,9 +370,24 @@ __global__ __launch_bounds__(kBlock) void catch_tally_kernel(const double *__res
     }
   }
   if (lane == 0) {
-    if (cy.label != 0) catch_send(table, cy);
+    if (cy.label != 0) catch_send<kRows>(table, cy, rw);
     if (n_unponded) atomicAdd(&st->unponded, n_unponded);
+    if (kRows && n_exits) atomicAdd(&st->exits, n_exits);
   }
+}
+
+__global__ __launch_bounds__(kBlock) void catch_tally_kernel(const double *__restrict__ w, const double *__restrict__ dem,
+                                                             const unsigned long long *__restrict__ masks, Geom g, int rpw,
+                                                             int nwaves, int *link, CatchRow *table, CatchStatus *st) {
+  catch_tally_body<false>(w, dem, masks, g, rpw, nwaves, link, table, st, CatchRows());
+}
+
+/* the same over the owned rows of a row block's view; rows of the table's boxes stay rows of the view (the merge shifts them) */
+__global__ __launch_bounds__(kBlock) void catch_tally_rows_kernel(const double *__restrict__ w, const double *__restrict__ dem,
+                                                                  const unsigned long long *__restrict__ masks, Geom g, int rpw,
+                                                                  int nwaves, int *link, CatchRow *table, CatchStatus *st,
+                                                                  CatchRows rw) {
+  catch_tally_body<true>(w, dem, masks, g, rpw, nwaves, link, table, st, rw);
 }
 
 }  // namespace
@@ -406,6 +516,362 @@ extern "C" int wdpm_catch_phase_ms(wdpm_ponds *h, double *ms) {
   if (!h->timing) return wdpm_fail("wdpm_catch_phase_ms: the handle records no events (set WDPM_PONDS_TIMING=1 before it is made)");
   if (!h->valid || !h->catch_valid) return wdpm_fail("wdpm_catch_phase_ms: %s", kNoTable);
   for (int i = 0; i < WDPM_CATCH_PHASES; i++) ms[i] = h->catch_ms[i];
+  return 0;
+}
+
+/* ---- row blocks (include/wdpm_group_pond_catchments.h) ----------------------------------------------------------------------- */
+#include <ctime>
+#include <string>
+
+#include "wdpm_catch_stitch.h"
+
+namespace {
+const char kNoGroupTable[] = "no catchment table: the last label call on this handle was not a wdpm_group_catch_label that succeeded";
+
+/* after a failure with work queued: let every rank's stream run dry, so that nothing still reads what the caller may free */
+int group_catch_drain(wdpm_group_ponds *h) {
+  std::string msg = wdpm_last_error();
+  for (wdpm_ponds *p : h->r)
+    if (hipSetDevice(p->x->p.device) == hipSuccess) (void)hipStreamSynchronize(p->x->stream);
+  return wdpm_fail("%s", msg.c_str());
+}
+
+double ms_between(const timespec &a, const timespec &b) { return (double)(b.tv_sec - a.tv_sec) * 1e3 + (double)(b.tv_nsec - a.tv_nsec) * 1e-6; }
+
+CatchRows rows_of(const wdpm_group_ponds *gh, int i) {
+  const wdpm_ponds *h = gh->r[i];
+  CatchRows rw;
+  rw.ra = gh->own_lo[i] - gh->view0[i];
+  rw.rb = rw.ra + gh->own_rows[i];
+  rw.halo = (i > 0 ? 1 : 0) | (i + 1 < gh->n ? 2 : 0);
+  rw.nkeys = h->d_ckeys + (size_t)2 * h->g.ncp;
+  rw.slot_of = h->d_slot_of;
+  rw.exit_basin = h->d_cexit;
+  return rw;
+}
+
+/* Rank i's seam keys behind its scan (group_label calls this for every rank before the first wait): they reach the host with the
+ * seam labels.  The rank's buffers are made here, at its first call. */
+int group_catch_seams(wdpm_group_ponds *gh, int i) {
+  wdpm_ponds *h = gh->r[i];
+  wdpm_ctx *x = h->x;
+  const Geom g = h->g;
+  const hipStream_t sm = x->stream;
+  const size_t ncp = (size_t)g.ncp;
+  const long long cells = (long long)g.rows * g.ncp;
+  HIP_TRY(hipSetDevice(x->p.device));
+  if (!h->d_link) {
+    const hipError_t e = guarded_malloc(h, (void **)&h->d_link, (size_t)cells * sizeof(int));
+    if (e != hipSuccess) { h->d_link = nullptr; return wdpm_fail("wdpm_group_catch_label: no device memory for the links of %lld cells: %s", cells, hipGetErrorString(e)); }
+  }
+  if (!h->d_cstat) {
+    hipError_t e = hipMalloc(&h->d_cstat, sizeof(CatchStatus));
+    if (e != hipSuccess) { h->d_cstat = nullptr; return wdpm_fail("wdpm_group_catch_label: no device memory for the status words: %s", hipGetErrorString(e)); }
+    e = hipHostMalloc(&h->h_cstat, sizeof(CatchStatus));
+    if (e != hipSuccess) { h->h_cstat = nullptr; (void)hipFree(h->d_cstat); h->d_cstat = nullptr; return wdpm_fail("wdpm_group_catch_label: no pinned host memory for the status words: %s", hipGetErrorString(e)); }
+  }
+  if (!h->d_ckeys) {
+    hipError_t e = guarded_malloc(h, (void **)&h->d_ckeys, 4 * ncp * sizeof(unsigned long long));
+    if (e != hipSuccess) { h->d_ckeys = nullptr; return wdpm_fail("wdpm_group_catch_label: no device memory for four rows of level keys: %s", hipGetErrorString(e)); }
+  }
+  if (!h->d_cexit) {
+    hipError_t e = guarded_malloc(h, (void **)&h->d_cexit, 4 * ncp * sizeof(int));
+    if (e != hipSuccess) { h->d_cexit = nullptr; return wdpm_fail("wdpm_group_catch_label: no device memory for four rows of exits: %s", hipGetErrorString(e)); }
+  }
+  if (!h->h_ckeys) {
+    const hipError_t e = hipHostMalloc(&h->h_ckeys, 4 * ncp * sizeof(unsigned long long));
+    if (e != hipSuccess) { h->h_ckeys = nullptr; return wdpm_fail("wdpm_group_catch_label: no pinned host memory for four rows of level keys: %s", hipGetErrorString(e)); }
+  }
+  if (!h->h_cexit) {
+    const hipError_t e = hipHostMalloc(&h->h_cexit, 6 * ncp * sizeof(int));
+    if (e != hipSuccess) { h->h_cexit = nullptr; return wdpm_fail("wdpm_group_catch_label: no pinned host memory for six rows of links: %s", hipGetErrorString(e)); }
+  }
+  const size_t off = (size_t)h->row_off * ncp;
+  const CatchRows rw = rows_of(gh, i);
+  hipLaunchKernelGGL(catch_seam_keys_kernel, dim3(blocks_for(2 * g.ncp, kBlock)), dim3(kBlock), 0, sm, x->d_w[x->cur] + off, x->d_dem + off,
+                     g, rw.halo, h->d_ckeys, h->d_link);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h->h_ckeys, h->d_ckeys, 2 * ncp * sizeof(unsigned long long), hipMemcpyDeviceToHost, sm));
+  return 0;
+}
+
+/* one batch of jump rounds of rank i with the look that follows it on its way: the counts, and the links of the rank's first and
+ * last owned row, which are final once the counts say so */
+int group_catch_batch(wdpm_ponds *h) {
+  const Geom g = h->g;
+  const hipStream_t sm = h->x->stream;
+  const long long cells = (long long)g.rows * g.ncp;
+  if (h->timing) HIP_TRY(hipEventRecord(h->catch_ev[2], sm));
+  for (int b = 0; b < kCatchBatch; b++, h->catch_rounds++)
+    hipLaunchKernelGGL(catch_jump_kernel, dim3(blocks_for(cells, kBlock)), dim3(kBlock), 0, sm, h->d_link, (int)cells, h->catch_rounds, h->d_cstat);
+  if (h->timing) HIP_TRY(hipEventRecord(h->catch_ev[3], sm));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h->h_cstat, h->d_cstat, sizeof(CatchStatus), hipMemcpyDeviceToHost, sm));
+  HIP_TRY(hipMemcpyAsync(h->h_cexit, h->d_link + (size_t)g.ncp, (size_t)g.ncp * sizeof(int), hipMemcpyDeviceToHost, sm));
+  HIP_TRY(hipMemcpyAsync(h->h_cexit + g.ncp, h->d_link + (size_t)(g.rows - 2) * g.ncp, (size_t)g.ncp * sizeof(int), hipMemcpyDeviceToHost, sm));
+  return 0;
+}
+
+/* Rank i's rim work, then its receivers and its first batch of jump rounds, behind its table kernels, nothing waited for. */
+int group_catch_rank(wdpm_group_ponds *gh, int i, const std::vector<std::vector<int>> &map, long long ponds) {
+  if (group_rims_rank(gh, i, map, ponds)) return 1;
+  wdpm_ponds *h = gh->r[i];
+  wdpm_ctx *x = h->x;
+  const Geom g = h->g;
+  const hipStream_t sm = x->stream;
+  const size_t ncp = (size_t)g.ncp;
+  if (!wdpm_catch_stitch::codes_fit(ponds, g.ncp))
+    return wdpm_fail("wdpm_group_catch_label: %lld ponds on %d padded columns: pond codes and exit codes of a link would meet "
+                     "(N + 2 * columns + 2 > 2^31)", ponds, g.ncp);
+  HIP_TRY(hipSetDevice(x->p.device));
+  const long long held = h->rim_slots, cap = held + 2 * (long long)g.ncp;      /* the rims' slots, then up to 2 * ncp remote ponds */
+  if (cap > h->catch_cap) {
+    guarded_free(h, h->d_catch);
+    h->d_catch = nullptr;
+    h->catch_cap = 0;
+    const hipError_t e = guarded_malloc(h, (void **)&h->d_catch, (size_t)cap * sizeof(CatchRow));
+    if (e != hipSuccess) return wdpm_fail("wdpm_group_catch_label: no device memory for %lld catchment rows: %s", cap, hipGetErrorString(e));
+    h->catch_cap = cap;
+  }
+  if (cap > h->h_catch_cap) {
+    if (h->h_catch) (void)hipHostFree(h->h_catch);
+    h->h_catch = nullptr;
+    h->h_catch_cap = 0;
+    const hipError_t e = hipHostMalloc(&h->h_catch, (size_t)cap * sizeof(wdpm_pond_catchment));
+    if (e != hipSuccess) { h->h_catch = nullptr; return wdpm_fail("wdpm_group_catch_label: no pinned host memory for %lld catchment rows: %s", cap, hipGetErrorString(e)); }
+    h->h_catch_cap = cap;
+  }
+  if (ponds > 0 && held == 0) {        /* the rim work made no slots: none of the whole raster's ponds lies in or beside these rows */
+    if (ponds + 1 > h->slot_cap) {
+      guarded_free(h, h->d_slot_of);
+      h->d_slot_of = nullptr;
+      h->slot_cap = 0;
+      const hipError_t e = guarded_malloc(h, (void **)&h->d_slot_of, (size_t)(ponds + 1) * sizeof(int));
+      if (e != hipSuccess) return wdpm_fail("wdpm_group_catch_label: no device memory for the slots of %lld ponds: %s", ponds, hipGetErrorString(e));
+      h->slot_cap = ponds + 1;
+    }
+    HIP_TRY(hipMemsetAsync(h->d_slot_of, 0x7f, (size_t)(ponds + 1) * sizeof(int), sm));
+  }
+  const CatchRows rw = rows_of(gh, i);
+  for (int side = 0; side < 2; side++) {          /* the keys of the rows beside the rank's own, as their owners wrote them */
+    if (!(rw.halo & (1 << side))) continue;
+    const unsigned long long *src = gh->r[side ? i + 1 : i - 1]->h_ckeys + (side ? 0 : ncp);
+    unsigned long long *stage = h->h_ckeys + (2 + side) * ncp;
+    memcpy(stage, src, ncp * sizeof(unsigned long long));
+    HIP_TRY(hipMemcpyAsync(h->d_ckeys + (2 + side) * ncp, stage, ncp * sizeof(unsigned long long), hipMemcpyHostToDevice, sm));
+  }
+  const size_t off = (size_t)h->row_off * ncp;
+  const double *w = x->d_w[x->cur] + off, *dem = x->d_dem + off;
+  const int rpw = ponds_rows_per_wave(g.nseg, g.rows, h->forced_rpw);
+  const int nwaves = ((rw.rb - rw.ra + rpw - 1) / rpw) * g.nsc;
+  HIP_TRY(hipMemsetAsync(h->d_cstat, 0, sizeof(CatchStatus), sm));
+  if (h->timing) HIP_TRY(hipEventRecord(h->catch_ev[0], sm));
+  hipLaunchKernelGGL(catch_init_rows_kernel, dim3(blocks_for(cap, kBlock)), dim3(kBlock), 0, sm, h->d_catch, cap);
+  hipLaunchKernelGGL(catch_receivers_rows_kernel, dim3(blocks_for(nwaves, kWaves)), dim3(kBlock), 0, sm, w, dem, h->d_masks, h->d_labels, g,
+                     rpw, nwaves, h->d_link, h->d_catch, h->d_cstat, rw);
+  if (h->timing) HIP_TRY(hipEventRecord(h->catch_ev[1], sm));
+  h->catch_rounds = 0;
+  h->catch_slots = h->catch_remote = 0;
+  h->catch_ms[0] = h->catch_ms[1] = h->catch_ms[2] = 0.0;
+  return group_catch_batch(h);
+}
+
+/* after a wait: the time of events a and b of rank p onto phase k */
+int group_catch_time(wdpm_ponds *p, int a, int b, int k) {
+  if (!p->timing) return 0;
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, p->catch_ev[a], p->catch_ev[b]));
+  p->catch_ms[k] += ms;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int wdpm_group_catch_label(wdpm_group_ponds *h, double min_depth, int64_t *nponds) {
+  if (!h) return wdpm_fail("wdpm_group_catch_label: null handle");
+  if (!(min_depth >= 0.0) || std::isinf(min_depth))
+    return wdpm_fail("wdpm_group_catch_label: min_depth must be finite and >= 0 (got %g)", min_depth);
+  int64_t n = 0;
+  /* every rank: scan, seam keys | stitch | table, rims, receivers, a first batch of jump rounds - and one wait per rank */
+  if (group_label(h, min_depth, &n, group_catch_rank, group_catch_seams)) return 1;
+  if (group_rims_merge(h, "wdpm_group_catch_label", n)) return 1;
+  const int nr = h->n, ncp = h->ncp;
+  for (int i = 0; i < nr; i++) {
+    HIP_TRY(hipSetDevice(h->r[i]->x->p.device));
+    if (group_catch_time(h->r[i], 0, 1, 0) || group_catch_time(h->r[i], 2, 3, 1)) return 1;
+  }
+  /* further batches for the ranks that need them: every rank's batch is queued before any rank's look */
+  std::vector<char> open((size_t)nr);
+  for (;;) {
+    bool any = false;
+    for (int i = 0; i < nr; i++) {
+      wdpm_ponds *p = h->r[i];
+      open[(size_t)i] = p->h_cstat->unres[p->catch_rounds - 1] != 0u;
+      if (!open[(size_t)i]) continue;
+      any = true;
+      if (p->catch_rounds >= kCatchRoundCap)
+        return wdpm_fail("wdpm_group_catch_label: %u cells of rank %d are still on their way after %d rounds of pointer jumping, which "
+                         "halve every descent: the link raster is damaged", p->h_cstat->unres[p->catch_rounds - 1], i, p->catch_rounds);
+    }
+    if (!any) break;
+    for (int i = 0; i < nr; i++)
+      if (open[(size_t)i] && (hipSetDevice(h->r[i]->x->p.device) != hipSuccess || group_catch_batch(h->r[i]))) return group_catch_drain(h);
+    bool bad = false;
+    std::string first_msg;
+    for (int i = 0; i < nr; i++) {
+      if (!open[(size_t)i]) continue;
+      wdpm_ponds *p = h->r[i];
+      if (hipSetDevice(p->x->p.device) != hipSuccess || wdpm_stream_sync(p->x, p->x->stream) || group_catch_time(p, 2, 3, 1)) {
+        if (!bad) first_msg = wdpm_last_error();
+        bad = true;
+      }
+    }
+    if (bad) return wdpm_fail("%s", first_msg.c_str());
+  }
+
+  /* the exits: every rank's two rows of links are on the host */
+  timespec t0, t1, t2, t3;
+  clock_gettime(CLOCK_MONOTONIC, &t0);
+  std::vector<wdpm_catch_stitch::RankLinks> links((size_t)nr);
+  for (int i = 0; i < nr; i++) {
+    const wdpm_ponds *p = h->r[i];
+    links[(size_t)i].top = p->h_cexit;
+    links[(size_t)i].bottom = p->g.rows == 3 ? p->h_cexit : p->h_cexit + ncp;      /* one row between the view's first and last */
+  }
+  wdpm_catch_stitch::Resolved res;
+  std::string err;
+  if (wdpm_catch_stitch::resolve(links, ncp, res, err)) return wdpm_fail("wdpm_group_catch_label: %s", err.c_str());
+  for (int i = 0; i < nr; i++) {
+    wdpm_ponds *p = h->r[i];
+    std::vector<int> &remote = p->catch_remote_label;
+    wdpm_catch_stitch::remote_labels(res.exit_basin[(size_t)i], ncp, h->table.data(), h->view0[i], h->view0[i] + p->g.rows - 1, remote);
+    p->catch_slots = (long long)(p->slot_label.size() + remote.size());
+    p->catch_remote = (long long)remote.size();
+    if (p->catch_slots > p->catch_cap) return wdpm_fail("wdpm_group_catch_label: rank %d would hold %lld catchment rows of %lld", i, p->catch_slots, p->catch_cap);
+    memcpy(p->h_cexit + (size_t)2 * ncp, res.exit_basin[(size_t)i].data(), (size_t)2 * ncp * sizeof(int));
+    if (!remote.empty()) memcpy(p->h_cexit + (size_t)4 * ncp, remote.data(), remote.size() * sizeof(int));
+  }
+  clock_gettime(CLOCK_MONOTONIC, &t1);
+
+  /* every rank: where its exits end, the slots of its remote ponds, tally and finish, its rows on their way down */
+  for (int i = 0; i < nr; i++) {
+    wdpm_ponds *p = h->r[i];
+    wdpm_ctx *x = p->x;
+    const Geom g = p->g;
+    const hipStream_t sm = x->stream;
+    const CatchRows rw = rows_of(h, i);
+    const size_t off = (size_t)p->row_off * g.ncp;
+    const double *w = x->d_w[x->cur] + off, *dem = x->d_dem + off;
+    const int rpw = ponds_rows_per_wave(g.nseg, g.rows, p->forced_rpw);
+    const int nwaves = ((rw.rb - rw.ra + rpw - 1) / rpw) * g.nsc;
+    const int base = (int)(p->catch_slots - p->catch_remote);
+    /* the first call that fails is the one the message names; nothing is queued behind it */
+    hipError_t e = hipSetDevice(x->p.device);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(p->d_cexit, p->h_cexit + (size_t)2 * ncp, (size_t)(2 * ncp + p->catch_remote) * sizeof(int), hipMemcpyHostToDevice, sm);
+    if (e == hipSuccess && p->timing) e = hipEventRecord(p->catch_ev[4], sm);
+    if (e == hipSuccess) {
+      if (p->catch_remote)
+        hipLaunchKernelGGL(catch_remote_slots_kernel, dim3(blocks_for(p->catch_remote, kBlock)), dim3(kBlock), 0, sm, p->d_cexit + (size_t)2 * ncp,
+                           (int)p->catch_remote, base, p->d_slot_of);
+      hipLaunchKernelGGL(catch_tally_rows_kernel, dim3(blocks_for(nwaves, kWaves)), dim3(kBlock), 0, sm, w, dem, p->d_masks, g, rpw, nwaves,
+                         p->d_link, p->d_catch, p->d_cstat, rw);
+      if (p->catch_slots) hipLaunchKernelGGL(catch_finish_kernel, dim3(blocks_for(p->catch_slots, kBlock)), dim3(kBlock), 0, sm, p->d_catch, p->catch_slots);
+      e = hipGetLastError();                                 /* of the launches */
+    }
+    if (e == hipSuccess && p->timing) e = hipEventRecord(p->catch_ev[5], sm);
+    if (e == hipSuccess && p->catch_slots)
+      e = hipMemcpyAsync(p->h_catch, p->d_catch, (size_t)p->catch_slots * sizeof(wdpm_pond_catchment), hipMemcpyDeviceToHost, sm);
+    if (e == hipSuccess) e = hipMemcpyAsync(p->h_cstat, p->d_cstat, sizeof(CatchStatus), hipMemcpyDeviceToHost, sm);
+    if (e != hipSuccess) {
+      (void)wdpm_fail("wdpm_group_catch_label: queueing the tally of rank %d failed: %s", i, hipGetErrorString(e));
+      return group_catch_drain(h);
+    }
+  }
+  {
+    bool bad = false;
+    std::string first_msg;
+    for (int i = 0; i < nr; i++) {
+      wdpm_ponds *p = h->r[i];
+      if (hipSetDevice(p->x->p.device) != hipSuccess || wdpm_stream_sync(p->x, p->x->stream) || group_catch_time(p, 4, 5, 2)) {
+        if (!bad) first_msg = wdpm_last_error();
+        bad = true;
+      }
+    }
+    if (bad) return wdpm_fail("%s", first_msg.c_str());
+  }
+
+  clock_gettime(CLOCK_MONOTONIC, &t2);
+  std::vector<wdpm_catch_stitch::RankCatch> ranks((size_t)nr);
+  long long remote_sum = 0;
+  for (int i = 0; i < nr; i++) {
+    const wdpm_ponds *p = h->r[i];
+    const CatchStatus &st = *p->h_cstat;
+    /* a remote slot was made for every pond a cell of the facing rows ends in; those that took a cell of this rank count */
+    for (long long s = p->catch_slots - p->catch_remote; s < p->catch_slots; s++) remote_sum += p->h_catch[s].catch_cells > 0;
+    ranks[(size_t)i] = {p->h_catch, p->slot_label.data(), p->catch_slots, p->catch_remote_label.data(), p->catch_remote, h->view0[i], (long long)st.slope, (long long)st.pit,
+                        (long long)st.unponded, (long long)st.exits, (long long)p->catch_rounds};
+  }
+  h->catchments.resize((size_t)n);
+  wdpm_catch_stitch::Totals tot;
+  if (wdpm_catch_stitch::merge(ranks, n, h->table.data(), h->catchments.data(), tot, err)) return wdpm_fail("wdpm_group_catch_label: %s", err.c_str());
+  clock_gettime(CLOCK_MONOTONIC, &t3);
+  h->catch_stats.slope_cells = tot.slope;
+  h->catch_stats.pit_cells = tot.pit;
+  h->catch_stats.unponded_cells = tot.unponded;
+  h->catch_stats.rounds = tot.rounds;
+  h->catch_stats.ponds = n;
+  h->catch_stats.ranks = nr;
+  h->catch_stats.exits = tot.exits;
+  h->catch_stats.crossings = res.crossings;
+  h->catch_stats.remote = remote_sum;
+  h->catch_stats.resolve_ms = ms_between(t0, t1) + ms_between(t2, t3);
+  h->catch_valid = true;
+  if (nponds) *nponds = n;
+  return 0;
+}
+
+extern "C" int wdpm_group_catch_table(wdpm_group_ponds *h, wdpm_pond_catchment *out, int64_t capacity) {
+  if (!h) return wdpm_fail("wdpm_group_catch_table: null handle");
+  if (!h->valid || !h->catch_valid) return wdpm_fail("wdpm_group_catch_table: %s", kNoGroupTable);
+  const long long n = h->stats.ponds;
+  if (capacity < n) return wdpm_fail("wdpm_group_catch_table: capacity %lld is too small for %lld ponds", (long long)capacity, n);
+  if (n == 0) return 0;
+  if (!out) return wdpm_fail("wdpm_group_catch_table: null output");
+  memcpy(out, h->catchments.data(), (size_t)n * sizeof(wdpm_pond_catchment));
+  return 0;
+}
+
+extern "C" int wdpm_group_catch_basins(wdpm_group_ponds *h, int32_t *padded) {
+  if (!h) return wdpm_fail("wdpm_group_catch_basins: null handle");
+  if (!padded) return wdpm_fail("wdpm_group_catch_basins: null output");
+  if (!h->valid || !h->catch_valid) return wdpm_fail("wdpm_group_catch_basins: %s", kNoGroupTable);
+  /* every rank's owned rows, to where they lie in the whole raster, one after another as wdpm_group_ponds_labels brings them */
+  for (int i = 0; i < h->n; i++) {
+    wdpm_ponds *p = h->r[i];
+    if (wdpm_synchronize(p->x)) return 1;
+    HIP_TRY(hipMemcpyAsync(padded + (size_t)h->own_lo[i] * h->ncp, p->d_link + (size_t)(h->own_lo[i] - h->view0[i]) * h->ncp,
+                           (size_t)h->own_rows[i] * h->ncp * sizeof(int32_t), hipMemcpyDeviceToHost, p->x->stream));
+    if (wdpm_stream_sync(p->x, p->x->stream)) return 1;
+  }
+  return 0;
+}
+
+extern "C" int wdpm_group_catch_stats(wdpm_group_ponds *h, wdpm_group_catchment_stats *out) {
+  if (!h) return wdpm_fail("wdpm_group_catch_stats: null handle");
+  if (!out) return wdpm_fail("wdpm_group_catch_stats: null output");
+  if (!h->valid || !h->catch_valid) return wdpm_fail("wdpm_group_catch_stats: %s", kNoGroupTable);
+  *out = h->catch_stats;
+  return 0;
+}
+
+extern "C" int wdpm_group_catch_phase_ms(wdpm_group_ponds *h, int32_t rank, double *ms) {
+  if (!h) return wdpm_fail("wdpm_group_catch_phase_ms: null handle");
+  if (!ms) return wdpm_fail("wdpm_group_catch_phase_ms: null output");
+  if (rank < 0 || rank >= h->n) return wdpm_fail("wdpm_group_catch_phase_ms: rank %d of %d", rank, h->n);
+  if (!h->timing) return wdpm_fail("wdpm_group_catch_phase_ms: the handle records no events (set WDPM_PONDS_TIMING=1 before it is made)");
+  if (!h->valid || !h->catch_valid) return wdpm_fail("wdpm_group_catch_phase_ms: %s", kNoGroupTable);
+  for (int i = 0; i < WDPM_CATCH_PHASES; i++) ms[i] = h->r[rank]->catch_ms[i];
   return 0;
 }
 #endif  /* WDPM_PONDS_EMULATION */

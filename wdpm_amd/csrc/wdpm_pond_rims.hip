@@ -360,11 +360,9 @@ extern "C" int wdpm_rims_phase_ms(wdpm_ponds *h, double *ms) {
 
 #include "wdpm_rims_merge.h"
 
-namespace {
-
 /* Rank i's rim work behind its table kernels, on its stream, nothing waited for (group_label calls this for every rank before the
  * first wait).  The rows beside the rank's own come from the neighbours' seam rows through the stitch's numbers. */
-int group_rims_rank(wdpm_group_ponds *gh, int i, const std::vector<std::vector<int>> &map, long long ponds) {
+int wdpm_pond_detail::group_rims_rank(wdpm_group_ponds *gh, int i, const std::vector<std::vector<int>> &map, long long ponds) {
   wdpm_ponds *h = gh->r[i];
   wdpm_ctx *x = h->x;
   const Geom g = h->g;
@@ -473,14 +471,8 @@ int group_rims_rank(wdpm_group_ponds *gh, int i, const std::vector<std::vector<i
   return 0;
 }
 
-}  // namespace
-
-extern "C" int wdpm_group_rims_label(wdpm_group_ponds *h, double min_depth, int64_t *nponds) {
-  if (!h) return wdpm_fail("wdpm_group_rims_label: null handle");
-  if (!(min_depth >= 0.0) || std::isinf(min_depth))
-    return wdpm_fail("wdpm_group_rims_label: min_depth must be finite and >= 0 (got %g)", min_depth);
-  int64_t n = 0;
-  if (group_label(h, min_depth, &n, group_rims_rank)) return 1;       /* every stream has run dry: one wait per rank ended both tables */
+/* after group_label(.., group_rims_rank) has returned: the ranks' rim rows into h->rims */
+int wdpm_pond_detail::group_rims_merge(wdpm_group_ponds *h, const char *caller, long long n) {
   h->valid = false;                                                     /* until the rims are merged as well */
   std::vector<wdpm_rims_merge::RankRims> ranks((size_t)h->n);
   long long slots = 0, foreign = 0;
@@ -502,7 +494,7 @@ extern "C" int wdpm_group_rims_label(wdpm_group_ponds *h, double min_depth, int6
   clock_gettime(CLOCK_MONOTONIC, &t0);
   h->rims.resize((size_t)n);
   std::string err;
-  if (wdpm_rims_merge::merge(ranks, n, h->rims.data(), err)) return wdpm_fail("wdpm_group_rims_label: %s", err.c_str());
+  if (wdpm_rims_merge::merge(ranks, n, h->rims.data(), err)) return wdpm_fail("%s: %s", caller, err.c_str());
   clock_gettime(CLOCK_MONOTONIC, &t1);
   h->rim_stats.ranks = h->n;
   h->rim_stats.slots = slots;
@@ -510,6 +502,16 @@ extern "C" int wdpm_group_rims_label(wdpm_group_ponds *h, double min_depth, int6
   h->rim_stats.merge_ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
   h->valid = true;
   h->rims_valid = true;
+  return 0;
+}
+
+extern "C" int wdpm_group_rims_label(wdpm_group_ponds *h, double min_depth, int64_t *nponds) {
+  if (!h) return wdpm_fail("wdpm_group_rims_label: null handle");
+  if (!(min_depth >= 0.0) || std::isinf(min_depth))
+    return wdpm_fail("wdpm_group_rims_label: min_depth must be finite and >= 0 (got %g)", min_depth);
+  int64_t n = 0;
+  if (group_label(h, min_depth, &n, group_rims_rank)) return 1;       /* every stream has run dry: one wait per rank ended both tables */
+  if (group_rims_merge(h, "wdpm_group_rims_label", n)) return 1;
   if (nponds) *nponds = n;
   return 0;
 }

@@ -488,6 +488,15 @@ void release(wdpm_ponds *h) {
   h->catch_cap = 0;
   h->d_cstat = h->h_cstat = nullptr;
   h->catch_valid = false;
+  guarded_free(h, h->d_ckeys);
+  guarded_free(h, h->d_cexit);
+  if (h->h_ckeys) (void)hipHostFree(h->h_ckeys);
+  if (h->h_cexit) (void)hipHostFree(h->h_cexit);
+  if (h->h_catch) (void)hipHostFree(h->h_catch);
+  h->d_ckeys = h->h_ckeys = nullptr;
+  h->d_cexit = h->h_cexit = nullptr;
+  h->h_catch = nullptr;
+  h->h_catch_cap = 0;
   guarded_free(h, h->d_outlets);
   if (h->d_ostat) (void)hipFree(h->d_ostat);
   if (h->h_ostat) (void)hipHostFree(h->h_ostat);
@@ -614,10 +623,16 @@ wdpm_ponds *make_handle(wdpm_ctx *ctx, int row_off, int rows, bool seams) {
   if (h->timing)
     for (int i = 0; i < WDPM_RIMS_PHASES + 1; i++)
       if (hipEventCreate(&h->rim_ev[i]) != hipSuccess) { h->timing = false; break; }
-  for (int i = 0; i < 5; i++) h->catch_ev[i] = nullptr;
+  h->d_ckeys = h->h_ckeys = nullptr;
+  h->d_cexit = h->h_cexit = nullptr;
+  h->h_catch = nullptr;
+  h->h_catch_cap = 0;
+  h->catch_slots = h->catch_remote = 0;
+  h->catch_rounds = 0;
+  for (int i = 0; i < kCatchEvents; i++) h->catch_ev[i] = nullptr;
   for (int i = 0; i < WDPM_CATCH_PHASES; i++) h->catch_ms[i] = 0.0;
   if (h->timing)
-    for (int i = 0; i < 5; i++)
+    for (int i = 0; i < kCatchEvents; i++)
       if (hipEventCreate(&h->catch_ev[i]) != hipSuccess) { h->timing = false; break; }
   for (int i = 0; i < WDPM_OUTLETS_PHASES + 1; i++) h->outlet_ev[i] = nullptr;
   for (int i = 0; i < WDPM_OUTLETS_PHASES; i++) h->outlet_ms[i] = 0.0;
@@ -785,7 +800,7 @@ void destroy_handle(wdpm_ponds *h) {
     if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
   for (int i = 0; i < WDPM_RIMS_PHASES + 1; i++)
     if (h->rim_ev[i]) (void)hipEventDestroy(h->rim_ev[i]);
-  for (int i = 0; i < 5; i++)
+  for (int i = 0; i < kCatchEvents; i++)
     if (h->catch_ev[i]) (void)hipEventDestroy(h->catch_ev[i]);
   for (int i = 0; i < WDPM_OUTLETS_PHASES + 1; i++)
     if (h->outlet_ev[i]) (void)hipEventDestroy(h->outlet_ev[i]);
@@ -868,9 +883,11 @@ extern "C" int wdpm_group_ponds_create(wdpm_group_ponds **out, wdpm_group *grp) 
   h->n = n;
   h->valid = false;
   h->rims_valid = false;
+  h->catch_valid = false;
   h->timing = true;
   memset(&h->stats, 0, sizeof h->stats);
   memset(&h->rim_stats, 0, sizeof h->rim_stats);
+  memset(&h->catch_stats, 0, sizeof h->catch_stats);
   for (int i = 0; i < n; i++) {
     wdpm_rank *rk = wdpm_group_rank(grp, i);
     wdpm_ctx *x = rk ? wdpm_rank_ctx(rk) : nullptr;
@@ -930,13 +947,15 @@ extern "C" int wdpm_group_ponds_label(wdpm_group_ponds *h, double min_depth, int
   return group_label(h, min_depth, nponds, nullptr);
 }
 
-int wdpm_pond_detail::group_label(wdpm_group_ponds *h, double min_depth, int64_t *nponds, group_rims_queue rims) {
+int wdpm_pond_detail::group_label(wdpm_group_ponds *h, double min_depth, int64_t *nponds, group_rims_queue rims,
+                                  group_seams_queue seam_rows) {
   h->valid = false;
   h->rims_valid = false;            /* a rim table belongs to the label call that made it */
+  h->catch_valid = false;           /* and so does a catchment table */
   const int n = h->n;
   /* every rank up to its scan, on its own stream and device, before the first wait */
   for (int i = 0; i < n; i++)
-    if (label_queue(h->r[i], min_depth)) return drain_and_fail(h);
+    if (label_queue(h->r[i], min_depth) || (seam_rows && seam_rows(h, i))) return drain_and_fail(h);
   std::vector<wdpm_stitch::RankSeams> seams((size_t)n);
   bool bad = false;
   std::string first_msg;

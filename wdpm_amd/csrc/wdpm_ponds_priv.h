@@ -33,6 +33,7 @@
 #include "../../include/wdpm_group_pond_rims.h"
 #include "../../include/wdpm_pond_catchments.h"
 #include "../../include/wdpm_pond_outlets.h"
+#include "../../include/wdpm_group_pond_catchments.h"
 
 namespace wdpm_pond_detail {
 
@@ -82,12 +83,14 @@ static_assert(sizeof(CatchRow) == sizeof(wdpm_pond_catchment) && sizeof(CatchRow
 constexpr int kCatchRoundCap = 40;
 constexpr int kCatchBatch = 4;
 constexpr int kCatchHops = 4;        /* links one thread follows in one round */
+constexpr int kCatchEvents = 6;      /* HIP events a handle keeps for the catchment phases */
 static_assert(kCatchRoundCap % kCatchBatch == 0, "whole batches up to the cap");
 
 /* what the catchment kernels count for the host: unres[k] is the number of cells round k left with a link that is no terminal */
 struct CatchStatus {
   unsigned long long slope, pit, unponded;
   unsigned unres[kCatchRoundCap];
+  unsigned long long exits;          /* row blocks: owned cells whose link was an exit when the tally met it */
 };
 
 /* the outlet table as the device accumulates it: wdpm_pond_outlet with the pour level as its order-preserving image (~0: no pass
@@ -238,9 +241,21 @@ struct wdpm_ponds {
   long long catch_cap;
   wdpm_pond_detail::CatchStatus *d_cstat, *h_cstat;   /* h_cstat pinned */
   bool catch_valid;
-  hipEvent_t catch_ev[5];           /* init | receivers | jump rounds | tally, finish */
+  hipEvent_t catch_ev[wdpm_pond_detail::kCatchEvents];   /* init | receivers | jump rounds | tally, finish; row blocks: 0-1 receivers, 2-3 a batch of */
+                                    /* jump rounds, 4-5 tally */
   double catch_ms[WDPM_CATCH_PHASES];
   wdpm_pond_catchment_stats catch_stats;
+  /* catchments of a row block (wdpm_group_catch_label): d_catch then holds one row per SLOT - the rims' slots, then the rank's
+   * remote ponds - and d_link's rows 0 and g.rows - 1 belong to the neighbours */
+  unsigned long long *d_ckeys;      /* 4 x g.ncp level keys: the rank's first and last owned row, then the rows beside them */
+  unsigned long long *h_ckeys;      /* pinned, laid out likewise: two rows on their way down, two on their way up */
+  int *d_cexit;                     /* 4 x g.ncp: where each exit ends (2 x g.ncp), the remote ponds' labels */
+  int *h_cexit;                     /* pinned, 6 x g.ncp: the links of the first and last owned row on their way down, then as d_cexit */
+  wdpm_pond_catchment *h_catch;     /* pinned: the finished catchment rows on their way down */
+  long long h_catch_cap;
+  long long catch_slots, catch_remote;   /* of the call under way */
+  int catch_rounds;
+  std::vector<int> catch_remote_label;   /* the whole-raster labels of the remote slots, which follow the rims' slots (slot_label) */
   /* outlets (wdpm_pond_outlets.hip): the table of the last wdpm_outlets_label; every label call takes outlets_valid away first */
   wdpm_pond_detail::OutletRow *d_outlets;
   long long outlets_cap;
@@ -251,7 +266,7 @@ struct wdpm_ponds {
   wdpm_pond_outlet_stats outlet_stats;
 };
 
-/* the handle of include/wdpm_group_ponds.h and include/wdpm_group_pond_rims.h */
+/* the handle of include/wdpm_group_ponds.h, include/wdpm_group_pond_rims.h and include/wdpm_group_pond_catchments.h */
 struct wdpm_group_ponds {
   wdpm_group *grp;
   int n;                                   /* ranks */
@@ -265,6 +280,10 @@ struct wdpm_group_ponds {
   std::vector<wdpm_pond_rim> rims;
   bool rims_valid;
   wdpm_group_rim_stats rim_stats;
+  /* catchments: the merged table of the last wdpm_group_catch_label; every label call takes catch_valid away first */
+  std::vector<wdpm_pond_catchment> catchments;
+  bool catch_valid;
+  wdpm_group_catchment_stats catch_stats;
 };
 
 namespace wdpm_pond_detail {
@@ -275,7 +294,15 @@ __attribute__((visibility("hidden"))) void guarded_free(wdpm_ponds *h, void *p);
  * before any rank is waited for, rims(h, i, map) queues that rank's rim work, map[rank][local label - 1] being the stitch's
  * numbers.  One wait per rank then ends both. */
 typedef int (*group_rims_queue)(wdpm_group_ponds *h, int rank, const std::vector<std::vector<int>> &map, long long ponds);
-__attribute__((visibility("hidden"))) int group_label(wdpm_group_ponds *h, double min_depth, int64_t *nponds, group_rims_queue rims);
+/* `seams` (may be null): called for rank i right after its scan is queued and before any rank is waited for, so that what it
+ * sends to the host arrives with the seam labels. */
+typedef int (*group_seams_queue)(wdpm_group_ponds *h, int rank);
+__attribute__((visibility("hidden"))) int group_label(wdpm_group_ponds *h, double min_depth, int64_t *nponds, group_rims_queue rims,
+                                                      group_seams_queue seams = nullptr);
+/* wdpm_pond_rims.hip: the rims argument of wdpm_group_rims_label, and what that call does once group_label has returned - the
+ * ranks' rim rows merged into h->rims, h->valid and h->rims_valid set.  wdpm_group_catch_label runs both and adds its own. */
+__attribute__((visibility("hidden"))) int group_rims_rank(wdpm_group_ponds *h, int rank, const std::vector<std::vector<int>> &map, long long ponds);
+__attribute__((visibility("hidden"))) int group_rims_merge(wdpm_group_ponds *h, const char *caller, long long ponds);
 }  // namespace wdpm_pond_detail
 #endif
 

@@ -1,7 +1,7 @@
 """ctypes binding of include/wdpm_ponds.h, include/wdpm_group_ponds.h, include/wdpm_pond_rims.h, include/wdpm_group_pond_rims.h,
-include/wdpm_pond_catchments.h and include/wdpm_pond_outlets.h: the pond inventory of a context's current water raster, of a raster
-spread over the row blocks of a rowblock.Group, the rim of every pond of either, and the catchment and the outlet of every pond of a
-whole raster.
+include/wdpm_pond_catchments.h, include/wdpm_pond_outlets.h and include/wdpm_group_pond_catchments.h: the pond inventory of a
+context's current water raster, of a raster spread over the row blocks of a rowblock.Group, the rim and the catchment of every pond
+of either, and the outlet of every pond of a whole raster.
 
 Product library only (the symbols are not part of the ABI of include/wdpm.h, and ``capi.SYMBOLS`` does not list them).
 
@@ -23,6 +23,8 @@ Product library only (the symbols are not part of the ABI of include/wdpm.h, and
         n = ponds.label(0.001)
         n = ponds.label_rims(0.001) # every rank takes the rims of its own rows; the host merges them
         rims = ponds.rims()         # RIM_DTYPE, coordinates of the whole raster
+        n = ponds.label_catchments(0.001)   # and every rank's receivers, jump rounds and tally; the host ends the descents that
+        basins = ponds.basins()     # cross row blocks and adds the ranks' tables up (CATCH_DTYPE, coordinates of the whole raster)
 """
 from __future__ import annotations
 
@@ -174,12 +176,29 @@ GROUP_RIM_SYMBOLS = {
 }
 
 
+class GroupCatchStatsStruct(C.Structure):
+    """struct wdpm_group_catchment_stats"""
+    _fields_ = [("slope_cells", C.c_int64), ("pit_cells", C.c_int64), ("unponded_cells", C.c_int64), ("rounds", C.c_int64),
+                ("ponds", C.c_int64), ("ranks", C.c_int64), ("exits", C.c_int64), ("crossings", C.c_int64), ("remote", C.c_int64),
+                ("resolve_ms", C.c_double)]
+
+
+# every symbol include/wdpm_group_pond_catchments.h declares
+GROUP_CATCH_SYMBOLS = {
+    "wdpm_group_catch_label": (C.c_int, [_vp, C.c_double, C.POINTER(C.c_int64)]),
+    "wdpm_group_catch_table": (C.c_int, [_vp, _vp, C.c_int64]),
+    "wdpm_group_catch_basins": (C.c_int, [_vp, _vp]),
+    "wdpm_group_catch_stats": (C.c_int, [_vp, C.POINTER(GroupCatchStatsStruct)]),
+    "wdpm_group_catch_phase_ms": (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_double)]),
+}
+
+
 def bind(lib: capi.Lib):
     """Set the prototypes on a loaded product library; a library without the symbols is an error (no fallback)."""
     if getattr(lib, "_ponds_bound", False):
         return lib.dll
     for name, (res, args) in list(SYMBOLS.items()) + list(GROUP_SYMBOLS.items()) + list(RIM_SYMBOLS.items()) + \
-            list(GROUP_RIM_SYMBOLS.items()) + list(CATCH_SYMBOLS.items()) + list(OUTLET_SYMBOLS.items()):
+            list(GROUP_RIM_SYMBOLS.items()) + list(CATCH_SYMBOLS.items()) + list(OUTLET_SYMBOLS.items()) + list(GROUP_CATCH_SYMBOLS.items()):
         try:
             fn = getattr(lib.dll, name)
         except AttributeError:
@@ -400,3 +419,29 @@ class GroupPonds(_Handle):
     def rims_phase_ms(self, rank: int) -> dict:
         """milliseconds of one rank's rim pass and locate pass in the last label_rims() (handles made with WDPM_PONDS_TIMING=1)"""
         return self._phase_ms(self.dll.wdpm_group_rims_phase_ms, RIM_PHASES, int(rank))
+
+    def label_catchments(self, min_depth: float) -> int:
+        """label_rims(min_depth), and every rank's catchment pass on the same water; table(), labels(), stats(), rank_stats() and
+        rims() answer as after label_rims()."""
+        return self._label(self.dll.wdpm_group_catch_label, min_depth)
+
+    def catchments(self, capacity: int | None = None) -> np.ndarray:
+        """One row per pond (CATCH_DTYPE) of the last label_catchments(), coordinates of the whole raster; fails after label() or
+        label_rims()."""
+        return self._table(self.dll.wdpm_group_catch_table, CATCH_DTYPE, "catchments", capacity)
+
+    def basins(self) -> np.ndarray:
+        """int32, padded like labels(), every rank's owned rows where they lie: k > 0 for pond k and the cells that drain to it,
+        0 for cells that drain to a pit, -1 for cells without a level"""
+        out = np.empty(self.shape, dtype=np.int32)
+        self.lib.check(self.dll.wdpm_group_catch_basins(self._h, out.ctypes.data))
+        return out
+
+    def catchment_stats(self) -> dict:
+        """the counts of Ponds.catchment_stats for the whole raster, then ranks, exits, crossings, remote and resolve_ms"""
+        return self._stats(self.dll.wdpm_group_catch_stats, GroupCatchStatsStruct)
+
+    def catchment_phase_ms(self, rank: int) -> dict:
+        """milliseconds of one rank's receiver pass, jump rounds and tally in the last label_catchments() (handles made with
+        WDPM_PONDS_TIMING=1)"""
+        return self._phase_ms(self.dll.wdpm_group_catch_phase_ms, CATCH_PHASES, int(rank))
