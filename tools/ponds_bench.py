@@ -25,6 +25,10 @@
                       outlet phases beside the table phase of the SAME calls, their ratios, and their rates under the byte model
                       of 20 B per cell and pass (basin, dem, w) and of 4 B per cell (a row that holds no pass reads its basins
                       alone) against the yardstick (default --out profiles/r15/pond_outlets.json)
+                      With --devices: GroupPonds.label_outlets (include/wdpm_group_pond_outlets.h) - per-rank passes and locate
+                      phases and their sums over the ranks, the host's merge_ms, seam_outlets and split_ponds; then the whole-raster
+                      call on the same water in the same process, the yardstick of those sums (default --out
+                      profiles/r17/pond_outlets_group.json)
     ... --iterations K   instead of the job's own number of iterations before the inventory
 
 Per job: one untimed label call, then five timed ones (wall clock around the call, which ends with the stream idle; HIP events
@@ -212,6 +216,24 @@ def group_job(hip, a, bd, bw, iters, rec):
                 group_rims_job(p, rec, len(devices))
             if a.catchments:
                 group_catchments_job(p, rec, len(devices))
+            if a.outlets:
+                group_outlets_job(p, rec, len(devices))
+    if a.outlets:                                              # the yardstick: the whole-raster call on the same water, same process
+        with hip.context(module="add", nrows=n, ncols=n, missingvalue=MISS) as ctx:
+            ctx.upload(bd, bw)
+            if iters > 0:
+                ctx.run_block(iters, 0.005 / 1000)
+            with Ponds(ctx) as p:
+                p.label_outlets(0.001)
+                phases = {k: [] for k in OUTLET_PHASES}
+                for _ in range(5):
+                    p.label_outlets(0.001)
+                    for k, v in p.outlet_phase_ms().items():
+                        phases[k].append(v)
+                whole = {k: statistics.median(v) for k, v in phases.items()}
+                o = rec["outlets"]
+                o.update(whole_raster_phase_ms=whole, whole_raster_phase_ms_all=phases, whole_raster_stats=p.outlet_stats())
+                o["sum_over_ranks_over_whole_raster"] = {k: o["phase_sum_over_ranks_ms"][k] / whole[k] if whole[k] > 0 else None for k in OUTLET_PHASES}
     if a.catchments:                                           # the yardstick: the whole-raster call on the same water, same process
         with hip.context(module="add", nrows=n, ncols=n, missingvalue=MISS) as ctx:
             ctx.upload(bd, bw)
@@ -286,6 +308,35 @@ def group_catchments_job(p, rec, nranks):
                              inflow_cells=int(catch["inflow_cells"].sum()), guard_bad=p.guard_bad())
 
 
+def group_outlets_job(p, rec, nranks):
+    """after the label calls: one untimed label_outlets (allocates every rank's slots, keys and rows), five timed ones"""
+    p.label_outlets(0.001)
+    wall, merge = [], []
+    phases = [{k: [] for k in OUTLET_PHASES} for _ in range(nranks)]
+    table_ms = [[] for _ in range(nranks)]
+    for _ in range(5):
+        t0 = time.perf_counter()
+        p.label_outlets(0.001)
+        wall.append((time.perf_counter() - t0) * 1e3)
+        merge.append(p.outlet_stats()["merge_ms"])
+        for i in range(nranks):
+            for k, v in p.outlet_phase_ms(i).items():
+                phases[i][k].append(v)
+            table_ms[i].append(p.phase_ms(i)["table"])
+    table, stats = p.outlets(), p.outlet_stats()
+    sums = {k: statistics.median([sum(phases[i][k][j] for i in range(nranks)) for j in range(5)]) for k in OUTLET_PHASES}   # per call, over ranks
+    rec["outlets"] = dict(label_outlets_wall_ms=statistics.median(wall), label_outlets_wall_ms_all=wall,
+                          rank_phase_ms=[{k: statistics.median(v) for k, v in ph.items()} for ph in phases], rank_phase_ms_all=phases,
+                          phase_sum_over_ranks_ms=sums, rank_table_ms_same_calls=[statistics.median(v) for v in table_ms],
+                          merge_ms=statistics.median(merge), merge_ms_all=merge, stats=stats, seam_outlets=stats["seam_outlets"],
+                          split_ponds=stats["split_ponds"], fill_cells=int(table["fill_cells"].sum()),
+                          largest_divide=int(table["divide_cells"].max()) if len(table) else 0, guard_bad=p.guard_bad())
+    for i in range(nranks):
+        print(f"rank {i}: passes {rec['outlets']['rank_phase_ms'][i]['passes']:.3f} ms  locate {rec['outlets']['rank_phase_ms'][i]['locate']:.3f} ms",
+              file=sys.stderr)
+    print(f"merge_ms {rec['outlets']['merge_ms']:.3f}", file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("job", choices=["wet", "ponds", "noise"])
@@ -302,14 +353,13 @@ def main():
     ap.add_argument("--iterations", type=int, help="iterations before the inventory, instead of the job's own")
     a = ap.parse_args()
     if not a.out:
-        a.out = os.path.join(ROOT, "profiles", *(("r16", "pond_catchments_group.json") if a.devices and a.catchments else
+        a.out = os.path.join(ROOT, "profiles", *(("r17", "pond_outlets_group.json") if a.devices and a.outlets else
+                                                  ("r16", "pond_catchments_group.json") if a.devices and a.catchments else
                                                   ("r13", "pond_rims_group.json") if a.devices and a.rims else
                                                   ("r11", "ponds_group.json") if a.devices else
                                                   ("r15", "pond_outlets.json") if a.outlets else
                                                   ("r14", "pond_catchments.json") if a.catchments else
                                                   ("r12", "pond_rims.json") if a.rims else ("r10", "ponds.json")))
-    if a.outlets and a.devices:
-        raise SystemExit("--outlets: outlets are taken on whole rasters only (include/wdpm_pond_outlets.h)")
     hip = wdpm_amd.load_hip()
     n = a.n
     dem = hip.synth_dem(n, n)

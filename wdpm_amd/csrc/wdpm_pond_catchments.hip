@@ -783,6 +783,9 @@ extern "C" int wdpm_group_catch_label(wdpm_group_ponds *h, double min_depth, int
     if (e == hipSuccess && p->catch_slots)
       e = hipMemcpyAsync(p->h_catch, p->d_catch, (size_t)p->catch_slots * sizeof(wdpm_pond_catchment), hipMemcpyDeviceToHost, sm);
     if (e == hipSuccess) e = hipMemcpyAsync(p->h_cstat, p->d_cstat, sizeof(CatchStatus), hipMemcpyDeviceToHost, sm);
+    /* the rank's first and last owned row as basins, where their links lay: what an outlet pass hands the facing ranks */
+    if (e == hipSuccess) e = hipMemcpyAsync(p->h_cexit, p->d_link + (size_t)rw.ra * g.ncp, (size_t)g.ncp * sizeof(int), hipMemcpyDeviceToHost, sm);
+    if (e == hipSuccess) e = hipMemcpyAsync(p->h_cexit + g.ncp, p->d_link + (size_t)(rw.rb - 1) * g.ncp, (size_t)g.ncp * sizeof(int), hipMemcpyDeviceToHost, sm);
     if (e != hipSuccess) {
       (void)wdpm_fail("wdpm_group_catch_label: queueing the tally of rank %d failed: %s", i, hipGetErrorString(e));
       return group_catch_drain(h);

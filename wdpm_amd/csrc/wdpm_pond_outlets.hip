@@ -22,8 +22,16 @@
  *   finish   index and direction to the four coordinates, to_basin from the basin raster, the key back to a double; +inf, -1 and
  *            zeros for a pond without a pass; the counts for wdpm_outlets_stats
  *
- * Everything that steers a loop is wave-uniform.  tests/outlets_emu_main.cpp compiles the kernels for the host under sanitizers
- * with WDPM_PONDS_EMULATION defined, as tests/catch_emu_main.cpp does with wdpm_pond_catchments.hip, and leaves the host half out.
+ * Over row blocks (include/wdpm_group_pond_outlets.h) every rank runs the same bodies over its owned rows (kRows) and owns every
+ * pass (a, b) whose a lies there.  The one row beyond either end holds the whole-raster basins its owner sent (they go up into the
+ * link raster's rows 0 and rows - 1) and is known by the level keys the catchment pass left in the rank's seam-key buffer: a halo
+ * row's dem and w are never read.  The table is indexed through the label -> slot table of the rims and catchments.  The pour key
+ * must be final over ALL ranks before anything is filled, so the host stands between passes and locate (wdpm_outlets_merge.h): the
+ * ranks' keys come down, the lowest per pond goes back up, and locate offers view_index * 8 + direction against that key.
+ *
+ * Everything that steers a loop is wave-uniform.  tests/outlets_emu_main.cpp and tests/group_outlets_emu_main.cpp compile the
+ * kernels for the host under sanitizers with WDPM_PONDS_EMULATION defined, as tests/catch_emu_main.cpp does with
+ * wdpm_pond_catchments.hip, and leave the host half out.
  */
 #include "wdpm_ponds_priv.h"
 
@@ -32,6 +40,21 @@ using namespace wdpm_pond_detail;
 namespace {
 
 constexpr unsigned long long kNone = ~0ull;        /* no pour key, no pair yet */
+
+/* What a row block's kernels know beyond a whole raster's (kRows; wave-uniform all of it): the owned rows [ra, rb) of the view, over
+ * which the strips are cut; which of view rows 0 and g.rows - 1 belong to a neighbour (halo bit 0: the one above, bit 1: the one
+ * below) - of those the basins are their owner's, sent up into the link raster, the level keys come from nkeys (2 x ncp, written by
+ * their owners) and neither dem nor w is ever read; the table is indexed through slot_of. */
+struct OutRows {
+  int ra, rb, halo;
+  const unsigned long long *nkeys;
+  const int *slot_of;
+};
+
+template <bool kRows>
+__device__ __forceinline__ int out_slot(const OutRows &rw, int L) {
+  return kRows ? rw.slot_of[L] : L - 1;
+}
 
 /* the key of the level of a cell that has one (basin >= 0): dem + w where there is water to add, dem where there is none */
 __device__ __forceinline__ unsigned long long level_key(double e, double d) { return depth_key(d > 0.0 ? e + d : e); }
@@ -82,13 +105,20 @@ __device__ __forceinline__ bool out_quiet(const OutWin &up, const OutWin &cur, c
 }
 
 /* Level keys of row r's cells that have a basin (those alone have a level and lie inside the raster).  Every load is issued before
- * the first is used: dem and w of a cell do not wait for each other. */
+ * the first is used: dem and w of a cell do not wait for each other.  A neighbour's row (kRows) brings its owner's keys. */
+template <bool kRows>
 __device__ __forceinline__ void out_fill(OutWin &x, const double *__restrict__ w, const double *__restrict__ dem, const Geom &g, int r,
-                                         int c, int lane) {
+                                         int c, int lane, const OutRows &rw) {
   if (x.has) return;
   x.has = true;
   if (x.val < 0) return;
   const int ce = lane == 0 ? c - 1 : c + 1;
+  if (kRows && ((r == 0 && (rw.halo & 1)) || (r == g.rows - 1 && (rw.halo & 2)))) {     /* dem and w of a halo row are not current */
+    const unsigned long long *nk = rw.nkeys + (r == 0 ? 0 : g.ncp);
+    if (x.b >= 0) x.key = nk[c];
+    if (x.eb >= 0) x.ek = nk[ce];
+    return;
+  }
   double e = 0.0, d = 0.0, ee = 0.0, de = 0.0;
   if (x.b >= 0) {
     e = dem[r * g.ncp + c];
@@ -128,14 +158,15 @@ __device__ __forceinline__ bool out_lowest(const OutWin &up, const OutWin &cur, 
 }
 
 /* ---- passes ---------------------------------------------------------------------------------------------------------------- */
-__global__ __launch_bounds__(kBlock) void outlet_passes_kernel(const double *__restrict__ w, const double *__restrict__ dem,
-                                                               const int *__restrict__ basins, Geom g, int rpw, int nwaves,
-                                                               OutletRow *table) {
+template <bool kRows>
+__device__ __forceinline__ void outlet_passes_body(const double *__restrict__ w, const double *__restrict__ dem,
+                                                   const int *__restrict__ basins, const Geom &g, int rpw, int nwaves, OutletRow *table,
+                                                   const OutRows &rw) {
   const int wid = blockIdx.x * kWaves + (threadIdx.x >> 6);
   if (wid >= nwaves) return;
   const int lane = threadIdx.x & 63;
   const int strip = wid / g.nsc, s = wid - strip * g.nsc;
-  const int r0 = strip * rpw, r1 = min(r0 + rpw, g.rows);
+  const int r0 = (kRows ? rw.ra : 0) + strip * rpw, r1 = min(r0 + rpw, kRows ? rw.rb : g.rows);
   const int c = s * kSeg + lane;
   int cy_label = 0;                        /* what the wave holds for one label and has not yet sent */
   unsigned long long cy_min = kNone, cy_divide = 0ull;
@@ -144,9 +175,9 @@ __global__ __launch_bounds__(kBlock) void outlet_passes_kernel(const double *__r
   for (int r = r0; r < r1; r++, up = cur, cur = dn) {
     dn = out_open(basins, g, r + 1, c, lane);
     if (out_quiet(up, cur, dn)) continue;
-    out_fill(up, w, dem, g, r - 1, c, lane);
-    out_fill(cur, w, dem, g, r, c, lane);
-    out_fill(dn, w, dem, g, r + 1, c, lane);
+    out_fill<kRows>(up, w, dem, g, r - 1, c, lane, rw);
+    out_fill<kRows>(cur, w, dem, g, r, c, lane, rw);
+    out_fill<kRows>(dn, w, dem, g, r + 1, c, lane, rw);
     unsigned long long height;
     int dir;
     const bool found = out_lowest(up, cur, dn, lane, height, dir);
@@ -161,8 +192,9 @@ __global__ __launch_bounds__(kBlock) void outlet_passes_kernel(const double *__r
       const unsigned long long lo = wave_min(cand == L ? height : kNone);
       if (cy_label != L) {                 /* down the rows: the same label goes on gathering, another one sends first */
         if (cy_label != 0 && lane == 0) {
-          atomic_min_if(&table[cy_label - 1].pour_key, cy_min);
-          atomicAdd(&table[cy_label - 1].divide_cells, cy_divide);
+          OutletRow *t = table + out_slot<kRows>(rw, cy_label);
+          atomic_min_if(&t->pour_key, cy_min);
+          atomicAdd(&t->divide_cells, cy_divide);
         }
         cy_label = L;
         cy_min = kNone;
@@ -174,41 +206,61 @@ __global__ __launch_bounds__(kBlock) void outlet_passes_kernel(const double *__r
     }
   }
   if (cy_label != 0 && lane == 0) {
-    atomic_min_if(&table[cy_label - 1].pour_key, cy_min);
-    atomicAdd(&table[cy_label - 1].divide_cells, cy_divide);
+    OutletRow *t = table + out_slot<kRows>(rw, cy_label);
+    atomic_min_if(&t->pour_key, cy_min);
+    atomicAdd(&t->divide_cells, cy_divide);
   }
+}
+
+__global__ __launch_bounds__(kBlock) void outlet_passes_kernel(const double *__restrict__ w, const double *__restrict__ dem,
+                                                               const int *__restrict__ basins, Geom g, int rpw, int nwaves,
+                                                               OutletRow *table) {
+  outlet_passes_body<false>(w, dem, basins, g, rpw, nwaves, table, OutRows());
+}
+
+/* the same over the owned rows of a row block's view: every pass (a, b) whose a the rank owns */
+__global__ __launch_bounds__(kBlock) void outlet_passes_rows_kernel(const double *__restrict__ w, const double *__restrict__ dem,
+                                                                    const int *__restrict__ basins, Geom g, int rpw, int nwaves,
+                                                                    OutletRow *table, OutRows rw) {
+  outlet_passes_body<true>(w, dem, basins, g, rpw, nwaves, table, rw);
 }
 
 /* ---- locate ---------------------------------------------------------------------------------------------------------------- */
 /* what a wave of the locate pass holds for one label */
 struct FillCarry {
   int label;               /* 0: nothing held */
+  int slot;                /* the label's table row */
   unsigned long long pour, cells, q;
 };
 
-/* the carry turns to label L: what it held goes out, and L's final pour key comes in */
-__device__ __forceinline__ void fill_turn(FillCarry &cy, OutletRow *table, int L, int lane) {
+/* the carry turns to label L: what it held goes out, and L's final pour key comes in.  A whole raster's row is L - 1 and needs no
+ * slot: the carry's stays unused there. */
+template <bool kRows>
+__device__ __forceinline__ void fill_turn(FillCarry &cy, OutletRow *table, int L, int lane, const OutRows &rw) {
   if (cy.label == L) return;
   if (cy.label != 0 && cy.cells != 0ull && lane == 0) {
-    atomicAdd(&table[cy.label - 1].fill_cells, cy.cells);
-    atomicAdd(&table[cy.label - 1].fill_q, cy.q);
+    atomicAdd(&table[kRows ? cy.slot : cy.label - 1].fill_cells, cy.cells);
+    atomicAdd(&table[kRows ? cy.slot : cy.label - 1].fill_q, cy.q);
   }
   cy.label = L;
-  cy.pour = L ? table[L - 1].pour_key : kNone;
+  if (kRows) cy.slot = L ? rw.slot_of[L] : 0;
+  cy.pour = L ? table[kRows ? cy.slot : L - 1].pour_key : kNone;
   cy.cells = cy.q = 0ull;
 }
 
-__global__ __launch_bounds__(kBlock) void outlet_locate_kernel(const double *__restrict__ w, const double *__restrict__ dem,
-                                                               const int *__restrict__ basins, Geom g, int rpw, int nwaves,
-                                                               OutletRow *table, OutletStatus *st) {
+template <bool kRows>
+__device__ __forceinline__ void outlet_locate_body(const double *__restrict__ w, const double *__restrict__ dem,
+                                                   const int *__restrict__ basins, const Geom &g, int rpw, int nwaves, OutletRow *table,
+                                                   OutletStatus *st, const OutRows &rw) {
   const int wid = blockIdx.x * kWaves + (threadIdx.x >> 6);
   if (wid >= nwaves) return;
   const int lane = threadIdx.x & 63;
   const int strip = wid / g.nsc, s = wid - strip * g.nsc;
-  const int r0 = strip * rpw, r1 = min(r0 + rpw, g.rows);
+  const int r0 = (kRows ? rw.ra : 0) + strip * rpw, r1 = min(r0 + rpw, kRows ? rw.rb : g.rows);
   const int c = s * kSeg + lane;
   FillCarry cy;
   cy.label = 0;
+  cy.slot = 0;
   cy.pour = kNone;
   cy.cells = cy.q = 0ull;
 
@@ -218,16 +270,16 @@ __global__ __launch_bounds__(kBlock) void outlet_locate_kernel(const double *__r
     if (!cur.pond) continue;
     const bool quiet = out_quiet(up, cur, dn);
     if (quiet) {                           /* one basin, cur.val > 0, and no pass here: without an outlet there is nothing to fill */
-      fill_turn(cy, table, cur.val, lane);
+      fill_turn<kRows>(cy, table, cur.val, lane, rw);
       if (cy.pour == kNone) continue;
     }
-    out_fill(cur, w, dem, g, r, c, lane);
+    out_fill<kRows>(cur, w, dem, g, r, c, lane, rw);
     unsigned long long height = kNone;
     int dir = 0;
     bool found = false;
     if (!quiet) {
-      out_fill(up, w, dem, g, r - 1, c, lane);
-      out_fill(dn, w, dem, g, r + 1, c, lane);
+      out_fill<kRows>(up, w, dem, g, r - 1, c, lane, rw);
+      out_fill<kRows>(dn, w, dem, g, r + 1, c, lane, rw);
       found = out_lowest(up, cur, dn, lane, height, dir);
     }
 
@@ -236,10 +288,10 @@ __global__ __launch_bounds__(kBlock) void outlet_locate_kernel(const double *__r
       const unsigned long long pending = __ballot(cand != 0);
       if (pending == 0ull) break;
       const int L = __shfl(cand, __builtin_ctzll(pending));
-      fill_turn(cy, table, L, lane);
+      fill_turn<kRows>(cy, table, L, lane, rw);
       const bool mine = cand == L;
       if (mine && found && height == cy.pour)
-        atomic_min_if(&table[L - 1].pair, (unsigned long long)(r * g.ncp + c) * 8ull + (unsigned long long)dir);
+        atomic_min_if(&table[kRows ? cy.slot : L - 1].pair, (unsigned long long)(r * g.ncp + c) * 8ull + (unsigned long long)dir);
       const bool below = mine && cy.pour != kNone && cur.key < cy.pour;
       const unsigned long long belowm = __ballot(below);
       if (belowm != 0ull) {
@@ -252,7 +304,21 @@ __global__ __launch_bounds__(kBlock) void outlet_locate_kernel(const double *__r
       if (mine) cand = 0;
     }
   }
-  fill_turn(cy, table, 0, lane);
+  fill_turn<kRows>(cy, table, 0, lane, rw);
+}
+
+__global__ __launch_bounds__(kBlock) void outlet_locate_kernel(const double *__restrict__ w, const double *__restrict__ dem,
+                                                               const int *__restrict__ basins, Geom g, int rpw, int nwaves,
+                                                               OutletRow *table, OutletStatus *st) {
+  outlet_locate_body<false>(w, dem, basins, g, rpw, nwaves, table, st, OutRows());
+}
+
+/* the same over the owned rows of a row block's view, against the pour keys the host merged over all ranks: the pair is a view
+ * index, and a rank that holds fill cells of a pond and none of its passes fills to the right level all the same */
+__global__ __launch_bounds__(kBlock) void outlet_locate_rows_kernel(const double *__restrict__ w, const double *__restrict__ dem,
+                                                                    const int *__restrict__ basins, Geom g, int rpw, int nwaves,
+                                                                    OutletRow *table, OutletStatus *st, OutRows rw) {
+  outlet_locate_body<true>(w, dem, basins, g, rpw, nwaves, table, st, rw);
 }
 
 /* ---- init, finish ---------------------------------------------------------------------------------------------------------- */
@@ -309,6 +375,33 @@ __global__ __launch_bounds__(kBlock) void outlet_finish_kernel(OutletRow *t, lon
     if (landm) atomicAdd(&st->to_land, (unsigned long long)__popcll(landm));
     if (divide) atomicAdd(&st->divide, divide);
   }
+}
+
+/* ---- row blocks: what goes between the ranks and the host -------------------------------------------------------------------- */
+/* after the passes: every slot's pour key and divide count, side by side for one copy down (n keys, then n counts) */
+__global__ __launch_bounds__(kBlock) void outlet_pour_down_kernel(const OutletRow *__restrict__ t, long long n, unsigned long long *__restrict__ out) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  out[i] = t[i].pour_key;
+  out[n + i] = t[i].divide_cells;
+}
+
+/* before the locate pass: every slot takes its pond's pour key as the host merged it over all ranks */
+__global__ __launch_bounds__(kBlock) void outlet_pour_up_kernel(OutletRow *__restrict__ t, long long n, const unsigned long long *__restrict__ keys) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) t[i].pour_key = keys[i];
+}
+
+/* after the locate pass: to_basin of every slot that offered a pair, from the view - the pair's b may lie in a neighbour's row, whose
+ * basins the view holds.  Key and pair stay as they are: the host decodes the winner's (wdpm_outlets_merge.h). */
+__global__ __launch_bounds__(kBlock) void outlet_finish_rows_kernel(OutletRow *t, long long n, const int *__restrict__ basins, int ncp) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const unsigned long long pair = t[i].pair;
+  if (pair == kNone) return;
+  const int from = (int)(pair >> 3), i8 = (int)(pair & 7ull);
+  const int dr = (i8 < 3 ? -1 : i8 < 5 ? 0 : 1), dc = (i8 < 3 ? i8 - 1 : i8 == 3 ? -1 : i8 == 4 ? 1 : i8 - 6);
+  t[i].to_basin = basins[from + dr * ncp + dc];
 }
 
 }  // namespace
@@ -409,6 +502,274 @@ extern "C" int wdpm_outlets_phase_ms(wdpm_ponds *h, double *ms) {
   if (!h->timing) return wdpm_fail("wdpm_outlets_phase_ms: the handle records no events (set WDPM_PONDS_TIMING=1 before it is made)");
   if (!h->valid || !h->outlets_valid) return wdpm_fail("wdpm_outlets_phase_ms: %s", kNoTable);
   for (int i = 0; i < WDPM_OUTLETS_PHASES; i++) ms[i] = h->outlet_ms[i];
+  return 0;
+}
+
+/* ---- row blocks (include/wdpm_group_pond_outlets.h) -------------------------------------------------------------------------- */
+#include <ctime>
+#include <string>
+
+#include "wdpm_outlets_merge.h"
+
+static_assert(sizeof(wdpm_outlets_merge::SlotRow) == sizeof(OutletRow) && offsetof(wdpm_outlets_merge::SlotRow, pair) == offsetof(OutletRow, pair) &&
+              offsetof(wdpm_outlets_merge::SlotRow, to_basin) == offsetof(OutletRow, to_basin) &&
+              offsetof(wdpm_outlets_merge::SlotRow, fill_q) == offsetof(OutletRow, fill_q), "the merge reads the slots' rows as the device leaves them");
+
+namespace {
+const char kNoGroupTable[] = "no outlet table: the last label call on this handle was not a wdpm_group_outlets_label that succeeded";
+
+/* after a failure with work queued: let every rank's stream run dry, so that nothing still reads what the caller may free */
+int group_outlets_drain(wdpm_group_ponds *h) {
+  std::string msg = wdpm_last_error();
+  for (wdpm_ponds *p : h->r)
+    if (hipSetDevice(p->x->p.device) == hipSuccess) (void)hipStreamSynchronize(p->x->stream);
+  return wdpm_fail("%s", msg.c_str());
+}
+
+double ms_between(const timespec &a, const timespec &b) { return (double)(b.tv_sec - a.tv_sec) * 1e3 + (double)(b.tv_nsec - a.tv_nsec) * 1e-6; }
+
+OutRows rows_of(const wdpm_group_ponds *gh, int i) {
+  const wdpm_ponds *h = gh->r[i];
+  OutRows rw;
+  rw.ra = gh->own_lo[i] - gh->view0[i];
+  rw.rb = rw.ra + gh->own_rows[i];
+  rw.halo = (i > 0 ? 1 : 0) | (i + 1 < gh->n ? 2 : 0);
+  rw.nkeys = h->d_ckeys + (size_t)2 * h->g.ncp;       /* the rows beside the rank's own, as the catchment pass brought them */
+  rw.slot_of = h->d_slot_of;
+  return rw;
+}
+
+/* rank i's buffers for `slots` table rows; nothing is queued */
+int group_outlets_buffers(wdpm_ponds *h, int i, long long slots) {
+  HIP_TRY(hipSetDevice(h->x->p.device));
+  if (!h->d_ostat) {
+    hipError_t e = hipMalloc(&h->d_ostat, sizeof(OutletStatus));
+    if (e != hipSuccess) { h->d_ostat = nullptr; return wdpm_fail("wdpm_group_outlets_label: no device memory for the status words of rank %d: %s", i, hipGetErrorString(e)); }
+    e = hipHostMalloc(&h->h_ostat, sizeof(OutletStatus));
+    if (e != hipSuccess) { h->h_ostat = nullptr; (void)hipFree(h->d_ostat); h->d_ostat = nullptr; return wdpm_fail("wdpm_group_outlets_label: no pinned host memory for the status words of rank %d: %s", i, hipGetErrorString(e)); }
+  }
+  if (!h->h_oseam) {
+    const hipError_t e = hipHostMalloc(&h->h_oseam, (size_t)2 * h->g.ncp * sizeof(int));
+    if (e != hipSuccess) { h->h_oseam = nullptr; return wdpm_fail("wdpm_group_outlets_label: no pinned host memory for two rows of basins of rank %d: %s", i, hipGetErrorString(e)); }
+  }
+  if (slots > h->outlets_cap) {
+    guarded_free(h, h->d_outlets);
+    h->d_outlets = nullptr;
+    h->outlets_cap = 0;
+    const hipError_t e = guarded_malloc(h, (void **)&h->d_outlets, (size_t)slots * sizeof(OutletRow));
+    if (e != hipSuccess) return wdpm_fail("wdpm_group_outlets_label: no device memory for %lld outlet rows of rank %d: %s", slots, i, hipGetErrorString(e));
+    h->outlets_cap = slots;
+  }
+  if (slots > h->okeys_cap) {
+    guarded_free(h, h->d_okeys);
+    if (h->h_okeys) (void)hipHostFree(h->h_okeys);
+    h->d_okeys = h->h_okeys = nullptr;
+    h->okeys_cap = 0;
+    hipError_t e = guarded_malloc(h, (void **)&h->d_okeys, (size_t)2 * slots * sizeof(unsigned long long));
+    if (e != hipSuccess) { h->d_okeys = nullptr; return wdpm_fail("wdpm_group_outlets_label: no device memory for the pour keys of %lld slots of rank %d: %s", slots, i, hipGetErrorString(e)); }
+    e = hipHostMalloc(&h->h_okeys, (size_t)3 * slots * sizeof(unsigned long long));
+    if (e != hipSuccess) { h->h_okeys = nullptr; guarded_free(h, h->d_okeys); h->d_okeys = nullptr; return wdpm_fail("wdpm_group_outlets_label: no pinned host memory for the pour keys of %lld slots of rank %d: %s", slots, i, hipGetErrorString(e)); }
+    h->okeys_cap = slots;
+  }
+  if (slots > h->h_outlets_cap) {
+    if (h->h_outlets) (void)hipHostFree(h->h_outlets);
+    h->h_outlets = nullptr;
+    h->h_outlets_cap = 0;
+    const hipError_t e = hipHostMalloc(&h->h_outlets, (size_t)slots * sizeof(OutletRow));
+    if (e != hipSuccess) { h->h_outlets = nullptr; return wdpm_fail("wdpm_group_outlets_label: no pinned host memory for %lld outlet rows of rank %d: %s", slots, i, hipGetErrorString(e)); }
+    h->h_outlets_cap = slots;
+  }
+  return 0;
+}
+
+/* one wait per rank that has work queued; the first message stays */
+int group_outlets_wait(wdpm_group_ponds *gh, int ev_a, int ev_b, int phase) {
+  bool bad = false;
+  std::string first_msg;
+  for (int i = 0; i < gh->n; i++) {
+    wdpm_ponds *p = gh->r[i];
+    if (p->catch_slots == 0) continue;
+    bool failed = hipSetDevice(p->x->p.device) != hipSuccess || wdpm_stream_sync(p->x, p->x->stream);
+    if (!failed && p->timing) {
+      float ms = 0.f;
+      const hipError_t e = hipEventElapsedTime(&ms, p->outlet_ev[ev_a], p->outlet_ev[ev_b]);
+      if (e != hipSuccess) failed = wdpm_fail("wdpm_group_outlets_label: the events of rank %d cannot be read: %s", i, hipGetErrorString(e)) != 0;
+      p->outlet_ms[phase] = ms;
+    }
+    if (failed) {
+      if (!bad) first_msg = wdpm_last_error();
+      bad = true;
+    }
+  }
+  return bad ? wdpm_fail("%s", first_msg.c_str()) : 0;
+}
+}  // namespace
+
+extern "C" int wdpm_group_outlets_label(wdpm_group_ponds *h, double min_depth, int64_t *nponds) {
+  if (!h) return wdpm_fail("wdpm_group_outlets_label: null handle");
+  if (!(min_depth >= 0.0) || std::isinf(min_depth))
+    return wdpm_fail("wdpm_group_outlets_label: min_depth must be finite and >= 0 (got %g)", min_depth);
+  int64_t n = 0;
+  const int rc = wdpm_group_catch_label(h, min_depth, &n);    /* leaves basins, seam keys, slots and the seam basins on the host */
+  h->valid = false;                                           /* a wdpm_group_outlets_label that fails leaves no table of any kind */
+  if (rc) return 1;
+  const int nr = h->n, ncp = h->ncp;
+  for (int i = 0; i < nr; i++) {
+    wdpm_ponds *p = h->r[i];
+    p->outlet_ms[0] = p->outlet_ms[1] = 0.0;
+    if (n > 0 && p->catch_slots > 0 && group_outlets_buffers(p, i, p->catch_slots)) return 1;
+  }
+  h->outlets.assign((size_t)n, wdpm_pond_outlet());
+  wdpm_outlets_merge::Totals tot;
+  double merge_ms = 0.0;
+  if (n > 0) {                                                /* no pond, no outlet: nothing to launch */
+    /* (A) every rank: the facing ranks' seam basins into its halo rows, init, passes, keys and divide counts on their way down */
+    for (int i = 0; i < nr; i++) {
+      wdpm_ponds *p = h->r[i];
+      if (p->catch_slots == 0) continue;                      /* no basin > 0 in its rows: no pass starts there */
+      wdpm_ctx *x = p->x;
+      const Geom g = p->g;
+      const hipStream_t sm = x->stream;
+      const OutRows rw = rows_of(h, i);
+      const long long slots = p->catch_slots;
+      const size_t off = (size_t)p->row_off * g.ncp;
+      const double *w = x->d_w[x->cur] + off, *dem = x->d_dem + off;
+      const int rpw = ponds_rows_per_wave(g.nseg, g.rows, p->forced_rpw);
+      const int nwaves = ((rw.rb - rw.ra + rpw - 1) / rpw) * g.nsc;
+      hipError_t e = hipSetDevice(x->p.device);
+      if (e == hipSuccess) e = hipMemsetAsync(p->d_ostat, 0, sizeof(OutletStatus), sm);
+      if (e == hipSuccess && p->timing) e = hipEventRecord(p->outlet_ev[0], sm);
+      for (int side = 0; side < 2 && e == hipSuccess; side++) {
+        if (!(rw.halo & (1 << side))) continue;
+        const int *src = side ? h->r[i + 1]->h_cexit : h->r[i - 1]->h_cexit + ncp;      /* the first row below, the last row above */
+        memcpy(p->h_oseam + (size_t)side * ncp, src, (size_t)ncp * sizeof(int));
+        e = hipMemcpyAsync(p->d_link + (size_t)(side ? g.rows - 1 : 0) * g.ncp, p->h_oseam + (size_t)side * ncp, (size_t)ncp * sizeof(int),
+                           hipMemcpyHostToDevice, sm);
+      }
+      if (e == hipSuccess) {
+        hipLaunchKernelGGL(outlet_init_kernel, dim3(blocks_for(slots, kBlock)), dim3(kBlock), 0, sm, p->d_outlets, slots);
+        hipLaunchKernelGGL(outlet_passes_rows_kernel, dim3(blocks_for(nwaves, kWaves)), dim3(kBlock), 0, sm, w, dem, p->d_link, g, rpw, nwaves,
+                           p->d_outlets, rw);
+        hipLaunchKernelGGL(outlet_pour_down_kernel, dim3(blocks_for(slots, kBlock)), dim3(kBlock), 0, sm, p->d_outlets, slots, p->d_okeys);
+        e = hipGetLastError();
+      }
+      if (e == hipSuccess && p->timing) e = hipEventRecord(p->outlet_ev[1], sm);
+      if (e == hipSuccess) e = hipMemcpyAsync(p->h_okeys, p->d_okeys, (size_t)2 * slots * sizeof(unsigned long long), hipMemcpyDeviceToHost, sm);
+      if (e != hipSuccess) {
+        (void)wdpm_fail("wdpm_group_outlets_label: queueing the passes of rank %d failed: %s", i, hipGetErrorString(e));
+        return group_outlets_drain(h);
+      }
+    }
+    if (group_outlets_wait(h, 0, 1, 0)) return 1;
+
+    timespec t0, t1, t2, t3;
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    std::vector<wdpm_outlets_merge::Rank> ranks((size_t)nr);
+    std::vector<unsigned long long *> up((size_t)nr);
+    for (int i = 0; i < nr; i++) {
+      const wdpm_ponds *p = h->r[i];
+      wdpm_outlets_merge::Rank &rk = ranks[(size_t)i];
+      rk.label = p->slot_label.data();
+      rk.slots = p->catch_slots;
+      rk.remote = p->catch_remote_label.data();
+      rk.nremote = p->catch_remote;
+      rk.key = p->h_okeys;
+      rk.divide = p->h_okeys + p->catch_slots;
+      rk.rows = reinterpret_cast<const wdpm_outlets_merge::SlotRow *>(p->h_outlets);
+      rk.row_shift = h->view0[i];
+      rk.own_lo = h->own_lo[i];
+      rk.own_rows = h->own_rows[i];
+      up[(size_t)i] = p->h_okeys + (size_t)2 * p->okeys_cap;
+    }
+    std::vector<unsigned long long> pour_key((size_t)n);
+    std::vector<long long> divide((size_t)n);
+    std::string err;
+    if (wdpm_outlets_merge::pour(ranks, n, pour_key.data(), divide.data(), up, err)) return wdpm_fail("wdpm_group_outlets_label: %s", err.c_str());
+    clock_gettime(CLOCK_MONOTONIC, &t1);
+
+    /* (B) every rank: the merged keys into its slots, locate, finish, its rows and its status word on their way down */
+    for (int i = 0; i < nr; i++) {
+      wdpm_ponds *p = h->r[i];
+      if (p->catch_slots == 0) continue;
+      wdpm_ctx *x = p->x;
+      const Geom g = p->g;
+      const hipStream_t sm = x->stream;
+      const OutRows rw = rows_of(h, i);
+      const long long slots = p->catch_slots;
+      const size_t off = (size_t)p->row_off * g.ncp;
+      const double *w = x->d_w[x->cur] + off, *dem = x->d_dem + off;
+      const int rpw = ponds_rows_per_wave(g.nseg, g.rows, p->forced_rpw);
+      const int nwaves = ((rw.rb - rw.ra + rpw - 1) / rpw) * g.nsc;
+      hipError_t e = hipSetDevice(x->p.device);
+      if (e == hipSuccess && p->timing) e = hipEventRecord(p->outlet_ev[1], sm);
+      if (e == hipSuccess) e = hipMemcpyAsync(p->d_okeys, up[(size_t)i], (size_t)slots * sizeof(unsigned long long), hipMemcpyHostToDevice, sm);
+      if (e == hipSuccess) {
+        hipLaunchKernelGGL(outlet_pour_up_kernel, dim3(blocks_for(slots, kBlock)), dim3(kBlock), 0, sm, p->d_outlets, slots, p->d_okeys);
+        hipLaunchKernelGGL(outlet_locate_rows_kernel, dim3(blocks_for(nwaves, kWaves)), dim3(kBlock), 0, sm, w, dem, p->d_link, g, rpw, nwaves,
+                           p->d_outlets, p->d_ostat, rw);
+        hipLaunchKernelGGL(outlet_finish_rows_kernel, dim3(blocks_for(slots, kBlock)), dim3(kBlock), 0, sm, p->d_outlets, slots, p->d_link, g.ncp);
+        e = hipGetLastError();
+      }
+      if (e == hipSuccess && p->timing) e = hipEventRecord(p->outlet_ev[2], sm);
+      if (e == hipSuccess) e = hipMemcpyAsync(p->h_outlets, p->d_outlets, (size_t)slots * sizeof(OutletRow), hipMemcpyDeviceToHost, sm);
+      if (e == hipSuccess) e = hipMemcpyAsync(p->h_ostat, p->d_ostat, sizeof(OutletStatus), hipMemcpyDeviceToHost, sm);
+      if (e != hipSuccess) {
+        (void)wdpm_fail("wdpm_group_outlets_label: queueing the locate pass of rank %d failed: %s", i, hipGetErrorString(e));
+        return group_outlets_drain(h);
+      }
+    }
+    if (group_outlets_wait(h, 1, 2, 1)) return 1;
+    for (int i = 0; i < nr; i++)
+      if (h->r[i]->catch_slots > 0 && h->r[i]->h_ostat->deep)
+        return wdpm_fail("wdpm_group_outlets_label: a cell of a pond's basin in the rows of rank %d lies 512 m or more below the pond's outlet, or "
+                         "not a finite depth below it: fill_q (a 64-bit sum of depths in units of 2^-24 m) is only safe below that depth", i);
+
+    clock_gettime(CLOCK_MONOTONIC, &t2);
+    if (wdpm_outlets_merge::merge(ranks, n, ncp, pour_key.data(), divide.data(), h->outlets.data(), tot, err))
+      return wdpm_fail("wdpm_group_outlets_label: %s", err.c_str());
+    clock_gettime(CLOCK_MONOTONIC, &t3);
+    merge_ms = ms_between(t0, t1) + ms_between(t2, t3);
+  }
+  h->outlet_stats.ponds = n;
+  h->outlet_stats.no_outlet = tot.no_outlet;
+  h->outlet_stats.to_land = tot.to_land;
+  h->outlet_stats.divide_cells = tot.divide_cells;
+  h->outlet_stats.ranks = nr;
+  h->outlet_stats.seam_outlets = tot.seam_outlets;
+  h->outlet_stats.split_ponds = tot.split_ponds;
+  h->outlet_stats.merge_ms = merge_ms;
+  h->outlets_valid = true;
+  h->valid = true;
+  if (nponds) *nponds = n;
+  return 0;
+}
+
+extern "C" int wdpm_group_outlets_table(wdpm_group_ponds *h, wdpm_pond_outlet *out, int64_t capacity) {
+  if (!h) return wdpm_fail("wdpm_group_outlets_table: null handle");
+  if (!h->valid || !h->outlets_valid) return wdpm_fail("wdpm_group_outlets_table: %s", kNoGroupTable);
+  const long long n = h->stats.ponds;
+  if (capacity < n) return wdpm_fail("wdpm_group_outlets_table: capacity %lld is too small for %lld ponds", (long long)capacity, n);
+  if (n == 0) return 0;
+  if (!out) return wdpm_fail("wdpm_group_outlets_table: null output");
+  memcpy(out, h->outlets.data(), (size_t)n * sizeof(wdpm_pond_outlet));
+  return 0;
+}
+
+extern "C" int wdpm_group_outlets_stats(wdpm_group_ponds *h, wdpm_group_outlet_stats *out) {
+  if (!h) return wdpm_fail("wdpm_group_outlets_stats: null handle");
+  if (!out) return wdpm_fail("wdpm_group_outlets_stats: null output");
+  if (!h->valid || !h->outlets_valid) return wdpm_fail("wdpm_group_outlets_stats: %s", kNoGroupTable);
+  *out = h->outlet_stats;
+  return 0;
+}
+
+extern "C" int wdpm_group_outlets_phase_ms(wdpm_group_ponds *h, int32_t rank, double *ms) {
+  if (!h) return wdpm_fail("wdpm_group_outlets_phase_ms: null handle");
+  if (!ms) return wdpm_fail("wdpm_group_outlets_phase_ms: null output");
+  if (rank < 0 || rank >= h->n) return wdpm_fail("wdpm_group_outlets_phase_ms: rank %d of %d", rank, h->n);
+  if (!h->timing) return wdpm_fail("wdpm_group_outlets_phase_ms: the handle records no events (set WDPM_PONDS_TIMING=1 before it is made)");
+  if (!h->valid || !h->outlets_valid) return wdpm_fail("wdpm_group_outlets_phase_ms: %s", kNoGroupTable);
+  for (int i = 0; i < WDPM_OUTLETS_PHASES; i++) ms[i] = h->r[rank]->outlet_ms[i];
   return 0;
 }
 #endif  /* WDPM_PONDS_EMULATION */

@@ -504,6 +504,14 @@ void release(wdpm_ponds *h) {
   h->outlets_cap = 0;
   h->d_ostat = h->h_ostat = nullptr;
   h->outlets_valid = false;
+  guarded_free(h, h->d_okeys);
+  if (h->h_okeys) (void)hipHostFree(h->h_okeys);
+  if (h->h_outlets) (void)hipHostFree(h->h_outlets);
+  if (h->h_oseam) (void)hipHostFree(h->h_oseam);
+  h->d_okeys = h->h_okeys = nullptr;
+  h->h_outlets = nullptr;
+  h->h_oseam = nullptr;
+  h->okeys_cap = h->h_outlets_cap = 0;
   if (h->h_beside) (void)hipHostFree(h->h_beside);
   if (h->h_rims) (void)hipHostFree(h->h_rims);
   h->d_slot_of = h->d_foreign = nullptr;
@@ -605,6 +613,10 @@ wdpm_ponds *make_handle(wdpm_ctx *ctx, int row_off, int rows, bool seams) {
   h->d_ostat = h->h_ostat = nullptr;
   h->outlets_valid = false;
   memset(&h->outlet_stats, 0, sizeof h->outlet_stats);
+  h->d_okeys = h->h_okeys = nullptr;
+  h->h_outlets = nullptr;
+  h->h_oseam = nullptr;
+  h->okeys_cap = h->h_outlets_cap = 0;
   h->nb = 0;
   { const char *re = getenv("WDPM_PONDS_ROWS_PER_WAVE"); h->forced_rpw = re ? atoi(re) : 0; }
   h->rpw = 1;
@@ -884,7 +896,9 @@ extern "C" int wdpm_group_ponds_create(wdpm_group_ponds **out, wdpm_group *grp) 
   h->valid = false;
   h->rims_valid = false;
   h->catch_valid = false;
+  h->outlets_valid = false;
   h->timing = true;
+  memset(&h->outlet_stats, 0, sizeof h->outlet_stats);
   memset(&h->stats, 0, sizeof h->stats);
   memset(&h->rim_stats, 0, sizeof h->rim_stats);
   memset(&h->catch_stats, 0, sizeof h->catch_stats);
@@ -952,6 +966,7 @@ int wdpm_pond_detail::group_label(wdpm_group_ponds *h, double min_depth, int64_t
   h->valid = false;
   h->rims_valid = false;            /* a rim table belongs to the label call that made it */
   h->catch_valid = false;           /* and so does a catchment table */
+  h->outlets_valid = false;         /* and an outlet table */
   const int n = h->n;
   /* every rank up to its scan, on its own stream and device, before the first wait */
   for (int i = 0; i < n; i++)

@@ -34,6 +34,7 @@
 #include "../../include/wdpm_pond_catchments.h"
 #include "../../include/wdpm_pond_outlets.h"
 #include "../../include/wdpm_group_pond_catchments.h"
+#include "../../include/wdpm_group_pond_outlets.h"
 
 namespace wdpm_pond_detail {
 
@@ -250,7 +251,8 @@ struct wdpm_ponds {
   unsigned long long *d_ckeys;      /* 4 x g.ncp level keys: the rank's first and last owned row, then the rows beside them */
   unsigned long long *h_ckeys;      /* pinned, laid out likewise: two rows on their way down, two on their way up */
   int *d_cexit;                     /* 4 x g.ncp: where each exit ends (2 x g.ncp), the remote ponds' labels */
-  int *h_cexit;                     /* pinned, 6 x g.ncp: the links of the first and last owned row on their way down, then as d_cexit */
+  int *h_cexit;                     /* pinned, 6 x g.ncp: the links of the first and last owned row on their way down (and, behind the */
+                                    /* tally, the same rows as basins: the seam basins of the outlet pass), then as d_cexit */
   wdpm_pond_catchment *h_catch;     /* pinned: the finished catchment rows on their way down */
   long long h_catch_cap;
   long long catch_slots, catch_remote;   /* of the call under way */
@@ -264,9 +266,17 @@ struct wdpm_ponds {
   hipEvent_t outlet_ev[WDPM_OUTLETS_PHASES + 1];      /* init, passes | locate, finish */
   double outlet_ms[WDPM_OUTLETS_PHASES];
   wdpm_pond_outlet_stats outlet_stats;
+  /* outlets of a row block (wdpm_group_outlets_label): d_outlets then holds one row per SLOT, as d_catch does */
+  unsigned long long *d_okeys;      /* 2 x okeys_cap: every slot's pour key and divide count on their way down, the merged keys on their way up */
+  unsigned long long *h_okeys;      /* pinned, 3 x okeys_cap: keys and counts as they came down, then the merged keys */
+  long long okeys_cap;
+  wdpm_pond_detail::OutletRow *h_outlets;   /* pinned: the slots' rows on their way down */
+  long long h_outlets_cap;
+  int *h_oseam;                     /* pinned, 2 x g.ncp: the facing ranks' seam basins on their way up */
 };
 
-/* the handle of include/wdpm_group_ponds.h, include/wdpm_group_pond_rims.h and include/wdpm_group_pond_catchments.h */
+/* the handle of include/wdpm_group_ponds.h, include/wdpm_group_pond_rims.h, include/wdpm_group_pond_catchments.h and
+ * include/wdpm_group_pond_outlets.h */
 struct wdpm_group_ponds {
   wdpm_group *grp;
   int n;                                   /* ranks */
@@ -284,6 +294,10 @@ struct wdpm_group_ponds {
   std::vector<wdpm_pond_catchment> catchments;
   bool catch_valid;
   wdpm_group_catchment_stats catch_stats;
+  /* outlets: the merged table of the last wdpm_group_outlets_label; every label call takes outlets_valid away first */
+  std::vector<wdpm_pond_outlet> outlets;
+  bool outlets_valid;
+  wdpm_group_outlet_stats outlet_stats;
 };
 
 namespace wdpm_pond_detail {

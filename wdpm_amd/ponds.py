@@ -1,7 +1,7 @@
 """ctypes binding of include/wdpm_ponds.h, include/wdpm_group_ponds.h, include/wdpm_pond_rims.h, include/wdpm_group_pond_rims.h,
-include/wdpm_pond_catchments.h, include/wdpm_pond_outlets.h and include/wdpm_group_pond_catchments.h: the pond inventory of a
-context's current water raster, of a raster spread over the row blocks of a rowblock.Group, the rim and the catchment of every pond
-of either, and the outlet of every pond of a whole raster.
+include/wdpm_pond_catchments.h, include/wdpm_pond_outlets.h, include/wdpm_group_pond_catchments.h and
+include/wdpm_group_pond_outlets.h: the pond inventory of a context's current water raster, of a raster spread over the row blocks of
+a rowblock.Group, and the rim, the catchment and the outlet of every pond of either.
 
 Product library only (the symbols are not part of the ABI of include/wdpm.h, and ``capi.SYMBOLS`` does not list them).
 
@@ -25,6 +25,8 @@ Product library only (the symbols are not part of the ABI of include/wdpm.h, and
         rims = ponds.rims()         # RIM_DTYPE, coordinates of the whole raster
         n = ponds.label_catchments(0.001)   # and every rank's receivers, jump rounds and tally; the host ends the descents that
         basins = ponds.basins()     # cross row blocks and adds the ranks' tables up (CATCH_DTYPE, coordinates of the whole raster)
+        n = ponds.label_outlets(0.001)      # and every rank's passes; the host makes the pour levels final between the two passes
+        outlets = ponds.outlets()   # OUTLET_DTYPE, coordinates of the whole raster
 """
 from __future__ import annotations
 
@@ -193,12 +195,28 @@ GROUP_CATCH_SYMBOLS = {
 }
 
 
+class GroupOutletStatsStruct(C.Structure):
+    """struct wdpm_group_outlet_stats"""
+    _fields_ = [("ponds", C.c_int64), ("no_outlet", C.c_int64), ("to_land", C.c_int64), ("divide_cells", C.c_int64),
+                ("ranks", C.c_int64), ("seam_outlets", C.c_int64), ("split_ponds", C.c_int64), ("merge_ms", C.c_double)]
+
+
+# every symbol include/wdpm_group_pond_outlets.h declares
+GROUP_OUTLET_SYMBOLS = {
+    "wdpm_group_outlets_label": (C.c_int, [_vp, C.c_double, C.POINTER(C.c_int64)]),
+    "wdpm_group_outlets_table": (C.c_int, [_vp, _vp, C.c_int64]),
+    "wdpm_group_outlets_stats": (C.c_int, [_vp, C.POINTER(GroupOutletStatsStruct)]),
+    "wdpm_group_outlets_phase_ms": (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_double)]),
+}
+
+
 def bind(lib: capi.Lib):
     """Set the prototypes on a loaded product library; a library without the symbols is an error (no fallback)."""
     if getattr(lib, "_ponds_bound", False):
         return lib.dll
     for name, (res, args) in list(SYMBOLS.items()) + list(GROUP_SYMBOLS.items()) + list(RIM_SYMBOLS.items()) + \
-            list(GROUP_RIM_SYMBOLS.items()) + list(CATCH_SYMBOLS.items()) + list(OUTLET_SYMBOLS.items()) + list(GROUP_CATCH_SYMBOLS.items()):
+            list(GROUP_RIM_SYMBOLS.items()) + list(CATCH_SYMBOLS.items()) + list(OUTLET_SYMBOLS.items()) + list(GROUP_CATCH_SYMBOLS.items()) + \
+            list(GROUP_OUTLET_SYMBOLS.items()):
         try:
             fn = getattr(lib.dll, name)
         except AttributeError:
@@ -445,3 +463,22 @@ class GroupPonds(_Handle):
         """milliseconds of one rank's receiver pass, jump rounds and tally in the last label_catchments() (handles made with
         WDPM_PONDS_TIMING=1)"""
         return self._phase_ms(self.dll.wdpm_group_catch_phase_ms, CATCH_PHASES, int(rank))
+
+    def label_outlets(self, min_depth: float) -> int:
+        """label_catchments(min_depth), and every rank's outlet pass on the same water; every older query answers as after
+        label_catchments()."""
+        return self._label(self.dll.wdpm_group_outlets_label, min_depth)
+
+    def outlets(self, capacity: int | None = None) -> np.ndarray:
+        """One row per pond (OUTLET_DTYPE) of the last label_outlets(), coordinates of the whole raster; fails after any lesser
+        label call."""
+        return self._table(self.dll.wdpm_group_outlets_table, OUTLET_DTYPE, "outlets", capacity)
+
+    def outlet_stats(self) -> dict:
+        """the counts of Ponds.outlet_stats for the whole raster, then ranks, seam_outlets, split_ponds and merge_ms"""
+        return self._stats(self.dll.wdpm_group_outlets_stats, GroupOutletStatsStruct)
+
+    def outlet_phase_ms(self, rank: int) -> dict:
+        """milliseconds of one rank's pass over the pairs and of its locate pass in the last label_outlets() (handles made with
+        WDPM_PONDS_TIMING=1)"""
+        return self._phase_ms(self.dll.wdpm_group_outlets_phase_ms, OUTLET_PHASES, int(rank))
