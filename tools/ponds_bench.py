@@ -29,6 +29,10 @@
                       phases and their sums over the ranks, the host's merge_ms, seam_outlets and split_ponds; then the whole-raster
                       call on the same water in the same process, the yardstick of those sums (default --out
                       profiles/r17/pond_outlets_group.json)
+    ... --curves      the stage curves of the ponds as well (include/wdpm_pond_curves.h): five more timed calls of label_curves, the
+                      bed and stages phases beside the table, passes and locate phases of the SAME calls, their ratios, and their
+                      rates under the byte model of 12 B per cell and pass (int32 basin, fp64 dem) against the yardstick (default
+                      --out profiles/r18/pond_curves.json)
     ... --iterations K   instead of the job's own number of iterations before the inventory
 
 Per job: one untimed label call, then five timed ones (wall clock around the call, which ends with the stream idle; HIP events
@@ -56,7 +60,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 import wdpm_amd  # noqa: E402
-from wdpm_amd.ponds import CATCH_PHASES, OUTLET_PHASES, PHASES, RIM_PHASES, GroupPonds, Ponds  # noqa: E402
+from wdpm_amd.ponds import CATCH_PHASES, CURVE_PHASES, OUTLET_PHASES, PHASES, RIM_PHASES, GroupPonds, Ponds  # noqa: E402
 
 MISS = -99999.0
 
@@ -176,6 +180,36 @@ def outlets_job(ctx, p, rec, n):
     o["gbps"] = {k: {"20B": 20 * cells / (med[k] * 1e6), "4B": 4 * cells / (med[k] * 1e6)} if med[k] > 0 else None for k in OUTLET_PHASES}
     if rec.get("hbm_yardstick_gbps"):
         o["of_yardstick"] = {k: {m: r / rec["hbm_yardstick_gbps"] for m, r in v.items()} if v else None for k, v in o["gbps"].items()}
+
+
+def curves_job(ctx, p, rec, n):
+    """after the label calls: one untimed label_curves (allocates the curve table and everything below it), five timed ones"""
+    p.label_curves(0.001)
+    beside_names = ("table", "passes", "locate")
+    wall, phases, beside = [], {k: [] for k in CURVE_PHASES}, {k: [] for k in beside_names}
+    for _ in range(5):
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        p.label_curves(0.001)
+        wall.append((time.perf_counter() - t0) * 1e3)
+        for k, v in p.curve_phase_ms().items():
+            phases[k].append(v)
+        beside["table"].append(p.phase_ms()["table"])
+        for k, v in p.outlet_phase_ms().items():
+            beside[k].append(v)
+    table, stats = p.curves(), p.curve_stats()
+    med = {k: statistics.median(v) for k, v in phases.items()}
+    bmed = {k: statistics.median(v) for k, v in beside.items()}
+    cells = (n + 2) * (n + 2)
+    c = rec["curves"] = dict(
+        label_curves_wall_ms=statistics.median(wall), label_curves_wall_ms_all=wall, phase_ms=med, phase_ms_all=phases,
+        beside_ms_same_calls=bmed, beside_ms_all=beside,
+        over={b: {k: med[k] / bmed[b] if bmed[b] > 0 else None for k in CURVE_PHASES} for b in beside_names}, stats=stats,
+        basin_cells_with_a_curve=int(stats["stage_cells"]), largest_stage_count=int(table["cells"][:, -1].max()) if len(table) else 0,
+        table_bytes=int(table.nbytes), bytes_model={"per_pass_12B": 12 * cells}, guard_bad=p.guard_bad())
+    c["gbps_12B"] = {k: 12 * cells / (med[k] * 1e6) if med[k] > 0 else None for k in CURVE_PHASES}
+    if rec.get("hbm_yardstick_gbps"):
+        c["of_yardstick"] = {k: v / rec["hbm_yardstick_gbps"] if v else None for k, v in c["gbps_12B"].items()}
 
 
 def yardstick_gbps(path):
@@ -350,6 +384,7 @@ def main():
     ap.add_argument("--catchments", action="store_true",
                     help="time label_catchments as well, interleaved with label_rims: the receiver, jump and tally phases")
     ap.add_argument("--outlets", action="store_true", help="time label_outlets as well: the passes and locate phases beside the table phase")
+    ap.add_argument("--curves", action="store_true", help="time label_curves as well: the bed and stages phases beside table, passes and locate")
     ap.add_argument("--iterations", type=int, help="iterations before the inventory, instead of the job's own")
     a = ap.parse_args()
     if not a.out:
@@ -357,6 +392,7 @@ def main():
                                                   ("r16", "pond_catchments_group.json") if a.devices and a.catchments else
                                                   ("r13", "pond_rims_group.json") if a.devices and a.rims else
                                                   ("r11", "ponds_group.json") if a.devices else
+                                                  ("r18", "pond_curves.json") if a.curves else
                                                   ("r15", "pond_outlets.json") if a.outlets else
                                                   ("r14", "pond_catchments.json") if a.catchments else
                                                   ("r12", "pond_rims.json") if a.rims else ("r10", "ponds.json")))
@@ -382,6 +418,8 @@ def main():
     rec = dict(job=a.job, n=n, iterations=iters, build=hip.dll.wdpm_build_info().decode())
     if a.yardstick:
         rec["hbm_yardstick_gbps"] = yardstick_gbps(a.yardstick)
+    if a.devices and a.curves:
+        raise SystemExit("--curves: stage curves are taken on whole rasters only (no --devices)")
     if a.devices:
         group_job(hip, a, bd, bw, iters, rec)
         line = json.dumps(rec)
@@ -428,6 +466,8 @@ def main():
                 catchments_job(ctx, p, rec, n)
             if a.outlets:
                 outlets_job(ctx, p, rec, n)
+            if a.curves:
+                curves_job(ctx, p, rec, n)
         if not a.no_scipy:
             try:
                 import scipy.ndimage as ndi

@@ -1,0 +1,342 @@
+/*
+ * wdpm_pond_curves.hip — the stage curve of every pond (include/wdpm_pond_curves.h): the lowest ground of the pond's basin, and the
+ * cells and the storage of the basin below sixteen levels between that bed and the pond's pour level; from the basin raster, the DEM
+ * and the outlet table a wdpm_outlets_label leaves on the device.  gfx950.  A unit of its own beside wdpm_ponds.hip,
+ * wdpm_pond_rims.hip, wdpm_pond_catchments.hip and wdpm_pond_outlets.hip: not in the launch ledger, not among the sources
+ * wdpm_build_info() hashes.
+ *
+ * A wave owns one 64-column segment over rows_per_wave rows (ponds_rows_per_wave), as in the other units.  Neither pass has a
+ * stencil - a cell wants its own basin and its own dem - so there is no window and no exchange of columns.
+ *
+ *   init     bed keys to the maximum, the pour level of the outlet table into top_level, counts and sums to zero
+ *   bed      a row's basins; a row with no basin > 0 reads no dem.  Otherwise per wave BY LABEL a butterfly minimum of the dem keys,
+ *            carried down the rows while the label stays, and one atomic_min_if on the pond's bed key per (wave, label change)
+ *   stages   after every bed key is final.  A lane keeps bed and top of its own basin and reloads them only when its basin differs
+ *            from the one it held; a row whose lanes hold no basin > 0 with a finite top reads the basins alone, and one whose
+ *            cells all stand at or above their top is done after its dem.  The sixteen heights are formed by the rule of
+ *            wdpm_curves_stage_level, and every lane adds its cell to sixteen counts and sixteen sums of its own, all in
+ *            registers (the stage loops are unrolled: nothing is indexed at run time).  What the lanes hold for one label goes
+ *            out when a lane's label changes, and at the end of the strip: per wave BY LABEL a butterfly sum per stage and one add
+ *            of the count and one of the sum to the pond's row; a stage whose count is zero in the wave sends nothing.  Counts
+ *            and sums are cumulative as they are defined, there is no prefix sum afterwards.  A term of 512 m or more, or one
+ *            that is not finite, sets a status word
+ *   finish   the bed key back to a double; the counts for wdpm_curves_stats
+ *
+ * Everything that steers a loop is wave-uniform.  tests/curves_emu_main.cpp compiles the kernels for the host under sanitizers with
+ * WDPM_PONDS_EMULATION defined, as tests/outlets_emu_main.cpp does with wdpm_pond_outlets.hip, and leaves the host half out.
+ */
+#include "wdpm_ponds_priv.h"
+
+using namespace wdpm_pond_detail;
+
+#ifdef __clang__
+#pragma clang fp contract(off)            /* the stage rule is three rounded operations, whatever the command line says */
+#endif
+#ifdef WDPM_PONDS_EMULATION
+#define WDPM_CURVES_BOTH
+#else
+#define WDPM_CURVES_BOTH __host__ __device__
+#endif
+
+namespace {
+
+constexpr unsigned long long kNoBed = ~0ull;      /* no cell of the basin seen yet */
+constexpr int kStages = WDPM_CURVE_STAGES;
+
+/* The stage rule of include/wdpm_pond_curves.h for 0 < s < 16: one subtraction, one multiplication by the exact s / 16, one
+ * addition.  Device, host and the host emulation all come here. */
+WDPM_CURVES_BOTH inline double stage_between(double bed, double top, int s) {
+  const double span = top - bed;
+  const double part = span * ((double)s * 0.0625);
+  return bed + part;
+}
+
+/* butterflies: every lane ends with the wave's sum */
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  return v;
+}
+__device__ __forceinline__ unsigned wave_sum(unsigned v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  return v;
+}
+
+/* ---- init ------------------------------------------------------------------------------------------------------------------ */
+/* one thread per 64-bit word of the table: word 0 of a row is the bed key, word 1 the top level, the rest counts and sums */
+__global__ __launch_bounds__(kBlock) void curves_init_kernel(CurveRow *t, long long n, const wdpm_pond_outlet *__restrict__ outlets) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n * kCurveWords) return;
+  const long long k = i / kCurveWords;
+  const int j = (int)(i - k * kCurveWords);
+  unsigned long long v = 0ull;
+  if (j == 0) v = kNoBed;
+  if (j == 1) v = (unsigned long long)__double_as_longlong(outlets[k].pour_level);
+  reinterpret_cast<unsigned long long *>(t)[i] = v;
+}
+
+/* ---- bed ------------------------------------------------------------------------------------------------------------------- */
+__global__ __launch_bounds__(kBlock) void curves_bed_kernel(const double *__restrict__ dem, const int *__restrict__ basins, Geom g, int rpw,
+                                                            int nwaves, CurveRow *table) {
+  const int wid = blockIdx.x * kWaves + (threadIdx.x >> 6);
+  if (wid >= nwaves) return;
+  const int lane = threadIdx.x & 63;
+  const int strip = wid / g.nsc, s = wid - strip * g.nsc;
+  const int r0 = strip * rpw, r1 = min(r0 + rpw, g.rows);
+  const int c = s * kSeg + lane;
+  const bool inside = c < g.ncp;
+  int cy_label = 0;                        /* what the wave holds for one label and has not yet sent */
+  unsigned long long cy_min = kNoBed;
+
+  for (int r = r0; r < r1; r++) {
+    const int b = inside ? basins[r * g.ncp + c] : -1;
+    if (__ballot(b > 0) == 0ull) continue;
+    const unsigned long long key = b > 0 ? depth_key(dem[r * g.ncp + c]) : kNoBed;
+    /* per wave, by label */
+    int cand = b > 0 ? b : 0;
+    for (;;) {
+      const unsigned long long pending = __ballot(cand != 0);
+      if (pending == 0ull) break;
+      const int L = __shfl(cand, __builtin_ctzll(pending));
+      const unsigned long long lo = wave_min(cand == L ? key : kNoBed);
+      if (cy_label != L) {                 /* down the rows: the same label goes on gathering, another one sends first */
+        if (cy_label != 0 && lane == 0) atomic_min_if(&table[cy_label - 1].bed_key, cy_min);
+        cy_label = L;
+        cy_min = kNoBed;
+      }
+      cy_min = lo < cy_min ? lo : cy_min;
+      if (cand == L) cand = 0;
+    }
+  }
+  if (cy_label != 0 && lane == 0) atomic_min_if(&table[cy_label - 1].bed_key, cy_min);
+}
+
+/* ---- stages ---------------------------------------------------------------------------------------------------------------- */
+/* what one lane holds for one label: its cells below every stage and their depths in quanta */
+struct StageAcc {
+  int label;                               /* 0: nothing held */
+  unsigned n[kStages];
+  unsigned long long q[kStages];
+};
+
+/* The lanes with `go` send what they hold: per wave by label, a butterfly sum per stage, lane 0 adds it to the pond's row.  Every
+ * lane takes part in the exchanges. */
+__device__ __forceinline__ void stages_send(StageAcc &a, bool go, CurveRow *table, int lane) {
+  int cand = go ? a.label : 0;
+  for (;;) {
+    const unsigned long long pending = __ballot(cand != 0);
+    if (pending == 0ull) break;
+    const int L = __shfl(cand, __builtin_ctzll(pending));
+    const bool mine = cand == L;
+    CurveRow *t = table + (L - 1);
+#pragma unroll
+    for (int s = 0; s < kStages; s++) {
+      const unsigned cnt = wave_sum(mine ? a.n[s] : 0u);
+      if (cnt != 0u) {                     /* wave-uniform */
+        const unsigned long long sum = wave_sum(mine ? a.q[s] : 0ull);
+        if (lane == 0) {
+          atomicAdd(&t->cells[s], (unsigned long long)cnt);
+          if (sum != 0ull) atomicAdd(&t->q[s], sum);
+        }
+      }
+      if (mine) {
+        a.n[s] = 0u;
+        a.q[s] = 0ull;
+      }
+    }
+    if (mine) {
+      a.label = 0;
+      cand = 0;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void curves_stages_kernel(const double *__restrict__ dem, const int *__restrict__ basins, Geom g,
+                                                               int rpw, int nwaves, CurveRow *table, CurveStatus *st) {
+  const int wid = blockIdx.x * kWaves + (threadIdx.x >> 6);
+  if (wid >= nwaves) return;
+  const int lane = threadIdx.x & 63;
+  const int strip = wid / g.nsc, sc = wid - strip * g.nsc;
+  const int r0 = strip * rpw, r1 = min(r0 + rpw, g.rows);
+  const int c = sc * kSeg + lane;
+  const bool inside = c < g.ncp;
+  int held = 0;                            /* the basin whose bed and top the lane holds */
+  double bed = 0.0, top = 0.0;
+  unsigned long long topkey = 0ull;
+  StageAcc a;
+  a.label = 0;
+#pragma unroll
+  for (int s = 0; s < kStages; s++) {
+    a.n[s] = 0u;
+    a.q[s] = 0ull;
+  }
+  bool bad = false;
+
+  for (int r = r0; r < r1; r++) {
+    const int b = inside ? basins[r * g.ncp + c] : -1;
+    if (__ballot(b > 0) == 0ull) continue;
+    if (b > 0 && b != held) {              /* every bed key is final: the bed pass has ended */
+      const CurveRow *t = table + (b - 1);
+      bed = depth_from_key(t->bed_key);
+      top = t->top_level;
+      topkey = depth_key(top);
+      held = b;
+    }
+    const bool live = b > 0 && top < __builtin_inf();          /* a pond with an outlet: the pour level is finite or +inf */
+    if (__ballot(live) == 0ull) continue;
+    const double e = live ? dem[r * g.ncp + c] : 0.0;
+    const unsigned long long ekey = depth_key(e);
+    const bool wet = live && ekey < topkey;                     /* below the last stage, or below none */
+    if (__ballot(wet) == 0ull) continue;
+    const bool turn = wet && a.label != 0 && a.label != b;
+    if (__ballot(turn) != 0ull) stages_send(a, turn, table, lane);
+    if (wet) a.label = b;
+#pragma unroll
+    for (int s = 1; s <= kStages; s++) {
+      const double h = s == kStages ? top : stage_between(bed, top, s);
+      const double depth = h - e;
+      const bool below = wet && ekey < depth_key(h);
+      const bool ok = depth < 512.0;                            /* not 512 m or more, +inf, NaN */
+      bad = bad || (below && !ok);
+      if (below && ok) {
+        a.n[s - 1] += 1u;
+        a.q[s - 1] += (unsigned long long)rint(depth * 16777216.0);
+      }
+    }
+  }
+  stages_send(a, a.label != 0, table, lane);
+  if (bad) st->deep = 1u;
+}
+
+/* ---- finish ---------------------------------------------------------------------------------------------------------------- */
+/* the accumulated row becomes a wdpm_pond_curve in place; every lane stays for the counts */
+__global__ __launch_bounds__(kBlock) void curves_finish_kernel(CurveRow *t, long long n, CurveStatus *st) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  const bool live = i < n;
+  bool none = false, flat = false;
+  unsigned long long cells = 0ull;
+  if (live) {
+    const double bed = depth_from_key(t[i].bed_key), top = t[i].top_level;
+    t[i].bed_key = (unsigned long long)__double_as_longlong(bed);
+    none = !(top < __builtin_inf());
+    flat = top == bed;
+    cells = t[i].cells[kStages - 1];
+  }
+  const unsigned long long nonem = __ballot(none), flatm = __ballot(flat);
+  cells = wave_sum(cells);
+  if ((threadIdx.x & 63) == 0) {
+    if (nonem) atomicAdd(&st->no_curve, (unsigned long long)__popcll(nonem));
+    if (flatm) atomicAdd(&st->flat, (unsigned long long)__popcll(flatm));
+    if (cells) atomicAdd(&st->stage_cells, cells);
+  }
+}
+
+}  // namespace
+
+#ifndef WDPM_PONDS_EMULATION
+/* ---- host ------------------------------------------------------------------------------------------------------------------ */
+namespace {
+const char kNoTable[] = "no curve table: the last label call on this handle was not a wdpm_curves_label that succeeded";
+}  // namespace
+
+extern "C" double wdpm_curves_stage_level(double bed, double top, int s) {
+  if (s < 0 || s > kStages) return std::nan("");
+  if (s == 0) return bed;
+  if (s == kStages) return top;
+  return stage_between(bed, top, s);
+}
+
+extern "C" int wdpm_curves_label(wdpm_ponds *h, double min_depth, int64_t *nponds) {
+  if (!h) return wdpm_fail("wdpm_curves_label: null handle");
+  if (!(min_depth >= 0.0) || std::isinf(min_depth)) return wdpm_fail("wdpm_curves_label: min_depth must be finite and >= 0 (got %g)", min_depth);
+  if (h->seams) return wdpm_fail("wdpm_curves_label: the handle views a row block: stage curves are taken on whole rasters only");
+  int64_t n = 0;
+  if (wdpm_outlets_label(h, min_depth, &n)) return 1;         /* leaves basin raster, outlet table and the stream as this pass wants them */
+  h->valid = false;                                           /* a wdpm_curves_label that fails leaves no table of any kind */
+  wdpm_ctx *x = h->x;
+  const Geom g = h->g;
+  const hipStream_t sm = x->stream;
+  HIP_TRY(hipSetDevice(x->p.device));
+  if (!h->d_vstat) {
+    hipError_t e = hipMalloc(&h->d_vstat, sizeof(CurveStatus));
+    if (e != hipSuccess) { h->d_vstat = nullptr; return wdpm_fail("wdpm_curves_label: no device memory for the status words: %s", hipGetErrorString(e)); }
+    e = hipHostMalloc(&h->h_vstat, sizeof(CurveStatus));
+    if (e != hipSuccess) { h->h_vstat = nullptr; (void)hipFree(h->d_vstat); h->d_vstat = nullptr; return wdpm_fail("wdpm_curves_label: no pinned host memory for the status words: %s", hipGetErrorString(e)); }
+  }
+  if (n > h->curves_cap) {                                    /* sized from N, like the pond table */
+    guarded_free(h, h->d_curves);
+    h->d_curves = nullptr;
+    h->curves_cap = 0;
+    const hipError_t e = guarded_malloc(h, (void **)&h->d_curves, (size_t)n * sizeof(CurveRow));
+    if (e != hipSuccess) return wdpm_fail("wdpm_curves_label: no device memory for the curves of %lld ponds: %s", (long long)n, hipGetErrorString(e));
+    h->curves_cap = n;
+  }
+  h->curve_ms[0] = h->curve_ms[1] = 0.0;
+  memset(h->h_vstat, 0, sizeof(CurveStatus));
+  if (n > 0) {                                                /* no pond, no curve: nothing to launch */
+    const double *dem = x->d_dem + (size_t)h->row_off * g.ncp;
+    const int rpw = ponds_rows_per_wave(g.nseg, g.rows, h->forced_rpw);
+    const int nwaves = ((g.rows + rpw - 1) / rpw) * g.nsc;
+    const unsigned nblocks = blocks_for(n, kBlock), iblocks = blocks_for((long long)n * kCurveWords, kBlock), wblocks = blocks_for(nwaves, kWaves);
+    const wdpm_pond_outlet *outlets = reinterpret_cast<const wdpm_pond_outlet *>(h->d_outlets);
+    HIP_TRY(hipMemsetAsync(h->d_vstat, 0, sizeof(CurveStatus), sm));
+    if (h->timing) HIP_TRY(hipEventRecord(h->curve_ev[0], sm));
+    hipLaunchKernelGGL(curves_init_kernel, dim3(iblocks), dim3(kBlock), 0, sm, h->d_curves, (long long)n, outlets);
+    hipLaunchKernelGGL(curves_bed_kernel, dim3(wblocks), dim3(kBlock), 0, sm, dem, h->d_link, g, rpw, nwaves, h->d_curves);
+    if (h->timing) HIP_TRY(hipEventRecord(h->curve_ev[1], sm));
+    hipLaunchKernelGGL(curves_stages_kernel, dim3(wblocks), dim3(kBlock), 0, sm, dem, h->d_link, g, rpw, nwaves, h->d_curves, h->d_vstat);
+    hipLaunchKernelGGL(curves_finish_kernel, dim3(nblocks), dim3(kBlock), 0, sm, h->d_curves, (long long)n, h->d_vstat);
+    if (h->timing) HIP_TRY(hipEventRecord(h->curve_ev[2], sm));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h->h_vstat, h->d_vstat, sizeof(CurveStatus), hipMemcpyDeviceToHost, sm));
+    if (wdpm_stream_sync(x, sm)) return 1;
+    if (h->timing)
+      for (int i = 0; i < WDPM_CURVES_PHASES; i++) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, h->curve_ev[i], h->curve_ev[i + 1]));
+        h->curve_ms[i] = ms;
+      }
+  }
+  if (h->h_vstat->deep)
+    return wdpm_fail("wdpm_curves_label: a cell of a pond's basin lies 512 m or more below a stage of the pond's curve, or not a finite "
+                     "depth below it: q (64-bit sums of depths in units of 2^-24 m) is only safe below that depth");
+  h->curve_stats.ponds = n;
+  h->curve_stats.no_curve = (int64_t)h->h_vstat->no_curve;
+  h->curve_stats.flat = (int64_t)h->h_vstat->flat;
+  h->curve_stats.stage_cells = (int64_t)h->h_vstat->stage_cells;
+  h->curves_valid = true;
+  h->valid = true;
+  if (nponds) *nponds = n;
+  return 0;
+}
+
+extern "C" int wdpm_curves_table(wdpm_ponds *h, wdpm_pond_curve *out, int64_t capacity) {
+  if (!h) return wdpm_fail("wdpm_curves_table: null handle");
+  if (!h->valid || !h->curves_valid) return wdpm_fail("wdpm_curves_table: %s", kNoTable);
+  const long long n = h->stats.ponds;
+  if (capacity < n) return wdpm_fail("wdpm_curves_table: capacity %lld is too small for %lld ponds", (long long)capacity, n);
+  if (n == 0) return 0;
+  if (!out) return wdpm_fail("wdpm_curves_table: null output");
+  if (wdpm_synchronize(h->x)) return 1;
+  HIP_TRY(hipMemcpyAsync(out, h->d_curves, (size_t)n * sizeof(wdpm_pond_curve), hipMemcpyDeviceToHost, h->x->stream));
+  return wdpm_stream_sync(h->x, h->x->stream);
+}
+
+extern "C" int wdpm_curves_stats(wdpm_ponds *h, wdpm_pond_curve_stats *out) {
+  if (!h) return wdpm_fail("wdpm_curves_stats: null handle");
+  if (!out) return wdpm_fail("wdpm_curves_stats: null output");
+  if (!h->valid || !h->curves_valid) return wdpm_fail("wdpm_curves_stats: %s", kNoTable);
+  *out = h->curve_stats;
+  return 0;
+}
+
+extern "C" int wdpm_curves_phase_ms(wdpm_ponds *h, double *ms) {
+  if (!h) return wdpm_fail("wdpm_curves_phase_ms: null handle");
+  if (!ms) return wdpm_fail("wdpm_curves_phase_ms: null output");
+  if (!h->timing) return wdpm_fail("wdpm_curves_phase_ms: the handle records no events (set WDPM_PONDS_TIMING=1 before it is made)");
+  if (!h->valid || !h->curves_valid) return wdpm_fail("wdpm_curves_phase_ms: %s", kNoTable);
+  for (int i = 0; i < WDPM_CURVES_PHASES; i++) ms[i] = h->curve_ms[i];
+  return 0;
+}
+#endif  /* WDPM_PONDS_EMULATION */

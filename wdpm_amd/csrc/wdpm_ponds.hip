@@ -512,6 +512,13 @@ void release(wdpm_ponds *h) {
   h->h_outlets = nullptr;
   h->h_oseam = nullptr;
   h->okeys_cap = h->h_outlets_cap = 0;
+  guarded_free(h, h->d_curves);
+  if (h->d_vstat) (void)hipFree(h->d_vstat);
+  if (h->h_vstat) (void)hipHostFree(h->h_vstat);
+  h->d_curves = nullptr;
+  h->curves_cap = 0;
+  h->d_vstat = h->h_vstat = nullptr;
+  h->curves_valid = false;
   if (h->h_beside) (void)hipHostFree(h->h_beside);
   if (h->h_rims) (void)hipHostFree(h->h_rims);
   h->d_slot_of = h->d_foreign = nullptr;
@@ -617,6 +624,11 @@ wdpm_ponds *make_handle(wdpm_ctx *ctx, int row_off, int rows, bool seams) {
   h->h_outlets = nullptr;
   h->h_oseam = nullptr;
   h->okeys_cap = h->h_outlets_cap = 0;
+  h->d_curves = nullptr;
+  h->curves_cap = 0;
+  h->d_vstat = h->h_vstat = nullptr;
+  h->curves_valid = false;
+  memset(&h->curve_stats, 0, sizeof h->curve_stats);
   h->nb = 0;
   { const char *re = getenv("WDPM_PONDS_ROWS_PER_WAVE"); h->forced_rpw = re ? atoi(re) : 0; }
   h->rpw = 1;
@@ -651,6 +663,11 @@ wdpm_ponds *make_handle(wdpm_ctx *ctx, int row_off, int rows, bool seams) {
   if (h->timing)
     for (int i = 0; i < WDPM_OUTLETS_PHASES + 1; i++)
       if (hipEventCreate(&h->outlet_ev[i]) != hipSuccess) { h->timing = false; break; }
+  for (int i = 0; i < WDPM_CURVES_PHASES + 1; i++) h->curve_ev[i] = nullptr;
+  for (int i = 0; i < WDPM_CURVES_PHASES; i++) h->curve_ms[i] = 0.0;
+  if (h->timing)
+    for (int i = 0; i < WDPM_CURVES_PHASES + 1; i++)
+      if (hipEventCreate(&h->curve_ev[i]) != hipSuccess) { h->timing = false; break; }
   return h;
 }
 
@@ -666,6 +683,7 @@ int label_queue(wdpm_ponds *h, double min_depth) {
   h->rims_valid = false;            /* a rim table belongs to the label call that made it (wdpm_pond_rims.hip) */
   h->catch_valid = false;           /* and so does a catchment table (wdpm_pond_catchments.hip) */
   h->outlets_valid = false;         /* and an outlet table (wdpm_pond_outlets.hip) */
+  h->curves_valid = false;          /* and a curve table (wdpm_pond_curves.hip) */
   /* the raster as a reader sees it: side stream joined, owed drain() and threshold flush applied (what wdpm_count_stats asks for) */
   if (wdpm_synchronize(x)) return 1;
   if (wdpm_apply_owed_flush(x)) return 1;
@@ -816,6 +834,8 @@ void destroy_handle(wdpm_ponds *h) {
     if (h->catch_ev[i]) (void)hipEventDestroy(h->catch_ev[i]);
   for (int i = 0; i < WDPM_OUTLETS_PHASES + 1; i++)
     if (h->outlet_ev[i]) (void)hipEventDestroy(h->outlet_ev[i]);
+  for (int i = 0; i < WDPM_CURVES_PHASES + 1; i++)
+    if (h->curve_ev[i]) (void)hipEventDestroy(h->curve_ev[i]);
   delete h;
 }
 

@@ -1,6 +1,6 @@
 /*
  * wdpm_ponds_priv.h — what the units of the pond inventory share: wdpm_ponds.hip (labels and table), wdpm_pond_rims.hip
- * (rims), wdpm_pond_catchments.hip (catchments) and wdpm_pond_outlets.hip (outlets).  Geometry, the order-preserving image of a
+ * (rims), wdpm_pond_catchments.hip (catchments), wdpm_pond_outlets.hip (outlets) and wdpm_pond_curves.hip (stage curves).  Geometry, the order-preserving image of a
  * double, the table rows as the device accumulates them, the wave helpers of the kernels (a lane's neighbour, the wave's extremum,
  * the look before an atomic) and - outside the host emulations of the tests, which define WDPM_PONDS_EMULATION and bring stand-ins
  * for the HIP device language (tests/hip_emu.h) - the handle itself with its guarded allocator.  Private: nothing here is exported,
@@ -35,6 +35,7 @@
 #include "../../include/wdpm_pond_outlets.h"
 #include "../../include/wdpm_group_pond_catchments.h"
 #include "../../include/wdpm_group_pond_outlets.h"
+#include "../../include/wdpm_pond_curves.h"
 
 namespace wdpm_pond_detail {
 
@@ -110,6 +111,25 @@ static_assert(offsetof(wdpm_pond_outlet, from_row) == offsetof(OutletRow, pair) 
 struct OutletStatus {
   unsigned long long no_outlet, to_land, divide;
   unsigned deep;           /* a fill term of >= 512 m, or one that is not finite */
+  unsigned pad;
+};
+
+/* the curve table as the device accumulates it: wdpm_pond_curve with the bed level as its order-preserving image (~0: no cell yet);
+ * the top level is a double from the start (the outlet table's finished pour_level) */
+struct CurveRow {
+  unsigned long long bed_key;
+  double top_level;
+  unsigned long long cells[WDPM_CURVE_STAGES], q[WDPM_CURVE_STAGES];
+};
+static_assert(sizeof(CurveRow) == sizeof(wdpm_pond_curve) && sizeof(CurveRow) == 272, "the device curve table is copied out as wdpm_pond_curve");
+static_assert(offsetof(wdpm_pond_curve, top_level) == offsetof(CurveRow, top_level) && offsetof(wdpm_pond_curve, cells) == offsetof(CurveRow, cells) &&
+              offsetof(wdpm_pond_curve, q) == offsetof(CurveRow, q), "the finish kernel rewrites a row in place");
+constexpr int kCurveWords = (int)(sizeof(CurveRow) / sizeof(unsigned long long));
+
+/* what the curve kernels count for the host */
+struct CurveStatus {
+  unsigned long long no_curve, flat, stage_cells;
+  unsigned deep;           /* a term of q of >= 512 m, or one that is not finite */
   unsigned pad;
 };
 
@@ -273,6 +293,14 @@ struct wdpm_ponds {
   wdpm_pond_detail::OutletRow *h_outlets;   /* pinned: the slots' rows on their way down */
   long long h_outlets_cap;
   int *h_oseam;                     /* pinned, 2 x g.ncp: the facing ranks' seam basins on their way up */
+  /* stage curves (wdpm_pond_curves.hip): the table of the last wdpm_curves_label; every label call takes curves_valid away first */
+  wdpm_pond_detail::CurveRow *d_curves;
+  long long curves_cap;
+  wdpm_pond_detail::CurveStatus *d_vstat, *h_vstat;   /* h_vstat pinned */
+  bool curves_valid;
+  hipEvent_t curve_ev[WDPM_CURVES_PHASES + 1];        /* init, bed | stages, finish */
+  double curve_ms[WDPM_CURVES_PHASES];
+  wdpm_pond_curve_stats curve_stats;
 };
 
 /* the handle of include/wdpm_group_ponds.h, include/wdpm_group_pond_rims.h, include/wdpm_group_pond_catchments.h and

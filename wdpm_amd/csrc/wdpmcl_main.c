@@ -41,6 +41,7 @@
 #include "../../include/wdpm_pond_rims.h"
 #include "../../include/wdpm_pond_catchments.h"
 #include "../../include/wdpm_pond_outlets.h"
+#include "../../include/wdpm_pond_curves.h"
 /* the pond inventory is the HIP library's alone: weak references, so that this file also links against a back-end that
  * exports include/wdpm.h and nothing else (WDPM_PONDS then says so and writes no file) */
 #pragma weak wdpm_ponds_create
@@ -62,6 +63,10 @@
 #pragma weak wdpm_outlets_label
 #pragma weak wdpm_outlets_table
 #pragma weak wdpm_outlets_stats
+#pragma weak wdpm_curves_label
+#pragma weak wdpm_curves_table
+#pragma weak wdpm_curves_stats
+#pragma weak wdpm_curves_stage_level
 #include "arcascii.h"
 
 #define ITER_PER_BLOCK 1000 /* IterationNum, WDPMCL.c:597 */
@@ -654,19 +659,23 @@ typedef struct {
   wdpm_pond *rows; int64_t n; int64_t guard_bad; int64_t blocks, joined; wdpm_pond_rim *rims;
   wdpm_pond_catchment *catch; wdpm_pond_catchment_stats catch_stats;
   wdpm_pond_outlet *outlets; wdpm_pond_outlet_stats outlet_stats;
+  wdpm_pond_curve *curves; wdpm_pond_curve_stats curve_stats;
 } pond_inventory;
 
 /* with_rims (WDPM_POND_RIMS, include/wdpm_pond_rims.h; the caller has seen that the back-end has them): one wdpm_rims_label serves
  * the pond table and the rim table.  with_catch (WDPM_POND_CATCHMENTS, include/wdpm_pond_catchments.h; likewise): one
  * wdpm_catch_label serves all three, whichever of the files are asked for.  with_outlets (WDPM_POND_OUTLETS,
  * include/wdpm_pond_outlets.h; likewise, and the caller then sets with_rims too: the headroom wants the surface): one
- * wdpm_outlets_label serves all four. */
-static int take_inventory(wdpm_ctx *c, double min_depth, pond_inventory *inv, int with_rims, int with_catch, int with_outlets) {
+ * wdpm_outlets_label serves all four.  with_curves (WDPM_POND_CURVES, include/wdpm_pond_curves.h; likewise): one wdpm_curves_label
+ * serves all five. */
+static int take_inventory(wdpm_ctx *c, double min_depth, pond_inventory *inv, int with_rims, int with_catch, int with_outlets,
+                          int with_curves) {
   wdpm_ponds *h = NULL;
   inv->rows = NULL;
   inv->rims = NULL;
   inv->catch = NULL;
   inv->outlets = NULL;
+  inv->curves = NULL;
   inv->n = 0;
   inv->guard_bad = 0;
   inv->blocks = 1;
@@ -677,7 +686,8 @@ static int take_inventory(wdpm_ctx *c, double min_depth, pond_inventory *inv, in
   }
   int rc = wdpm_ponds_create(&h, c);
   if (!rc)
-    rc = with_outlets ? wdpm_outlets_label(h, min_depth, &inv->n)
+    rc = with_curves  ? wdpm_curves_label(h, min_depth, &inv->n)
+       : with_outlets ? wdpm_outlets_label(h, min_depth, &inv->n)
          : with_catch ? wdpm_catch_label(h, min_depth, &inv->n)
          : with_rims  ? wdpm_rims_label(h, min_depth, &inv->n)
                       : wdpm_ponds_label(h, min_depth, &inv->n);
@@ -686,7 +696,9 @@ static int take_inventory(wdpm_ctx *c, double min_depth, pond_inventory *inv, in
     if (with_rims) inv->rims = (wdpm_pond_rim *)malloc((size_t)(inv->n > 0 ? inv->n : 1) * sizeof(wdpm_pond_rim));
     if (with_catch) inv->catch = (wdpm_pond_catchment *)malloc((size_t)(inv->n > 0 ? inv->n : 1) * sizeof(wdpm_pond_catchment));
     if (with_outlets) inv->outlets = (wdpm_pond_outlet *)malloc((size_t)(inv->n > 0 ? inv->n : 1) * sizeof(wdpm_pond_outlet));
-    if (!inv->rows || (with_rims && !inv->rims) || (with_catch && !inv->catch) || (with_outlets && !inv->outlets)) {
+    if (with_curves) inv->curves = (wdpm_pond_curve *)malloc((size_t)(inv->n > 0 ? inv->n : 1) * sizeof(wdpm_pond_curve));
+    if (!inv->rows || (with_rims && !inv->rims) || (with_catch && !inv->catch) || (with_outlets && !inv->outlets) ||
+        (with_curves && !inv->curves)) {
       wdpm_set_last_error("out of host memory for the pond table");
       rc = 1;
     }
@@ -697,6 +709,8 @@ static int take_inventory(wdpm_ctx *c, double min_depth, pond_inventory *inv, in
   if (!rc && with_catch) rc = wdpm_catch_stats(h, &inv->catch_stats);
   if (!rc && with_outlets) rc = wdpm_outlets_table(h, inv->outlets, inv->n);
   if (!rc && with_outlets) rc = wdpm_outlets_stats(h, &inv->outlet_stats);
+  if (!rc && with_curves) rc = wdpm_curves_table(h, inv->curves, inv->n);
+  if (!rc && with_curves) rc = wdpm_curves_stats(h, &inv->curve_stats);
   if (!rc && getenv("WDPM_GUARD_KB")) rc = wdpm_ponds_guard_bad(h, &inv->guard_bad);
   if (rc) {
     fprintf(stderr, "WDPMCL: pond inventory failed, no file written: %s\n", wdpm_last_error());
@@ -704,10 +718,12 @@ static int take_inventory(wdpm_ctx *c, double min_depth, pond_inventory *inv, in
     free(inv->rims);
     free(inv->catch);
     free(inv->outlets);
+    free(inv->curves);
     inv->rows = NULL;
     inv->rims = NULL;
     inv->catch = NULL;
     inv->outlets = NULL;
+    inv->curves = NULL;
   }
   wdpm_ponds_destroy(h);
   return rc;
@@ -721,6 +737,7 @@ static int take_group_inventory(wdpm_group *grp, double min_depth, pond_inventor
   inv->rims = NULL;
   inv->catch = NULL;
   inv->outlets = NULL;
+  inv->curves = NULL;
   inv->n = 0;
   inv->guard_bad = 0;
   inv->blocks = 1;
@@ -857,6 +874,37 @@ static int write_outlets(const char *path, const pond_inventory *inv, double cel
   const wdpm_pond_outlet_stats *os = &inv->outlet_stats;
   fprintf(stderr, "WDPMCL: pond outlets: %lld pond%s written to %s (%lld without an outlet, %lld spill onto land that ends in a pit, %lld cells on the divides)\n",
           (long long)inv->n, inv->n == 1 ? "" : "s", path, (long long)os->no_outlet, (long long)os->to_land, (long long)os->divide_cells);
+  return 0;
+}
+
+/* WDPM_POND_CURVES=<path>: the stage curve of every pond of the same inventory (include/wdpm_pond_curves.h): one line `stage 0` with
+ * the lowest ground of the pond's basin and zeros, and - where the pond has an outlet - one line per stage 1..16 with its level
+ * (wdpm_curves_stage_level; stage 16 is the pour level), the cells of the basin whose ground lies below it and their area, and the
+ * storage below it in quanta of 2^-24 m and in cubic metres.  Doubles as %.17g. */
+static int write_curves(const char *path, const pond_inventory *inv, double cellarea) {
+  FILE *f = fopen(path, "w");
+  if (!f) {
+    fprintf(stderr, "WDPMCL: cannot write pond curves %s\n", path);
+    return 1;
+  }
+  fprintf(f, "label,stage,level_m,cells,area_m2,q,volume_m3\n");
+  for (int64_t k = 0; k < inv->n; k++) {
+    const wdpm_pond_curve *v = &inv->curves[k];
+    fprintf(f, "%lld,0,%.17g,0,%.17g,0,%.17g\n", (long long)(k + 1), v->bed_level, 0.0, 0.0);
+    if (!(v->top_level < INFINITY)) continue;
+    for (int s = 1; s <= WDPM_CURVE_STAGES; s++)
+      fprintf(f, "%lld,%d,%.17g,%lld,%.17g,%llu,%.17g\n", (long long)(k + 1), s, wdpm_curves_stage_level(v->bed_level, v->top_level, s),
+              (long long)v->cells[s - 1], (double)v->cells[s - 1] * cellarea, (unsigned long long)v->q[s - 1],
+              ldexp((double)v->q[s - 1], -24) * cellarea);
+  }
+  const int bad = ferror(f);
+  if (fclose(f) != 0 || bad) {
+    fprintf(stderr, "WDPMCL: error writing pond curves %s\n", path);
+    return 1;
+  }
+  const wdpm_pond_curve_stats *vs = &inv->curve_stats;
+  fprintf(stderr, "WDPMCL: pond curves: %lld pond%s written to %s (%lld without a curve, %lld flat, %lld cells below the last stage)\n",
+          (long long)inv->n, inv->n == 1 ? "" : "s", path, (long long)vs->no_curve, (long long)vs->flat, (long long)vs->stage_cells);
   return 0;
 }
 
@@ -1135,21 +1183,38 @@ int main(int argc, char **argv) {
     ponds_failed = 1;
     outlets_path = NULL;
   }
-  if (ponds_path || rims_path || catch_path || outlets_path) {
+  /* ... and their stage curves (WDPM_POND_CURVES), alone or beside any of them: whole rasters only */
+  const char *curves_path = getenv("WDPM_POND_CURVES");
+  if (curves_path && !*curves_path) curves_path = NULL;
+  if (curves_path && ndev > 1) {
+    fprintf(stderr, "WDPMCL: pond curves: the raster lies in %d row blocks and stage curves are taken on a whole raster only, no file written to %s\n",
+            ndev, curves_path);
+    ponds_failed = 1;
+    curves_path = NULL;
+  }
+  if (curves_path && (!wdpm_curves_label || !wdpm_curves_table || !wdpm_curves_stats || !wdpm_curves_stage_level || !wdpm_outlets_table ||
+                      !wdpm_outlets_stats || !wdpm_rims_table || !wdpm_catch_table || !wdpm_catch_stats)) {
+    fprintf(stderr, "WDPMCL: pond curves: back-end %s has none, no file written\n", wdpm_backend_name());
+    ponds_failed = 1;
+    curves_path = NULL;
+  }
+  if (ponds_path || rims_path || catch_path || outlets_path || curves_path) {
     phase("statistics + download");
     const int failed = ndev == 1 ? take_inventory(wdpm_rank_ctx(wdpm_group_rank(ctx, 0)), ponds_min_depth, &inv,
                                                   rims_path != NULL || catch_path != NULL || outlets_path != NULL,
-                                                  catch_path != NULL || outlets_path != NULL, outlets_path != NULL)
+                                                  catch_path != NULL || outlets_path != NULL, outlets_path != NULL, curves_path != NULL)
                                  : take_group_inventory(ctx, ponds_min_depth, &inv);
     if (failed) ponds_failed = 1;
     if (!failed && ponds_path && write_inventory(ponds_path, &inv, st.cellarea)) ponds_failed = 1;
     if (!failed && rims_path && write_rims(rims_path, &inv)) ponds_failed = 1;
     if (!failed && catch_path && write_catchments(catch_path, &inv, st.cellarea)) ponds_failed = 1;
     if (!failed && outlets_path && write_outlets(outlets_path, &inv, st.cellarea)) ponds_failed = 1;
+    if (!failed && curves_path && write_curves(curves_path, &inv, st.cellarea)) ponds_failed = 1;
     free(inv.rows);
     free(inv.rims);
     free(inv.catch);
     free(inv.outlets);
+    free(inv.curves);
     phase("pond inventory");
   }
   int64_t guard_bad = inv.guard_bad;

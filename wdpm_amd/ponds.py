@@ -1,7 +1,8 @@
 """ctypes binding of include/wdpm_ponds.h, include/wdpm_group_ponds.h, include/wdpm_pond_rims.h, include/wdpm_group_pond_rims.h,
-include/wdpm_pond_catchments.h, include/wdpm_pond_outlets.h, include/wdpm_group_pond_catchments.h and
-include/wdpm_group_pond_outlets.h: the pond inventory of a context's current water raster, of a raster spread over the row blocks of
-a rowblock.Group, and the rim, the catchment and the outlet of every pond of either.
+include/wdpm_pond_catchments.h, include/wdpm_pond_outlets.h, include/wdpm_group_pond_catchments.h,
+include/wdpm_group_pond_outlets.h and include/wdpm_pond_curves.h: the pond inventory of a context's current water raster, of a raster
+spread over the row blocks of a rowblock.Group, the rim, the catchment and the outlet of every pond of either, and on whole rasters
+the stage curve of every pond.
 
 Product library only (the symbols are not part of the ABI of include/wdpm.h, and ``capi.SYMBOLS`` does not list them).
 
@@ -18,6 +19,9 @@ Product library only (the symbols are not part of the ABI of include/wdpm.h, and
         n = ponds.label_outlets(0.001)      # all of the above, and where every basin spills
         outlets = ponds.outlets()   # pour level, the pass (from, to, into which basin), divide, flooded cells, storage left (OUTLET_DTYPE)
         headroom = outlets["pour_level"] - rims["surface_max"]
+        n = ponds.label_curves(0.001)       # all of the above, and every basin's flooded cells and storage at sixteen stages
+        curves = ponds.curves()     # bed level, top level (the pour level), cells[16], q[16] (CURVE_DTYPE)
+        levels = stage_levels(curves["bed_level"][0], curves["top_level"][0])   # the seventeen heights of pond 1, stage 0..16
 
     with rowblock.Group(...) as grp, GroupPonds(grp) as ponds:     # the same calls, the same answer, every rank labelled in place
         n = ponds.label(0.001)
@@ -42,6 +46,8 @@ PHASES = ("mask", "merge", "flatten", "scan", "table", "finish")   # wdpm_ponds_
 RIM_PHASES = ("rims", "locate")                                    # wdpm_rims_phase_ms
 CATCH_PHASES = ("receivers", "jump", "tally")                      # wdpm_catch_phase_ms
 OUTLET_PHASES = ("passes", "locate")                               # wdpm_outlets_phase_ms
+CURVE_PHASES = ("bed", "stages")                                   # wdpm_curves_phase_ms
+CURVE_STAGES = 16                                                  # WDPM_CURVE_STAGES
 
 
 class PondStruct(C.Structure):
@@ -144,6 +150,30 @@ OUTLET_SYMBOLS = {
 }
 
 
+class CurveStruct(C.Structure):
+    """struct wdpm_pond_curve"""
+    _fields_ = [("bed_level", C.c_double), ("top_level", C.c_double), ("cells", C.c_int64 * CURVE_STAGES),
+                ("q", C.c_uint64 * CURVE_STAGES)]
+
+
+class CurveStatsStruct(C.Structure):
+    """struct wdpm_pond_curve_stats"""
+    _fields_ = [("ponds", C.c_int64), ("no_curve", C.c_int64), ("flat", C.c_int64), ("stage_cells", C.c_int64)]
+
+
+CURVE_DTYPE = np.dtype([("bed_level", "<f8"), ("top_level", "<f8"), ("cells", "<i8", (CURVE_STAGES,)), ("q", "<u8", (CURVE_STAGES,))])
+assert CURVE_DTYPE.itemsize == C.sizeof(CurveStruct) == 272 and C.sizeof(CurveStatsStruct) == 32
+
+# every symbol include/wdpm_pond_curves.h declares
+CURVE_SYMBOLS = {
+    "wdpm_curves_label": (C.c_int, [_vp, C.c_double, C.POINTER(C.c_int64)]),
+    "wdpm_curves_table": (C.c_int, [_vp, _vp, C.c_int64]),
+    "wdpm_curves_stats": (C.c_int, [_vp, C.POINTER(CurveStatsStruct)]),
+    "wdpm_curves_phase_ms": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "wdpm_curves_stage_level": (C.c_double, [C.c_double, C.c_double, C.c_int]),
+}
+
+
 class GroupStatsStruct(C.Structure):
     """struct wdpm_group_pond_stats"""
     _fields_ = [("ranks", C.c_int64), ("ponds", C.c_int64), ("local_ponds", C.c_int64), ("stitch_unions", C.c_int64),
@@ -216,7 +246,7 @@ def bind(lib: capi.Lib):
         return lib.dll
     for name, (res, args) in list(SYMBOLS.items()) + list(GROUP_SYMBOLS.items()) + list(RIM_SYMBOLS.items()) + \
             list(GROUP_RIM_SYMBOLS.items()) + list(CATCH_SYMBOLS.items()) + list(OUTLET_SYMBOLS.items()) + list(GROUP_CATCH_SYMBOLS.items()) + \
-            list(GROUP_OUTLET_SYMBOLS.items()):
+            list(GROUP_OUTLET_SYMBOLS.items()) + list(CURVE_SYMBOLS.items()):
         try:
             fn = getattr(lib.dll, name)
         except AttributeError:
@@ -273,9 +303,9 @@ class _Handle:
         self.n = n.value
         return n.value
 
-    def _table(self, fn, dtype, method, capacity) -> np.ndarray:
+    def _table(self, fn, dtype, method, capacity, labelled_by=None) -> np.ndarray:
         if self.n is None:
-            raise capi.WdpmError(f"{type(self).__name__}.{method}: {_LABELLED_BY[method]}() has not succeeded on this handle")
+            raise capi.WdpmError(f"{type(self).__name__}.{method}: {labelled_by or _LABELLED_BY[method]}() has not succeeded on this handle")
         cap = self.n if capacity is None else int(capacity)
         out = np.zeros(max(cap, 0), dtype=dtype)
         self.lib.check(fn(self._h, out.ctypes.data, cap))
@@ -381,6 +411,31 @@ class Ponds(_Handle):
         """milliseconds of the pass over the pairs and of the locate pass of the last label_outlets() (handles made with
         WDPM_PONDS_TIMING=1)"""
         return self._phase_ms(self.dll.wdpm_outlets_phase_ms, OUTLET_PHASES)
+
+    def label_curves(self, min_depth: float) -> int:
+        """label_outlets(min_depth), then the curve pass on the same water; every older query answers as after label_outlets()."""
+        return self._label(self.dll.wdpm_curves_label, min_depth)
+
+    def curves(self, capacity: int | None = None) -> np.ndarray:
+        """One row per pond (CURVE_DTYPE) of the last label_curves(); fails after any lesser label call.  cells[s - 1] and q[s - 1]
+        are the cells of the pond's basin whose ground lies strictly below stage s of stage_levels(bed_level, top_level) and their
+        depths below it in VOLUME_QUANTUM metres; a pond without an outlet has top_level +inf and zeros."""
+        return self._table(self.dll.wdpm_curves_table, CURVE_DTYPE, "curves", capacity, labelled_by="label_curves")
+
+    def curve_stats(self) -> dict:
+        return self._stats(self.dll.wdpm_curves_stats, CurveStatsStruct)
+
+    def curve_phase_ms(self) -> dict:
+        """milliseconds of the bed pass and of the stage pass of the last label_curves() (handles made with WDPM_PONDS_TIMING=1)"""
+        return self._phase_ms(self.dll.wdpm_curves_phase_ms, CURVE_PHASES)
+
+
+def stage_levels(bed: float, top: float, lib: capi.Lib | None = None) -> np.ndarray:
+    """The seventeen stage heights 0..16 of a curve row, from the library's own wdpm_curves_stage_level (`lib`: a loaded product
+    library; default the one load_hip() finds).  Stage 0 is the bed, stage 16 the top; with top +inf there is no curve and
+    everything past the bed is not finite."""
+    dll = bind(capi.load_hip() if lib is None else lib)
+    return np.array([dll.wdpm_curves_stage_level(float(bed), float(top), s) for s in range(CURVE_STAGES + 1)], dtype=np.float64)
 
 
 class GroupPonds(_Handle):
