@@ -34,6 +34,7 @@
                       rates under the byte model of 12 B per cell and pass (int32 basin, fp64 dem) against the yardstick (default
                       --out profiles/r18/pond_curves.json)
     ... --iterations K   instead of the job's own number of iterations before the inventory
+    ... --lib FILE       another build of the library (tools/build_alt.sh NAME REV) instead of the tree's: the same job on the parent
 
 Per job: one untimed label call, then five timed ones (wall clock around the call, which ends with the stream idle; HIP events
 around every kernel with WDPM_PONDS_TIMING=1), medians; one steady iteration launch of the same context as the unit; the bytes
@@ -386,6 +387,7 @@ def main():
     ap.add_argument("--outlets", action="store_true", help="time label_outlets as well: the passes and locate phases beside the table phase")
     ap.add_argument("--curves", action="store_true", help="time label_curves as well: the bed and stages phases beside table, passes and locate")
     ap.add_argument("--iterations", type=int, help="iterations before the inventory, instead of the job's own")
+    ap.add_argument("--lib", metavar="FILE", help="time this build of the library (tools/build_alt.sh) instead of the tree's own")
     a = ap.parse_args()
     if not a.out:
         a.out = os.path.join(ROOT, "profiles", *(("r17", "pond_outlets_group.json") if a.devices and a.outlets else
@@ -396,7 +398,7 @@ def main():
                                                   ("r15", "pond_outlets.json") if a.outlets else
                                                   ("r14", "pond_catchments.json") if a.catchments else
                                                   ("r12", "pond_rims.json") if a.rims else ("r10", "ponds.json")))
-    hip = wdpm_amd.load_hip()
+    hip = wdpm_amd.load(a.lib) if a.lib else wdpm_amd.load_hip()
     n = a.n
     dem = hip.synth_dem(n, n)
     if a.job == "wet":

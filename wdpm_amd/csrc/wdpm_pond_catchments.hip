@@ -400,7 +400,7 @@ const char kNoTable[] = "no catchment table: the last label call on this handle 
 
 extern "C" int wdpm_catch_label(wdpm_ponds *h, double min_depth, int64_t *nponds) {
   if (!h) return wdpm_fail("wdpm_catch_label: null handle");
-  if (!(min_depth >= 0.0) || std::isinf(min_depth)) return wdpm_fail("wdpm_catch_label: min_depth must be finite and >= 0 (got %g)", min_depth);
+  if (check_min_depth("wdpm_catch_label", min_depth)) return 1;
   if (h->seams) return wdpm_fail("wdpm_catch_label: the handle views a row block: catchments are taken on whole rasters only");
   const Geom g = h->g;
   const long long cells = (long long)g.rows * g.ncp;
@@ -411,143 +411,91 @@ extern "C" int wdpm_catch_label(wdpm_ponds *h, double min_depth, int64_t *nponds
   wdpm_ctx *x = h->x;
   const hipStream_t sm = x->stream;
   HIP_TRY(hipSetDevice(x->p.device));
-  if (!h->d_link) {
-    const hipError_t e = guarded_malloc(h, (void **)&h->d_link, (size_t)cells * sizeof(int));
-    if (e != hipSuccess) { h->d_link = nullptr; return wdpm_fail("wdpm_catch_label: no device memory for the links of %lld cells: %s", cells, hipGetErrorString(e)); }
-  }
-  if (!h->d_cstat) {
-    hipError_t e = hipMalloc(&h->d_cstat, sizeof(CatchStatus));
-    if (e != hipSuccess) { h->d_cstat = nullptr; return wdpm_fail("wdpm_catch_label: no device memory for the status words: %s", hipGetErrorString(e)); }
-    e = hipHostMalloc(&h->h_cstat, sizeof(CatchStatus));
-    if (e != hipSuccess) { h->h_cstat = nullptr; (void)hipFree(h->d_cstat); h->d_cstat = nullptr; return wdpm_fail("wdpm_catch_label: no pinned host memory for the status words: %s", hipGetErrorString(e)); }
-  }
-  if (n > h->catch_cap) {                                     /* sized from N, like the pond table */
-    guarded_free(h, h->d_catch);
-    h->d_catch = nullptr;
-    h->catch_cap = 0;
-    const hipError_t e = guarded_malloc(h, (void **)&h->d_catch, (size_t)n * sizeof(CatchRow));
-    if (e != hipSuccess) return wdpm_fail("wdpm_catch_label: no device memory for the catchments of %lld ponds: %s", (long long)n, hipGetErrorString(e));
-    h->catch_cap = n;
-  }
+  const char *what;
+  hipError_t e = grow(h, h->cat.link, cells);
+  if (e != hipSuccess) return wdpm_fail("wdpm_catch_label: no device memory for the links of %lld cells: %s", cells, hipGetErrorString(e));
+  e = ensure(h->cat.status, &what);
+  if (e != hipSuccess) return wdpm_fail("wdpm_catch_label: no %s memory for the status words: %s", what, hipGetErrorString(e));
+  e = grow(h, h->cat.table, n);                               /* sized from N, like the pond table */
+  if (e != hipSuccess) return wdpm_fail("wdpm_catch_label: no device memory for the catchments of %lld ponds: %s", (long long)n, hipGetErrorString(e));
   const size_t off = (size_t)h->row_off * g.ncp;
   const double *w = x->d_w[x->cur] + off, *dem = x->d_dem + off;
-  const int rpw = ponds_rows_per_wave(g.nseg, g.rows, h->forced_rpw);
-  const int nwaves = ((g.rows + rpw - 1) / rpw) * g.nsc;
+  const Waves wv = waves_for(h, g.rows);
+  const int rpw = wv.rpw, nwaves = wv.nwaves;
   const unsigned nblocks = blocks_for(n, kBlock), wblocks = blocks_for(nwaves, kWaves), cblocks = blocks_for(cells, kBlock);
-#define CATCH_MARK(i) do { if (h->timing) HIP_TRY(hipEventRecord(h->catch_ev[i], sm)); } while (0)
-  HIP_TRY(hipMemsetAsync(h->d_cstat, 0, sizeof(CatchStatus), sm));
-  CATCH_MARK(0);
-  if (n > 0) hipLaunchKernelGGL(catch_init_kernel, dim3(nblocks), dim3(kBlock), 0, sm, h->d_catch, h->d_table, (long long)n);
-  CATCH_MARK(1);
-  hipLaunchKernelGGL(catch_receivers_kernel, dim3(wblocks), dim3(kBlock), 0, sm, w, dem, h->d_masks, h->d_labels, g, rpw, nwaves, h->d_link,
-                     h->d_catch, h->d_cstat);
-  CATCH_MARK(2);
+  HIP_TRY(hipMemsetAsync(h->cat.status.d, 0, sizeof(CatchStatus), sm));
+  HIP_TRY(h->cat.timer.mark(h->timing, 0, sm));
+  if (n > 0) hipLaunchKernelGGL(catch_init_kernel, dim3(nblocks), dim3(kBlock), 0, sm, h->cat.table.p, h->lab.table.p, (long long)n);
+  HIP_TRY(h->cat.timer.mark(h->timing, 1, sm));
+  hipLaunchKernelGGL(catch_receivers_kernel, dim3(wblocks), dim3(kBlock), 0, sm, w, dem, h->lab.masks.p, h->lab.labels.p, g, rpw, nwaves, h->cat.link.p,
+                     h->cat.table.p, h->cat.status.d);
+  HIP_TRY(h->cat.timer.mark(h->timing, 2, sm));
   /* rounds in batches: one look of the host per batch.  A defect ends as an error here, never as a loop that goes on. */
   int rounds = 0;
   for (;;) {
     for (int b = 0; b < kCatchBatch; b++, rounds++)
-      hipLaunchKernelGGL(catch_jump_kernel, dim3(cblocks), dim3(kBlock), 0, sm, h->d_link, (int)cells, rounds, h->d_cstat);
+      hipLaunchKernelGGL(catch_jump_kernel, dim3(cblocks), dim3(kBlock), 0, sm, h->cat.link.p, (int)cells, rounds, h->cat.status.d);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h->h_cstat, h->d_cstat, sizeof(CatchStatus), hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipMemcpyAsync(h->cat.status.h, h->cat.status.d, sizeof(CatchStatus), hipMemcpyDeviceToHost, sm));
     if (wdpm_stream_sync(x, sm)) return 1;
-    if (h->h_cstat->unres[rounds - 1] == 0u) break;
+    if (h->cat.status.h->unres[rounds - 1] == 0u) break;
     if (rounds >= kCatchRoundCap)
       return wdpm_fail("wdpm_catch_label: %u cells are still on their way after %d rounds of pointer jumping, which halve every descent: "
-                       "the link raster is damaged", h->h_cstat->unres[rounds - 1], rounds);
+                       "the link raster is damaged", h->cat.status.h->unres[rounds - 1], rounds);
   }
-  CATCH_MARK(3);
-  hipLaunchKernelGGL(catch_tally_kernel, dim3(wblocks), dim3(kBlock), 0, sm, w, dem, h->d_masks, g, rpw, nwaves, h->d_link, h->d_catch,
-                     h->d_cstat);
-  if (n > 0) hipLaunchKernelGGL(catch_finish_kernel, dim3(nblocks), dim3(kBlock), 0, sm, h->d_catch, (long long)n);
-  CATCH_MARK(4);
-#undef CATCH_MARK
+  HIP_TRY(h->cat.timer.mark(h->timing, 3, sm));
+  hipLaunchKernelGGL(catch_tally_kernel, dim3(wblocks), dim3(kBlock), 0, sm, w, dem, h->lab.masks.p, g, rpw, nwaves, h->cat.link.p, h->cat.table.p,
+                     h->cat.status.d);
+  if (n > 0) hipLaunchKernelGGL(catch_finish_kernel, dim3(nblocks), dim3(kBlock), 0, sm, h->cat.table.p, (long long)n);
+  HIP_TRY(h->cat.timer.mark(h->timing, 4, sm));
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(h->h_cstat, h->d_cstat, sizeof(CatchStatus), hipMemcpyDeviceToHost, sm));
+  HIP_TRY(hipMemcpyAsync(h->cat.status.h, h->cat.status.d, sizeof(CatchStatus), hipMemcpyDeviceToHost, sm));
   if (wdpm_stream_sync(x, sm)) return 1;
   if (h->timing) {
-    float ms[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int i = 0; i < 4; i++) HIP_TRY(hipEventElapsedTime(&ms[i], h->catch_ev[i], h->catch_ev[i + 1]));
-    h->catch_ms[0] = ms[1];
-    h->catch_ms[1] = ms[2];
-    h->catch_ms[2] = (double)ms[0] + (double)ms[3];
+    double ms[4] = {0.0, 0.0, 0.0, 0.0};              /* init | receivers | jump rounds | tally, finish */
+    for (int i = 0; i < 4; i++) HIP_TRY(h->cat.timer.read(i, i + 1, &ms[i]));
+    h->cat.timer.ms[0] = ms[1];
+    h->cat.timer.ms[1] = ms[2];
+    h->cat.timer.ms[2] = ms[0] + ms[3];
   }
-  h->catch_stats.slope_cells = (int64_t)h->h_cstat->slope;
-  h->catch_stats.pit_cells = (int64_t)h->h_cstat->pit;
-  h->catch_stats.unponded_cells = (int64_t)h->h_cstat->unponded;
-  h->catch_stats.rounds = rounds;
-  h->catch_stats.ponds = n;
-  h->catch_valid = true;
+  h->cat.stats.slope_cells = (int64_t)h->cat.status.h->slope;
+  h->cat.stats.pit_cells = (int64_t)h->cat.status.h->pit;
+  h->cat.stats.unponded_cells = (int64_t)h->cat.status.h->unponded;
+  h->cat.stats.rounds = rounds;
+  h->cat.stats.ponds = n;
+  h->cat.valid = true;
   if (nponds) *nponds = n;
   return 0;
 }
 
 extern "C" int wdpm_catch_table(wdpm_ponds *h, wdpm_pond_catchment *out, int64_t capacity) {
-  if (!h) return wdpm_fail("wdpm_catch_table: null handle");
-  if (!h->valid || !h->catch_valid) return wdpm_fail("wdpm_catch_table: %s", kNoTable);
-  const long long n = h->stats.ponds;
-  if (capacity < n) return wdpm_fail("wdpm_catch_table: capacity %lld is too small for %lld ponds", (long long)capacity, n);
-  if (n == 0) return 0;
-  if (!out) return wdpm_fail("wdpm_catch_table: null output");
-  if (wdpm_synchronize(h->x)) return 1;
-  HIP_TRY(hipMemcpyAsync(out, h->d_catch, (size_t)n * sizeof(wdpm_pond_catchment), hipMemcpyDeviceToHost, h->x->stream));
-  return wdpm_stream_sync(h->x, h->x->stream);
+  return table_out("wdpm_catch_table", h, &wdpm_ponds::cat, kNoTable, out, capacity);
 }
 
 extern "C" int wdpm_catch_basins(wdpm_ponds *h, int32_t *padded) {
-  if (!h) return wdpm_fail("wdpm_catch_basins: null handle");
-  if (!padded) return wdpm_fail("wdpm_catch_basins: null output");
-  if (!h->valid || !h->catch_valid) return wdpm_fail("wdpm_catch_basins: %s", kNoTable);
-  if (wdpm_synchronize(h->x)) return 1;
-  HIP_TRY(hipMemcpyAsync(padded, h->d_link, (size_t)h->g.rows * h->g.ncp * sizeof(int32_t), hipMemcpyDeviceToHost, h->x->stream));
-  return wdpm_stream_sync(h->x, h->x->stream);
+  if (check_args("wdpm_catch_basins", h, padded, false)) return 1;
+  if (!h->lab.valid || !h->cat.valid) return wdpm_fail("wdpm_catch_basins: %s", kNoTable);
+  return download(h, padded, h->cat.link.p, (size_t)h->g.rows * h->g.ncp * sizeof(int32_t));
 }
 
 extern "C" int wdpm_catch_stats(wdpm_ponds *h, wdpm_pond_catchment_stats *out) {
-  if (!h) return wdpm_fail("wdpm_catch_stats: null handle");
-  if (!out) return wdpm_fail("wdpm_catch_stats: null output");
-  if (!h->valid || !h->catch_valid) return wdpm_fail("wdpm_catch_stats: %s", kNoTable);
-  *out = h->catch_stats;
-  return 0;
+  return stats_out("wdpm_catch_stats", h, &wdpm_ponds::cat, kNoTable, out);
 }
 
 extern "C" int wdpm_catch_phase_ms(wdpm_ponds *h, double *ms) {
-  if (!h) return wdpm_fail("wdpm_catch_phase_ms: null handle");
-  if (!ms) return wdpm_fail("wdpm_catch_phase_ms: null output");
-  if (!h->timing) return wdpm_fail("wdpm_catch_phase_ms: the handle records no events (set WDPM_PONDS_TIMING=1 before it is made)");
-  if (!h->valid || !h->catch_valid) return wdpm_fail("wdpm_catch_phase_ms: %s", kNoTable);
-  for (int i = 0; i < WDPM_CATCH_PHASES; i++) ms[i] = h->catch_ms[i];
-  return 0;
+  return phase_ms_out("wdpm_catch_phase_ms", h, &wdpm_ponds::cat, kNoTable, ms);
 }
 
 /* ---- row blocks (include/wdpm_group_pond_catchments.h) ----------------------------------------------------------------------- */
-#include <ctime>
-#include <string>
-
 #include "wdpm_catch_stitch.h"
 
 namespace {
 const char kNoGroupTable[] = "no catchment table: the last label call on this handle was not a wdpm_group_catch_label that succeeded";
 
-/* after a failure with work queued: let every rank's stream run dry, so that nothing still reads what the caller may free */
-int group_catch_drain(wdpm_group_ponds *h) {
-  std::string msg = wdpm_last_error();
-  for (wdpm_ponds *p : h->r)
-    if (hipSetDevice(p->x->p.device) == hipSuccess) (void)hipStreamSynchronize(p->x->stream);
-  return wdpm_fail("%s", msg.c_str());
-}
-
-double ms_between(const timespec &a, const timespec &b) { return (double)(b.tv_sec - a.tv_sec) * 1e3 + (double)(b.tv_nsec - a.tv_nsec) * 1e-6; }
-
 CatchRows rows_of(const wdpm_group_ponds *gh, int i) {
   const wdpm_ponds *h = gh->r[i];
-  CatchRows rw;
-  rw.ra = gh->own_lo[i] - gh->view0[i];
-  rw.rb = rw.ra + gh->own_rows[i];
-  rw.halo = (i > 0 ? 1 : 0) | (i + 1 < gh->n ? 2 : 0);
-  rw.nkeys = h->d_ckeys + (size_t)2 * h->g.ncp;
-  rw.slot_of = h->d_slot_of;
-  rw.exit_basin = h->d_cexit;
-  return rw;
+  const OwnedRows own = owned_rows(gh, i);
+  return {own.ra, own.rb, own.halo, h->cat.keys.p + (size_t)2 * h->g.ncp, h->rim.slot_of.p, h->cat.exits.p};
 }
 
 /* Rank i's seam keys behind its scan (group_label calls this for every rank before the first wait): they reach the host with the
@@ -560,38 +508,25 @@ int group_catch_seams(wdpm_group_ponds *gh, int i) {
   const size_t ncp = (size_t)g.ncp;
   const long long cells = (long long)g.rows * g.ncp;
   HIP_TRY(hipSetDevice(x->p.device));
-  if (!h->d_link) {
-    const hipError_t e = guarded_malloc(h, (void **)&h->d_link, (size_t)cells * sizeof(int));
-    if (e != hipSuccess) { h->d_link = nullptr; return wdpm_fail("wdpm_group_catch_label: no device memory for the links of %lld cells: %s", cells, hipGetErrorString(e)); }
-  }
-  if (!h->d_cstat) {
-    hipError_t e = hipMalloc(&h->d_cstat, sizeof(CatchStatus));
-    if (e != hipSuccess) { h->d_cstat = nullptr; return wdpm_fail("wdpm_group_catch_label: no device memory for the status words: %s", hipGetErrorString(e)); }
-    e = hipHostMalloc(&h->h_cstat, sizeof(CatchStatus));
-    if (e != hipSuccess) { h->h_cstat = nullptr; (void)hipFree(h->d_cstat); h->d_cstat = nullptr; return wdpm_fail("wdpm_group_catch_label: no pinned host memory for the status words: %s", hipGetErrorString(e)); }
-  }
-  if (!h->d_ckeys) {
-    hipError_t e = guarded_malloc(h, (void **)&h->d_ckeys, 4 * ncp * sizeof(unsigned long long));
-    if (e != hipSuccess) { h->d_ckeys = nullptr; return wdpm_fail("wdpm_group_catch_label: no device memory for four rows of level keys: %s", hipGetErrorString(e)); }
-  }
-  if (!h->d_cexit) {
-    hipError_t e = guarded_malloc(h, (void **)&h->d_cexit, 4 * ncp * sizeof(int));
-    if (e != hipSuccess) { h->d_cexit = nullptr; return wdpm_fail("wdpm_group_catch_label: no device memory for four rows of exits: %s", hipGetErrorString(e)); }
-  }
-  if (!h->h_ckeys) {
-    const hipError_t e = hipHostMalloc(&h->h_ckeys, 4 * ncp * sizeof(unsigned long long));
-    if (e != hipSuccess) { h->h_ckeys = nullptr; return wdpm_fail("wdpm_group_catch_label: no pinned host memory for four rows of level keys: %s", hipGetErrorString(e)); }
-  }
-  if (!h->h_cexit) {
-    const hipError_t e = hipHostMalloc(&h->h_cexit, 6 * ncp * sizeof(int));
-    if (e != hipSuccess) { h->h_cexit = nullptr; return wdpm_fail("wdpm_group_catch_label: no pinned host memory for six rows of links: %s", hipGetErrorString(e)); }
-  }
+  const char *what;
+  hipError_t e = grow(h, h->cat.link, cells);
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_catch_label: no device memory for the links of %lld cells: %s", cells, hipGetErrorString(e));
+  e = ensure(h->cat.status, &what);
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_catch_label: no %s memory for the status words: %s", what, hipGetErrorString(e));
+  e = grow(h, h->cat.keys, 4LL * g.ncp);
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_catch_label: no device memory for four rows of level keys: %s", hipGetErrorString(e));
+  e = grow(h, h->cat.exits, 4LL * g.ncp);
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_catch_label: no device memory for four rows of exits: %s", hipGetErrorString(e));
+  e = grow(h, h->cat.h_keys, 4LL * g.ncp);
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_catch_label: no pinned host memory for four rows of level keys: %s", hipGetErrorString(e));
+  e = grow(h, h->cat.h_exits, 6LL * g.ncp);
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_catch_label: no pinned host memory for six rows of links: %s", hipGetErrorString(e));
   const size_t off = (size_t)h->row_off * ncp;
   const CatchRows rw = rows_of(gh, i);
   hipLaunchKernelGGL(catch_seam_keys_kernel, dim3(blocks_for(2 * g.ncp, kBlock)), dim3(kBlock), 0, sm, x->d_w[x->cur] + off, x->d_dem + off,
-                     g, rw.halo, h->d_ckeys, h->d_link);
+                     g, rw.halo, h->cat.keys.p, h->cat.link.p);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(h->h_ckeys, h->d_ckeys, 2 * ncp * sizeof(unsigned long long), hipMemcpyDeviceToHost, sm));
+  HIP_TRY(hipMemcpyAsync(h->cat.h_keys.p, h->cat.keys.p, 2 * ncp * sizeof(unsigned long long), hipMemcpyDeviceToHost, sm));
   return 0;
 }
 
@@ -601,14 +536,14 @@ int group_catch_batch(wdpm_ponds *h) {
   const Geom g = h->g;
   const hipStream_t sm = h->x->stream;
   const long long cells = (long long)g.rows * g.ncp;
-  if (h->timing) HIP_TRY(hipEventRecord(h->catch_ev[2], sm));
-  for (int b = 0; b < kCatchBatch; b++, h->catch_rounds++)
-    hipLaunchKernelGGL(catch_jump_kernel, dim3(blocks_for(cells, kBlock)), dim3(kBlock), 0, sm, h->d_link, (int)cells, h->catch_rounds, h->d_cstat);
-  if (h->timing) HIP_TRY(hipEventRecord(h->catch_ev[3], sm));
+  HIP_TRY(h->cat.timer.mark(h->timing, 2, sm));
+  for (int b = 0; b < kCatchBatch; b++, h->cat.rounds++)
+    hipLaunchKernelGGL(catch_jump_kernel, dim3(blocks_for(cells, kBlock)), dim3(kBlock), 0, sm, h->cat.link.p, (int)cells, h->cat.rounds, h->cat.status.d);
+  HIP_TRY(h->cat.timer.mark(h->timing, 3, sm));
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(h->h_cstat, h->d_cstat, sizeof(CatchStatus), hipMemcpyDeviceToHost, sm));
-  HIP_TRY(hipMemcpyAsync(h->h_cexit, h->d_link + (size_t)g.ncp, (size_t)g.ncp * sizeof(int), hipMemcpyDeviceToHost, sm));
-  HIP_TRY(hipMemcpyAsync(h->h_cexit + g.ncp, h->d_link + (size_t)(g.rows - 2) * g.ncp, (size_t)g.ncp * sizeof(int), hipMemcpyDeviceToHost, sm));
+  HIP_TRY(hipMemcpyAsync(h->cat.status.h, h->cat.status.d, sizeof(CatchStatus), hipMemcpyDeviceToHost, sm));
+  HIP_TRY(hipMemcpyAsync(h->cat.h_exits.p, h->cat.link.p + (size_t)g.ncp, (size_t)g.ncp * sizeof(int), hipMemcpyDeviceToHost, sm));
+  HIP_TRY(hipMemcpyAsync(h->cat.h_exits.p + g.ncp, h->cat.link.p + (size_t)(g.rows - 2) * g.ncp, (size_t)g.ncp * sizeof(int), hipMemcpyDeviceToHost, sm));
   return 0;
 }
 
@@ -624,64 +559,46 @@ int group_catch_rank(wdpm_group_ponds *gh, int i, const std::vector<std::vector<
     return wdpm_fail("wdpm_group_catch_label: %lld ponds on %d padded columns: pond codes and exit codes of a link would meet "
                      "(N + 2 * columns + 2 > 2^31)", ponds, g.ncp);
   HIP_TRY(hipSetDevice(x->p.device));
-  const long long held = h->rim_slots, cap = held + 2 * (long long)g.ncp;      /* the rims' slots, then up to 2 * ncp remote ponds */
-  if (cap > h->catch_cap) {
-    guarded_free(h, h->d_catch);
-    h->d_catch = nullptr;
-    h->catch_cap = 0;
-    const hipError_t e = guarded_malloc(h, (void **)&h->d_catch, (size_t)cap * sizeof(CatchRow));
-    if (e != hipSuccess) return wdpm_fail("wdpm_group_catch_label: no device memory for %lld catchment rows: %s", cap, hipGetErrorString(e));
-    h->catch_cap = cap;
-  }
-  if (cap > h->h_catch_cap) {
-    if (h->h_catch) (void)hipHostFree(h->h_catch);
-    h->h_catch = nullptr;
-    h->h_catch_cap = 0;
-    const hipError_t e = hipHostMalloc(&h->h_catch, (size_t)cap * sizeof(wdpm_pond_catchment));
-    if (e != hipSuccess) { h->h_catch = nullptr; return wdpm_fail("wdpm_group_catch_label: no pinned host memory for %lld catchment rows: %s", cap, hipGetErrorString(e)); }
-    h->h_catch_cap = cap;
-  }
+  const long long held = h->rim.slots, cap = held + 2 * (long long)g.ncp;      /* the rims' slots, then up to 2 * ncp remote ponds */
+  hipError_t e = grow(h, h->cat.table, cap);
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_catch_label: no device memory for %lld catchment rows: %s", cap, hipGetErrorString(e));
+  e = grow(h, h->cat.h_table, cap);
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_catch_label: no pinned host memory for %lld catchment rows: %s", cap, hipGetErrorString(e));
   if (ponds > 0 && held == 0) {        /* the rim work made no slots: none of the whole raster's ponds lies in or beside these rows */
-    if (ponds + 1 > h->slot_cap) {
-      guarded_free(h, h->d_slot_of);
-      h->d_slot_of = nullptr;
-      h->slot_cap = 0;
-      const hipError_t e = guarded_malloc(h, (void **)&h->d_slot_of, (size_t)(ponds + 1) * sizeof(int));
-      if (e != hipSuccess) return wdpm_fail("wdpm_group_catch_label: no device memory for the slots of %lld ponds: %s", ponds, hipGetErrorString(e));
-      h->slot_cap = ponds + 1;
-    }
-    HIP_TRY(hipMemsetAsync(h->d_slot_of, 0x7f, (size_t)(ponds + 1) * sizeof(int), sm));
+    e = grow(h, h->rim.slot_of, ponds + 1);
+    if (e != hipSuccess) return wdpm_fail("wdpm_group_catch_label: no device memory for the slots of %lld ponds: %s", ponds, hipGetErrorString(e));
+    HIP_TRY(hipMemsetAsync(h->rim.slot_of.p, 0x7f, (size_t)(ponds + 1) * sizeof(int), sm));
   }
   const CatchRows rw = rows_of(gh, i);
   for (int side = 0; side < 2; side++) {          /* the keys of the rows beside the rank's own, as their owners wrote them */
     if (!(rw.halo & (1 << side))) continue;
-    const unsigned long long *src = gh->r[side ? i + 1 : i - 1]->h_ckeys + (side ? 0 : ncp);
-    unsigned long long *stage = h->h_ckeys + (2 + side) * ncp;
+    const unsigned long long *src = gh->r[side ? i + 1 : i - 1]->cat.h_keys.p + (side ? 0 : ncp);
+    unsigned long long *stage = h->cat.h_keys.p + (2 + side) * ncp;
     memcpy(stage, src, ncp * sizeof(unsigned long long));
-    HIP_TRY(hipMemcpyAsync(h->d_ckeys + (2 + side) * ncp, stage, ncp * sizeof(unsigned long long), hipMemcpyHostToDevice, sm));
+    HIP_TRY(hipMemcpyAsync(h->cat.keys.p + (2 + side) * ncp, stage, ncp * sizeof(unsigned long long), hipMemcpyHostToDevice, sm));
   }
   const size_t off = (size_t)h->row_off * ncp;
   const double *w = x->d_w[x->cur] + off, *dem = x->d_dem + off;
-  const int rpw = ponds_rows_per_wave(g.nseg, g.rows, h->forced_rpw);
-  const int nwaves = ((rw.rb - rw.ra + rpw - 1) / rpw) * g.nsc;
-  HIP_TRY(hipMemsetAsync(h->d_cstat, 0, sizeof(CatchStatus), sm));
-  if (h->timing) HIP_TRY(hipEventRecord(h->catch_ev[0], sm));
-  hipLaunchKernelGGL(catch_init_rows_kernel, dim3(blocks_for(cap, kBlock)), dim3(kBlock), 0, sm, h->d_catch, cap);
-  hipLaunchKernelGGL(catch_receivers_rows_kernel, dim3(blocks_for(nwaves, kWaves)), dim3(kBlock), 0, sm, w, dem, h->d_masks, h->d_labels, g,
-                     rpw, nwaves, h->d_link, h->d_catch, h->d_cstat, rw);
-  if (h->timing) HIP_TRY(hipEventRecord(h->catch_ev[1], sm));
-  h->catch_rounds = 0;
-  h->catch_slots = h->catch_remote = 0;
-  h->catch_ms[0] = h->catch_ms[1] = h->catch_ms[2] = 0.0;
+  const Waves wv = waves_for(h, rw.rb - rw.ra);
+  const int rpw = wv.rpw, nwaves = wv.nwaves;
+  HIP_TRY(hipMemsetAsync(h->cat.status.d, 0, sizeof(CatchStatus), sm));
+  HIP_TRY(h->cat.timer.mark(h->timing, 0, sm));
+  hipLaunchKernelGGL(catch_init_rows_kernel, dim3(blocks_for(cap, kBlock)), dim3(kBlock), 0, sm, h->cat.table.p, cap);
+  hipLaunchKernelGGL(catch_receivers_rows_kernel, dim3(blocks_for(nwaves, kWaves)), dim3(kBlock), 0, sm, w, dem, h->lab.masks.p, h->lab.labels.p, g,
+                     rpw, nwaves, h->cat.link.p, h->cat.table.p, h->cat.status.d, rw);
+  HIP_TRY(h->cat.timer.mark(h->timing, 1, sm));
+  h->cat.rounds = 0;
+  h->cat.slots = h->cat.remote = 0;
+  h->cat.timer.clear();
   return group_catch_batch(h);
 }
 
 /* after a wait: the time of events a and b of rank p onto phase k */
 int group_catch_time(wdpm_ponds *p, int a, int b, int k) {
   if (!p->timing) return 0;
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, p->catch_ev[a], p->catch_ev[b]));
-  p->catch_ms[k] += ms;
+  double ms = 0.0;
+  HIP_TRY(p->cat.timer.read(a, b, &ms));
+  p->cat.timer.ms[k] += ms;
   return 0;
 }
 
@@ -689,8 +606,7 @@ int group_catch_time(wdpm_ponds *p, int a, int b, int k) {
 
 extern "C" int wdpm_group_catch_label(wdpm_group_ponds *h, double min_depth, int64_t *nponds) {
   if (!h) return wdpm_fail("wdpm_group_catch_label: null handle");
-  if (!(min_depth >= 0.0) || std::isinf(min_depth))
-    return wdpm_fail("wdpm_group_catch_label: min_depth must be finite and >= 0 (got %g)", min_depth);
+  if (check_min_depth("wdpm_group_catch_label", min_depth)) return 1;
   int64_t n = 0;
   /* every rank: scan, seam keys | stitch | table, rims, receivers, a first batch of jump rounds - and one wait per rank */
   if (group_label(h, min_depth, &n, group_catch_rank, group_catch_seams)) return 1;
@@ -706,16 +622,16 @@ extern "C" int wdpm_group_catch_label(wdpm_group_ponds *h, double min_depth, int
     bool any = false;
     for (int i = 0; i < nr; i++) {
       wdpm_ponds *p = h->r[i];
-      open[(size_t)i] = p->h_cstat->unres[p->catch_rounds - 1] != 0u;
+      open[(size_t)i] = p->cat.status.h->unres[p->cat.rounds - 1] != 0u;
       if (!open[(size_t)i]) continue;
       any = true;
-      if (p->catch_rounds >= kCatchRoundCap)
+      if (p->cat.rounds >= kCatchRoundCap)
         return wdpm_fail("wdpm_group_catch_label: %u cells of rank %d are still on their way after %d rounds of pointer jumping, which "
-                         "halve every descent: the link raster is damaged", p->h_cstat->unres[p->catch_rounds - 1], i, p->catch_rounds);
+                         "halve every descent: the link raster is damaged", p->cat.status.h->unres[p->cat.rounds - 1], i, p->cat.rounds);
     }
     if (!any) break;
     for (int i = 0; i < nr; i++)
-      if (open[(size_t)i] && (hipSetDevice(h->r[i]->x->p.device) != hipSuccess || group_catch_batch(h->r[i]))) return group_catch_drain(h);
+      if (open[(size_t)i] && (hipSetDevice(h->r[i]->x->p.device) != hipSuccess || group_catch_batch(h->r[i]))) return group_drain(h);
     bool bad = false;
     std::string first_msg;
     for (int i = 0; i < nr; i++) {
@@ -735,21 +651,21 @@ extern "C" int wdpm_group_catch_label(wdpm_group_ponds *h, double min_depth, int
   std::vector<wdpm_catch_stitch::RankLinks> links((size_t)nr);
   for (int i = 0; i < nr; i++) {
     const wdpm_ponds *p = h->r[i];
-    links[(size_t)i].top = p->h_cexit;
-    links[(size_t)i].bottom = p->g.rows == 3 ? p->h_cexit : p->h_cexit + ncp;      /* one row between the view's first and last */
+    links[(size_t)i].top = p->cat.h_exits.p;
+    links[(size_t)i].bottom = p->g.rows == 3 ? p->cat.h_exits.p : p->cat.h_exits.p + ncp;      /* one row between the view's first and last */
   }
   wdpm_catch_stitch::Resolved res;
   std::string err;
   if (wdpm_catch_stitch::resolve(links, ncp, res, err)) return wdpm_fail("wdpm_group_catch_label: %s", err.c_str());
   for (int i = 0; i < nr; i++) {
     wdpm_ponds *p = h->r[i];
-    std::vector<int> &remote = p->catch_remote_label;
-    wdpm_catch_stitch::remote_labels(res.exit_basin[(size_t)i], ncp, h->table.data(), h->view0[i], h->view0[i] + p->g.rows - 1, remote);
-    p->catch_slots = (long long)(p->slot_label.size() + remote.size());
-    p->catch_remote = (long long)remote.size();
-    if (p->catch_slots > p->catch_cap) return wdpm_fail("wdpm_group_catch_label: rank %d would hold %lld catchment rows of %lld", i, p->catch_slots, p->catch_cap);
-    memcpy(p->h_cexit + (size_t)2 * ncp, res.exit_basin[(size_t)i].data(), (size_t)2 * ncp * sizeof(int));
-    if (!remote.empty()) memcpy(p->h_cexit + (size_t)4 * ncp, remote.data(), remote.size() * sizeof(int));
+    std::vector<int> &remote = p->cat.remote_label;
+    wdpm_catch_stitch::remote_labels(res.exit_basin[(size_t)i], ncp, h->lab.rows.data(), h->view0[i], h->view0[i] + p->g.rows - 1, remote);
+    p->cat.slots = (long long)(p->rim.slot_label.size() + remote.size());
+    p->cat.remote = (long long)remote.size();
+    if (p->cat.slots > p->cat.table.cap) return wdpm_fail("wdpm_group_catch_label: rank %d would hold %lld catchment rows of %lld", i, p->cat.slots, p->cat.table.cap);
+    memcpy(p->cat.h_exits.p + (size_t)2 * ncp, res.exit_basin[(size_t)i].data(), (size_t)2 * ncp * sizeof(int));
+    if (!remote.empty()) memcpy(p->cat.h_exits.p + (size_t)4 * ncp, remote.data(), remote.size() * sizeof(int));
   }
   clock_gettime(CLOCK_MONOTONIC, &t1);
 
@@ -762,33 +678,33 @@ extern "C" int wdpm_group_catch_label(wdpm_group_ponds *h, double min_depth, int
     const CatchRows rw = rows_of(h, i);
     const size_t off = (size_t)p->row_off * g.ncp;
     const double *w = x->d_w[x->cur] + off, *dem = x->d_dem + off;
-    const int rpw = ponds_rows_per_wave(g.nseg, g.rows, p->forced_rpw);
-    const int nwaves = ((rw.rb - rw.ra + rpw - 1) / rpw) * g.nsc;
-    const int base = (int)(p->catch_slots - p->catch_remote);
+    const Waves wv = waves_for(p, rw.rb - rw.ra);
+    const int rpw = wv.rpw, nwaves = wv.nwaves;
+    const int base = (int)(p->cat.slots - p->cat.remote);
     /* the first call that fails is the one the message names; nothing is queued behind it */
     hipError_t e = hipSetDevice(x->p.device);
     if (e == hipSuccess)
-      e = hipMemcpyAsync(p->d_cexit, p->h_cexit + (size_t)2 * ncp, (size_t)(2 * ncp + p->catch_remote) * sizeof(int), hipMemcpyHostToDevice, sm);
-    if (e == hipSuccess && p->timing) e = hipEventRecord(p->catch_ev[4], sm);
+      e = hipMemcpyAsync(p->cat.exits.p, p->cat.h_exits.p + (size_t)2 * ncp, (size_t)(2 * ncp + p->cat.remote) * sizeof(int), hipMemcpyHostToDevice, sm);
+    if (e == hipSuccess) e = p->cat.timer.mark(p->timing, 4, sm);
     if (e == hipSuccess) {
-      if (p->catch_remote)
-        hipLaunchKernelGGL(catch_remote_slots_kernel, dim3(blocks_for(p->catch_remote, kBlock)), dim3(kBlock), 0, sm, p->d_cexit + (size_t)2 * ncp,
-                           (int)p->catch_remote, base, p->d_slot_of);
-      hipLaunchKernelGGL(catch_tally_rows_kernel, dim3(blocks_for(nwaves, kWaves)), dim3(kBlock), 0, sm, w, dem, p->d_masks, g, rpw, nwaves,
-                         p->d_link, p->d_catch, p->d_cstat, rw);
-      if (p->catch_slots) hipLaunchKernelGGL(catch_finish_kernel, dim3(blocks_for(p->catch_slots, kBlock)), dim3(kBlock), 0, sm, p->d_catch, p->catch_slots);
+      if (p->cat.remote)
+        hipLaunchKernelGGL(catch_remote_slots_kernel, dim3(blocks_for(p->cat.remote, kBlock)), dim3(kBlock), 0, sm, p->cat.exits.p + (size_t)2 * ncp,
+                           (int)p->cat.remote, base, p->rim.slot_of.p);
+      hipLaunchKernelGGL(catch_tally_rows_kernel, dim3(blocks_for(nwaves, kWaves)), dim3(kBlock), 0, sm, w, dem, p->lab.masks.p, g, rpw, nwaves,
+                         p->cat.link.p, p->cat.table.p, p->cat.status.d, rw);
+      if (p->cat.slots) hipLaunchKernelGGL(catch_finish_kernel, dim3(blocks_for(p->cat.slots, kBlock)), dim3(kBlock), 0, sm, p->cat.table.p, p->cat.slots);
       e = hipGetLastError();                                 /* of the launches */
     }
-    if (e == hipSuccess && p->timing) e = hipEventRecord(p->catch_ev[5], sm);
-    if (e == hipSuccess && p->catch_slots)
-      e = hipMemcpyAsync(p->h_catch, p->d_catch, (size_t)p->catch_slots * sizeof(wdpm_pond_catchment), hipMemcpyDeviceToHost, sm);
-    if (e == hipSuccess) e = hipMemcpyAsync(p->h_cstat, p->d_cstat, sizeof(CatchStatus), hipMemcpyDeviceToHost, sm);
+    if (e == hipSuccess) e = p->cat.timer.mark(p->timing, 5, sm);
+    if (e == hipSuccess && p->cat.slots)
+      e = hipMemcpyAsync(p->cat.h_table.p, p->cat.table.p, (size_t)p->cat.slots * sizeof(wdpm_pond_catchment), hipMemcpyDeviceToHost, sm);
+    if (e == hipSuccess) e = hipMemcpyAsync(p->cat.status.h, p->cat.status.d, sizeof(CatchStatus), hipMemcpyDeviceToHost, sm);
     /* the rank's first and last owned row as basins, where their links lay: what an outlet pass hands the facing ranks */
-    if (e == hipSuccess) e = hipMemcpyAsync(p->h_cexit, p->d_link + (size_t)rw.ra * g.ncp, (size_t)g.ncp * sizeof(int), hipMemcpyDeviceToHost, sm);
-    if (e == hipSuccess) e = hipMemcpyAsync(p->h_cexit + g.ncp, p->d_link + (size_t)(rw.rb - 1) * g.ncp, (size_t)g.ncp * sizeof(int), hipMemcpyDeviceToHost, sm);
+    if (e == hipSuccess) e = hipMemcpyAsync(p->cat.h_exits.p, p->cat.link.p + (size_t)rw.ra * g.ncp, (size_t)g.ncp * sizeof(int), hipMemcpyDeviceToHost, sm);
+    if (e == hipSuccess) e = hipMemcpyAsync(p->cat.h_exits.p + g.ncp, p->cat.link.p + (size_t)(rw.rb - 1) * g.ncp, (size_t)g.ncp * sizeof(int), hipMemcpyDeviceToHost, sm);
     if (e != hipSuccess) {
       (void)wdpm_fail("wdpm_group_catch_label: queueing the tally of rank %d failed: %s", i, hipGetErrorString(e));
-      return group_catch_drain(h);
+      return group_drain(h);
     }
   }
   {
@@ -809,72 +725,53 @@ extern "C" int wdpm_group_catch_label(wdpm_group_ponds *h, double min_depth, int
   long long remote_sum = 0;
   for (int i = 0; i < nr; i++) {
     const wdpm_ponds *p = h->r[i];
-    const CatchStatus &st = *p->h_cstat;
+    const CatchStatus &st = *p->cat.status.h;
     /* a remote slot was made for every pond a cell of the facing rows ends in; those that took a cell of this rank count */
-    for (long long s = p->catch_slots - p->catch_remote; s < p->catch_slots; s++) remote_sum += p->h_catch[s].catch_cells > 0;
-    ranks[(size_t)i] = {p->h_catch, p->slot_label.data(), p->catch_slots, p->catch_remote_label.data(), p->catch_remote, h->view0[i], (long long)st.slope, (long long)st.pit,
-                        (long long)st.unponded, (long long)st.exits, (long long)p->catch_rounds};
+    for (long long s = p->cat.slots - p->cat.remote; s < p->cat.slots; s++) remote_sum += p->cat.h_table.p[s].catch_cells > 0;
+    ranks[(size_t)i] = {p->cat.h_table.p, p->rim.slot_label.data(), p->cat.slots, p->cat.remote_label.data(), p->cat.remote, h->view0[i], (long long)st.slope, (long long)st.pit,
+                        (long long)st.unponded, (long long)st.exits, (long long)p->cat.rounds};
   }
-  h->catchments.resize((size_t)n);
+  h->cat.rows.resize((size_t)n);
   wdpm_catch_stitch::Totals tot;
-  if (wdpm_catch_stitch::merge(ranks, n, h->table.data(), h->catchments.data(), tot, err)) return wdpm_fail("wdpm_group_catch_label: %s", err.c_str());
+  if (wdpm_catch_stitch::merge(ranks, n, h->lab.rows.data(), h->cat.rows.data(), tot, err)) return wdpm_fail("wdpm_group_catch_label: %s", err.c_str());
   clock_gettime(CLOCK_MONOTONIC, &t3);
-  h->catch_stats.slope_cells = tot.slope;
-  h->catch_stats.pit_cells = tot.pit;
-  h->catch_stats.unponded_cells = tot.unponded;
-  h->catch_stats.rounds = tot.rounds;
-  h->catch_stats.ponds = n;
-  h->catch_stats.ranks = nr;
-  h->catch_stats.exits = tot.exits;
-  h->catch_stats.crossings = res.crossings;
-  h->catch_stats.remote = remote_sum;
-  h->catch_stats.resolve_ms = ms_between(t0, t1) + ms_between(t2, t3);
-  h->catch_valid = true;
+  h->cat.stats.slope_cells = tot.slope;
+  h->cat.stats.pit_cells = tot.pit;
+  h->cat.stats.unponded_cells = tot.unponded;
+  h->cat.stats.rounds = tot.rounds;
+  h->cat.stats.ponds = n;
+  h->cat.stats.ranks = nr;
+  h->cat.stats.exits = tot.exits;
+  h->cat.stats.crossings = res.crossings;
+  h->cat.stats.remote = remote_sum;
+  h->cat.stats.resolve_ms = ms_between(t0, t1) + ms_between(t2, t3);
+  h->cat.valid = true;
   if (nponds) *nponds = n;
   return 0;
 }
 
 extern "C" int wdpm_group_catch_table(wdpm_group_ponds *h, wdpm_pond_catchment *out, int64_t capacity) {
-  if (!h) return wdpm_fail("wdpm_group_catch_table: null handle");
-  if (!h->valid || !h->catch_valid) return wdpm_fail("wdpm_group_catch_table: %s", kNoGroupTable);
-  const long long n = h->stats.ponds;
-  if (capacity < n) return wdpm_fail("wdpm_group_catch_table: capacity %lld is too small for %lld ponds", (long long)capacity, n);
-  if (n == 0) return 0;
-  if (!out) return wdpm_fail("wdpm_group_catch_table: null output");
-  memcpy(out, h->catchments.data(), (size_t)n * sizeof(wdpm_pond_catchment));
-  return 0;
+  return table_out("wdpm_group_catch_table", h, &wdpm_group_ponds::cat, kNoGroupTable, out, capacity);
 }
 
 extern "C" int wdpm_group_catch_basins(wdpm_group_ponds *h, int32_t *padded) {
-  if (!h) return wdpm_fail("wdpm_group_catch_basins: null handle");
-  if (!padded) return wdpm_fail("wdpm_group_catch_basins: null output");
-  if (!h->valid || !h->catch_valid) return wdpm_fail("wdpm_group_catch_basins: %s", kNoGroupTable);
+  if (check_args("wdpm_group_catch_basins", h, padded, false)) return 1;
+  if (!h->lab.valid || !h->cat.valid) return wdpm_fail("wdpm_group_catch_basins: %s", kNoGroupTable);
   /* every rank's owned rows, to where they lie in the whole raster, one after another as wdpm_group_ponds_labels brings them */
   for (int i = 0; i < h->n; i++) {
     wdpm_ponds *p = h->r[i];
-    if (wdpm_synchronize(p->x)) return 1;
-    HIP_TRY(hipMemcpyAsync(padded + (size_t)h->own_lo[i] * h->ncp, p->d_link + (size_t)(h->own_lo[i] - h->view0[i]) * h->ncp,
-                           (size_t)h->own_rows[i] * h->ncp * sizeof(int32_t), hipMemcpyDeviceToHost, p->x->stream));
-    if (wdpm_stream_sync(p->x, p->x->stream)) return 1;
+    if (download(p, padded + (size_t)h->own_lo[i] * h->ncp, p->cat.link.p + (size_t)(h->own_lo[i] - h->view0[i]) * h->ncp,
+                 (size_t)h->own_rows[i] * h->ncp * sizeof(int32_t)))
+      return 1;
   }
   return 0;
 }
 
 extern "C" int wdpm_group_catch_stats(wdpm_group_ponds *h, wdpm_group_catchment_stats *out) {
-  if (!h) return wdpm_fail("wdpm_group_catch_stats: null handle");
-  if (!out) return wdpm_fail("wdpm_group_catch_stats: null output");
-  if (!h->valid || !h->catch_valid) return wdpm_fail("wdpm_group_catch_stats: %s", kNoGroupTable);
-  *out = h->catch_stats;
-  return 0;
+  return stats_out("wdpm_group_catch_stats", h, &wdpm_group_ponds::cat, kNoGroupTable, out);
 }
 
 extern "C" int wdpm_group_catch_phase_ms(wdpm_group_ponds *h, int32_t rank, double *ms) {
-  if (!h) return wdpm_fail("wdpm_group_catch_phase_ms: null handle");
-  if (!ms) return wdpm_fail("wdpm_group_catch_phase_ms: null output");
-  if (rank < 0 || rank >= h->n) return wdpm_fail("wdpm_group_catch_phase_ms: rank %d of %d", rank, h->n);
-  if (!h->timing) return wdpm_fail("wdpm_group_catch_phase_ms: the handle records no events (set WDPM_PONDS_TIMING=1 before it is made)");
-  if (!h->valid || !h->catch_valid) return wdpm_fail("wdpm_group_catch_phase_ms: %s", kNoGroupTable);
-  for (int i = 0; i < WDPM_CATCH_PHASES; i++) ms[i] = h->r[rank]->catch_ms[i];
-  return 0;
+  return group_phase_ms_out("wdpm_group_catch_phase_ms", h, &wdpm_group_ponds::cat, &wdpm_ponds::cat, kNoGroupTable, rank, ms);
 }
 #endif  /* WDPM_PONDS_EMULATION */

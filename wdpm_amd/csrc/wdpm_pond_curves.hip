@@ -249,94 +249,63 @@ extern "C" double wdpm_curves_stage_level(double bed, double top, int s) {
 
 extern "C" int wdpm_curves_label(wdpm_ponds *h, double min_depth, int64_t *nponds) {
   if (!h) return wdpm_fail("wdpm_curves_label: null handle");
-  if (!(min_depth >= 0.0) || std::isinf(min_depth)) return wdpm_fail("wdpm_curves_label: min_depth must be finite and >= 0 (got %g)", min_depth);
+  if (check_min_depth("wdpm_curves_label", min_depth)) return 1;
   if (h->seams) return wdpm_fail("wdpm_curves_label: the handle views a row block: stage curves are taken on whole rasters only");
   int64_t n = 0;
   if (wdpm_outlets_label(h, min_depth, &n)) return 1;         /* leaves basin raster, outlet table and the stream as this pass wants them */
-  h->valid = false;                                           /* a wdpm_curves_label that fails leaves no table of any kind */
+  h->lab.valid = false;                                       /* a wdpm_curves_label that fails leaves no table of any kind */
   wdpm_ctx *x = h->x;
   const Geom g = h->g;
   const hipStream_t sm = x->stream;
   HIP_TRY(hipSetDevice(x->p.device));
-  if (!h->d_vstat) {
-    hipError_t e = hipMalloc(&h->d_vstat, sizeof(CurveStatus));
-    if (e != hipSuccess) { h->d_vstat = nullptr; return wdpm_fail("wdpm_curves_label: no device memory for the status words: %s", hipGetErrorString(e)); }
-    e = hipHostMalloc(&h->h_vstat, sizeof(CurveStatus));
-    if (e != hipSuccess) { h->h_vstat = nullptr; (void)hipFree(h->d_vstat); h->d_vstat = nullptr; return wdpm_fail("wdpm_curves_label: no pinned host memory for the status words: %s", hipGetErrorString(e)); }
-  }
-  if (n > h->curves_cap) {                                    /* sized from N, like the pond table */
-    guarded_free(h, h->d_curves);
-    h->d_curves = nullptr;
-    h->curves_cap = 0;
-    const hipError_t e = guarded_malloc(h, (void **)&h->d_curves, (size_t)n * sizeof(CurveRow));
-    if (e != hipSuccess) return wdpm_fail("wdpm_curves_label: no device memory for the curves of %lld ponds: %s", (long long)n, hipGetErrorString(e));
-    h->curves_cap = n;
-  }
-  h->curve_ms[0] = h->curve_ms[1] = 0.0;
-  memset(h->h_vstat, 0, sizeof(CurveStatus));
+  const char *what;
+  hipError_t e = ensure(h->cur.status, &what);
+  if (e != hipSuccess) return wdpm_fail("wdpm_curves_label: no %s memory for the status words: %s", what, hipGetErrorString(e));
+  e = grow(h, h->cur.table, n);                               /* sized from N, like the pond table */
+  if (e != hipSuccess) return wdpm_fail("wdpm_curves_label: no device memory for the curves of %lld ponds: %s", (long long)n, hipGetErrorString(e));
+  h->cur.timer.clear();
+  memset(h->cur.status.h, 0, sizeof(CurveStatus));
   if (n > 0) {                                                /* no pond, no curve: nothing to launch */
     const double *dem = x->d_dem + (size_t)h->row_off * g.ncp;
-    const int rpw = ponds_rows_per_wave(g.nseg, g.rows, h->forced_rpw);
-    const int nwaves = ((g.rows + rpw - 1) / rpw) * g.nsc;
+    const Waves wv = waves_for(h, g.rows);
+    const int rpw = wv.rpw, nwaves = wv.nwaves;
     const unsigned nblocks = blocks_for(n, kBlock), iblocks = blocks_for((long long)n * kCurveWords, kBlock), wblocks = blocks_for(nwaves, kWaves);
-    const wdpm_pond_outlet *outlets = reinterpret_cast<const wdpm_pond_outlet *>(h->d_outlets);
-    HIP_TRY(hipMemsetAsync(h->d_vstat, 0, sizeof(CurveStatus), sm));
-    if (h->timing) HIP_TRY(hipEventRecord(h->curve_ev[0], sm));
-    hipLaunchKernelGGL(curves_init_kernel, dim3(iblocks), dim3(kBlock), 0, sm, h->d_curves, (long long)n, outlets);
-    hipLaunchKernelGGL(curves_bed_kernel, dim3(wblocks), dim3(kBlock), 0, sm, dem, h->d_link, g, rpw, nwaves, h->d_curves);
-    if (h->timing) HIP_TRY(hipEventRecord(h->curve_ev[1], sm));
-    hipLaunchKernelGGL(curves_stages_kernel, dim3(wblocks), dim3(kBlock), 0, sm, dem, h->d_link, g, rpw, nwaves, h->d_curves, h->d_vstat);
-    hipLaunchKernelGGL(curves_finish_kernel, dim3(nblocks), dim3(kBlock), 0, sm, h->d_curves, (long long)n, h->d_vstat);
-    if (h->timing) HIP_TRY(hipEventRecord(h->curve_ev[2], sm));
+    const wdpm_pond_outlet *outlets = reinterpret_cast<const wdpm_pond_outlet *>(h->out.table.p);
+    HIP_TRY(hipMemsetAsync(h->cur.status.d, 0, sizeof(CurveStatus), sm));
+    HIP_TRY(h->cur.timer.mark(h->timing, 0, sm));
+    hipLaunchKernelGGL(curves_init_kernel, dim3(iblocks), dim3(kBlock), 0, sm, h->cur.table.p, (long long)n, outlets);
+    hipLaunchKernelGGL(curves_bed_kernel, dim3(wblocks), dim3(kBlock), 0, sm, dem, h->cat.link.p, g, rpw, nwaves, h->cur.table.p);
+    HIP_TRY(h->cur.timer.mark(h->timing, 1, sm));
+    hipLaunchKernelGGL(curves_stages_kernel, dim3(wblocks), dim3(kBlock), 0, sm, dem, h->cat.link.p, g, rpw, nwaves, h->cur.table.p, h->cur.status.d);
+    hipLaunchKernelGGL(curves_finish_kernel, dim3(nblocks), dim3(kBlock), 0, sm, h->cur.table.p, (long long)n, h->cur.status.d);
+    HIP_TRY(h->cur.timer.mark(h->timing, 2, sm));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h->h_vstat, h->d_vstat, sizeof(CurveStatus), hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipMemcpyAsync(h->cur.status.h, h->cur.status.d, sizeof(CurveStatus), hipMemcpyDeviceToHost, sm));
     if (wdpm_stream_sync(x, sm)) return 1;
-    if (h->timing)
-      for (int i = 0; i < WDPM_CURVES_PHASES; i++) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, h->curve_ev[i], h->curve_ev[i + 1]));
-        h->curve_ms[i] = ms;
-      }
+    if (h->timing) HIP_TRY(h->cur.timer.read_all());
   }
-  if (h->h_vstat->deep)
+  if (h->cur.status.h->deep)
     return wdpm_fail("wdpm_curves_label: a cell of a pond's basin lies 512 m or more below a stage of the pond's curve, or not a finite "
                      "depth below it: q (64-bit sums of depths in units of 2^-24 m) is only safe below that depth");
-  h->curve_stats.ponds = n;
-  h->curve_stats.no_curve = (int64_t)h->h_vstat->no_curve;
-  h->curve_stats.flat = (int64_t)h->h_vstat->flat;
-  h->curve_stats.stage_cells = (int64_t)h->h_vstat->stage_cells;
-  h->curves_valid = true;
-  h->valid = true;
+  h->cur.stats.ponds = n;
+  h->cur.stats.no_curve = (int64_t)h->cur.status.h->no_curve;
+  h->cur.stats.flat = (int64_t)h->cur.status.h->flat;
+  h->cur.stats.stage_cells = (int64_t)h->cur.status.h->stage_cells;
+  h->cur.valid = true;
+  h->lab.valid = true;
   if (nponds) *nponds = n;
   return 0;
 }
 
 extern "C" int wdpm_curves_table(wdpm_ponds *h, wdpm_pond_curve *out, int64_t capacity) {
-  if (!h) return wdpm_fail("wdpm_curves_table: null handle");
-  if (!h->valid || !h->curves_valid) return wdpm_fail("wdpm_curves_table: %s", kNoTable);
-  const long long n = h->stats.ponds;
-  if (capacity < n) return wdpm_fail("wdpm_curves_table: capacity %lld is too small for %lld ponds", (long long)capacity, n);
-  if (n == 0) return 0;
-  if (!out) return wdpm_fail("wdpm_curves_table: null output");
-  if (wdpm_synchronize(h->x)) return 1;
-  HIP_TRY(hipMemcpyAsync(out, h->d_curves, (size_t)n * sizeof(wdpm_pond_curve), hipMemcpyDeviceToHost, h->x->stream));
-  return wdpm_stream_sync(h->x, h->x->stream);
+  return table_out("wdpm_curves_table", h, &wdpm_ponds::cur, kNoTable, out, capacity);
 }
 
 extern "C" int wdpm_curves_stats(wdpm_ponds *h, wdpm_pond_curve_stats *out) {
-  if (!h) return wdpm_fail("wdpm_curves_stats: null handle");
-  if (!out) return wdpm_fail("wdpm_curves_stats: null output");
-  if (!h->valid || !h->curves_valid) return wdpm_fail("wdpm_curves_stats: %s", kNoTable);
-  *out = h->curve_stats;
-  return 0;
+  return stats_out("wdpm_curves_stats", h, &wdpm_ponds::cur, kNoTable, out);
 }
 
 extern "C" int wdpm_curves_phase_ms(wdpm_ponds *h, double *ms) {
-  if (!h) return wdpm_fail("wdpm_curves_phase_ms: null handle");
-  if (!ms) return wdpm_fail("wdpm_curves_phase_ms: null output");
-  if (!h->timing) return wdpm_fail("wdpm_curves_phase_ms: the handle records no events (set WDPM_PONDS_TIMING=1 before it is made)");
-  if (!h->valid || !h->curves_valid) return wdpm_fail("wdpm_curves_phase_ms: %s", kNoTable);
-  for (int i = 0; i < WDPM_CURVES_PHASES; i++) ms[i] = h->curve_ms[i];
-  return 0;
+  return phase_ms_out("wdpm_curves_phase_ms", h, &wdpm_ponds::cur, kNoTable, ms);
 }
 #endif  /* WDPM_PONDS_EMULATION */

@@ -414,101 +414,67 @@ const char kNoTable[] = "no outlet table: the last label call on this handle was
 
 extern "C" int wdpm_outlets_label(wdpm_ponds *h, double min_depth, int64_t *nponds) {
   if (!h) return wdpm_fail("wdpm_outlets_label: null handle");
-  if (!(min_depth >= 0.0) || std::isinf(min_depth)) return wdpm_fail("wdpm_outlets_label: min_depth must be finite and >= 0 (got %g)", min_depth);
+  if (check_min_depth("wdpm_outlets_label", min_depth)) return 1;
   if (h->seams) return wdpm_fail("wdpm_outlets_label: the handle views a row block: outlets are taken on whole rasters only");
   int64_t n = 0;
   if (wdpm_catch_label(h, min_depth, &n)) return 1;           /* leaves the basin raster and the stream as this pass wants them */
-  h->valid = false;                                           /* a wdpm_outlets_label that fails leaves no table of any kind */
+  h->lab.valid = false;                                       /* a wdpm_outlets_label that fails leaves no table of any kind */
   wdpm_ctx *x = h->x;
   const Geom g = h->g;
   const hipStream_t sm = x->stream;
   HIP_TRY(hipSetDevice(x->p.device));
-  if (!h->d_ostat) {
-    hipError_t e = hipMalloc(&h->d_ostat, sizeof(OutletStatus));
-    if (e != hipSuccess) { h->d_ostat = nullptr; return wdpm_fail("wdpm_outlets_label: no device memory for the status words: %s", hipGetErrorString(e)); }
-    e = hipHostMalloc(&h->h_ostat, sizeof(OutletStatus));
-    if (e != hipSuccess) { h->h_ostat = nullptr; (void)hipFree(h->d_ostat); h->d_ostat = nullptr; return wdpm_fail("wdpm_outlets_label: no pinned host memory for the status words: %s", hipGetErrorString(e)); }
-  }
-  if (n > h->outlets_cap) {                                   /* sized from N, like the pond table */
-    guarded_free(h, h->d_outlets);
-    h->d_outlets = nullptr;
-    h->outlets_cap = 0;
-    const hipError_t e = guarded_malloc(h, (void **)&h->d_outlets, (size_t)n * sizeof(OutletRow));
-    if (e != hipSuccess) return wdpm_fail("wdpm_outlets_label: no device memory for the outlets of %lld ponds: %s", (long long)n, hipGetErrorString(e));
-    h->outlets_cap = n;
-  }
-  h->outlet_ms[0] = h->outlet_ms[1] = 0.0;
-  memset(h->h_ostat, 0, sizeof(OutletStatus));
+  const char *what;
+  hipError_t e = ensure(h->out.status, &what);
+  if (e != hipSuccess) return wdpm_fail("wdpm_outlets_label: no %s memory for the status words: %s", what, hipGetErrorString(e));
+  e = grow(h, h->out.table, n);                               /* sized from N, like the pond table */
+  if (e != hipSuccess) return wdpm_fail("wdpm_outlets_label: no device memory for the outlets of %lld ponds: %s", (long long)n, hipGetErrorString(e));
+  h->out.timer.clear();
+  memset(h->out.status.h, 0, sizeof(OutletStatus));
   if (n > 0) {                                                /* no pond, no outlet: nothing to launch */
     const size_t off = (size_t)h->row_off * g.ncp;
     const double *w = x->d_w[x->cur] + off, *dem = x->d_dem + off;
-    const int rpw = ponds_rows_per_wave(g.nseg, g.rows, h->forced_rpw);
-    const int nwaves = ((g.rows + rpw - 1) / rpw) * g.nsc;
+    const Waves wv = waves_for(h, g.rows);
+    const int rpw = wv.rpw, nwaves = wv.nwaves;
     const unsigned nblocks = blocks_for(n, kBlock), wblocks = blocks_for(nwaves, kWaves);
-    HIP_TRY(hipMemsetAsync(h->d_ostat, 0, sizeof(OutletStatus), sm));
-    if (h->timing) HIP_TRY(hipEventRecord(h->outlet_ev[0], sm));
-    hipLaunchKernelGGL(outlet_init_kernel, dim3(nblocks), dim3(kBlock), 0, sm, h->d_outlets, (long long)n);
-    hipLaunchKernelGGL(outlet_passes_kernel, dim3(wblocks), dim3(kBlock), 0, sm, w, dem, h->d_link, g, rpw, nwaves, h->d_outlets);
-    if (h->timing) HIP_TRY(hipEventRecord(h->outlet_ev[1], sm));
-    hipLaunchKernelGGL(outlet_locate_kernel, dim3(wblocks), dim3(kBlock), 0, sm, w, dem, h->d_link, g, rpw, nwaves, h->d_outlets, h->d_ostat);
-    hipLaunchKernelGGL(outlet_finish_kernel, dim3(nblocks), dim3(kBlock), 0, sm, h->d_outlets, (long long)n, h->d_link, g.ncp, h->d_ostat);
-    if (h->timing) HIP_TRY(hipEventRecord(h->outlet_ev[2], sm));
+    HIP_TRY(hipMemsetAsync(h->out.status.d, 0, sizeof(OutletStatus), sm));
+    HIP_TRY(h->out.timer.mark(h->timing, 0, sm));
+    hipLaunchKernelGGL(outlet_init_kernel, dim3(nblocks), dim3(kBlock), 0, sm, h->out.table.p, (long long)n);
+    hipLaunchKernelGGL(outlet_passes_kernel, dim3(wblocks), dim3(kBlock), 0, sm, w, dem, h->cat.link.p, g, rpw, nwaves, h->out.table.p);
+    HIP_TRY(h->out.timer.mark(h->timing, 1, sm));
+    hipLaunchKernelGGL(outlet_locate_kernel, dim3(wblocks), dim3(kBlock), 0, sm, w, dem, h->cat.link.p, g, rpw, nwaves, h->out.table.p, h->out.status.d);
+    hipLaunchKernelGGL(outlet_finish_kernel, dim3(nblocks), dim3(kBlock), 0, sm, h->out.table.p, (long long)n, h->cat.link.p, g.ncp, h->out.status.d);
+    HIP_TRY(h->out.timer.mark(h->timing, 2, sm));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h->h_ostat, h->d_ostat, sizeof(OutletStatus), hipMemcpyDeviceToHost, sm));
+    HIP_TRY(hipMemcpyAsync(h->out.status.h, h->out.status.d, sizeof(OutletStatus), hipMemcpyDeviceToHost, sm));
     if (wdpm_stream_sync(x, sm)) return 1;
-    if (h->timing)
-      for (int i = 0; i < WDPM_OUTLETS_PHASES; i++) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, h->outlet_ev[i], h->outlet_ev[i + 1]));
-        h->outlet_ms[i] = ms;
-      }
+    if (h->timing) HIP_TRY(h->out.timer.read_all());
   }
-  if (h->h_ostat->deep)
+  if (h->out.status.h->deep)
     return wdpm_fail("wdpm_outlets_label: a cell of a pond's basin lies 512 m or more below the pond's outlet, or not a finite depth "
                      "below it: fill_q (a 64-bit sum of depths in units of 2^-24 m) is only safe below that depth");
-  h->outlet_stats.ponds = n;
-  h->outlet_stats.no_outlet = (int64_t)h->h_ostat->no_outlet;
-  h->outlet_stats.to_land = (int64_t)h->h_ostat->to_land;
-  h->outlet_stats.divide_cells = (int64_t)h->h_ostat->divide;
-  h->outlets_valid = true;
-  h->valid = true;
+  h->out.stats.ponds = n;
+  h->out.stats.no_outlet = (int64_t)h->out.status.h->no_outlet;
+  h->out.stats.to_land = (int64_t)h->out.status.h->to_land;
+  h->out.stats.divide_cells = (int64_t)h->out.status.h->divide;
+  h->out.valid = true;
+  h->lab.valid = true;
   if (nponds) *nponds = n;
   return 0;
 }
 
 extern "C" int wdpm_outlets_table(wdpm_ponds *h, wdpm_pond_outlet *out, int64_t capacity) {
-  if (!h) return wdpm_fail("wdpm_outlets_table: null handle");
-  if (!h->valid || !h->outlets_valid) return wdpm_fail("wdpm_outlets_table: %s", kNoTable);
-  const long long n = h->stats.ponds;
-  if (capacity < n) return wdpm_fail("wdpm_outlets_table: capacity %lld is too small for %lld ponds", (long long)capacity, n);
-  if (n == 0) return 0;
-  if (!out) return wdpm_fail("wdpm_outlets_table: null output");
-  if (wdpm_synchronize(h->x)) return 1;
-  HIP_TRY(hipMemcpyAsync(out, h->d_outlets, (size_t)n * sizeof(wdpm_pond_outlet), hipMemcpyDeviceToHost, h->x->stream));
-  return wdpm_stream_sync(h->x, h->x->stream);
+  return table_out("wdpm_outlets_table", h, &wdpm_ponds::out, kNoTable, out, capacity);
 }
 
 extern "C" int wdpm_outlets_stats(wdpm_ponds *h, wdpm_pond_outlet_stats *out) {
-  if (!h) return wdpm_fail("wdpm_outlets_stats: null handle");
-  if (!out) return wdpm_fail("wdpm_outlets_stats: null output");
-  if (!h->valid || !h->outlets_valid) return wdpm_fail("wdpm_outlets_stats: %s", kNoTable);
-  *out = h->outlet_stats;
-  return 0;
+  return stats_out("wdpm_outlets_stats", h, &wdpm_ponds::out, kNoTable, out);
 }
 
 extern "C" int wdpm_outlets_phase_ms(wdpm_ponds *h, double *ms) {
-  if (!h) return wdpm_fail("wdpm_outlets_phase_ms: null handle");
-  if (!ms) return wdpm_fail("wdpm_outlets_phase_ms: null output");
-  if (!h->timing) return wdpm_fail("wdpm_outlets_phase_ms: the handle records no events (set WDPM_PONDS_TIMING=1 before it is made)");
-  if (!h->valid || !h->outlets_valid) return wdpm_fail("wdpm_outlets_phase_ms: %s", kNoTable);
-  for (int i = 0; i < WDPM_OUTLETS_PHASES; i++) ms[i] = h->outlet_ms[i];
-  return 0;
+  return phase_ms_out("wdpm_outlets_phase_ms", h, &wdpm_ponds::out, kNoTable, ms);
 }
 
 /* ---- row blocks (include/wdpm_group_pond_outlets.h) -------------------------------------------------------------------------- */
-#include <ctime>
-#include <string>
-
 #include "wdpm_outlets_merge.h"
 
 static_assert(sizeof(wdpm_outlets_merge::SlotRow) == sizeof(OutletRow) && offsetof(wdpm_outlets_merge::SlotRow, pair) == offsetof(OutletRow, pair) &&
@@ -518,67 +484,31 @@ static_assert(sizeof(wdpm_outlets_merge::SlotRow) == sizeof(OutletRow) && offset
 namespace {
 const char kNoGroupTable[] = "no outlet table: the last label call on this handle was not a wdpm_group_outlets_label that succeeded";
 
-/* after a failure with work queued: let every rank's stream run dry, so that nothing still reads what the caller may free */
-int group_outlets_drain(wdpm_group_ponds *h) {
-  std::string msg = wdpm_last_error();
-  for (wdpm_ponds *p : h->r)
-    if (hipSetDevice(p->x->p.device) == hipSuccess) (void)hipStreamSynchronize(p->x->stream);
-  return wdpm_fail("%s", msg.c_str());
-}
-
-double ms_between(const timespec &a, const timespec &b) { return (double)(b.tv_sec - a.tv_sec) * 1e3 + (double)(b.tv_nsec - a.tv_nsec) * 1e-6; }
-
+/* the rows beside the rank's own come as the catchment pass brought them */
 OutRows rows_of(const wdpm_group_ponds *gh, int i) {
   const wdpm_ponds *h = gh->r[i];
-  OutRows rw;
-  rw.ra = gh->own_lo[i] - gh->view0[i];
-  rw.rb = rw.ra + gh->own_rows[i];
-  rw.halo = (i > 0 ? 1 : 0) | (i + 1 < gh->n ? 2 : 0);
-  rw.nkeys = h->d_ckeys + (size_t)2 * h->g.ncp;       /* the rows beside the rank's own, as the catchment pass brought them */
-  rw.slot_of = h->d_slot_of;
-  return rw;
+  const OwnedRows own = owned_rows(gh, i);
+  return {own.ra, own.rb, own.halo, h->cat.keys.p + (size_t)2 * h->g.ncp, h->rim.slot_of.p};
 }
 
 /* rank i's buffers for `slots` table rows; nothing is queued */
 int group_outlets_buffers(wdpm_ponds *h, int i, long long slots) {
   HIP_TRY(hipSetDevice(h->x->p.device));
-  if (!h->d_ostat) {
-    hipError_t e = hipMalloc(&h->d_ostat, sizeof(OutletStatus));
-    if (e != hipSuccess) { h->d_ostat = nullptr; return wdpm_fail("wdpm_group_outlets_label: no device memory for the status words of rank %d: %s", i, hipGetErrorString(e)); }
-    e = hipHostMalloc(&h->h_ostat, sizeof(OutletStatus));
-    if (e != hipSuccess) { h->h_ostat = nullptr; (void)hipFree(h->d_ostat); h->d_ostat = nullptr; return wdpm_fail("wdpm_group_outlets_label: no pinned host memory for the status words of rank %d: %s", i, hipGetErrorString(e)); }
-  }
-  if (!h->h_oseam) {
-    const hipError_t e = hipHostMalloc(&h->h_oseam, (size_t)2 * h->g.ncp * sizeof(int));
-    if (e != hipSuccess) { h->h_oseam = nullptr; return wdpm_fail("wdpm_group_outlets_label: no pinned host memory for two rows of basins of rank %d: %s", i, hipGetErrorString(e)); }
-  }
-  if (slots > h->outlets_cap) {
-    guarded_free(h, h->d_outlets);
-    h->d_outlets = nullptr;
-    h->outlets_cap = 0;
-    const hipError_t e = guarded_malloc(h, (void **)&h->d_outlets, (size_t)slots * sizeof(OutletRow));
-    if (e != hipSuccess) return wdpm_fail("wdpm_group_outlets_label: no device memory for %lld outlet rows of rank %d: %s", slots, i, hipGetErrorString(e));
-    h->outlets_cap = slots;
-  }
-  if (slots > h->okeys_cap) {
-    guarded_free(h, h->d_okeys);
-    if (h->h_okeys) (void)hipHostFree(h->h_okeys);
-    h->d_okeys = h->h_okeys = nullptr;
-    h->okeys_cap = 0;
-    hipError_t e = guarded_malloc(h, (void **)&h->d_okeys, (size_t)2 * slots * sizeof(unsigned long long));
-    if (e != hipSuccess) { h->d_okeys = nullptr; return wdpm_fail("wdpm_group_outlets_label: no device memory for the pour keys of %lld slots of rank %d: %s", slots, i, hipGetErrorString(e)); }
-    e = hipHostMalloc(&h->h_okeys, (size_t)3 * slots * sizeof(unsigned long long));
-    if (e != hipSuccess) { h->h_okeys = nullptr; guarded_free(h, h->d_okeys); h->d_okeys = nullptr; return wdpm_fail("wdpm_group_outlets_label: no pinned host memory for the pour keys of %lld slots of rank %d: %s", slots, i, hipGetErrorString(e)); }
-    h->okeys_cap = slots;
-  }
-  if (slots > h->h_outlets_cap) {
-    if (h->h_outlets) (void)hipHostFree(h->h_outlets);
-    h->h_outlets = nullptr;
-    h->h_outlets_cap = 0;
-    const hipError_t e = hipHostMalloc(&h->h_outlets, (size_t)slots * sizeof(OutletRow));
-    if (e != hipSuccess) { h->h_outlets = nullptr; return wdpm_fail("wdpm_group_outlets_label: no pinned host memory for %lld outlet rows of rank %d: %s", slots, i, hipGetErrorString(e)); }
-    h->h_outlets_cap = slots;
-  }
+  const char *what;
+  hipError_t e = ensure(h->out.status, &what);
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_outlets_label: no %s memory for the status words of rank %d: %s", what, i, hipGetErrorString(e));
+  e = grow(h, h->out.h_seam, 2LL * h->g.ncp);
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_outlets_label: no pinned host memory for two rows of basins of rank %d: %s", i, hipGetErrorString(e));
+  e = grow(h, h->out.table, slots);
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_outlets_label: no device memory for %lld outlet rows of rank %d: %s", slots, i, hipGetErrorString(e));
+  if (2 * slots > h->out.keys.cap) { reset(h, h->out.keys); reset(h, h->out.h_keys); }   /* the two grow together: both go before either comes */
+  e = grow(h, h->out.keys, 2 * slots);
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_outlets_label: no device memory for the pour keys of %lld slots of rank %d: %s", slots, i, hipGetErrorString(e));
+  e = grow(h, h->out.h_keys, 3 * slots);
+  if (e != hipSuccess) reset(h, h->out.keys);         /* neither without the other: the next call makes both again */
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_outlets_label: no pinned host memory for the pour keys of %lld slots of rank %d: %s", slots, i, hipGetErrorString(e));
+  e = grow(h, h->out.h_table, slots);
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_outlets_label: no pinned host memory for %lld outlet rows of rank %d: %s", slots, i, hipGetErrorString(e));
   return 0;
 }
 
@@ -588,13 +518,11 @@ int group_outlets_wait(wdpm_group_ponds *gh, int ev_a, int ev_b, int phase) {
   std::string first_msg;
   for (int i = 0; i < gh->n; i++) {
     wdpm_ponds *p = gh->r[i];
-    if (p->catch_slots == 0) continue;
+    if (p->cat.slots == 0) continue;
     bool failed = hipSetDevice(p->x->p.device) != hipSuccess || wdpm_stream_sync(p->x, p->x->stream);
     if (!failed && p->timing) {
-      float ms = 0.f;
-      const hipError_t e = hipEventElapsedTime(&ms, p->outlet_ev[ev_a], p->outlet_ev[ev_b]);
+      const hipError_t e = p->out.timer.read(ev_a, ev_b, &p->out.timer.ms[phase]);
       if (e != hipSuccess) failed = wdpm_fail("wdpm_group_outlets_label: the events of rank %d cannot be read: %s", i, hipGetErrorString(e)) != 0;
-      p->outlet_ms[phase] = ms;
     }
     if (failed) {
       if (!bad) first_msg = wdpm_last_error();
@@ -607,57 +535,56 @@ int group_outlets_wait(wdpm_group_ponds *gh, int ev_a, int ev_b, int phase) {
 
 extern "C" int wdpm_group_outlets_label(wdpm_group_ponds *h, double min_depth, int64_t *nponds) {
   if (!h) return wdpm_fail("wdpm_group_outlets_label: null handle");
-  if (!(min_depth >= 0.0) || std::isinf(min_depth))
-    return wdpm_fail("wdpm_group_outlets_label: min_depth must be finite and >= 0 (got %g)", min_depth);
+  if (check_min_depth("wdpm_group_outlets_label", min_depth)) return 1;
   int64_t n = 0;
   const int rc = wdpm_group_catch_label(h, min_depth, &n);    /* leaves basins, seam keys, slots and the seam basins on the host */
-  h->valid = false;                                           /* a wdpm_group_outlets_label that fails leaves no table of any kind */
+  h->lab.valid = false;                                       /* a wdpm_group_outlets_label that fails leaves no table of any kind */
   if (rc) return 1;
   const int nr = h->n, ncp = h->ncp;
   for (int i = 0; i < nr; i++) {
     wdpm_ponds *p = h->r[i];
-    p->outlet_ms[0] = p->outlet_ms[1] = 0.0;
-    if (n > 0 && p->catch_slots > 0 && group_outlets_buffers(p, i, p->catch_slots)) return 1;
+    p->out.timer.clear();
+    if (n > 0 && p->cat.slots > 0 && group_outlets_buffers(p, i, p->cat.slots)) return 1;
   }
-  h->outlets.assign((size_t)n, wdpm_pond_outlet());
+  h->out.rows.assign((size_t)n, wdpm_pond_outlet());
   wdpm_outlets_merge::Totals tot;
   double merge_ms = 0.0;
   if (n > 0) {                                                /* no pond, no outlet: nothing to launch */
     /* (A) every rank: the facing ranks' seam basins into its halo rows, init, passes, keys and divide counts on their way down */
     for (int i = 0; i < nr; i++) {
       wdpm_ponds *p = h->r[i];
-      if (p->catch_slots == 0) continue;                      /* no basin > 0 in its rows: no pass starts there */
+      if (p->cat.slots == 0) continue;                      /* no basin > 0 in its rows: no pass starts there */
       wdpm_ctx *x = p->x;
       const Geom g = p->g;
       const hipStream_t sm = x->stream;
       const OutRows rw = rows_of(h, i);
-      const long long slots = p->catch_slots;
+      const long long slots = p->cat.slots;
       const size_t off = (size_t)p->row_off * g.ncp;
       const double *w = x->d_w[x->cur] + off, *dem = x->d_dem + off;
-      const int rpw = ponds_rows_per_wave(g.nseg, g.rows, p->forced_rpw);
-      const int nwaves = ((rw.rb - rw.ra + rpw - 1) / rpw) * g.nsc;
+      const Waves wv = waves_for(p, rw.rb - rw.ra);
+      const int rpw = wv.rpw, nwaves = wv.nwaves;
       hipError_t e = hipSetDevice(x->p.device);
-      if (e == hipSuccess) e = hipMemsetAsync(p->d_ostat, 0, sizeof(OutletStatus), sm);
-      if (e == hipSuccess && p->timing) e = hipEventRecord(p->outlet_ev[0], sm);
+      if (e == hipSuccess) e = hipMemsetAsync(p->out.status.d, 0, sizeof(OutletStatus), sm);
+      if (e == hipSuccess) e = p->out.timer.mark(p->timing, 0, sm);
       for (int side = 0; side < 2 && e == hipSuccess; side++) {
         if (!(rw.halo & (1 << side))) continue;
-        const int *src = side ? h->r[i + 1]->h_cexit : h->r[i - 1]->h_cexit + ncp;      /* the first row below, the last row above */
-        memcpy(p->h_oseam + (size_t)side * ncp, src, (size_t)ncp * sizeof(int));
-        e = hipMemcpyAsync(p->d_link + (size_t)(side ? g.rows - 1 : 0) * g.ncp, p->h_oseam + (size_t)side * ncp, (size_t)ncp * sizeof(int),
+        const int *src = side ? h->r[i + 1]->cat.h_exits.p : h->r[i - 1]->cat.h_exits.p + ncp;      /* the first row below, the last row above */
+        memcpy(p->out.h_seam.p + (size_t)side * ncp, src, (size_t)ncp * sizeof(int));
+        e = hipMemcpyAsync(p->cat.link.p + (size_t)(side ? g.rows - 1 : 0) * g.ncp, p->out.h_seam.p + (size_t)side * ncp, (size_t)ncp * sizeof(int),
                            hipMemcpyHostToDevice, sm);
       }
       if (e == hipSuccess) {
-        hipLaunchKernelGGL(outlet_init_kernel, dim3(blocks_for(slots, kBlock)), dim3(kBlock), 0, sm, p->d_outlets, slots);
-        hipLaunchKernelGGL(outlet_passes_rows_kernel, dim3(blocks_for(nwaves, kWaves)), dim3(kBlock), 0, sm, w, dem, p->d_link, g, rpw, nwaves,
-                           p->d_outlets, rw);
-        hipLaunchKernelGGL(outlet_pour_down_kernel, dim3(blocks_for(slots, kBlock)), dim3(kBlock), 0, sm, p->d_outlets, slots, p->d_okeys);
+        hipLaunchKernelGGL(outlet_init_kernel, dim3(blocks_for(slots, kBlock)), dim3(kBlock), 0, sm, p->out.table.p, slots);
+        hipLaunchKernelGGL(outlet_passes_rows_kernel, dim3(blocks_for(nwaves, kWaves)), dim3(kBlock), 0, sm, w, dem, p->cat.link.p, g, rpw, nwaves,
+                           p->out.table.p, rw);
+        hipLaunchKernelGGL(outlet_pour_down_kernel, dim3(blocks_for(slots, kBlock)), dim3(kBlock), 0, sm, p->out.table.p, slots, p->out.keys.p);
         e = hipGetLastError();
       }
-      if (e == hipSuccess && p->timing) e = hipEventRecord(p->outlet_ev[1], sm);
-      if (e == hipSuccess) e = hipMemcpyAsync(p->h_okeys, p->d_okeys, (size_t)2 * slots * sizeof(unsigned long long), hipMemcpyDeviceToHost, sm);
+      if (e == hipSuccess) e = p->out.timer.mark(p->timing, 1, sm);
+      if (e == hipSuccess) e = hipMemcpyAsync(p->out.h_keys.p, p->out.keys.p, (size_t)2 * slots * sizeof(unsigned long long), hipMemcpyDeviceToHost, sm);
       if (e != hipSuccess) {
         (void)wdpm_fail("wdpm_group_outlets_label: queueing the passes of rank %d failed: %s", i, hipGetErrorString(e));
-        return group_outlets_drain(h);
+        return group_drain(h);
       }
     }
     if (group_outlets_wait(h, 0, 1, 0)) return 1;
@@ -669,17 +596,17 @@ extern "C" int wdpm_group_outlets_label(wdpm_group_ponds *h, double min_depth, i
     for (int i = 0; i < nr; i++) {
       const wdpm_ponds *p = h->r[i];
       wdpm_outlets_merge::Rank &rk = ranks[(size_t)i];
-      rk.label = p->slot_label.data();
-      rk.slots = p->catch_slots;
-      rk.remote = p->catch_remote_label.data();
-      rk.nremote = p->catch_remote;
-      rk.key = p->h_okeys;
-      rk.divide = p->h_okeys + p->catch_slots;
-      rk.rows = reinterpret_cast<const wdpm_outlets_merge::SlotRow *>(p->h_outlets);
+      rk.label = p->rim.slot_label.data();
+      rk.slots = p->cat.slots;
+      rk.remote = p->cat.remote_label.data();
+      rk.nremote = p->cat.remote;
+      rk.key = p->out.h_keys.p;
+      rk.divide = p->out.h_keys.p + p->cat.slots;
+      rk.rows = reinterpret_cast<const wdpm_outlets_merge::SlotRow *>(p->out.h_table.p);
       rk.row_shift = h->view0[i];
       rk.own_lo = h->own_lo[i];
       rk.own_rows = h->own_rows[i];
-      up[(size_t)i] = p->h_okeys + (size_t)2 * p->okeys_cap;
+      up[(size_t)i] = p->out.h_keys.p + 2 * p->cat.slots;       /* behind the 2 x slots words that came down */
     }
     std::vector<unsigned long long> pour_key((size_t)n);
     std::vector<long long> divide((size_t)n);
@@ -690,86 +617,69 @@ extern "C" int wdpm_group_outlets_label(wdpm_group_ponds *h, double min_depth, i
     /* (B) every rank: the merged keys into its slots, locate, finish, its rows and its status word on their way down */
     for (int i = 0; i < nr; i++) {
       wdpm_ponds *p = h->r[i];
-      if (p->catch_slots == 0) continue;
+      if (p->cat.slots == 0) continue;
       wdpm_ctx *x = p->x;
       const Geom g = p->g;
       const hipStream_t sm = x->stream;
       const OutRows rw = rows_of(h, i);
-      const long long slots = p->catch_slots;
+      const long long slots = p->cat.slots;
       const size_t off = (size_t)p->row_off * g.ncp;
       const double *w = x->d_w[x->cur] + off, *dem = x->d_dem + off;
-      const int rpw = ponds_rows_per_wave(g.nseg, g.rows, p->forced_rpw);
-      const int nwaves = ((rw.rb - rw.ra + rpw - 1) / rpw) * g.nsc;
+      const Waves wv = waves_for(p, rw.rb - rw.ra);
+      const int rpw = wv.rpw, nwaves = wv.nwaves;
       hipError_t e = hipSetDevice(x->p.device);
-      if (e == hipSuccess && p->timing) e = hipEventRecord(p->outlet_ev[1], sm);
-      if (e == hipSuccess) e = hipMemcpyAsync(p->d_okeys, up[(size_t)i], (size_t)slots * sizeof(unsigned long long), hipMemcpyHostToDevice, sm);
+      if (e == hipSuccess) e = p->out.timer.mark(p->timing, 1, sm);
+      if (e == hipSuccess) e = hipMemcpyAsync(p->out.keys.p, up[(size_t)i], (size_t)slots * sizeof(unsigned long long), hipMemcpyHostToDevice, sm);
       if (e == hipSuccess) {
-        hipLaunchKernelGGL(outlet_pour_up_kernel, dim3(blocks_for(slots, kBlock)), dim3(kBlock), 0, sm, p->d_outlets, slots, p->d_okeys);
-        hipLaunchKernelGGL(outlet_locate_rows_kernel, dim3(blocks_for(nwaves, kWaves)), dim3(kBlock), 0, sm, w, dem, p->d_link, g, rpw, nwaves,
-                           p->d_outlets, p->d_ostat, rw);
-        hipLaunchKernelGGL(outlet_finish_rows_kernel, dim3(blocks_for(slots, kBlock)), dim3(kBlock), 0, sm, p->d_outlets, slots, p->d_link, g.ncp);
+        hipLaunchKernelGGL(outlet_pour_up_kernel, dim3(blocks_for(slots, kBlock)), dim3(kBlock), 0, sm, p->out.table.p, slots, p->out.keys.p);
+        hipLaunchKernelGGL(outlet_locate_rows_kernel, dim3(blocks_for(nwaves, kWaves)), dim3(kBlock), 0, sm, w, dem, p->cat.link.p, g, rpw, nwaves,
+                           p->out.table.p, p->out.status.d, rw);
+        hipLaunchKernelGGL(outlet_finish_rows_kernel, dim3(blocks_for(slots, kBlock)), dim3(kBlock), 0, sm, p->out.table.p, slots, p->cat.link.p, g.ncp);
         e = hipGetLastError();
       }
-      if (e == hipSuccess && p->timing) e = hipEventRecord(p->outlet_ev[2], sm);
-      if (e == hipSuccess) e = hipMemcpyAsync(p->h_outlets, p->d_outlets, (size_t)slots * sizeof(OutletRow), hipMemcpyDeviceToHost, sm);
-      if (e == hipSuccess) e = hipMemcpyAsync(p->h_ostat, p->d_ostat, sizeof(OutletStatus), hipMemcpyDeviceToHost, sm);
+      if (e == hipSuccess) e = p->out.timer.mark(p->timing, 2, sm);
+      if (e == hipSuccess) e = hipMemcpyAsync(p->out.h_table.p, p->out.table.p, (size_t)slots * sizeof(OutletRow), hipMemcpyDeviceToHost, sm);
+      if (e == hipSuccess) e = hipMemcpyAsync(p->out.status.h, p->out.status.d, sizeof(OutletStatus), hipMemcpyDeviceToHost, sm);
       if (e != hipSuccess) {
         (void)wdpm_fail("wdpm_group_outlets_label: queueing the locate pass of rank %d failed: %s", i, hipGetErrorString(e));
-        return group_outlets_drain(h);
+        return group_drain(h);
       }
     }
     if (group_outlets_wait(h, 1, 2, 1)) return 1;
     for (int i = 0; i < nr; i++)
-      if (h->r[i]->catch_slots > 0 && h->r[i]->h_ostat->deep)
+      if (h->r[i]->cat.slots > 0 && h->r[i]->out.status.h->deep)
         return wdpm_fail("wdpm_group_outlets_label: a cell of a pond's basin in the rows of rank %d lies 512 m or more below the pond's outlet, or "
                          "not a finite depth below it: fill_q (a 64-bit sum of depths in units of 2^-24 m) is only safe below that depth", i);
 
     clock_gettime(CLOCK_MONOTONIC, &t2);
-    if (wdpm_outlets_merge::merge(ranks, n, ncp, pour_key.data(), divide.data(), h->outlets.data(), tot, err))
+    if (wdpm_outlets_merge::merge(ranks, n, ncp, pour_key.data(), divide.data(), h->out.rows.data(), tot, err))
       return wdpm_fail("wdpm_group_outlets_label: %s", err.c_str());
     clock_gettime(CLOCK_MONOTONIC, &t3);
     merge_ms = ms_between(t0, t1) + ms_between(t2, t3);
   }
-  h->outlet_stats.ponds = n;
-  h->outlet_stats.no_outlet = tot.no_outlet;
-  h->outlet_stats.to_land = tot.to_land;
-  h->outlet_stats.divide_cells = tot.divide_cells;
-  h->outlet_stats.ranks = nr;
-  h->outlet_stats.seam_outlets = tot.seam_outlets;
-  h->outlet_stats.split_ponds = tot.split_ponds;
-  h->outlet_stats.merge_ms = merge_ms;
-  h->outlets_valid = true;
-  h->valid = true;
+  h->out.stats.ponds = n;
+  h->out.stats.no_outlet = tot.no_outlet;
+  h->out.stats.to_land = tot.to_land;
+  h->out.stats.divide_cells = tot.divide_cells;
+  h->out.stats.ranks = nr;
+  h->out.stats.seam_outlets = tot.seam_outlets;
+  h->out.stats.split_ponds = tot.split_ponds;
+  h->out.stats.merge_ms = merge_ms;
+  h->out.valid = true;
+  h->lab.valid = true;
   if (nponds) *nponds = n;
   return 0;
 }
 
 extern "C" int wdpm_group_outlets_table(wdpm_group_ponds *h, wdpm_pond_outlet *out, int64_t capacity) {
-  if (!h) return wdpm_fail("wdpm_group_outlets_table: null handle");
-  if (!h->valid || !h->outlets_valid) return wdpm_fail("wdpm_group_outlets_table: %s", kNoGroupTable);
-  const long long n = h->stats.ponds;
-  if (capacity < n) return wdpm_fail("wdpm_group_outlets_table: capacity %lld is too small for %lld ponds", (long long)capacity, n);
-  if (n == 0) return 0;
-  if (!out) return wdpm_fail("wdpm_group_outlets_table: null output");
-  memcpy(out, h->outlets.data(), (size_t)n * sizeof(wdpm_pond_outlet));
-  return 0;
+  return table_out("wdpm_group_outlets_table", h, &wdpm_group_ponds::out, kNoGroupTable, out, capacity);
 }
 
 extern "C" int wdpm_group_outlets_stats(wdpm_group_ponds *h, wdpm_group_outlet_stats *out) {
-  if (!h) return wdpm_fail("wdpm_group_outlets_stats: null handle");
-  if (!out) return wdpm_fail("wdpm_group_outlets_stats: null output");
-  if (!h->valid || !h->outlets_valid) return wdpm_fail("wdpm_group_outlets_stats: %s", kNoGroupTable);
-  *out = h->outlet_stats;
-  return 0;
+  return stats_out("wdpm_group_outlets_stats", h, &wdpm_group_ponds::out, kNoGroupTable, out);
 }
 
 extern "C" int wdpm_group_outlets_phase_ms(wdpm_group_ponds *h, int32_t rank, double *ms) {
-  if (!h) return wdpm_fail("wdpm_group_outlets_phase_ms: null handle");
-  if (!ms) return wdpm_fail("wdpm_group_outlets_phase_ms: null output");
-  if (rank < 0 || rank >= h->n) return wdpm_fail("wdpm_group_outlets_phase_ms: rank %d of %d", rank, h->n);
-  if (!h->timing) return wdpm_fail("wdpm_group_outlets_phase_ms: the handle records no events (set WDPM_PONDS_TIMING=1 before it is made)");
-  if (!h->valid || !h->outlets_valid) return wdpm_fail("wdpm_group_outlets_phase_ms: %s", kNoGroupTable);
-  for (int i = 0; i < WDPM_OUTLETS_PHASES; i++) ms[i] = h->r[rank]->outlet_ms[i];
-  return 0;
+  return group_phase_ms_out("wdpm_group_outlets_phase_ms", h, &wdpm_group_ponds::out, &wdpm_ponds::out, kNoGroupTable, rank, ms);
 }
 #endif  /* WDPM_PONDS_EMULATION */

@@ -289,7 +289,7 @@ __global__ __launch_bounds__(kBlock) void rims_finish_kernel(RimRow *t, long lon
 /* ---- host ------------------------------------------------------------------------------------------------------------------ */
 extern "C" int wdpm_rims_label(wdpm_ponds *h, double min_depth, int64_t *nponds) {
   if (!h) return wdpm_fail("wdpm_rims_label: null handle");
-  if (!(min_depth >= 0.0) || std::isinf(min_depth)) return wdpm_fail("wdpm_rims_label: min_depth must be finite and >= 0 (got %g)", min_depth);
+  if (check_min_depth("wdpm_rims_label", min_depth)) return 1;
   if (h->seams) return wdpm_fail("wdpm_rims_label: the handle views a row block: rims are taken on whole rasters only");
   int64_t n = 0;
   if (wdpm_ponds_label(h, min_depth, &n)) return 1;           /* leaves masks, labels and the stream as the rim pass wants them */
@@ -297,67 +297,45 @@ extern "C" int wdpm_rims_label(wdpm_ponds *h, double min_depth, int64_t *nponds)
   const Geom g = h->g;
   const hipStream_t sm = x->stream;
   HIP_TRY(hipSetDevice(x->p.device));
-  if (n > h->rims_cap) {                                      /* sized from N, like the pond table */
-    guarded_free(h, h->d_rims);
-    h->d_rims = nullptr;
-    h->rims_cap = 0;
-    const hipError_t e = guarded_malloc(h, (void **)&h->d_rims, (size_t)n * sizeof(RimRow));
-    if (e != hipSuccess) return wdpm_fail("wdpm_rims_label: no device memory for the rims of %lld ponds: %s", (long long)n, hipGetErrorString(e));
-    h->rims_cap = n;
-  }
-  h->rim_ms[0] = h->rim_ms[1] = 0.0;
+  const hipError_t e = grow(h, h->rim.table, n);              /* sized from N, like the pond table */
+  if (e != hipSuccess) return wdpm_fail("wdpm_rims_label: no device memory for the rims of %lld ponds: %s", (long long)n, hipGetErrorString(e));
+  h->rim.timer.clear();
   if (n > 0) {                                                /* no pond, no rim: nothing to launch */
     const size_t off = (size_t)h->row_off * g.ncp;
     const double *w = x->d_w[x->cur] + off, *dem = x->d_dem + off;
-    const int rpw = ponds_rows_per_wave(g.nseg, g.rows, h->forced_rpw);
-    const int nwaves = ((g.rows + rpw - 1) / rpw) * g.nsc;
+    const Waves wv = waves_for(h, g.rows);
+    const int rpw = wv.rpw, nwaves = wv.nwaves;
     const unsigned nblocks = blocks_for(n, kBlock), wblocks = blocks_for(nwaves, kWaves);
-    if (h->timing) HIP_TRY(hipEventRecord(h->rim_ev[0], sm));
-    hipLaunchKernelGGL(rims_init_kernel, dim3(nblocks), dim3(kBlock), 0, sm, h->d_rims, (long long)n);
-    hipLaunchKernelGGL(rims_pass_kernel, dim3(wblocks), dim3(kBlock), 0, sm, w, dem, h->d_masks, h->d_labels, g, rpw, nwaves, h->d_rims);
-    if (h->timing) HIP_TRY(hipEventRecord(h->rim_ev[1], sm));
-    hipLaunchKernelGGL(rims_locate_kernel, dim3(wblocks), dim3(kBlock), 0, sm, w, dem, h->d_masks, h->d_labels, g, rpw, nwaves, h->d_rims);
-    hipLaunchKernelGGL(rims_finish_kernel, dim3(nblocks), dim3(kBlock), 0, sm, h->d_rims, (long long)n, g.ncp);
-    if (h->timing) HIP_TRY(hipEventRecord(h->rim_ev[2], sm));
+    HIP_TRY(h->rim.timer.mark(h->timing, 0, sm));
+    hipLaunchKernelGGL(rims_init_kernel, dim3(nblocks), dim3(kBlock), 0, sm, h->rim.table.p, (long long)n);
+    hipLaunchKernelGGL(rims_pass_kernel, dim3(wblocks), dim3(kBlock), 0, sm, w, dem, h->lab.masks.p, h->lab.labels.p, g, rpw, nwaves, h->rim.table.p);
+    HIP_TRY(h->rim.timer.mark(h->timing, 1, sm));
+    hipLaunchKernelGGL(rims_locate_kernel, dim3(wblocks), dim3(kBlock), 0, sm, w, dem, h->lab.masks.p, h->lab.labels.p, g, rpw, nwaves, h->rim.table.p);
+    hipLaunchKernelGGL(rims_finish_kernel, dim3(nblocks), dim3(kBlock), 0, sm, h->rim.table.p, (long long)n, g.ncp);
+    HIP_TRY(h->rim.timer.mark(h->timing, 2, sm));
     HIP_TRY(hipGetLastError());
     if (wdpm_stream_sync(x, sm)) return 1;
-    if (h->timing)
-      for (int i = 0; i < WDPM_RIMS_PHASES; i++) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, h->rim_ev[i], h->rim_ev[i + 1]));
-        h->rim_ms[i] = ms;
-      }
+    if (h->timing) HIP_TRY(h->rim.timer.read_all());
   }
-  h->rims_valid = true;
+  h->rim.valid = true;
   if (nponds) *nponds = n;
   return 0;
 }
 
+namespace {
+const char kNoTable[] = "no rim table: the last label call on this handle was not a wdpm_rims_label that succeeded";
+const char kNoGroupTable[] = "no rim table: the last label call on this handle was not a wdpm_group_rims_label that succeeded";
+}  // namespace
+
 extern "C" int wdpm_rims_table(wdpm_ponds *h, wdpm_pond_rim *out, int64_t capacity) {
-  if (!h) return wdpm_fail("wdpm_rims_table: null handle");
-  if (!h->valid || !h->rims_valid)
-    return wdpm_fail("wdpm_rims_table: no rim table: the last label call on this handle was not a wdpm_rims_label that succeeded");
-  const long long n = h->stats.ponds;
-  if (capacity < n) return wdpm_fail("wdpm_rims_table: capacity %lld is too small for %lld ponds", (long long)capacity, n);
-  if (n == 0) return 0;
-  if (!out) return wdpm_fail("wdpm_rims_table: null output");
-  if (wdpm_synchronize(h->x)) return 1;
-  HIP_TRY(hipMemcpyAsync(out, h->d_rims, (size_t)n * sizeof(wdpm_pond_rim), hipMemcpyDeviceToHost, h->x->stream));
-  return wdpm_stream_sync(h->x, h->x->stream);
+  return table_out("wdpm_rims_table", h, &wdpm_ponds::rim, kNoTable, out, capacity);
 }
 
 extern "C" int wdpm_rims_phase_ms(wdpm_ponds *h, double *ms) {
-  if (!h || !ms) return wdpm_fail("wdpm_rims_phase_ms: null argument");
-  if (!h->timing) return wdpm_fail("wdpm_rims_phase_ms: the handle records no events (set WDPM_PONDS_TIMING=1 before it is made)");
-  if (!h->valid || !h->rims_valid)
-    return wdpm_fail("wdpm_rims_phase_ms: no rim table: the last label call on this handle was not a wdpm_rims_label that succeeded");
-  for (int i = 0; i < WDPM_RIMS_PHASES; i++) ms[i] = h->rim_ms[i];
-  return 0;
+  return phase_ms_out("wdpm_rims_phase_ms", h, &wdpm_ponds::rim, kNoTable, ms, true);
 }
-/* ---- row blocks (include/wdpm_group_pond_rims.h) ----------------------------------------------------------------------------- */
-#include <ctime>
-#include <string>
 
+/* ---- row blocks (include/wdpm_group_pond_rims.h) ----------------------------------------------------------------------------- */
 #include "wdpm_rims_merge.h"
 
 /* Rank i's rim work behind its table kernels, on its stream, nothing waited for (group_label calls this for every rank before the
@@ -369,20 +347,16 @@ int wdpm_pond_detail::group_rims_rank(wdpm_group_ponds *gh, int i, const std::ve
   const hipStream_t sm = x->stream;
   const int ncp = g.ncp, nsc = g.nsc;
   const bool up = i > 0, dn = i + 1 < gh->n;
-  h->rim_ms[0] = h->rim_ms[1] = 0.0;
-  h->rim_slots = h->rim_foreign = 0;
-  h->slot_label.clear();
+  h->rim.timer.clear();
+  h->rim.slots = h->rim.nforeign = 0;
+  h->rim.slot_label.clear();
   if (ponds == 0) return 0;
   HIP_TRY(hipSetDevice(x->p.device));
-  if (!h->h_beside) {
-    const hipError_t e = hipHostMalloc(&h->h_beside, (size_t)2 * nsc * sizeof(unsigned long long) + (size_t)4 * ncp * sizeof(int));
-    if (e != hipSuccess) { h->h_beside = nullptr; return wdpm_fail("wdpm_group_rims_label: no pinned host memory for two rows: %s", hipGetErrorString(e)); }
-  }
-  if (!h->d_foreign) {
-    const hipError_t e = guarded_malloc(h, (void **)&h->d_foreign, (size_t)2 * ncp * sizeof(int));
-    if (e != hipSuccess) { h->d_foreign = nullptr; return wdpm_fail("wdpm_group_rims_label: no device memory for two rows of labels: %s", hipGetErrorString(e)); }
-  }
-  unsigned long long *bm = h->h_beside;             /* [2][nsc] */
+  hipError_t e = grow(h, h->rim.h_beside, 2LL * nsc + 2LL * ncp);     /* 2 x nsc masks, then 4 x ncp ints in the place of 2 x ncp words */
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_rims_label: no pinned host memory for two rows: %s", hipGetErrorString(e));
+  e = grow(h, h->rim.foreign, 2LL * ncp);
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_rims_label: no device memory for two rows of labels: %s", hipGetErrorString(e));
+  unsigned long long *bm = h->rim.h_beside.p;             /* [2][nsc] */
   int *bl = (int *)(bm + (size_t)2 * nsc);          /* [2][ncp] */
   int *bf = bl + (size_t)2 * ncp;                   /* up to 2 * ncp foreign labels */
   memset(bm, 0, (size_t)2 * nsc * sizeof(unsigned long long));
@@ -390,7 +364,7 @@ int wdpm_pond_detail::group_rims_rank(wdpm_group_ponds *gh, int i, const std::ve
   for (int side = 0; side < 2; side++) {
     if (side ? !dn : !up) continue;
     const int j = side ? i + 1 : i - 1;
-    const int *src = gh->r[j]->h_seam + (side ? 0 : ncp);     /* the lower rank's first owned row, the upper rank's last */
+    const int *src = gh->r[j]->lab.h_seam.p + (side ? 0 : ncp);     /* the lower rank's first owned row, the upper rank's last */
     for (int c = 0; c < ncp; c++)
       if (src[c]) {
         bl[side * ncp + c] = map[j][(size_t)src[c] - 1];
@@ -400,7 +374,7 @@ int wdpm_pond_detail::group_rims_rank(wdpm_group_ponds *gh, int i, const std::ve
   std::vector<int> own, foreign;
   for (int side = 0; side < 2; side++) {
     if (side ? !dn : !up) continue;
-    const int *src = h->h_seam + side * ncp;
+    const int *src = h->lab.h_seam.p + side * ncp;
     for (int c = 0; c < ncp; c++)
       if (src[c]) own.push_back(map[i][(size_t)src[c] - 1]);
   }
@@ -409,106 +383,84 @@ int wdpm_pond_detail::group_rims_rank(wdpm_group_ponds *gh, int i, const std::ve
   if (slots == 0) return 0;                         /* no pond in the rank's rows, none beside them */
   if (slots > (long long)0x7f7f7f7f) return wdpm_fail("wdpm_group_rims_label: rank %d would hold %lld rim rows", i, slots);
   for (long long k = 0; k < nforeign; k++) bf[k] = foreign[(size_t)k];
-  h->slot_label = map[i];
-  h->slot_label.insert(h->slot_label.end(), foreign.begin(), foreign.end());
+  h->rim.slot_label = map[i];
+  h->rim.slot_label.insert(h->rim.slot_label.end(), foreign.begin(), foreign.end());
 
-  if (slots > h->rims_cap) {
-    guarded_free(h, h->d_rims);
-    h->d_rims = nullptr;
-    h->rims_cap = 0;
-    const hipError_t e = guarded_malloc(h, (void **)&h->d_rims, (size_t)slots * sizeof(RimRow));
-    if (e != hipSuccess) return wdpm_fail("wdpm_group_rims_label: no device memory for the rims of %lld ponds: %s", slots, hipGetErrorString(e));
-    h->rims_cap = slots;
-  }
-  if (ponds + 1 > h->slot_cap) {
-    guarded_free(h, h->d_slot_of);
-    h->d_slot_of = nullptr;
-    h->slot_cap = 0;
-    const hipError_t e = guarded_malloc(h, (void **)&h->d_slot_of, (size_t)(ponds + 1) * sizeof(int));
-    if (e != hipSuccess) return wdpm_fail("wdpm_group_rims_label: no device memory for the slots of %lld ponds: %s", ponds, hipGetErrorString(e));
-    h->slot_cap = ponds + 1;
-  }
-  if (slots > h->h_rims_cap) {
-    if (h->h_rims) (void)hipHostFree(h->h_rims);
-    h->h_rims = nullptr;
-    h->h_rims_cap = 0;
-    const hipError_t e = hipHostMalloc(&h->h_rims, (size_t)slots * sizeof(wdpm_pond_rim));
-    if (e != hipSuccess) { h->h_rims = nullptr; return wdpm_fail("wdpm_group_rims_label: no pinned host memory for %lld rim rows: %s", slots, hipGetErrorString(e)); }
-    h->h_rims_cap = slots;
-  }
+  e = grow(h, h->rim.table, slots);
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_rims_label: no device memory for the rims of %lld ponds: %s", slots, hipGetErrorString(e));
+  e = grow(h, h->rim.slot_of, ponds + 1);
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_rims_label: no device memory for the slots of %lld ponds: %s", ponds, hipGetErrorString(e));
+  e = grow(h, h->rim.h_table, slots);
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_rims_label: no pinned host memory for %lld rim rows: %s", slots, hipGetErrorString(e));
 
   /* the rows beside the rank's own, into view rows 0 and g.rows - 1, which the label path left dry and unlabelled */
   for (int side = 0; side < 2; side++) {
     if (side ? !dn : !up) continue;
     const size_t row = side ? (size_t)g.rows - 1 : 0;
-    HIP_TRY(hipMemcpyAsync(h->d_labels + row * ncp, bl + (size_t)side * ncp, (size_t)ncp * sizeof(int), hipMemcpyHostToDevice, sm));
-    HIP_TRY(hipMemcpyAsync(h->d_masks + row * nsc, bm + (size_t)side * nsc, (size_t)nsc * sizeof(unsigned long long), hipMemcpyHostToDevice, sm));
+    HIP_TRY(hipMemcpyAsync(h->lab.labels.p + row * ncp, bl + (size_t)side * ncp, (size_t)ncp * sizeof(int), hipMemcpyHostToDevice, sm));
+    HIP_TRY(hipMemcpyAsync(h->lab.masks.p + row * nsc, bm + (size_t)side * nsc, (size_t)nsc * sizeof(unsigned long long), hipMemcpyHostToDevice, sm));
   }
-  if (nforeign) HIP_TRY(hipMemcpyAsync(h->d_foreign, bf, (size_t)nforeign * sizeof(int), hipMemcpyHostToDevice, sm));
+  if (nforeign) HIP_TRY(hipMemcpyAsync(h->rim.foreign.p, bf, (size_t)nforeign * sizeof(int), hipMemcpyHostToDevice, sm));
 
   const size_t off = (size_t)h->row_off * ncp;
   const double *w = x->d_w[x->cur] + off, *dem = x->d_dem + off;
-  const int ra = gh->own_lo[i] - gh->view0[i], rb = ra + gh->own_rows[i];      /* the owned rows, in rows of the view */
-  const int rpw = ponds_rows_per_wave(g.nseg, g.rows, h->forced_rpw);
-  const int nwaves = ((rb - ra + rpw - 1) / rpw) * nsc;
+  const OwnedRows orw = owned_rows(gh, i);
+  const int ra = orw.ra, rb = orw.rb;                 /* the owned rows, in rows of the view */
+  const Waves wv = waves_for(h, rb - ra);
+  const int rpw = wv.rpw, nwaves = wv.nwaves;
   const unsigned sblocks = blocks_for(slots, kBlock), wblocks = blocks_for(nwaves, kWaves);
-  if (h->timing) HIP_TRY(hipEventRecord(h->rim_ev[0], sm));
+  HIP_TRY(h->rim.timer.mark(h->timing, 0, sm));
   /* every entry above any slot (slots <= 0x7f7f7f7f); only the entries of the rank's own and foreign ponds are ever read */
-  HIP_TRY(hipMemsetAsync(h->d_slot_of, 0x7f, (size_t)(ponds + 1) * sizeof(int), sm));
-  hipLaunchKernelGGL(rims_slots_kernel, dim3(sblocks), dim3(kBlock), 0, sm, h->d_map, (int)nlocal, h->d_foreign, (int)nforeign, h->d_slot_of);
-  hipLaunchKernelGGL(rims_init_kernel, dim3(sblocks), dim3(kBlock), 0, sm, h->d_rims, slots);
-  hipLaunchKernelGGL(rims_pass_rows_kernel, dim3(wblocks), dim3(kBlock), 0, sm, w, dem, h->d_masks, h->d_labels, g, rpw, nwaves, h->d_rims,
-                     ra, rb, h->d_slot_of);
-  if (h->timing) HIP_TRY(hipEventRecord(h->rim_ev[1], sm));
-  hipLaunchKernelGGL(rims_locate_rows_kernel, dim3(wblocks), dim3(kBlock), 0, sm, w, dem, h->d_masks, h->d_labels, g, rpw, nwaves, h->d_rims,
-                     ra, rb, h->d_slot_of);
-  hipLaunchKernelGGL(rims_finish_kernel, dim3(sblocks), dim3(kBlock), 0, sm, h->d_rims, slots, ncp);
-  if (h->timing) HIP_TRY(hipEventRecord(h->rim_ev[2], sm));
+  HIP_TRY(hipMemsetAsync(h->rim.slot_of.p, 0x7f, (size_t)(ponds + 1) * sizeof(int), sm));
+  hipLaunchKernelGGL(rims_slots_kernel, dim3(sblocks), dim3(kBlock), 0, sm, h->lab.map.p, (int)nlocal, h->rim.foreign.p, (int)nforeign, h->rim.slot_of.p);
+  hipLaunchKernelGGL(rims_init_kernel, dim3(sblocks), dim3(kBlock), 0, sm, h->rim.table.p, slots);
+  hipLaunchKernelGGL(rims_pass_rows_kernel, dim3(wblocks), dim3(kBlock), 0, sm, w, dem, h->lab.masks.p, h->lab.labels.p, g, rpw, nwaves, h->rim.table.p,
+                     ra, rb, h->rim.slot_of.p);
+  HIP_TRY(h->rim.timer.mark(h->timing, 1, sm));
+  hipLaunchKernelGGL(rims_locate_rows_kernel, dim3(wblocks), dim3(kBlock), 0, sm, w, dem, h->lab.masks.p, h->lab.labels.p, g, rpw, nwaves, h->rim.table.p,
+                     ra, rb, h->rim.slot_of.p);
+  hipLaunchKernelGGL(rims_finish_kernel, dim3(sblocks), dim3(kBlock), 0, sm, h->rim.table.p, slots, ncp);
+  HIP_TRY(h->rim.timer.mark(h->timing, 2, sm));
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(h->h_rims, h->d_rims, (size_t)slots * sizeof(wdpm_pond_rim), hipMemcpyDeviceToHost, sm));
-  h->rim_slots = slots;
-  h->rim_foreign = nforeign;
+  HIP_TRY(hipMemcpyAsync(h->rim.h_table.p, h->rim.table.p, (size_t)slots * sizeof(wdpm_pond_rim), hipMemcpyDeviceToHost, sm));
+  h->rim.slots = slots;
+  h->rim.nforeign = nforeign;
   return 0;
 }
 
-/* after group_label(.., group_rims_rank) has returned: the ranks' rim rows into h->rims */
+/* after group_label(.., group_rims_rank) has returned: the ranks' rim rows into h->rim.rows */
 int wdpm_pond_detail::group_rims_merge(wdpm_group_ponds *h, const char *caller, long long n) {
-  h->valid = false;                                                     /* until the rims are merged as well */
+  h->lab.valid = false;                                                 /* until the rims are merged as well */
   std::vector<wdpm_rims_merge::RankRims> ranks((size_t)h->n);
   long long slots = 0, foreign = 0;
   for (int i = 0; i < h->n; i++) {
     wdpm_ponds *p = h->r[i];
-    if (h->timing && p->rim_slots > 0) {
+    if (h->timing && p->rim.slots > 0) {
       HIP_TRY(hipSetDevice(p->x->p.device));
-      for (int k = 0; k < WDPM_RIMS_PHASES; k++) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, p->rim_ev[k], p->rim_ev[k + 1]));
-        p->rim_ms[k] = ms;
-      }
+      HIP_TRY(p->rim.timer.read_all());
     }
-    ranks[(size_t)i] = {p->h_rims, p->slot_label.data(), p->rim_slots, h->view0[i]};
-    slots += p->rim_slots;
-    foreign += p->rim_foreign;
+    ranks[(size_t)i] = {p->rim.h_table.p, p->rim.slot_label.data(), p->rim.slots, h->view0[i]};
+    slots += p->rim.slots;
+    foreign += p->rim.nforeign;
   }
   timespec t0, t1;
   clock_gettime(CLOCK_MONOTONIC, &t0);
-  h->rims.resize((size_t)n);
+  h->rim.rows.resize((size_t)n);
   std::string err;
-  if (wdpm_rims_merge::merge(ranks, n, h->rims.data(), err)) return wdpm_fail("%s: %s", caller, err.c_str());
+  if (wdpm_rims_merge::merge(ranks, n, h->rim.rows.data(), err)) return wdpm_fail("%s: %s", caller, err.c_str());
   clock_gettime(CLOCK_MONOTONIC, &t1);
-  h->rim_stats.ranks = h->n;
-  h->rim_stats.slots = slots;
-  h->rim_stats.foreign = foreign;
-  h->rim_stats.merge_ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
-  h->valid = true;
-  h->rims_valid = true;
+  h->rim.stats.ranks = h->n;
+  h->rim.stats.slots = slots;
+  h->rim.stats.foreign = foreign;
+  h->rim.stats.merge_ms = ms_between(t0, t1);
+  h->lab.valid = true;
+  h->rim.valid = true;
   return 0;
 }
 
 extern "C" int wdpm_group_rims_label(wdpm_group_ponds *h, double min_depth, int64_t *nponds) {
   if (!h) return wdpm_fail("wdpm_group_rims_label: null handle");
-  if (!(min_depth >= 0.0) || std::isinf(min_depth))
-    return wdpm_fail("wdpm_group_rims_label: min_depth must be finite and >= 0 (got %g)", min_depth);
+  if (check_min_depth("wdpm_group_rims_label", min_depth)) return 1;
   int64_t n = 0;
   if (group_label(h, min_depth, &n, group_rims_rank)) return 1;       /* every stream has run dry: one wait per rank ended both tables */
   if (group_rims_merge(h, "wdpm_group_rims_label", n)) return 1;
@@ -517,32 +469,14 @@ extern "C" int wdpm_group_rims_label(wdpm_group_ponds *h, double min_depth, int6
 }
 
 extern "C" int wdpm_group_rims_table(wdpm_group_ponds *h, wdpm_pond_rim *out, int64_t capacity) {
-  if (!h) return wdpm_fail("wdpm_group_rims_table: null handle");
-  if (!h->valid || !h->rims_valid)
-    return wdpm_fail("wdpm_group_rims_table: no rim table: the last label call on this handle was not a wdpm_group_rims_label that succeeded");
-  const long long n = h->stats.ponds;
-  if (capacity < n) return wdpm_fail("wdpm_group_rims_table: capacity %lld is too small for %lld ponds", (long long)capacity, n);
-  if (n == 0) return 0;
-  if (!out) return wdpm_fail("wdpm_group_rims_table: null output");
-  memcpy(out, h->rims.data(), (size_t)n * sizeof(wdpm_pond_rim));
-  return 0;
+  return table_out("wdpm_group_rims_table", h, &wdpm_group_ponds::rim, kNoGroupTable, out, capacity);
 }
 
 extern "C" int wdpm_group_rims_stats(wdpm_group_ponds *h, wdpm_group_rim_stats *out) {
-  if (!h || !out) return wdpm_fail("wdpm_group_rims_stats: null argument");
-  if (!h->valid || !h->rims_valid)
-    return wdpm_fail("wdpm_group_rims_stats: no rim table: the last label call on this handle was not a wdpm_group_rims_label that succeeded");
-  *out = h->rim_stats;
-  return 0;
+  return stats_out("wdpm_group_rims_stats", h, &wdpm_group_ponds::rim, kNoGroupTable, out, true);
 }
 
 extern "C" int wdpm_group_rims_phase_ms(wdpm_group_ponds *h, int32_t rank, double *ms) {
-  if (!h || !ms) return wdpm_fail("wdpm_group_rims_phase_ms: null argument");
-  if (rank < 0 || rank >= h->n) return wdpm_fail("wdpm_group_rims_phase_ms: rank %d of %d", rank, h->n);
-  if (!h->timing) return wdpm_fail("wdpm_group_rims_phase_ms: the handle records no events (set WDPM_PONDS_TIMING=1 before it is made)");
-  if (!h->valid || !h->rims_valid)
-    return wdpm_fail("wdpm_group_rims_phase_ms: no rim table: the last label call on this handle was not a wdpm_group_rims_label that succeeded");
-  for (int i = 0; i < WDPM_RIMS_PHASES; i++) ms[i] = h->r[rank]->rim_ms[i];
-  return 0;
+  return group_phase_ms_out("wdpm_group_rims_phase_ms", h, &wdpm_group_ponds::rim, &wdpm_ponds::rim, kNoGroupTable, rank, ms, true);
 }
 #endif  /* WDPM_PONDS_EMULATION */

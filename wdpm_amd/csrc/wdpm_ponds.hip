@@ -24,9 +24,6 @@
  * wave helpers, the handle) lives in wdpm_ponds_priv.h. */
 #include "wdpm_ponds_priv.h"
 #ifndef WDPM_PONDS_EMULATION
-#include <ctime>
-#include <string>
-
 #include "wdpm_ponds_stitch.h"
 #endif
 
@@ -475,105 +472,47 @@ void guarded_free(wdpm_ponds *h, void *p) {
 
 namespace {
 
-/* frees every buffer and leaves the handle as it was made */
+/* gives every buffer back and leaves the handle as it was made: one line per holder */
 void release(wdpm_ponds *h) {
-  guarded_free(h, h->d_masks); guarded_free(h, h->d_rootmask); guarded_free(h, h->d_parent); guarded_free(h, h->d_labels);
-  guarded_free(h, h->d_cnt); guarded_free(h, h->d_ucnt); guarded_free(h, h->d_bsum); guarded_free(h, h->d_busum);
-  guarded_free(h, h->d_table); guarded_free(h, h->d_seam); guarded_free(h, h->d_map); guarded_free(h, h->d_rims);
-  guarded_free(h, h->d_slot_of); guarded_free(h, h->d_foreign); guarded_free(h, h->d_link); guarded_free(h, h->d_catch);
-  if (h->d_cstat) (void)hipFree(h->d_cstat);
-  if (h->h_cstat) (void)hipHostFree(h->h_cstat);
-  h->d_link = nullptr;
-  h->d_catch = nullptr;
-  h->catch_cap = 0;
-  h->d_cstat = h->h_cstat = nullptr;
-  h->catch_valid = false;
-  guarded_free(h, h->d_ckeys);
-  guarded_free(h, h->d_cexit);
-  if (h->h_ckeys) (void)hipHostFree(h->h_ckeys);
-  if (h->h_cexit) (void)hipHostFree(h->h_cexit);
-  if (h->h_catch) (void)hipHostFree(h->h_catch);
-  h->d_ckeys = h->h_ckeys = nullptr;
-  h->d_cexit = h->h_cexit = nullptr;
-  h->h_catch = nullptr;
-  h->h_catch_cap = 0;
-  guarded_free(h, h->d_outlets);
-  if (h->d_ostat) (void)hipFree(h->d_ostat);
-  if (h->h_ostat) (void)hipHostFree(h->h_ostat);
-  h->d_outlets = nullptr;
-  h->outlets_cap = 0;
-  h->d_ostat = h->h_ostat = nullptr;
-  h->outlets_valid = false;
-  guarded_free(h, h->d_okeys);
-  if (h->h_okeys) (void)hipHostFree(h->h_okeys);
-  if (h->h_outlets) (void)hipHostFree(h->h_outlets);
-  if (h->h_oseam) (void)hipHostFree(h->h_oseam);
-  h->d_okeys = h->h_okeys = nullptr;
-  h->h_outlets = nullptr;
-  h->h_oseam = nullptr;
-  h->okeys_cap = h->h_outlets_cap = 0;
-  guarded_free(h, h->d_curves);
-  if (h->d_vstat) (void)hipFree(h->d_vstat);
-  if (h->h_vstat) (void)hipHostFree(h->h_vstat);
-  h->d_curves = nullptr;
-  h->curves_cap = 0;
-  h->d_vstat = h->h_vstat = nullptr;
-  h->curves_valid = false;
-  if (h->h_beside) (void)hipHostFree(h->h_beside);
-  if (h->h_rims) (void)hipHostFree(h->h_rims);
-  h->d_slot_of = h->d_foreign = nullptr;
-  h->slot_cap = 0;
-  h->h_beside = nullptr;
-  h->h_rims = nullptr;
-  h->h_rims_cap = 0;
-  (void)hipFree(h->d_status);
-  if (h->h_status) (void)hipHostFree(h->h_status);
-  if (h->h_seam) (void)hipHostFree(h->h_seam);
-  if (h->h_map) (void)hipHostFree(h->h_map);
-  if (h->h_table) (void)hipHostFree(h->h_table);
-  h->h_map = nullptr;
-  h->h_table = nullptr;
-  h->stage_cap = 0;
-  h->d_masks = h->d_rootmask = h->d_busum = nullptr;
-  h->d_parent = h->d_labels = h->d_cnt = h->d_bsum = nullptr;
-  h->d_ucnt = nullptr;
-  h->d_status = h->h_status = nullptr;
-  h->d_seam = h->h_seam = h->d_map = nullptr;
-  h->map_cap = 0;
-  h->d_table = nullptr;
-  h->table_cap = 0;
-  h->d_rims = nullptr;
-  h->rims_cap = 0;
-  h->rims_valid = false;
-  h->allocated = false;
+  LabelUnit &l = h->lab;
+  reset(h, l.masks); reset(h, l.rootmask); reset(h, l.busum); reset(h, l.parent); reset(h, l.labels); reset(h, l.cnt); reset(h, l.bsum);
+  reset(h, l.ucnt); reset(h, l.status); reset(h, l.seam); reset(h, l.h_seam); reset(h, l.map); reset(h, l.h_map); reset(h, l.h_table);
+  reset(h, l.table);
+  reset(h, h->rim.table); reset(h, h->rim.slot_of); reset(h, h->rim.foreign); reset(h, h->rim.h_beside); reset(h, h->rim.h_table);
+  reset(h, h->cat.link); reset(h, h->cat.table); reset(h, h->cat.status); reset(h, h->cat.keys); reset(h, h->cat.h_keys);
+  reset(h, h->cat.exits); reset(h, h->cat.h_exits); reset(h, h->cat.h_table);
+  reset(h, h->out.table); reset(h, h->out.status); reset(h, h->out.keys); reset(h, h->out.h_keys); reset(h, h->out.h_table);
+  reset(h, h->out.h_seam);
+  reset(h, h->cur.table); reset(h, h->cur.status);
+  l.allocated = l.valid = h->rim.valid = h->cat.valid = h->out.valid = h->cur.valid = false;
 }
 
 int allocate(wdpm_ponds *h) {
-  if (h->allocated) return 0;
-  const size_t cells = (size_t)h->g.rows * h->g.ncp, nseg = (size_t)h->g.nseg;
-  h->nb = (int)((nseg + kScanTile - 1) / kScanTile);
-  hipError_t e = guarded_malloc(h, (void **)&h->d_masks, nseg * sizeof(unsigned long long));
-  if (e == hipSuccess) e = guarded_malloc(h, (void **)&h->d_rootmask, nseg * sizeof(unsigned long long));
-  if (e == hipSuccess) e = guarded_malloc(h, (void **)&h->d_parent, cells * sizeof(int));
-  if (e == hipSuccess) e = guarded_malloc(h, (void **)&h->d_labels, cells * sizeof(int));
-  if (e == hipSuccess) e = guarded_malloc(h, (void **)&h->d_cnt, nseg * sizeof(int));
-  if (e == hipSuccess) e = guarded_malloc(h, (void **)&h->d_ucnt, nseg * sizeof(unsigned));
-  if (e == hipSuccess) e = guarded_malloc(h, (void **)&h->d_bsum, (size_t)h->nb * sizeof(int));
-  if (e == hipSuccess) e = guarded_malloc(h, (void **)&h->d_busum, (size_t)h->nb * 2 * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMalloc(&h->d_status, sizeof(Status));
-  if (e == hipSuccess) e = hipHostMalloc(&h->h_status, sizeof(Status));
+  LabelUnit &l = h->lab;
+  if (l.allocated) return 0;
+  const long long cells = (long long)h->g.rows * h->g.ncp, nseg = h->g.nseg;
+  l.nb = (int)((nseg + kScanTile - 1) / kScanTile);
+  const char *what;
+  hipError_t e = grow(h, l.masks, nseg);
+  if (e == hipSuccess) e = grow(h, l.rootmask, nseg);
+  if (e == hipSuccess) e = grow(h, l.parent, cells);
+  if (e == hipSuccess) e = grow(h, l.labels, cells);
+  if (e == hipSuccess) e = grow(h, l.cnt, nseg);
+  if (e == hipSuccess) e = grow(h, l.ucnt, nseg);
+  if (e == hipSuccess) e = grow(h, l.bsum, l.nb);
+  if (e == hipSuccess) e = grow(h, l.busum, 2LL * l.nb);
+  if (e == hipSuccess) e = ensure(l.status, &what);
   if (h->seams) {
-    if (e == hipSuccess) e = guarded_malloc(h, (void **)&h->d_seam, (size_t)2 * h->g.ncp * sizeof(int));
-    if (e == hipSuccess) e = hipHostMalloc(&h->h_seam, (size_t)2 * h->g.ncp * sizeof(int));
+    if (e == hipSuccess) e = grow(h, l.seam, 2LL * h->g.ncp);
+    if (e == hipSuccess) e = grow(h, l.h_seam, 2LL * h->g.ncp);
   }
   if (e != hipSuccess) {
     release(h);                     /* what was taken so far: the next call starts from nothing again */
     return wdpm_fail("wdpm_ponds_label: device allocation failed: %s", hipGetErrorString(e));
   }
-  h->allocated = true;
+  l.allocated = true;
   return 0;
 }
-
 
 /* a handle on rows [row_off, row_off + rows) of ctx; reads the environment as include/wdpm_ponds.h says */
 wdpm_ponds *make_handle(wdpm_ctx *ctx, int row_off, int rows, bool seams) {
@@ -588,90 +527,16 @@ wdpm_ponds *make_handle(wdpm_ctx *ctx, int row_off, int rows, bool seams) {
   const char *e = getenv("WDPM_GUARD_KB");
   const long kb = e ? atol(e) : 0;
   h->guard = kb > 0 ? (size_t)kb * 1024 : 0;
-  h->allocated = false;
-  h->d_masks = h->d_rootmask = h->d_busum = nullptr;
-  h->d_parent = h->d_labels = h->d_cnt = h->d_bsum = nullptr;
-  h->d_ucnt = nullptr;
-  h->d_status = h->h_status = nullptr;
-  h->d_seam = h->h_seam = h->d_map = nullptr;
-  h->map_cap = 0;
-  h->h_map = nullptr;
-  h->h_table = nullptr;
-  h->stage_cap = 0;
-  h->d_table = nullptr;
-  h->table_cap = 0;
-  h->d_rims = nullptr;
-  h->rims_cap = 0;
-  h->rims_valid = false;
-  h->d_slot_of = h->d_foreign = nullptr;
-  h->slot_cap = 0;
-  h->h_beside = nullptr;
-  h->h_rims = nullptr;
-  h->h_rims_cap = 0;
-  h->rim_slots = h->rim_foreign = 0;
-  h->d_link = nullptr;
-  h->d_catch = nullptr;
-  h->catch_cap = 0;
-  h->d_cstat = h->h_cstat = nullptr;
-  h->catch_valid = false;
-  memset(&h->catch_stats, 0, sizeof h->catch_stats);
-  h->d_outlets = nullptr;
-  h->outlets_cap = 0;
-  h->d_ostat = h->h_ostat = nullptr;
-  h->outlets_valid = false;
-  memset(&h->outlet_stats, 0, sizeof h->outlet_stats);
-  h->d_okeys = h->h_okeys = nullptr;
-  h->h_outlets = nullptr;
-  h->h_oseam = nullptr;
-  h->okeys_cap = h->h_outlets_cap = 0;
-  h->d_curves = nullptr;
-  h->curves_cap = 0;
-  h->d_vstat = h->h_vstat = nullptr;
-  h->curves_valid = false;
-  memset(&h->curve_stats, 0, sizeof h->curve_stats);
-  h->nb = 0;
   { const char *re = getenv("WDPM_PONDS_ROWS_PER_WAVE"); h->forced_rpw = re ? atoi(re) : 0; }
-  h->rpw = 1;
-  memset(&h->last, 0, sizeof h->last);
-  h->valid = false;
-  memset(&h->stats, 0, sizeof h->stats);
   const char *te = getenv("WDPM_PONDS_TIMING");
   h->timing = te && atoi(te) != 0;
-  for (int i = 0; i < WDPM_PONDS_PHASES + 2; i++) h->ev[i] = nullptr;
-  for (int i = 0; i < WDPM_PONDS_PHASES; i++) h->phase_ms[i] = 0.0;
-  if (h->timing)
-    for (int i = 0; i < WDPM_PONDS_PHASES + 2; i++)
-      if (hipEventCreate(&h->ev[i]) != hipSuccess) { h->timing = false; break; }
-  for (int i = 0; i < WDPM_RIMS_PHASES + 1; i++) h->rim_ev[i] = nullptr;
-  for (int i = 0; i < WDPM_RIMS_PHASES; i++) h->rim_ms[i] = 0.0;
-  if (h->timing)
-    for (int i = 0; i < WDPM_RIMS_PHASES + 1; i++)
-      if (hipEventCreate(&h->rim_ev[i]) != hipSuccess) { h->timing = false; break; }
-  h->d_ckeys = h->h_ckeys = nullptr;
-  h->d_cexit = h->h_cexit = nullptr;
-  h->h_catch = nullptr;
-  h->h_catch_cap = 0;
-  h->catch_slots = h->catch_remote = 0;
-  h->catch_rounds = 0;
-  for (int i = 0; i < kCatchEvents; i++) h->catch_ev[i] = nullptr;
-  for (int i = 0; i < WDPM_CATCH_PHASES; i++) h->catch_ms[i] = 0.0;
-  if (h->timing)
-    for (int i = 0; i < kCatchEvents; i++)
-      if (hipEventCreate(&h->catch_ev[i]) != hipSuccess) { h->timing = false; break; }
-  for (int i = 0; i < WDPM_OUTLETS_PHASES + 1; i++) h->outlet_ev[i] = nullptr;
-  for (int i = 0; i < WDPM_OUTLETS_PHASES; i++) h->outlet_ms[i] = 0.0;
-  if (h->timing)
-    for (int i = 0; i < WDPM_OUTLETS_PHASES + 1; i++)
-      if (hipEventCreate(&h->outlet_ev[i]) != hipSuccess) { h->timing = false; break; }
-  for (int i = 0; i < WDPM_CURVES_PHASES + 1; i++) h->curve_ev[i] = nullptr;
-  for (int i = 0; i < WDPM_CURVES_PHASES; i++) h->curve_ms[i] = 0.0;
-  if (h->timing)
-    for (int i = 0; i < WDPM_CURVES_PHASES + 1; i++)
-      if (hipEventCreate(&h->curve_ev[i]) != hipSuccess) { h->timing = false; break; }
+  h->lab.timer.create(h->timing);
+  h->rim.timer.create(h->timing);
+  h->cat.timer.create(h->timing);
+  h->out.timer.create(h->timing);
+  h->cur.timer.create(h->timing);
   return h;
 }
-
-#define PONDS_MARK(i) do { if (h->timing) HIP_TRY(hipEventRecord(h->ev[i], sm)); } while (0)
 
 /* ---- a label call in four steps: the two that queue work never wait for it, so a group queues every rank before it waits for
  * the first.  wdpm_ponds_label runs them back to back. ---- */
@@ -679,11 +544,11 @@ wdpm_ponds *make_handle(wdpm_ctx *ctx, int row_off, int rows, bool seams) {
 /* 1: mask, merge, flatten, scan (and the seam rows of a row block), status words on their way to the host */
 int label_queue(wdpm_ponds *h, double min_depth) {
   wdpm_ctx *x = h->x;
-  h->valid = false;
-  h->rims_valid = false;            /* a rim table belongs to the label call that made it (wdpm_pond_rims.hip) */
-  h->catch_valid = false;           /* and so does a catchment table (wdpm_pond_catchments.hip) */
-  h->outlets_valid = false;         /* and an outlet table (wdpm_pond_outlets.hip) */
-  h->curves_valid = false;          /* and a curve table (wdpm_pond_curves.hip) */
+  h->lab.valid = false;
+  h->rim.valid = false;             /* a rim table belongs to the label call that made it (wdpm_pond_rims.hip) */
+  h->cat.valid = false;             /* and so does a catchment table (wdpm_pond_catchments.hip) */
+  h->out.valid = false;             /* and an outlet table (wdpm_pond_outlets.hip) */
+  h->cur.valid = false;             /* and a curve table (wdpm_pond_curves.hip) */
   /* the raster as a reader sees it: side stream joined, owed drain() and threshold flush applied (what wdpm_count_stats asks for) */
   if (wdpm_synchronize(x)) return 1;
   if (wdpm_apply_owed_flush(x)) return 1;
@@ -694,24 +559,24 @@ int label_queue(wdpm_ponds *h, double min_depth) {
   const double *w = x->d_w[x->cur] + off;
   const unsigned seg_blocks = blocks_for(g.nseg, kWaves);
 
-  HIP_TRY(hipMemsetAsync(h->d_status, 0, sizeof(Status), sm));
-  PONDS_MARK(0);
-  hipLaunchKernelGGL(ponds_mask_kernel, dim3(seg_blocks), dim3(kBlock), 0, sm, w, x->d_dem + off, g, min_depth, h->d_masks, h->d_parent, h->d_status);
-  PONDS_MARK(1);
-  hipLaunchKernelGGL(ponds_merge_kernel, dim3(seg_blocks), dim3(kBlock), 0, sm, h->d_masks, h->d_parent, g, h->d_ucnt);
-  PONDS_MARK(2);
-  hipLaunchKernelGGL(ponds_flatten_kernel, dim3(seg_blocks), dim3(kBlock), 0, sm, h->d_masks, h->d_parent, g, h->d_cnt, h->d_rootmask);
-  PONDS_MARK(3);
-  hipLaunchKernelGGL(ponds_scan_reduce_kernel, dim3(h->nb), dim3(kBlock), 0, sm, h->d_cnt, h->d_ucnt, g.nseg, h->d_bsum, h->d_busum);
-  hipLaunchKernelGGL(ponds_scan_sums_kernel, dim3(1), dim3(kBlock), 0, sm, h->d_bsum, h->d_busum, h->nb, h->d_status);
-  hipLaunchKernelGGL(ponds_scan_down_kernel, dim3(h->nb), dim3(kBlock), 0, sm, h->d_cnt, g.nseg, h->d_bsum);
+  HIP_TRY(hipMemsetAsync(h->lab.status.d, 0, sizeof(Status), sm));
+  HIP_TRY(h->lab.timer.mark(h->timing, 0, sm));
+  hipLaunchKernelGGL(ponds_mask_kernel, dim3(seg_blocks), dim3(kBlock), 0, sm, w, x->d_dem + off, g, min_depth, h->lab.masks.p, h->lab.parent.p, h->lab.status.d);
+  HIP_TRY(h->lab.timer.mark(h->timing, 1, sm));
+  hipLaunchKernelGGL(ponds_merge_kernel, dim3(seg_blocks), dim3(kBlock), 0, sm, h->lab.masks.p, h->lab.parent.p, g, h->lab.ucnt.p);
+  HIP_TRY(h->lab.timer.mark(h->timing, 2, sm));
+  hipLaunchKernelGGL(ponds_flatten_kernel, dim3(seg_blocks), dim3(kBlock), 0, sm, h->lab.masks.p, h->lab.parent.p, g, h->lab.cnt.p, h->lab.rootmask.p);
+  HIP_TRY(h->lab.timer.mark(h->timing, 3, sm));
+  hipLaunchKernelGGL(ponds_scan_reduce_kernel, dim3(h->lab.nb), dim3(kBlock), 0, sm, h->lab.cnt.p, h->lab.ucnt.p, g.nseg, h->lab.bsum.p, h->lab.busum.p);
+  hipLaunchKernelGGL(ponds_scan_sums_kernel, dim3(1), dim3(kBlock), 0, sm, h->lab.bsum.p, h->lab.busum.p, h->lab.nb, h->lab.status.d);
+  hipLaunchKernelGGL(ponds_scan_down_kernel, dim3(h->lab.nb), dim3(kBlock), 0, sm, h->lab.cnt.p, g.nseg, h->lab.bsum.p);
   if (h->seams)
-    hipLaunchKernelGGL(ponds_seam_kernel, dim3(blocks_for(2 * g.nsc, kWaves)), dim3(kBlock), 0, sm, h->d_masks, h->d_parent, h->d_cnt,
-                       h->d_rootmask, g, h->d_seam);
-  PONDS_MARK(4);
+    hipLaunchKernelGGL(ponds_seam_kernel, dim3(blocks_for(2 * g.nsc, kWaves)), dim3(kBlock), 0, sm, h->lab.masks.p, h->lab.parent.p, h->lab.cnt.p,
+                       h->lab.rootmask.p, g, h->lab.seam.p);
+  HIP_TRY(h->lab.timer.mark(h->timing, 4, sm));
   HIP_TRY(hipGetLastError());
-  if (h->seams) HIP_TRY(hipMemcpyAsync(h->h_seam, h->d_seam, (size_t)2 * g.ncp * sizeof(int), hipMemcpyDeviceToHost, sm));
-  HIP_TRY(hipMemcpyAsync(h->h_status, h->d_status, sizeof(Status), hipMemcpyDeviceToHost, sm));
+  if (h->seams) HIP_TRY(hipMemcpyAsync(h->lab.h_seam.p, h->lab.seam.p, (size_t)2 * g.ncp * sizeof(int), hipMemcpyDeviceToHost, sm));
+  HIP_TRY(hipMemcpyAsync(h->lab.status.h, h->lab.status.d, sizeof(Status), hipMemcpyDeviceToHost, sm));
   return 0;
 }
 
@@ -719,73 +584,55 @@ int label_queue(wdpm_ponds *h, double min_depth) {
 int label_status(wdpm_ponds *h, long long *n) {
   HIP_TRY(hipSetDevice(h->x->p.device));
   if (wdpm_stream_sync(h->x, h->x->stream)) return 1;
-  h->last = *h->h_status;
-  if (h->last.deep)
+  h->lab.last = *h->lab.status.h;
+  if (h->lab.last.deep)
     return wdpm_fail("wdpm_ponds_label: a pond cell holds 512 m of water or more: volume_q (a 64-bit sum of depths in units of "
                      "2^-24 m) is only safe below that depth");
-  *n = h->last.ponds;
+  *n = h->lab.last.ponds;
   return 0;
 }
 
 /* 3: the table kernels.  With `mapped` (row blocks; `map` holds n ints, copied here) the label raster takes map[label - 1] and the
- * finished table follows to h->h_table.  Map and table travel through pinned memory, so every transfer is queued like the
+ * finished table follows to h->lab.h_table.p.  Map and table travel through pinned memory, so every transfer is queued like the
  * kernels and the call returns without waiting for any of them; the pinned buffers grow only when N outgrows them. */
 int table_queue(wdpm_ponds *h, bool mapped, const int *map) {
   wdpm_ctx *x = h->x;
   const Geom g = h->g;
   const hipStream_t sm = x->stream;
-  const long long n = h->last.ponds;
+  const long long n = h->lab.last.ponds;
   const double *w = x->d_w[x->cur] + (size_t)h->row_off * g.ncp;
   HIP_TRY(hipSetDevice(x->p.device));
-  if (n > h->table_cap) {                       /* sized from N, now that N is known */
-    guarded_free(h, h->d_table);
-    h->d_table = nullptr;
-    h->table_cap = 0;
-    const hipError_t e = guarded_malloc(h, (void **)&h->d_table, (size_t)n * sizeof(PondRow));
-    if (e != hipSuccess) return wdpm_fail("wdpm_ponds_label: no device memory for a table of %lld ponds: %s", n, hipGetErrorString(e));
-    h->table_cap = n;
-  }
-  if (mapped && n > h->map_cap) {
-    guarded_free(h, h->d_map);
-    h->d_map = nullptr;
-    h->map_cap = 0;
-    const hipError_t e = guarded_malloc(h, (void **)&h->d_map, (size_t)n * sizeof(int));
+  hipError_t e = grow(h, h->lab.table, n);      /* sized from N, now that N is known */
+  if (e != hipSuccess) return wdpm_fail("wdpm_ponds_label: no device memory for a table of %lld ponds: %s", n, hipGetErrorString(e));
+  if (mapped) {
+    e = grow(h, h->lab.map, n);
     if (e != hipSuccess) return wdpm_fail("wdpm_group_ponds_label: no device memory for the numbers of %lld ponds: %s", n, hipGetErrorString(e));
-    h->map_cap = n;
-  }
-  if (mapped && n > h->stage_cap) {
-    if (h->h_map) (void)hipHostFree(h->h_map);
-    if (h->h_table) (void)hipHostFree(h->h_table);
-    h->h_map = nullptr;
-    h->h_table = nullptr;
-    h->stage_cap = 0;
-    hipError_t e = hipHostMalloc(&h->h_map, (size_t)n * sizeof(int));
-    if (e == hipSuccess) e = hipHostMalloc(&h->h_table, (size_t)n * sizeof(wdpm_pond));
+    if (n > h->lab.h_map.cap) { reset(h, h->lab.h_map); reset(h, h->lab.h_table); }   /* the two grow together: both go before either comes */
+    e = grow(h, h->lab.h_map, n);
+    if (e == hipSuccess) e = grow(h, h->lab.h_table, n);
     if (e != hipSuccess) return wdpm_fail("wdpm_group_ponds_label: no pinned host memory for %lld ponds: %s", n, hipGetErrorString(e));
-    h->stage_cap = n;
   }
   if (mapped && n > 0) {
-    memcpy(h->h_map, map, (size_t)n * sizeof(int));
-    HIP_TRY(hipMemcpyAsync(h->d_map, h->h_map, (size_t)n * sizeof(int), hipMemcpyHostToDevice, sm));
+    memcpy(h->lab.h_map.p, map, (size_t)n * sizeof(int));
+    HIP_TRY(hipMemcpyAsync(h->lab.map.p, h->lab.h_map.p, (size_t)n * sizeof(int), hipMemcpyHostToDevice, sm));
   }
-  const int rpw = h->rpw = ponds_rows_per_wave(g.nseg, g.rows, h->forced_rpw);
-  const int nwaves = ((g.rows + rpw - 1) / rpw) * g.nsc;
-  PONDS_MARK(5);
-  if (n > 0) hipLaunchKernelGGL(ponds_table_init_kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, sm, h->d_table, n);
+  const Waves wv = waves_for(h, g.rows);
+  const int rpw = h->lab.rpw = wv.rpw, nwaves = wv.nwaves;
+  HIP_TRY(h->lab.timer.mark(h->timing, 5, sm));
+  if (n > 0) hipLaunchKernelGGL(ponds_table_init_kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, sm, h->lab.table.p, n);
   if (mapped)
-    hipLaunchKernelGGL(ponds_table_mapped_kernel, dim3(blocks_for(nwaves, kWaves)), dim3(kBlock), 0, sm, w, h->d_masks, h->d_parent,
-                       h->d_cnt, h->d_rootmask, g, rpw, nwaves, h->d_labels, h->d_table, h->d_map);
+    hipLaunchKernelGGL(ponds_table_mapped_kernel, dim3(blocks_for(nwaves, kWaves)), dim3(kBlock), 0, sm, w, h->lab.masks.p, h->lab.parent.p,
+                       h->lab.cnt.p, h->lab.rootmask.p, g, rpw, nwaves, h->lab.labels.p, h->lab.table.p, h->lab.map.p);
   else
-    hipLaunchKernelGGL(ponds_table_kernel, dim3(blocks_for(nwaves, kWaves)), dim3(kBlock), 0, sm, w, h->d_masks, h->d_parent, h->d_cnt,
-                       h->d_rootmask, g, rpw, nwaves, h->d_labels, h->d_table);
-  PONDS_MARK(6);
-  if (n > 0) hipLaunchKernelGGL(ponds_table_finish_kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, sm, h->d_table, n);
-  PONDS_MARK(7);
+    hipLaunchKernelGGL(ponds_table_kernel, dim3(blocks_for(nwaves, kWaves)), dim3(kBlock), 0, sm, w, h->lab.masks.p, h->lab.parent.p, h->lab.cnt.p,
+                       h->lab.rootmask.p, g, rpw, nwaves, h->lab.labels.p, h->lab.table.p);
+  HIP_TRY(h->lab.timer.mark(h->timing, 6, sm));
+  if (n > 0) hipLaunchKernelGGL(ponds_table_finish_kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, sm, h->lab.table.p, n);
+  HIP_TRY(h->lab.timer.mark(h->timing, 7, sm));
   HIP_TRY(hipGetLastError());
-  if (mapped && n > 0) HIP_TRY(hipMemcpyAsync(h->h_table, h->d_table, (size_t)n * sizeof(wdpm_pond), hipMemcpyDeviceToHost, sm));
+  if (mapped && n > 0) HIP_TRY(hipMemcpyAsync(h->lab.h_table.p, h->lab.table.p, (size_t)n * sizeof(wdpm_pond), hipMemcpyDeviceToHost, sm));
   return 0;
 }
-#undef PONDS_MARK
 
 /* 4: wait for 3; the handle has an inventory */
 int table_wait(wdpm_ponds *h) {
@@ -794,19 +641,15 @@ int table_wait(wdpm_ponds *h) {
   if (h->timing) {
     /* mask, merge, flatten, scan, (host: status, table allocation), table init + table, finish */
     static const int from[WDPM_PONDS_PHASES] = {0, 1, 2, 3, 5, 6}, to[WDPM_PONDS_PHASES] = {1, 2, 3, 4, 6, 7};
-    for (int i = 0; i < WDPM_PONDS_PHASES; i++) {
-      float ms = 0.f;
-      HIP_TRY(hipEventElapsedTime(&ms, h->ev[from[i]], h->ev[to[i]]));
-      h->phase_ms[i] = ms;
-    }
+    for (int i = 0; i < WDPM_PONDS_PHASES; i++) HIP_TRY(h->lab.timer.read(from[i], to[i], &h->lab.timer.ms[i]));
   }
-  h->stats.segments = h->g.nseg;
-  h->stats.unions = (int64_t)h->last.unions;
-  h->stats.seam_unions = (int64_t)h->last.seam_unions;
-  h->stats.passes = 0;
-  h->stats.rows_per_wave = h->rpw;
-  h->stats.ponds = h->last.ponds;
-  h->valid = true;
+  h->lab.stats.segments = h->g.nseg;
+  h->lab.stats.unions = (int64_t)h->lab.last.unions;
+  h->lab.stats.seam_unions = (int64_t)h->lab.last.seam_unions;
+  h->lab.stats.passes = 0;
+  h->lab.stats.rows_per_wave = h->lab.rpw;
+  h->lab.stats.ponds = h->lab.last.ponds;
+  h->lab.valid = true;
   return 0;
 }
 
@@ -826,18 +669,16 @@ void destroy_handle(wdpm_ponds *h) {
   if (!h) return;
   (void)wdpm_synchronize(h->x);
   release(h);
-  for (int i = 0; i < WDPM_PONDS_PHASES + 2; i++)
-    if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-  for (int i = 0; i < WDPM_RIMS_PHASES + 1; i++)
-    if (h->rim_ev[i]) (void)hipEventDestroy(h->rim_ev[i]);
-  for (int i = 0; i < kCatchEvents; i++)
-    if (h->catch_ev[i]) (void)hipEventDestroy(h->catch_ev[i]);
-  for (int i = 0; i < WDPM_OUTLETS_PHASES + 1; i++)
-    if (h->outlet_ev[i]) (void)hipEventDestroy(h->outlet_ev[i]);
-  for (int i = 0; i < WDPM_CURVES_PHASES + 1; i++)
-    if (h->curve_ev[i]) (void)hipEventDestroy(h->curve_ev[i]);
+  h->lab.timer.destroy();
+  h->rim.timer.destroy();
+  h->cat.timer.destroy();
+  h->out.timer.destroy();
+  h->cur.timer.destroy();
   delete h;
 }
+
+const char kNoTable[] = "no inventory: wdpm_ponds_label has not succeeded on this handle";
+const char kNoGroupTable[] = "no inventory: wdpm_group_ponds_label has not succeeded on this handle";
 
 }  // namespace
 
@@ -856,7 +697,7 @@ extern "C" void wdpm_ponds_destroy(wdpm_ponds *h) { destroy_handle(h); }
 
 extern "C" int wdpm_ponds_label(wdpm_ponds *h, double min_depth, int64_t *nponds) {
   if (!h) return wdpm_fail("wdpm_ponds_label: null handle");
-  if (!(min_depth >= 0.0) || std::isinf(min_depth)) return wdpm_fail("wdpm_ponds_label: min_depth must be finite and >= 0 (got %g)", min_depth);
+  if (check_min_depth("wdpm_ponds_label", min_depth)) return 1;
   long long n = 0;
   if (label_queue(h, min_depth) || label_status(h, &n) || table_queue(h, false, nullptr) || table_wait(h)) return 1;
   if (nponds) *nponds = n;
@@ -864,23 +705,13 @@ extern "C" int wdpm_ponds_label(wdpm_ponds *h, double min_depth, int64_t *nponds
 }
 
 extern "C" int wdpm_ponds_table(wdpm_ponds *h, wdpm_pond *out, int64_t capacity) {
-  if (!h) return wdpm_fail("wdpm_ponds_table: null handle");
-  if (!h->valid) return wdpm_fail("wdpm_ponds_table: no inventory: wdpm_ponds_label has not succeeded on this handle");
-  const long long n = h->stats.ponds;
-  if (capacity < n) return wdpm_fail("wdpm_ponds_table: capacity %lld is too small for %lld ponds", (long long)capacity, n);
-  if (n == 0) return 0;
-  if (!out) return wdpm_fail("wdpm_ponds_table: null output");
-  if (wdpm_synchronize(h->x)) return 1;
-  HIP_TRY(hipMemcpyAsync(out, h->d_table, (size_t)n * sizeof(wdpm_pond), hipMemcpyDeviceToHost, h->x->stream));
-  return wdpm_stream_sync(h->x, h->x->stream);
+  return table_out("wdpm_ponds_table", h, &wdpm_ponds::lab, kNoTable, out, capacity);
 }
 
 extern "C" int wdpm_ponds_labels(wdpm_ponds *h, int32_t *padded) {
   if (!h || !padded) return wdpm_fail("wdpm_ponds_labels: null argument");
-  if (!h->valid) return wdpm_fail("wdpm_ponds_labels: no inventory: wdpm_ponds_label has not succeeded on this handle");
-  if (wdpm_synchronize(h->x)) return 1;
-  HIP_TRY(hipMemcpyAsync(padded, h->d_labels, (size_t)h->g.rows * h->g.ncp * sizeof(int32_t), hipMemcpyDeviceToHost, h->x->stream));
-  return wdpm_stream_sync(h->x, h->x->stream);
+  if (!h->lab.valid) return wdpm_fail("wdpm_ponds_labels: %s", kNoTable);
+  return download(h, padded, h->lab.labels.p, (size_t)h->g.rows * h->g.ncp * sizeof(int32_t));
 }
 
 extern "C" int wdpm_ponds_guard_bad(wdpm_ponds *h, int64_t *bytes) {
@@ -890,18 +721,11 @@ extern "C" int wdpm_ponds_guard_bad(wdpm_ponds *h, int64_t *bytes) {
 }
 
 extern "C" int wdpm_ponds_stats(wdpm_ponds *h, wdpm_pond_stats *out) {
-  if (!h || !out) return wdpm_fail("wdpm_ponds_stats: null argument");
-  if (!h->valid) return wdpm_fail("wdpm_ponds_stats: no inventory: wdpm_ponds_label has not succeeded on this handle");
-  *out = h->stats;
-  return 0;
+  return stats_out("wdpm_ponds_stats", h, &wdpm_ponds::lab, kNoTable, out, true);
 }
 
 extern "C" int wdpm_ponds_phase_ms(wdpm_ponds *h, double *ms) {
-  if (!h || !ms) return wdpm_fail("wdpm_ponds_phase_ms: null argument");
-  if (!h->timing) return wdpm_fail("wdpm_ponds_phase_ms: the handle records no events (set WDPM_PONDS_TIMING=1 before it is made)");
-  if (!h->valid) return wdpm_fail("wdpm_ponds_phase_ms: no inventory: wdpm_ponds_label has not succeeded on this handle");
-  for (int i = 0; i < WDPM_PONDS_PHASES; i++) ms[i] = h->phase_ms[i];
-  return 0;
+  return phase_ms_out("wdpm_ponds_phase_ms", h, &wdpm_ponds::lab, kNoTable, ms, true);
 }
 
 /* ---- row blocks (include/wdpm_group_ponds.h) --------------------------------------------------------------------------------- */
@@ -913,15 +737,6 @@ extern "C" int wdpm_group_ponds_create(wdpm_group_ponds **out, wdpm_group *grp) 
   wdpm_group_ponds *h = new wdpm_group_ponds();
   h->grp = grp;
   h->n = n;
-  h->valid = false;
-  h->rims_valid = false;
-  h->catch_valid = false;
-  h->outlets_valid = false;
-  h->timing = true;
-  memset(&h->outlet_stats, 0, sizeof h->outlet_stats);
-  memset(&h->stats, 0, sizeof h->stats);
-  memset(&h->rim_stats, 0, sizeof h->rim_stats);
-  memset(&h->catch_stats, 0, sizeof h->catch_stats);
   for (int i = 0; i < n; i++) {
     wdpm_rank *rk = wdpm_group_rank(grp, i);
     wdpm_ctx *x = rk ? wdpm_rank_ctx(rk) : nullptr;
@@ -964,33 +779,29 @@ extern "C" void wdpm_group_ponds_destroy(wdpm_group_ponds *h) {
   delete h;
 }
 
-namespace {
-/* after a failure with work queued: let every rank's stream run dry, so that nothing still reads what the caller may free */
-int drain_and_fail(wdpm_group_ponds *h) {
+extern "C" int wdpm_group_ponds_label(wdpm_group_ponds *h, double min_depth, int64_t *nponds) {
+  if (!h) return wdpm_fail("wdpm_group_ponds_label: null handle");
+  if (check_min_depth("wdpm_group_ponds_label", min_depth)) return 1;
+  return group_label(h, min_depth, nponds, nullptr);
+}
+
+int wdpm_pond_detail::group_drain(wdpm_group_ponds *h) {
   std::string msg = wdpm_last_error();
   for (wdpm_ponds *p : h->r)
     if (hipSetDevice(p->x->p.device) == hipSuccess) (void)hipStreamSynchronize(p->x->stream);
   return wdpm_fail("%s", msg.c_str());
 }
-}  // namespace
-
-extern "C" int wdpm_group_ponds_label(wdpm_group_ponds *h, double min_depth, int64_t *nponds) {
-  if (!h) return wdpm_fail("wdpm_group_ponds_label: null handle");
-  if (!(min_depth >= 0.0) || std::isinf(min_depth))
-    return wdpm_fail("wdpm_group_ponds_label: min_depth must be finite and >= 0 (got %g)", min_depth);
-  return group_label(h, min_depth, nponds, nullptr);
-}
 
 int wdpm_pond_detail::group_label(wdpm_group_ponds *h, double min_depth, int64_t *nponds, group_rims_queue rims,
                                   group_seams_queue seam_rows) {
-  h->valid = false;
-  h->rims_valid = false;            /* a rim table belongs to the label call that made it */
-  h->catch_valid = false;           /* and so does a catchment table */
-  h->outlets_valid = false;         /* and an outlet table */
+  h->lab.valid = false;
+  h->rim.valid = false;             /* a rim table belongs to the label call that made it */
+  h->cat.valid = false;             /* and so does a catchment table */
+  h->out.valid = false;             /* and an outlet table */
   const int n = h->n;
   /* every rank up to its scan, on its own stream and device, before the first wait */
   for (int i = 0; i < n; i++)
-    if (label_queue(h->r[i], min_depth) || (seam_rows && seam_rows(h, i))) return drain_and_fail(h);
+    if (label_queue(h->r[i], min_depth) || (seam_rows && seam_rows(h, i))) return group_drain(h);
   std::vector<wdpm_stitch::RankSeams> seams((size_t)n);
   bool bad = false;
   std::string first_msg;
@@ -1002,8 +813,8 @@ int wdpm_pond_detail::group_label(wdpm_group_ponds *h, double min_depth, int64_t
       continue;
     }
     seams[i].n = ni;
-    seams[i].top = h->r[i]->h_seam;
-    seams[i].bottom = h->r[i]->h_seam + h->ncp;
+    seams[i].top = h->r[i]->lab.h_seam.p;
+    seams[i].bottom = h->r[i]->lab.h_seam.p + h->ncp;
   }
   if (bad) return wdpm_fail("%s", first_msg.c_str());
 
@@ -1017,8 +828,8 @@ int wdpm_pond_detail::group_label(wdpm_group_ponds *h, double min_depth, int64_t
   /* every rank's table kernel, its labels written once as whole-raster numbers, and its own table on the way to the host:
    * all of it queued (pinned staging on both ways) before the first wait */
   for (int i = 0; i < n; i++) {
-    if (table_queue(h->r[i], true, res.map[i].data())) return drain_and_fail(h);
-    if (rims && rims(h, i, res.map, res.ponds)) return drain_and_fail(h);
+    if (table_queue(h->r[i], true, res.map[i].data())) return group_drain(h);
+    if (rims && rims(h, i, res.map, res.ponds)) return group_drain(h);
   }
   for (int i = 0; i < n; i++)
     if (table_wait(h->r[i])) {
@@ -1027,44 +838,36 @@ int wdpm_pond_detail::group_label(wdpm_group_ponds *h, double min_depth, int64_t
     }
   if (bad) return wdpm_fail("%s", first_msg.c_str());
 
-  h->table.assign((size_t)res.ponds, wdpm_pond());
+  h->lab.rows.assign((size_t)res.ponds, wdpm_pond());
   for (int i = 0; i < n; i++)
-    if (wdpm_stitch::fold_table(h->r[i]->h_table, res.map[i], h->view0[i], h->table.data(), err))
+    if (wdpm_stitch::fold_table(h->r[i]->lab.h_table.p, res.map[i], h->view0[i], h->lab.rows.data(), err))
       return wdpm_fail("wdpm_group_ponds_label: %s", err.c_str());
 
-  h->stats.ranks = n;
-  h->stats.ponds = res.ponds;
-  h->stats.local_ponds = res.local_ponds;
-  h->stats.stitch_unions = res.unions;
-  h->stats.merged = res.merged;
-  h->stats.stitch_ms = (double)(t1.tv_sec - t0.tv_sec) * 1e3 + (double)(t1.tv_nsec - t0.tv_nsec) * 1e-6;
-  h->valid = true;
+  h->lab.stats.ranks = n;
+  h->lab.stats.ponds = res.ponds;
+  h->lab.stats.local_ponds = res.local_ponds;
+  h->lab.stats.stitch_unions = res.unions;
+  h->lab.stats.merged = res.merged;
+  h->lab.stats.stitch_ms = ms_between(t0, t1);
+  h->lab.valid = true;
   if (nponds) *nponds = res.ponds;
   return 0;
 }
 
 extern "C" int wdpm_group_ponds_table(wdpm_group_ponds *h, wdpm_pond *out, int64_t capacity) {
-  if (!h) return wdpm_fail("wdpm_group_ponds_table: null handle");
-  if (!h->valid) return wdpm_fail("wdpm_group_ponds_table: no inventory: wdpm_group_ponds_label has not succeeded on this handle");
-  const long long n = h->stats.ponds;
-  if (capacity < n) return wdpm_fail("wdpm_group_ponds_table: capacity %lld is too small for %lld ponds", (long long)capacity, n);
-  if (n == 0) return 0;
-  if (!out) return wdpm_fail("wdpm_group_ponds_table: null output");
-  memcpy(out, h->table.data(), (size_t)n * sizeof(wdpm_pond));
-  return 0;
+  return table_out("wdpm_group_ponds_table", h, &wdpm_group_ponds::lab, kNoGroupTable, out, capacity);
 }
 
 extern "C" int wdpm_group_ponds_labels(wdpm_group_ponds *h, int32_t *padded) {
   if (!h || !padded) return wdpm_fail("wdpm_group_ponds_labels: null argument");
-  if (!h->valid) return wdpm_fail("wdpm_group_ponds_labels: no inventory: wdpm_group_ponds_label has not succeeded on this handle");
+  if (!h->lab.valid) return wdpm_fail("wdpm_group_ponds_labels: %s", kNoGroupTable);
   /* Every rank's owned rows, to where they lie in the whole raster.  The caller's raster is pageable memory, to which a copy is
    * synchronous whatever it is called: the ranks' rows come down one after another, as wdpm_group_download_water's do. */
   for (int i = 0; i < h->n; i++) {
     wdpm_ponds *p = h->r[i];
-    if (wdpm_synchronize(p->x)) return 1;
-    HIP_TRY(hipMemcpyAsync(padded + (size_t)h->own_lo[i] * h->ncp, p->d_labels + (size_t)(h->own_lo[i] - h->view0[i]) * h->ncp,
-                           (size_t)h->own_rows[i] * h->ncp * sizeof(int32_t), hipMemcpyDeviceToHost, p->x->stream));
-    if (wdpm_stream_sync(p->x, p->x->stream)) return 1;
+    if (download(p, padded + (size_t)h->own_lo[i] * h->ncp, p->lab.labels.p + (size_t)(h->own_lo[i] - h->view0[i]) * h->ncp,
+                 (size_t)h->own_rows[i] * h->ncp * sizeof(int32_t)))
+      return 1;
   }
   return 0;
 }
@@ -1078,26 +881,18 @@ extern "C" int wdpm_group_ponds_guard_bad(wdpm_group_ponds *h, int64_t *bytes) {
 }
 
 extern "C" int wdpm_group_ponds_stats(wdpm_group_ponds *h, wdpm_group_pond_stats *out) {
-  if (!h || !out) return wdpm_fail("wdpm_group_ponds_stats: null argument");
-  if (!h->valid) return wdpm_fail("wdpm_group_ponds_stats: no inventory: wdpm_group_ponds_label has not succeeded on this handle");
-  *out = h->stats;
-  return 0;
+  return stats_out("wdpm_group_ponds_stats", h, &wdpm_group_ponds::lab, kNoGroupTable, out, true);
 }
 
 extern "C" int wdpm_group_ponds_rank_stats(wdpm_group_ponds *h, int32_t rank, wdpm_pond_stats *out) {
   if (!h || !out) return wdpm_fail("wdpm_group_ponds_rank_stats: null argument");
   if (rank < 0 || rank >= h->n) return wdpm_fail("wdpm_group_ponds_rank_stats: rank %d of %d", rank, h->n);
-  if (!h->valid) return wdpm_fail("wdpm_group_ponds_rank_stats: no inventory: wdpm_group_ponds_label has not succeeded on this handle");
-  *out = h->r[rank]->stats;
+  if (!h->lab.valid) return wdpm_fail("wdpm_group_ponds_rank_stats: %s", kNoGroupTable);
+  *out = h->r[rank]->lab.stats;
   return 0;
 }
 
 extern "C" int wdpm_group_ponds_phase_ms(wdpm_group_ponds *h, int32_t rank, double *ms) {
-  if (!h || !ms) return wdpm_fail("wdpm_group_ponds_phase_ms: null argument");
-  if (rank < 0 || rank >= h->n) return wdpm_fail("wdpm_group_ponds_phase_ms: rank %d of %d", rank, h->n);
-  if (!h->timing) return wdpm_fail("wdpm_group_ponds_phase_ms: the handle records no events (set WDPM_PONDS_TIMING=1 before it is made)");
-  if (!h->valid) return wdpm_fail("wdpm_group_ponds_phase_ms: no inventory: wdpm_group_ponds_label has not succeeded on this handle");
-  for (int i = 0; i < WDPM_PONDS_PHASES; i++) ms[i] = h->r[rank]->phase_ms[i];
-  return 0;
+  return group_phase_ms_out("wdpm_group_ponds_phase_ms", h, &wdpm_group_ponds::lab, &wdpm_ponds::lab, kNoGroupTable, rank, ms, true);
 }
 #endif  /* WDPM_PONDS_EMULATION */

@@ -3,8 +3,9 @@
  * (rims), wdpm_pond_catchments.hip (catchments), wdpm_pond_outlets.hip (outlets) and wdpm_pond_curves.hip (stage curves).  Geometry, the order-preserving image of a
  * double, the table rows as the device accumulates them, the wave helpers of the kernels (a lane's neighbour, the wave's extremum,
  * the look before an atomic) and - outside the host emulations of the tests, which define WDPM_PONDS_EMULATION and bring stand-ins
- * for the HIP device language (tests/hip_emu.h) - the handle itself with its guarded allocator.  Private: nothing here is exported,
- * and no header under include/ knows it.
+ * for the HIP device language (tests/hip_emu.h) - the host side: the guarded allocator, the holders every buffer, status pair and
+ * phase timer of the handle is made of, the handle as one record per unit, the row-block helpers and the one implementation of
+ * each read-out ("The handle").  Private: nothing here is exported, and no header under include/ knows it.
  */
 #ifndef WDPM_PONDS_PRIV_H
 #define WDPM_PONDS_PRIV_H
@@ -16,6 +17,8 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <ctime>
+#include <string>
 #include <vector>
 
 #include "wdpm_ctx.h"
@@ -196,142 +199,216 @@ __device__ __forceinline__ void atomic_max_if(T *p, T v) {
   if (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < v) atomicMax(p, v);
 }
 
-#ifndef WDPM_PONDS_EMULATION
-struct Guarded { char *base; size_t bytes; };
-/* blocks of a launch with per_block items each (the host emulations bring their own with their launch) */
-inline unsigned blocks_for(long long items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
-#endif
-
 }  // namespace wdpm_pond_detail
 
 #ifndef WDPM_PONDS_EMULATION
+/* ---- host only: the handle, what it is made of, and what the units' entry points share -------------------------------------- */
+#pragma GCC visibility push(hidden)
+namespace wdpm_pond_detail {
+
+struct Guarded { char *base; size_t bytes; };
+/* blocks of a launch with per_block items each (the host emulations bring their own with their launch) */
+inline unsigned blocks_for(long long items, int per_block) { return (unsigned)((items + per_block - 1) / per_block); }
+
+/* device memory of the handle between two guard bands (when it carries any): wdpm_ponds_guard_bad looks at every band */
+hipError_t guarded_malloc(wdpm_ponds *h, void **p, size_t bytes);
+void guarded_free(wdpm_ponds *h, void *p);
+
+/* Holders.  Every buffer of the handle is one of these three, so that it starts empty, grows by one rule and is given back by one
+ * reset(): DevBuf is guarded device memory, PinBuf pinned host memory, both with their capacity in elements. */
+template <class T> struct DevBuf { T *p = nullptr; long long cap = 0; };
+template <class T> struct PinBuf { T *p = nullptr; long long cap = 0; };
+template <class T> void reset(wdpm_ponds *h, DevBuf<T> &b) { guarded_free(h, b.p); b.p = nullptr; b.cap = 0; }
+template <class T> void reset(wdpm_ponds *, PinBuf<T> &b) { if (b.p) (void)hipHostFree(b.p); b.p = nullptr; b.cap = 0; }
+/* Room for n elements: nothing when the buffer holds that many, else what it held is freed first (its contents are never wanted)
+ * and on failure it is left empty.  A buffer of one fixed size is made by its first call. */
+template <class T> hipError_t grow(wdpm_ponds *h, DevBuf<T> &b, long long n) {
+  if (n <= b.cap) return hipSuccess;
+  reset(h, b);
+  const hipError_t e = guarded_malloc(h, (void **)&b.p, (size_t)n * sizeof(T));
+  if (e == hipSuccess) b.cap = n; else b.p = nullptr;
+  return e;
+}
+template <class T> hipError_t grow(wdpm_ponds *h, PinBuf<T> &b, long long n) {
+  if (n <= b.cap) return hipSuccess;
+  reset(h, b);
+  const hipError_t e = hipHostMalloc(&b.p, (size_t)n * sizeof(T));
+  if (e == hipSuccess) b.cap = n; else b.p = nullptr;
+  return e;
+}
+
+/* the words a unit's kernels count for the host: one record on the device (no guard bands) and its pinned twin */
+template <class T> struct StatusPair { T *d = nullptr, *h = nullptr; };
+/* both at the first call, or neither; *what names the memory that ran out */
+template <class T> hipError_t ensure(StatusPair<T> &s, const char **what) {
+  if (s.d) return hipSuccess;
+  *what = "device";
+  hipError_t e = hipMalloc(&s.d, sizeof(T));
+  if (e != hipSuccess) { s.d = nullptr; return e; }
+  *what = "pinned host";
+  e = hipHostMalloc(&s.h, sizeof(T));
+  if (e != hipSuccess) { s.h = nullptr; (void)hipFree(s.d); s.d = nullptr; }
+  return e;
+}
+template <class T> void reset(wdpm_ponds *, StatusPair<T> &s) {
+  if (s.d) (void)hipFree(s.d);
+  if (s.h) (void)hipHostFree(s.h);
+  s.d = s.h = nullptr;
+}
+
+/* The HIP events of one unit and the milliseconds of its phases.  Which events bound which phase is the unit's business. */
+template <int kEvents, int kPhases> struct PhaseTimer {
+  static constexpr int phases = kPhases;
+  hipEvent_t ev[kEvents] = {};
+  double ms[kPhases] = {};
+  /* when the handle records events; one that cannot be made ends the recording for the whole handle */
+  void create(bool &timing) {
+    for (int i = 0; timing && i < kEvents; i++)
+      if (hipEventCreate(&ev[i]) != hipSuccess) timing = false;
+  }
+  void destroy() {
+    for (hipEvent_t &e : ev) {
+      if (e) (void)hipEventDestroy(e);
+      e = nullptr;
+    }
+  }
+  void clear() { for (double &m : ms) m = 0.0; }
+  hipError_t mark(bool timing, int i, hipStream_t s) { return timing ? hipEventRecord(ev[i], s) : hipSuccess; }
+  hipError_t read(int a, int b, double *out) {
+    float f = 0.f;
+    const hipError_t e = hipEventElapsedTime(&f, ev[a], ev[b]);
+    *out = f;
+    return e;
+  }
+  /* phase i lies between events i and i + 1 */
+  hipError_t read_all() {
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < kPhases && e == hipSuccess; i++) e = read(i, i + 1, &ms[i]);
+    return e;
+  }
+};
+
+/* One record per unit.  A row block's extra buffers lie in their unit's record; the whole-raster calls never touch them. */
+struct LabelUnit {                  /* wdpm_ponds.hip: labels and pond table */
+  bool allocated = false;           /* the buffers of one fixed size are there */
+  DevBuf<unsigned long long> masks, rootmask, busum;
+  DevBuf<int> parent, labels, cnt, bsum;
+  DevBuf<unsigned> ucnt;
+  StatusPair<Status> status;
+  DevBuf<int> seam;                 /* 2 x g.ncp labels (row blocks) */
+  PinBuf<int> h_seam;
+  DevBuf<int> map;                  /* local label - 1 -> label in the whole raster (row blocks) */
+  PinBuf<int> h_map;                /* staging (row blocks): the map on its way up, the finished table on its way down - a copy to */
+  PinBuf<wdpm_pond> h_table;        /* or from pageable memory would make the host wait inside the queueing step */
+  DevBuf<PondRow> table;
+  int nb = 0;                       /* blocks of the scan */
+  int rpw = 1;                      /* of the call under way */
+  Status last = {};                 /* status words of the call under way */
+  bool valid = false;               /* the last label call succeeded */
+  PhaseTimer<WDPM_PONDS_PHASES + 2, WDPM_PONDS_PHASES> timer;   /* the host reads the status between scan and table: two marks there */
+  wdpm_pond_stats stats = {};
+};
+struct RimUnit {                    /* wdpm_pond_rims.hip: the table of the last wdpm_rims_label; every label call takes `valid` away first */
+  DevBuf<RimRow> table;
+  bool valid = false;
+  PhaseTimer<WDPM_RIMS_PHASES + 1, WDPM_RIMS_PHASES> timer;
+  /* a row block (wdpm_group_rims_label): the table then holds one row per SLOT - the rank's local ponds, then its foreign ponds -
+   * and slot_of[label in the whole raster] says which */
+  DevBuf<int> slot_of;
+  DevBuf<int> foreign;              /* 2 x g.ncp: the foreign ponds' labels */
+  PinBuf<unsigned long long> h_beside;   /* staging: 2 x g.nsc wet masks, 2 x g.ncp labels of the rows beside the rank's own, 2 x g.ncp foreign labels */
+  PinBuf<wdpm_pond_rim> h_table;    /* the finished rim rows on their way down */
+  long long slots = 0, nforeign = 0;   /* of the call under way */
+  std::vector<int> slot_label;      /* slot -> label in the whole raster */
+};
+struct CatchUnit {                  /* wdpm_pond_catchments.hip: likewise for wdpm_catch_label */
+  DevBuf<int> link;                 /* g.rows x g.ncp: the link raster, the basin raster once a call has ended */
+  DevBuf<CatchRow> table;
+  StatusPair<CatchStatus> status;
+  bool valid = false;
+  /* events: init | receivers | jump rounds | tally, finish; row blocks: 0-1 receivers, 2-3 a batch of jump rounds, 4-5 tally */
+  PhaseTimer<kCatchEvents, WDPM_CATCH_PHASES> timer;
+  wdpm_pond_catchment_stats stats = {};
+  /* a row block (wdpm_group_catch_label): the table then holds one row per SLOT - the rims' slots, then the rank's remote ponds -
+   * and the link raster's rows 0 and g.rows - 1 belong to the neighbours */
+  DevBuf<unsigned long long> keys;  /* 4 x g.ncp level keys: the rank's first and last owned row, then the rows beside them */
+  PinBuf<unsigned long long> h_keys;   /* laid out likewise: two rows on their way down, two on their way up */
+  DevBuf<int> exits;                /* 4 x g.ncp: where each exit ends (2 x g.ncp), the remote ponds' labels */
+  PinBuf<int> h_exits;              /* 6 x g.ncp: the links of the first and last owned row on their way down (and, behind the tally, the */
+                                    /* same rows as basins: the seam basins of the outlet pass), then as `exits` */
+  PinBuf<wdpm_pond_catchment> h_table;   /* the finished catchment rows on their way down */
+  long long slots = 0, remote = 0;  /* of the call under way */
+  int rounds = 0;
+  std::vector<int> remote_label;    /* the whole-raster labels of the remote slots, which follow the rims' slots (slot_label) */
+};
+struct OutletUnit {                 /* wdpm_pond_outlets.hip: likewise for wdpm_outlets_label */
+  DevBuf<OutletRow> table;
+  StatusPair<OutletStatus> status;
+  bool valid = false;
+  PhaseTimer<WDPM_OUTLETS_PHASES + 1, WDPM_OUTLETS_PHASES> timer;   /* init, passes | locate, finish */
+  wdpm_pond_outlet_stats stats = {};
+  /* a row block (wdpm_group_outlets_label): the table then holds one row per SLOT, as the catchments' does.  keys and h_keys grow
+   * together, for C slots at a time */
+  DevBuf<unsigned long long> keys;  /* 2 x C: every slot's pour key and divide count on their way down, the merged keys on their way up */
+  PinBuf<unsigned long long> h_keys;   /* 3 x C: keys and counts as they came down, then, behind the 2 x slots words of the call, the merged keys */
+  PinBuf<OutletRow> h_table;        /* the slots' rows on their way down */
+  PinBuf<int> h_seam;               /* 2 x g.ncp: the facing ranks' seam basins on their way up */
+};
+struct CurveUnit {                  /* wdpm_pond_curves.hip: likewise for wdpm_curves_label */
+  DevBuf<CurveRow> table;
+  StatusPair<CurveStatus> status;
+  bool valid = false;
+  PhaseTimer<WDPM_CURVES_PHASES + 1, WDPM_CURVES_PHASES> timer;     /* init, bed | stages, finish */
+  wdpm_pond_curve_stats stats = {};
+};
+
+/* a merged table of a group: what the last label call of its kind left; every label call takes `valid` away first */
+template <class Row, class Stats> struct Merged {
+  std::vector<Row> rows;
+  bool valid = false;
+  Stats stats = {};
+};
+
+}  // namespace wdpm_pond_detail
+#pragma GCC visibility pop
+
 /* The handle labels a VIEW of its context: rows [row_off, row_off + g.rows) of the context's rasters, whose first and last row the
  * kernels take for the dry border.  wdpm_ponds_create views a whole-raster context; a row block of a group (wdpm_group_ponds_*) is
- * viewed as its owned rows with one row either side. */
+ * viewed as its owned rows with one row either side.
+ * A new buffer is one member of its unit's record, as a holder, and one line in release() (wdpm_ponds.hip): nothing else. */
 struct wdpm_ponds {
-  wdpm_ctx *x;
-  wdpm_pond_detail::Geom g;
-  int row_off;                      /* context row of the view's row 0 */
-  bool seams;                       /* a row block: the labels of rows 1 and g.rows - 2 come to the host with the status */
-  size_t guard;                     /* bytes of each guard band (WDPM_GUARD_KB when the handle was made) */
+  wdpm_ctx *x = nullptr;
+  wdpm_pond_detail::Geom g = {};
+  int row_off = 0;                  /* context row of the view's row 0 */
+  bool seams = false;               /* a row block: the labels of rows 1 and g.rows - 2 come to the host with the status */
+  size_t guard = 0;                 /* bytes of each guard band (WDPM_GUARD_KB when the handle was made) */
   std::vector<wdpm_pond_detail::Guarded> guards;
-  bool allocated;
-  unsigned long long *d_masks, *d_rootmask, *d_busum;
-  int *d_parent, *d_labels, *d_cnt, *d_bsum;
-  unsigned *d_ucnt;
-  wdpm_pond_detail::Status *d_status, *h_status;      /* h_status pinned */
-  int *d_seam, *h_seam;             /* 2 x g.ncp labels (seams); h_seam pinned */
-  int *d_map;                       /* local label - 1 -> label in the whole raster (seams) */
-  long long map_cap;
-  int *h_map;                       /* pinned staging (seams): the map on its way up, the finished table on its way down - */
-  wdpm_pond *h_table;               /* a copy to or from pageable memory would make the host wait inside the queueing step */
-  long long stage_cap;
-  wdpm_pond_detail::PondRow *d_table;
-  long long table_cap;
-  int nb;                           /* blocks of the scan */
-  int forced_rpw;                   /* WDPM_PONDS_ROWS_PER_WAVE when the handle was made, 0: the library chooses */
-  int rpw;                          /* of the call under way */
-  wdpm_pond_detail::Status last;    /* status words of the call under way */
-  bool valid;                       /* the last label call succeeded */
-  bool timing;                      /* WDPM_PONDS_TIMING=1 when the handle was made: HIP events around every kernel */
-  hipEvent_t ev[WDPM_PONDS_PHASES + 2];   /* the host reads the status between scan and table: two marks there */
-  double phase_ms[WDPM_PONDS_PHASES];
-  wdpm_pond_stats stats;
-  /* rims (wdpm_pond_rims.hip): the table of the last wdpm_rims_label; every label call takes rims_valid away first */
-  wdpm_pond_detail::RimRow *d_rims;
-  long long rims_cap;
-  bool rims_valid;
-  hipEvent_t rim_ev[WDPM_RIMS_PHASES + 1];   /* made with the others when the handle records events */
-  double rim_ms[WDPM_RIMS_PHASES];
-  /* rims of a row block (wdpm_group_rims_label): d_rims then holds one row per SLOT - the rank's local ponds, then its foreign
-   * ponds - and d_slot_of[label in the whole raster] says which */
-  int *d_slot_of;
-  long long slot_cap;               /* entries of d_slot_of */
-  int *d_foreign;                   /* 2 x g.ncp: the foreign ponds' labels */
-  unsigned long long *h_beside;     /* pinned staging: 2 x g.nsc wet masks, 2 x g.ncp labels of the rows beside the rank's own, */
-                                    /* 2 x g.ncp foreign labels */
-  wdpm_pond_rim *h_rims;            /* pinned: the finished rim rows on their way down */
-  long long h_rims_cap;
-  long long rim_slots;              /* of the call under way */
-  long long rim_foreign;
-  std::vector<int> slot_label;      /* slot -> label in the whole raster */
-  /* catchments (wdpm_pond_catchments.hip): link raster (the basin raster once a call has ended) and table of the last
-   * wdpm_catch_label; every label call takes catch_valid away first */
-  int *d_link;                      /* g.rows x g.ncp, allocated at the first wdpm_catch_label */
-  wdpm_pond_detail::CatchRow *d_catch;
-  long long catch_cap;
-  wdpm_pond_detail::CatchStatus *d_cstat, *h_cstat;   /* h_cstat pinned */
-  bool catch_valid;
-  hipEvent_t catch_ev[wdpm_pond_detail::kCatchEvents];   /* init | receivers | jump rounds | tally, finish; row blocks: 0-1 receivers, 2-3 a batch of */
-                                    /* jump rounds, 4-5 tally */
-  double catch_ms[WDPM_CATCH_PHASES];
-  wdpm_pond_catchment_stats catch_stats;
-  /* catchments of a row block (wdpm_group_catch_label): d_catch then holds one row per SLOT - the rims' slots, then the rank's
-   * remote ponds - and d_link's rows 0 and g.rows - 1 belong to the neighbours */
-  unsigned long long *d_ckeys;      /* 4 x g.ncp level keys: the rank's first and last owned row, then the rows beside them */
-  unsigned long long *h_ckeys;      /* pinned, laid out likewise: two rows on their way down, two on their way up */
-  int *d_cexit;                     /* 4 x g.ncp: where each exit ends (2 x g.ncp), the remote ponds' labels */
-  int *h_cexit;                     /* pinned, 6 x g.ncp: the links of the first and last owned row on their way down (and, behind the */
-                                    /* tally, the same rows as basins: the seam basins of the outlet pass), then as d_cexit */
-  wdpm_pond_catchment *h_catch;     /* pinned: the finished catchment rows on their way down */
-  long long h_catch_cap;
-  long long catch_slots, catch_remote;   /* of the call under way */
-  int catch_rounds;
-  std::vector<int> catch_remote_label;   /* the whole-raster labels of the remote slots, which follow the rims' slots (slot_label) */
-  /* outlets (wdpm_pond_outlets.hip): the table of the last wdpm_outlets_label; every label call takes outlets_valid away first */
-  wdpm_pond_detail::OutletRow *d_outlets;
-  long long outlets_cap;
-  wdpm_pond_detail::OutletStatus *d_ostat, *h_ostat;  /* h_ostat pinned */
-  bool outlets_valid;
-  hipEvent_t outlet_ev[WDPM_OUTLETS_PHASES + 1];      /* init, passes | locate, finish */
-  double outlet_ms[WDPM_OUTLETS_PHASES];
-  wdpm_pond_outlet_stats outlet_stats;
-  /* outlets of a row block (wdpm_group_outlets_label): d_outlets then holds one row per SLOT, as d_catch does */
-  unsigned long long *d_okeys;      /* 2 x okeys_cap: every slot's pour key and divide count on their way down, the merged keys on their way up */
-  unsigned long long *h_okeys;      /* pinned, 3 x okeys_cap: keys and counts as they came down, then the merged keys */
-  long long okeys_cap;
-  wdpm_pond_detail::OutletRow *h_outlets;   /* pinned: the slots' rows on their way down */
-  long long h_outlets_cap;
-  int *h_oseam;                     /* pinned, 2 x g.ncp: the facing ranks' seam basins on their way up */
-  /* stage curves (wdpm_pond_curves.hip): the table of the last wdpm_curves_label; every label call takes curves_valid away first */
-  wdpm_pond_detail::CurveRow *d_curves;
-  long long curves_cap;
-  wdpm_pond_detail::CurveStatus *d_vstat, *h_vstat;   /* h_vstat pinned */
-  bool curves_valid;
-  hipEvent_t curve_ev[WDPM_CURVES_PHASES + 1];        /* init, bed | stages, finish */
-  double curve_ms[WDPM_CURVES_PHASES];
-  wdpm_pond_curve_stats curve_stats;
+  int forced_rpw = 0;               /* WDPM_PONDS_ROWS_PER_WAVE when the handle was made, 0: the library chooses */
+  bool timing = false;              /* WDPM_PONDS_TIMING=1 when the handle was made: HIP events around every kernel */
+  wdpm_pond_detail::LabelUnit lab;
+  wdpm_pond_detail::RimUnit rim;
+  wdpm_pond_detail::CatchUnit cat;
+  wdpm_pond_detail::OutletUnit out;
+  wdpm_pond_detail::CurveUnit cur;
 };
 
 /* the handle of include/wdpm_group_ponds.h, include/wdpm_group_pond_rims.h, include/wdpm_group_pond_catchments.h and
  * include/wdpm_group_pond_outlets.h */
 struct wdpm_group_ponds {
-  wdpm_group *grp;
-  int n;                                   /* ranks */
-  int rows, ncp;                           /* the whole raster, padded */
+  wdpm_group *grp = nullptr;
+  int n = 0;                               /* ranks */
+  int rows = 0, ncp = 0;                   /* the whole raster, padded */
   std::vector<wdpm_ponds *> r;             /* one handle per rank, on its owned rows with one row either side */
   std::vector<int> own_lo, own_rows, view0;   /* whole-raster rows: first owned, how many owned, the view's row 0 */
-  std::vector<wdpm_pond> table;            /* the merged table of the last label call */
-  bool timing, valid;
-  wdpm_group_pond_stats stats;
-  /* rims: the merged table of the last wdpm_group_rims_label; every label call takes rims_valid away first */
-  std::vector<wdpm_pond_rim> rims;
-  bool rims_valid;
-  wdpm_group_rim_stats rim_stats;
-  /* catchments: the merged table of the last wdpm_group_catch_label; every label call takes catch_valid away first */
-  std::vector<wdpm_pond_catchment> catchments;
-  bool catch_valid;
-  wdpm_group_catchment_stats catch_stats;
-  /* outlets: the merged table of the last wdpm_group_outlets_label; every label call takes outlets_valid away first */
-  std::vector<wdpm_pond_outlet> outlets;
-  bool outlets_valid;
-  wdpm_group_outlet_stats outlet_stats;
+  bool timing = true;                      /* until a rank's handle records no events */
+  wdpm_pond_detail::Merged<wdpm_pond, wdpm_group_pond_stats> lab;
+  wdpm_pond_detail::Merged<wdpm_pond_rim, wdpm_group_rim_stats> rim;
+  wdpm_pond_detail::Merged<wdpm_pond_catchment, wdpm_group_catchment_stats> cat;
+  wdpm_pond_detail::Merged<wdpm_pond_outlet, wdpm_group_outlet_stats> out;
 };
 
+#pragma GCC visibility push(hidden)
 namespace wdpm_pond_detail {
-/* device memory of the handle between two guard bands (when it carries any): wdpm_ponds_guard_bad looks at every band */
-__attribute__((visibility("hidden"))) hipError_t guarded_malloc(wdpm_ponds *h, void **p, size_t bytes);
-__attribute__((visibility("hidden"))) void guarded_free(wdpm_ponds *h, void *p);
 /* wdpm_group_ponds_label, and with `rims` what wdpm_group_rims_label adds to it: after rank i's table kernels are queued and
  * before any rank is waited for, rims(h, i, map) queues that rank's rim work, map[rank][local label - 1] being the stitch's
  * numbers.  One wait per rank then ends both. */
@@ -339,13 +416,90 @@ typedef int (*group_rims_queue)(wdpm_group_ponds *h, int rank, const std::vector
 /* `seams` (may be null): called for rank i right after its scan is queued and before any rank is waited for, so that what it
  * sends to the host arrives with the seam labels. */
 typedef int (*group_seams_queue)(wdpm_group_ponds *h, int rank);
-__attribute__((visibility("hidden"))) int group_label(wdpm_group_ponds *h, double min_depth, int64_t *nponds, group_rims_queue rims,
-                                                      group_seams_queue seams = nullptr);
+int group_label(wdpm_group_ponds *h, double min_depth, int64_t *nponds, group_rims_queue rims, group_seams_queue seams = nullptr);
 /* wdpm_pond_rims.hip: the rims argument of wdpm_group_rims_label, and what that call does once group_label has returned - the
- * ranks' rim rows merged into h->rims, h->valid and h->rims_valid set.  wdpm_group_catch_label runs both and adds its own. */
-__attribute__((visibility("hidden"))) int group_rims_rank(wdpm_group_ponds *h, int rank, const std::vector<std::vector<int>> &map, long long ponds);
-__attribute__((visibility("hidden"))) int group_rims_merge(wdpm_group_ponds *h, const char *caller, long long ponds);
+ * ranks' rim rows merged into h->rim, h->lab.valid and h->rim.valid set.  wdpm_group_catch_label runs both and adds its own. */
+int group_rims_rank(wdpm_group_ponds *h, int rank, const std::vector<std::vector<int>> &map, long long ponds);
+int group_rims_merge(wdpm_group_ponds *h, const char *caller, long long ponds);
+/* after a failure with work queued: let every rank's stream run dry, so that nothing still reads what the caller may free; the
+ * message stays */
+int group_drain(wdpm_group_ponds *h);
+
+inline double ms_between(const timespec &a, const timespec &b) { return (double)(b.tv_sec - a.tv_sec) * 1e3 + (double)(b.tv_nsec - a.tv_nsec) * 1e-6; }
+
+/* the owned rows [ra, rb) of rank i in rows of its view; halo: bit 0 a rank above, bit 1 a rank below */
+struct OwnedRows { int ra, rb, halo; };
+inline OwnedRows owned_rows(const wdpm_group_ponds *gh, int i) {
+  const int ra = gh->own_lo[i] - gh->view0[i];
+  return {ra, ra + gh->own_rows[i], (i > 0 ? 1 : 0) | (i + 1 < gh->n ? 2 : 0)};
+}
+
+/* the waves of a kernel that walks `rows` rows of the view down its segment columns, each wave rpw rows of one column */
+struct Waves { int rpw, nwaves; };
+inline Waves waves_for(const wdpm_ponds *h, int rows) {
+  const int rpw = ponds_rows_per_wave(h->g.nseg, h->g.rows, h->forced_rpw);
+  return {rpw, ((rows + rpw - 1) / rpw) * h->g.nsc};
+}
+
+/* ---- what every unit's entry points check and hand out, in the order the headers under include/ promise ---- */
+inline int check_min_depth(const char *caller, double v) {
+  return (!(v >= 0.0) || std::isinf(v)) ? wdpm_fail("%s: min_depth must be finite and >= 0 (got %g)", caller, v) : 0;
+}
+/* `joint`: the two oldest units (labels, rims) answer a null handle and a null output with one message */
+inline int check_args(const char *caller, const void *h, const void *out, bool joint) {
+  if (joint) return (!h || !out) ? wdpm_fail("%s: null argument", caller) : 0;
+  if (!h) return wdpm_fail("%s: null handle", caller);
+  return out ? 0 : wdpm_fail("%s: null output", caller);
+}
+/* `bytes` of the handle's device memory to the caller's pageable memory, behind everything the context has queued */
+inline int download(wdpm_ponds *h, void *out, const void *dev, size_t bytes) {
+  if (wdpm_synchronize(h->x)) return 1;
+  HIP_TRY(hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, h->x->stream));
+  return wdpm_stream_sync(h->x, h->x->stream);
+}
+template <class U> int copy_rows(wdpm_ponds *h, U &u, void *out, size_t bytes) { return download(h, out, u.table.p, bytes); }
+template <class U> int copy_rows(wdpm_group_ponds *, U &u, void *out, size_t bytes) { memcpy(out, u.rows.data(), bytes); return 0; }
+
+/* *_table of handle type H (whole raster or group) and unit `unit`; `none` is the sentence for a handle without that table */
+template <class H, class U, class Row>
+int table_out(const char *caller, H *h, U H::*unit, const char *none, Row *out, int64_t capacity) {
+  if (!h) return wdpm_fail("%s: null handle", caller);
+  if (!h->lab.valid || !(h->*unit).valid) return wdpm_fail("%s: %s", caller, none);
+  const long long n = h->lab.stats.ponds;
+  if (capacity < n) return wdpm_fail("%s: capacity %lld is too small for %lld ponds", caller, (long long)capacity, n);
+  if (n == 0) return 0;
+  if (!out) return wdpm_fail("%s: null output", caller);
+  return copy_rows(h, h->*unit, out, (size_t)n * sizeof(Row));
+}
+template <class H, class U, class S>
+int stats_out(const char *caller, H *h, U H::*unit, const char *none, S *out, bool joint = false) {
+  if (check_args(caller, h, out, joint)) return 1;
+  if (!h->lab.valid || !(h->*unit).valid) return wdpm_fail("%s: %s", caller, none);
+  *out = (h->*unit).stats;
+  return 0;
+}
+/* *_phase_ms: `valid` is the handle's own unit, or the group's while `h` is one of its ranks */
+template <class U>
+int phase_ms_tail(const char *caller, bool timing, bool valid, const char *none, const wdpm_ponds *h, U wdpm_ponds::*unit, double *ms) {
+  if (!timing) return wdpm_fail("%s: the handle records no events (set WDPM_PONDS_TIMING=1 before it is made)", caller);
+  if (!valid) return wdpm_fail("%s: %s", caller, none);
+  for (int i = 0; i < (h->*unit).timer.phases; i++) ms[i] = (h->*unit).timer.ms[i];
+  return 0;
+}
+template <class U>
+int phase_ms_out(const char *caller, wdpm_ponds *h, U wdpm_ponds::*unit, const char *none, double *ms, bool joint = false) {
+  if (check_args(caller, h, ms, joint)) return 1;
+  return phase_ms_tail(caller, h->timing, h->lab.valid && (h->*unit).valid, none, h, unit, ms);
+}
+template <class G, class U>
+int group_phase_ms_out(const char *caller, wdpm_group_ponds *h, G wdpm_group_ponds::*merged, U wdpm_ponds::*unit, const char *none, int32_t rank, double *ms,
+                       bool joint = false) {
+  if (check_args(caller, h, ms, joint)) return 1;
+  if (rank < 0 || rank >= h->n) return wdpm_fail("%s: rank %d of %d", caller, rank, h->n);
+  return phase_ms_tail(caller, h->timing, h->lab.valid && (h->*merged).valid, none, h->r[rank], unit, ms);
+}
 }  // namespace wdpm_pond_detail
+#pragma GCC visibility pop
 #endif
 
 #endif
