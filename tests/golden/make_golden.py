@@ -28,6 +28,8 @@ reference executable, serial path cpu=0), and writes DATA only:
     python tests/golden/make_golden.py verify-oracle   (the CPU restatement against config 3's settled entries: 20 minutes)
     python tests/golden/make_golden.py synthcli    (synth_cli.json: the reference EXECUTABLE's add / drain / subtract chain on a synthetic 3072^2 DEM)
     python tests/golden/make_golden.py clifuzz     (cli_fuzz_ref.json.gz: the reference EXECUTABLE on the random jobs of tests/cli_fuzz.py)
+    python tests/golden/make_golden.py pondfiles [wdpmcl_main.c ...]   (cli_pond_files.json: the project's OWN command line, built from the
+                                                   sources named - by default the tree's, for a lock the parent commit's - on the cases of tests/cli_pond_cases.py; needs no reference)
 """
 import ctypes as C
 import gzip
@@ -314,6 +316,20 @@ def make_cli_fuzz():
         g.write(json.dumps(res, sort_keys=True).encode())
 
 
+def make_cli_pond_files(cli_sources):
+    """The project's own command line, built from `cli_sources` (the tree's when none is given; the sources of an earlier commit to
+    lock a refactor against it) and linked with the canned pond back-end tests/cli_ponds_stub.c, on the cases of
+    tests/cli_pond_cases.py: per case the exit status, the pond, guard and stub lines of stderr and the files written.
+    -> cli_pond_files.json"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import cli_pond_cases
+    with tempfile.TemporaryDirectory() as td:
+        res = cli_pond_cases.record([os.path.abspath(s) for s in cli_sources] or None, td)
+    with open(os.path.join(HERE, "cli_pond_files.json"), "w") as f:
+        json.dump(res, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 def verify_oracle_settled():
     """The CPU restatement (oracle/wdpm_oracle.c) against the SETTLED golden of config 3: two blocks of 1000 iterations at 4096^2, the
     threshold flush between them - twenty minutes of one core, so not part of the test suite (which pins the oracle at 4096^2 x 20 and on
@@ -576,6 +592,9 @@ def main():
         return
     if len(sys.argv) > 1 and sys.argv[1] == "clifuzz":
         make_cli_fuzz()
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "pondfiles":
+        make_cli_pond_files(sys.argv[2:])
         return
     if len(sys.argv) > 1 and sys.argv[1] == "merge":
         merge_settled()

@@ -8,7 +8,8 @@ import re
 import numpy as np
 import pytest
 
-from test_ponds_cli import ADD_MM, ITER, MISS, parse_csv, read_asc, run_cli
+from pond_cli import ADD_MM, ITER, job_args, read_asc, run_cli
+from test_ponds_cli import MISS, parse_csv
 
 pytestmark = pytest.mark.gpu
 
@@ -40,10 +41,10 @@ def binding_merged(hip, dem, devices):
 
 def test_three_row_blocks_write_the_one_device_inventory(hip, synth, tmp_path):
     dem, _ = read_asc(synth)
-    plain = run_cli(tmp_path, synth)
+    plain = run_cli(tmp_path, job_args(synth))
     one, three = tmp_path / "one.csv", tmp_path / "three.csv"
-    out1, raster1, err1 = run_cli(tmp_path, synth, WDPM_PONDS=str(one))
-    out3, raster3, err3 = run_cli(tmp_path, synth, WDPM_PONDS=str(three), WDPM_DEVICES="0,0,0", WDPM_TIMING="1")
+    out1, raster1, err1 = run_cli(tmp_path, job_args(synth), WDPM_PONDS=str(one))
+    out3, raster3, err3 = run_cli(tmp_path, job_args(synth), WDPM_PONDS=str(three), WDPM_DEVICES="0,0,0", WDPM_TIMING="1")
     assert (out1, raster1) == plain[:2] and (out3, raster3) == plain[:2]
     assert open(three, "rb").read() == open(one, "rb").read()
     rows = parse_csv(three)

@@ -6,31 +6,16 @@ import gzip
 import os
 import re
 import shutil
-import subprocess
-import sys
 import types
 
-import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
-
-sys.path.insert(0, GOLDEN)
-from make_golden import strip_timing  # noqa: E402
+from conftest import GOLDEN
+from pond_cli import ADD_MM, ITER, job_args, read_asc, run_cli
 
 pytestmark = pytest.mark.gpu
-HIP_CLI = os.path.join(ROOT, "wdpm_amd", "bin", "WDPMCL")
 COLUMNS = "label,catch_cells,catch_area_m2,inflow_cells,head_level_m,row_min,row_max,col_min,col_max"
 MISS = -99999.0
-ADD_MM, ITER = 300, 1000
-STRIPPED = ("WDPM_GPUS", "WDPM_DEVICES", "WDPM_PONDS", "WDPM_POND_RIMS", "WDPM_POND_CATCHMENTS", "WDPM_PONDS_MIN_DEPTH_MM")
-
-
-def read_asc(path):
-    with open(path) as f:
-        hdr = [f.readline().split() for _ in range(6)]
-        vals = np.array(f.read().split(), dtype=np.float64)
-    return vals.reshape(int(float(hdr[1][1])), int(float(hdr[0][1]))), float(hdr[4][1])
 
 
 def binding_catchments(hip, dem, min_depth):
@@ -63,15 +48,6 @@ def parse_csv(path):
     return [tuple(k(v) for k, v in zip(kinds, ln.split(","), strict=True)) for ln in lines[1:]]
 
 
-def run_cli(cwd, dem, status=0, **env):
-    base = {k: v for k, v in os.environ.items() if k not in STRIPPED}
-    args = [HIP_CLI, "add", dem, "NULL", "out.asc", "NULL", str(ADD_MM), "1.0", "1.0", "0", "0", "0.005", str(ITER)]
-    p = subprocess.run(args, cwd=cwd, capture_output=True, text=True, timeout=600, env=dict(base, **env))
-    assert p.returncode == status, p.stderr[-3000:]
-    with open(os.path.join(cwd, "out.asc"), "rb") as f:
-        return strip_timing(p.stdout), f.read(), p.stderr
-
-
 @pytest.fixture(scope="module")
 def job(tmp_path_factory, hip):
     """basin5; the run with none of the variables; the WDPM_PONDS and WDPM_POND_RIMS files of a run without the new variable"""
@@ -79,9 +55,9 @@ def job(tmp_path_factory, hip):
     with gzip.open(os.path.join(GOLDEN, "basin5.asc.gz"), "rb") as f, open(d / "basin5.asc", "wb") as g:
         shutil.copyfileobj(f, g)
     dem_path = str(d / "basin5.asc")
-    plain = run_cli(d, dem_path)
+    plain = run_cli(d, job_args(dem_path))
     ponds_csv, rims_csv = d / "ponds_before.csv", d / "rims_before.csv"
-    assert run_cli(d, dem_path, WDPM_PONDS=str(ponds_csv), WDPM_POND_RIMS=str(rims_csv))[:2] == plain[:2]
+    assert run_cli(d, job_args(dem_path), WDPM_PONDS=str(ponds_csv), WDPM_POND_RIMS=str(rims_csv))[:2] == plain[:2]
     return d, dem_path, plain, open(ponds_csv, "rb").read(), open(rims_csv, "rb").read()
 
 
@@ -93,7 +69,7 @@ def test_csv_is_the_binding_table_and_nothing_else_changes(hip, job, tmp_path):
     assert len(want) >= 1 and any(r[1] > 0 for r in want)
     # alone
     csv = tmp_path / "catch.csv"
-    out, raster, err = run_cli(tmp_path, dem_path, WDPM_POND_CATCHMENTS=str(csv))
+    out, raster, err = run_cli(tmp_path, job_args(dem_path), WDPM_POND_CATCHMENTS=str(csv))
     assert (out, raster) == plain[:2] and "pond catchments: %d pond" % len(want) in err
     said = re.search(r"\((\d+) slope cells, (\d+) pits, (\d+) cells drain to no pond, (\d+) rounds\)", err)
     assert said and tuple(map(int, said.groups())) == (stats["slope_cells"], stats["pit_cells"], stats["unponded_cells"], stats["rounds"])
@@ -102,14 +78,14 @@ def test_csv_is_the_binding_table_and_nothing_else_changes(hip, job, tmp_path):
     assert got == want, next((a, b) for a, b in zip(got, want) if a != b) if len(got) == len(want) else (len(got), len(want))
     alone = open(csv, "rb").read()
     # beside the other two: one label call serves all three files
-    out, raster, err = run_cli(tmp_path, dem_path, WDPM_POND_CATCHMENTS=str(csv), WDPM_POND_RIMS=str(tmp_path / "rims.csv"),
+    out, raster, err = run_cli(tmp_path, job_args(dem_path), WDPM_POND_CATCHMENTS=str(csv), WDPM_POND_RIMS=str(tmp_path / "rims.csv"),
                                WDPM_PONDS=str(tmp_path / "ponds.csv"))
     assert (out, raster) == plain[:2]
     assert open(tmp_path / "ponds.csv", "rb").read() == ponds_before and open(tmp_path / "rims.csv", "rb").read() == rims_before
     assert open(csv, "rb").read() == alone
     # beside one of them
     os.remove(tmp_path / "rims.csv")
-    out, raster, err = run_cli(tmp_path, dem_path, WDPM_POND_CATCHMENTS=str(csv), WDPM_POND_RIMS=str(tmp_path / "rims.csv"))
+    out, raster, err = run_cli(tmp_path, job_args(dem_path), WDPM_POND_CATCHMENTS=str(csv), WDPM_POND_RIMS=str(tmp_path / "rims.csv"))
     assert (out, raster) == plain[:2] and open(tmp_path / "rims.csv", "rb").read() == rims_before and open(csv, "rb").read() == alone
 
 
@@ -117,13 +93,13 @@ def test_min_depth_variable(hip, job, tmp_path):
     d, dem_path, plain, _, _ = job
     dem, cellsize = read_asc(dem_path)
     csv = tmp_path / "catch.csv"
-    run_cli(tmp_path, dem_path, WDPM_POND_CATCHMENTS=str(csv), WDPM_PONDS_MIN_DEPTH_MM="50")
+    run_cli(tmp_path, job_args(dem_path), WDPM_POND_CATCHMENTS=str(csv), WDPM_PONDS_MIN_DEPTH_MM="50")
     assert parse_csv(csv) == expected_rows(binding_catchments(hip, dem, 0.05)[0], cellsize)
 
 
 def test_two_row_blocks_are_refused_after_a_complete_run(job, tmp_path):
     d, dem_path, plain, ponds_before, _ = job
-    out, raster, err = run_cli(tmp_path, dem_path, status=4, WDPM_DEVICES="0,0", WDPM_POND_CATCHMENTS=str(tmp_path / "catch.csv"),
+    out, raster, err = run_cli(tmp_path, job_args(dem_path), status=4, WDPM_DEVICES="0,0", WDPM_POND_CATCHMENTS=str(tmp_path / "catch.csv"),
                                WDPM_PONDS=str(tmp_path / "ponds.csv"))
     assert (out, raster) == plain[:2]
     assert "pond catchments" in err and "row blocks" in err and not os.path.exists(tmp_path / "catch.csv")

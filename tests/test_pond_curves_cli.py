@@ -6,29 +6,22 @@ raster never change; and a raster in two row blocks is refused with exit status 
 WDPM_PONDS file - are complete."""
 import os
 import re
-import subprocess
-import sys
 import types
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
 from helpers import pad
 from pond_curves_model import STAGES, assert_same_curves
 from test_pond_curves import reference
-
-sys.path.insert(0, GOLDEN)
-from make_golden import strip_timing  # noqa: E402
+from pond_cli import ADD_MM, ITER, job_args, run_cli
 
 pytestmark = pytest.mark.gpu
-HIP_CLI = os.path.join(ROOT, "wdpm_amd", "bin", "WDPMCL")
 COLUMNS = "label,stage,level_m,cells,area_m2,q,volume_m3"
 MISS = -99999.0
-ADD_MM, ITER = 300, 1000        # one block of the command line's 1000 iterations
 CELLSIZE = 10.0
+JOB = job_args("dem.asc")
 OTHERS = {"WDPM_PONDS": "ponds.csv", "WDPM_POND_RIMS": "rims.csv", "WDPM_POND_CATCHMENTS": "catch.csv", "WDPM_POND_OUTLETS": "outlets.csv"}
-STRIPPED = ("WDPM_GPUS", "WDPM_DEVICES", "WDPM_PONDS_MIN_DEPTH_MM", "WDPM_POND_CURVES") + tuple(OTHERS)
 
 
 def small_dem():
@@ -78,15 +71,6 @@ def parse_csv(path):
     return [tuple(k(v) for k, v in zip(kinds, ln.split(","), strict=True)) for ln in lines[1:]]
 
 
-def run_cli(cwd, status=0, **env):
-    base = {k: v for k, v in os.environ.items() if k not in STRIPPED}
-    args = [HIP_CLI, "add", "dem.asc", "NULL", "out.asc", "NULL", str(ADD_MM), "1.0", "1.0", "0", "0", "0.005", str(ITER)]
-    p = subprocess.run(args, cwd=cwd, capture_output=True, text=True, timeout=300, env=dict(base, **env))
-    assert p.returncode == status, p.stderr[-3000:]
-    with open(os.path.join(cwd, "out.asc"), "rb") as f:
-        return strip_timing(p.stdout), f.read(), p.stderr
-
-
 @pytest.fixture(scope="module")
 def job(tmp_path_factory, hip):
     """the small job; the run with none of the variables; the four other files of a run without the new variable"""
@@ -94,8 +78,8 @@ def job(tmp_path_factory, hip):
     with open(d / "dem.asc", "w") as f:
         f.write("ncols 150\nnrows 60\nxllcorner 0\nyllcorner 0\ncellsize %g\nNODATA_value %d\n" % (CELLSIZE, int(MISS)))
         np.savetxt(f, small_dem(), fmt="%.4f")
-    plain = run_cli(d)
-    assert run_cli(d, **OTHERS)[:2] == plain[:2]
+    plain = run_cli(d, JOB)
+    assert run_cli(d, JOB, **OTHERS)[:2] == plain[:2]
     before = {k: open(d / v, "rb").read() for k, v in OTHERS.items()}
     for v in OTHERS.values():
         os.remove(d / v)
@@ -115,7 +99,7 @@ def test_csv_is_the_binding_table_and_nothing_else_changes(hip, job):
     assert_same_curves(table, stats, ref_table, ref_stats)
     # alone
     csv = d / "curves.csv"
-    out, raster, err = run_cli(d, WDPM_POND_CURVES=str(csv))
+    out, raster, err = run_cli(d, JOB, WDPM_POND_CURVES=str(csv))
     assert (out, raster) == plain[:2] and "pond curves: %d pond" % len(table) in err
     said = re.search(r"\((\d+) without a curve, (\d+) flat, (\d+) cells below the last stage\)", err)
     assert said and tuple(map(int, said.groups())) == (stats["no_curve"], stats["flat"], stats["stage_cells"])
@@ -124,14 +108,14 @@ def test_csv_is_the_binding_table_and_nothing_else_changes(hip, job):
     assert got == want, next((a, b) for a, b in zip(got, want) if a != b) if len(got) == len(want) else (len(got), len(want))
     alone = open(csv, "rb").read()
     # beside the other four: one label call serves all five files
-    out, raster, err = run_cli(d, WDPM_POND_CURVES=str(csv), **OTHERS)
+    out, raster, err = run_cli(d, JOB, WDPM_POND_CURVES=str(csv), **OTHERS)
     assert (out, raster) == plain[:2]
     for k, v in OTHERS.items():
         assert open(d / v, "rb").read() == before[k], k
         os.remove(d / v)
     assert open(csv, "rb").read() == alone
     # beside one of them
-    out, raster, err = run_cli(d, WDPM_POND_CURVES=str(csv), WDPM_POND_RIMS="rims.csv")
+    out, raster, err = run_cli(d, JOB, WDPM_POND_CURVES=str(csv), WDPM_POND_RIMS="rims.csv")
     assert (out, raster) == plain[:2] and open(d / "rims.csv", "rb").read() == before["WDPM_POND_RIMS"]
     assert open(csv, "rb").read() == alone
     os.remove(d / "rims.csv")
@@ -140,7 +124,7 @@ def test_csv_is_the_binding_table_and_nothing_else_changes(hip, job):
 
 def test_two_row_blocks_are_refused_after_a_complete_run(job):
     d, plain, before = job
-    out, raster, err = run_cli(d, status=4, WDPM_DEVICES="0,0", WDPM_POND_CURVES=str(d / "curves.csv"), WDPM_PONDS="ponds.csv")
+    out, raster, err = run_cli(d, JOB, status=4, WDPM_DEVICES="0,0", WDPM_POND_CURVES=str(d / "curves.csv"), WDPM_PONDS="ponds.csv")
     assert (out, raster) == plain[:2]
     assert "pond curves" in err and "row blocks" in err and not os.path.exists(d / "curves.csv")
     assert open(d / "ponds.csv", "rb").read() == before["WDPM_PONDS"]

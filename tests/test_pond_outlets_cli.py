@@ -7,32 +7,16 @@ import gzip
 import os
 import re
 import shutil
-import subprocess
-import sys
 import types
 
-import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
-
-sys.path.insert(0, GOLDEN)
-from make_golden import strip_timing  # noqa: E402
+from conftest import GOLDEN
+from pond_cli import ADD_MM, ITER, job_args, read_asc, run_cli
 
 pytestmark = pytest.mark.gpu
-HIP_CLI = os.path.join(ROOT, "wdpm_amd", "bin", "WDPMCL")
 COLUMNS = "label,pour_level_m,headroom_m,from_row,from_col,to_row,to_col,to_label,divide_cells,fill_cells,fill_area_m2,fill_q,fill_m3"
 MISS = -99999.0
-ADD_MM, ITER = 300, 1000
-STRIPPED = ("WDPM_GPUS", "WDPM_DEVICES", "WDPM_PONDS", "WDPM_POND_RIMS", "WDPM_POND_CATCHMENTS", "WDPM_POND_OUTLETS",
-            "WDPM_PONDS_MIN_DEPTH_MM")
-
-
-def read_asc(path):
-    with open(path) as f:
-        hdr = [f.readline().split() for _ in range(6)]
-        vals = np.array(f.read().split(), dtype=np.float64)
-    return vals.reshape(int(float(hdr[1][1])), int(float(hdr[0][1]))), float(hdr[4][1])
 
 
 def binding_outlets(hip, dem, min_depth):
@@ -71,15 +55,6 @@ def parse_csv(path):
     return [tuple(k(v) for k, v in zip(kinds, ln.split(","), strict=True)) for ln in lines[1:]]
 
 
-def run_cli(cwd, dem, status=0, **env):
-    base = {k: v for k, v in os.environ.items() if k not in STRIPPED}
-    args = [HIP_CLI, "add", dem, "NULL", "out.asc", "NULL", str(ADD_MM), "1.0", "1.0", "0", "0", "0.005", str(ITER)]
-    p = subprocess.run(args, cwd=cwd, capture_output=True, text=True, timeout=600, env=dict(base, **env))
-    assert p.returncode == status, p.stderr[-3000:]
-    with open(os.path.join(cwd, "out.asc"), "rb") as f:
-        return strip_timing(p.stdout), f.read(), p.stderr
-
-
 @pytest.fixture(scope="module")
 def job(tmp_path_factory, hip):
     """basin5; the run with none of the variables; the three other files of a run without the new variable"""
@@ -87,9 +62,9 @@ def job(tmp_path_factory, hip):
     with gzip.open(os.path.join(GOLDEN, "basin5.asc.gz"), "rb") as f, open(d / "basin5.asc", "wb") as g:
         shutil.copyfileobj(f, g)
     dem_path = str(d / "basin5.asc")
-    plain = run_cli(d, dem_path)
+    plain = run_cli(d, job_args(dem_path))
     before = {"WDPM_PONDS": d / "ponds_before.csv", "WDPM_POND_RIMS": d / "rims_before.csv", "WDPM_POND_CATCHMENTS": d / "catch_before.csv"}
-    assert run_cli(d, dem_path, **{k: str(v) for k, v in before.items()})[:2] == plain[:2]
+    assert run_cli(d, job_args(dem_path), **{k: str(v) for k, v in before.items()})[:2] == plain[:2]
     return d, dem_path, plain, {k: open(v, "rb").read() for k, v in before.items()}
 
 
@@ -101,7 +76,7 @@ def test_csv_is_the_binding_table_and_nothing_else_changes(hip, job, tmp_path):
     assert len(want) >= 1 and any(r[3] >= 0 for r in want)
     # alone
     csv = tmp_path / "outlets.csv"
-    out, raster, err = run_cli(tmp_path, dem_path, WDPM_POND_OUTLETS=str(csv))
+    out, raster, err = run_cli(tmp_path, job_args(dem_path), WDPM_POND_OUTLETS=str(csv))
     assert (out, raster) == plain[:2] and "pond outlets: %d pond" % len(want) in err
     said = re.search(r"\((\d+) without an outlet, (\d+) spill onto land that ends in a pit, (\d+) cells on the divides\)", err)
     assert said and tuple(map(int, said.groups())) == (stats["no_outlet"], stats["to_land"], stats["divide_cells"])
@@ -111,14 +86,14 @@ def test_csv_is_the_binding_table_and_nothing_else_changes(hip, job, tmp_path):
     alone = open(csv, "rb").read()
     # beside the other three: one label call serves all four files
     others = {"WDPM_PONDS": tmp_path / "ponds.csv", "WDPM_POND_RIMS": tmp_path / "rims.csv", "WDPM_POND_CATCHMENTS": tmp_path / "catch.csv"}
-    out, raster, err = run_cli(tmp_path, dem_path, WDPM_POND_OUTLETS=str(csv), **{k: str(v) for k, v in others.items()})
+    out, raster, err = run_cli(tmp_path, job_args(dem_path), WDPM_POND_OUTLETS=str(csv), **{k: str(v) for k, v in others.items()})
     assert (out, raster) == plain[:2]
     for k, v in others.items():
         assert open(v, "rb").read() == before[k], k
     assert open(csv, "rb").read() == alone
     # beside one of them
     os.remove(others["WDPM_POND_RIMS"])
-    out, raster, err = run_cli(tmp_path, dem_path, WDPM_POND_OUTLETS=str(csv), WDPM_POND_RIMS=str(others["WDPM_POND_RIMS"]))
+    out, raster, err = run_cli(tmp_path, job_args(dem_path), WDPM_POND_OUTLETS=str(csv), WDPM_POND_RIMS=str(others["WDPM_POND_RIMS"]))
     assert (out, raster) == plain[:2] and open(others["WDPM_POND_RIMS"], "rb").read() == before["WDPM_POND_RIMS"]
     assert open(csv, "rb").read() == alone
 
@@ -127,14 +102,14 @@ def test_min_depth_variable(hip, job, tmp_path):
     d, dem_path, plain, _ = job
     dem, cellsize = read_asc(dem_path)
     csv = tmp_path / "outlets.csv"
-    run_cli(tmp_path, dem_path, WDPM_POND_OUTLETS=str(csv), WDPM_PONDS_MIN_DEPTH_MM="50")
+    run_cli(tmp_path, job_args(dem_path), WDPM_POND_OUTLETS=str(csv), WDPM_PONDS_MIN_DEPTH_MM="50")
     table, rims, _ = binding_outlets(hip, dem, 0.05)
     assert parse_csv(csv) == expected_rows(table, rims, cellsize)
 
 
 def test_two_row_blocks_are_refused_after_a_complete_run(job, tmp_path):
     d, dem_path, plain, before = job
-    out, raster, err = run_cli(tmp_path, dem_path, status=4, WDPM_DEVICES="0,0", WDPM_POND_OUTLETS=str(tmp_path / "outlets.csv"),
+    out, raster, err = run_cli(tmp_path, job_args(dem_path), status=4, WDPM_DEVICES="0,0", WDPM_POND_OUTLETS=str(tmp_path / "outlets.csv"),
                                WDPM_PONDS=str(tmp_path / "ponds.csv"))
     assert (out, raster) == plain[:2]
     assert "pond outlets" in err and "row blocks" in err and not os.path.exists(tmp_path / "outlets.csv")

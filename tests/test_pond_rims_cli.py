@@ -5,31 +5,16 @@ status 4 after a run whose own outputs - and whose WDPM_PONDS file - are complet
 import gzip
 import os
 import shutil
-import subprocess
-import sys
 import types
 
-import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
-
-sys.path.insert(0, GOLDEN)
-from make_golden import strip_timing  # noqa: E402
+from conftest import GOLDEN
+from pond_cli import ADD_MM, ITER, job_args, read_asc, run_cli
 
 pytestmark = pytest.mark.gpu
-HIP_CLI = os.path.join(ROOT, "wdpm_amd", "bin", "WDPMCL")
 COLUMNS = "label,surface_min_m,surface_max_m,rim_level_m,freeboard_m,rim_row,rim_col,rim_cells,wall_cells"
 MISS = -99999.0
-ADD_MM, ITER = 300, 1000
-STRIPPED = ("WDPM_GPUS", "WDPM_DEVICES", "WDPM_PONDS", "WDPM_POND_RIMS", "WDPM_PONDS_MIN_DEPTH_MM")
-
-
-def read_asc(path):
-    with open(path) as f:
-        hdr = [f.readline().split() for _ in range(6)]
-        vals = np.array(f.read().split(), dtype=np.float64)
-    return vals.reshape(int(float(hdr[1][1])), int(float(hdr[0][1])))
 
 
 def binding_rims(hip, dem, min_depth):
@@ -66,15 +51,6 @@ def parse_csv(path):
     return [tuple(k(v) for k, v in zip(kinds, ln.split(","), strict=True)) for ln in lines[1:]]
 
 
-def run_cli(cwd, dem, status=0, **env):
-    base = {k: v for k, v in os.environ.items() if k not in STRIPPED}
-    args = [HIP_CLI, "add", dem, "NULL", "out.asc", "NULL", str(ADD_MM), "1.0", "1.0", "0", "0", "0.005", str(ITER)]
-    p = subprocess.run(args, cwd=cwd, capture_output=True, text=True, timeout=600, env=dict(base, **env))
-    assert p.returncode == status, p.stderr[-3000:]
-    with open(os.path.join(cwd, "out.asc"), "rb") as f:
-        return strip_timing(p.stdout), f.read(), p.stderr
-
-
 @pytest.fixture(scope="module")
 def job(tmp_path_factory, hip):
     """basin5, the run with neither variable, and the rim table of the binding at the default threshold"""
@@ -82,26 +58,26 @@ def job(tmp_path_factory, hip):
     with gzip.open(os.path.join(GOLDEN, "basin5.asc.gz"), "rb") as f, open(d / "basin5.asc", "wb") as g:
         shutil.copyfileobj(f, g)
     dem_path = str(d / "basin5.asc")
-    plain = run_cli(d, dem_path)
+    plain = run_cli(d, job_args(dem_path))
     ponds_alone = d / "ponds_alone.csv"
-    assert run_cli(d, dem_path, WDPM_PONDS=str(ponds_alone))[:2] == plain[:2]
+    assert run_cli(d, job_args(dem_path), WDPM_PONDS=str(ponds_alone))[:2] == plain[:2]
     return d, dem_path, plain, open(ponds_alone, "rb").read()
 
 
 def test_csv_is_the_binding_table_and_nothing_else_changes(hip, job, tmp_path):
     d, dem_path, plain, ponds_alone = job
-    want = expected_rows(binding_rims(hip, read_asc(dem_path), 0.001))
+    want = expected_rows(binding_rims(hip, read_asc(dem_path)[0], 0.001))
     assert len(want) >= 1 and any(r[7] > 0 for r in want)
     # alone
     csv = tmp_path / "rims.csv"
-    out, raster, err = run_cli(tmp_path, dem_path, WDPM_POND_RIMS=str(csv))
+    out, raster, err = run_cli(tmp_path, job_args(dem_path), WDPM_POND_RIMS=str(csv))
     assert (out, raster) == plain[:2] and "pond rims: %d pond" % len(want) in err
     assert not os.path.exists(tmp_path / "ponds.csv")
     got = parse_csv(csv)
     assert got == want, next((a, b) for a, b in zip(got, want) if a != b) if len(got) == len(want) else (len(got), len(want))
     alone = open(csv, "rb").read()
     # beside WDPM_PONDS: one label call serves both files
-    out, raster, err = run_cli(tmp_path, dem_path, WDPM_POND_RIMS=str(csv), WDPM_PONDS=str(tmp_path / "ponds.csv"))
+    out, raster, err = run_cli(tmp_path, job_args(dem_path), WDPM_POND_RIMS=str(csv), WDPM_PONDS=str(tmp_path / "ponds.csv"))
     assert (out, raster) == plain[:2]
     assert open(tmp_path / "ponds.csv", "rb").read() == ponds_alone and open(csv, "rb").read() == alone
 
@@ -109,13 +85,13 @@ def test_csv_is_the_binding_table_and_nothing_else_changes(hip, job, tmp_path):
 def test_min_depth_variable(hip, job, tmp_path):
     d, dem_path, plain, _ = job
     csv = tmp_path / "rims.csv"
-    run_cli(tmp_path, dem_path, WDPM_POND_RIMS=str(csv), WDPM_PONDS_MIN_DEPTH_MM="50")
-    assert parse_csv(csv) == expected_rows(binding_rims(hip, read_asc(dem_path), 0.05))
+    run_cli(tmp_path, job_args(dem_path), WDPM_POND_RIMS=str(csv), WDPM_PONDS_MIN_DEPTH_MM="50")
+    assert parse_csv(csv) == expected_rows(binding_rims(hip, read_asc(dem_path)[0], 0.05))
 
 
 def test_two_row_blocks_are_refused_after_a_complete_run(job, tmp_path):
     d, dem_path, plain, ponds_alone = job
-    out, raster, err = run_cli(tmp_path, dem_path, status=4, WDPM_DEVICES="0,0", WDPM_POND_RIMS=str(tmp_path / "rims.csv"),
+    out, raster, err = run_cli(tmp_path, job_args(dem_path), status=4, WDPM_DEVICES="0,0", WDPM_POND_RIMS=str(tmp_path / "rims.csv"),
                                WDPM_PONDS=str(tmp_path / "ponds.csv"))
     assert (out, raster) == plain[:2]
     assert "pond rims" in err and "row blocks" in err and not os.path.exists(tmp_path / "rims.csv")

@@ -6,34 +6,17 @@ import gzip
 import os
 import re
 import shutil
-import subprocess
-import sys
 import types
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
-
-sys.path.insert(0, GOLDEN)
-from make_golden import strip_timing  # noqa: E402
+from conftest import GOLDEN
+from pond_cli import ADD_MM, ITER, job_args, read_asc, run_cli
 
 pytestmark = pytest.mark.gpu
-HIP_CLI = os.path.join(ROOT, "wdpm_amd", "bin", "WDPMCL")
 COLUMNS = "label,row,col,cells,area_m2,volume_q,volume_m3,max_depth_m,row_min,row_max,col_min,col_max"
 MISS = -99999.0
-ADD_MM, ITER = 300, 1000        # one block of 1000 iterations
-
-
-def job_args(dem):
-    return ["add", dem, "NULL", "out.asc", "NULL", str(ADD_MM), "1.0", "1.0", "0", "0", "0.005", str(ITER)]
-
-
-def read_asc(path):
-    with open(path) as f:
-        hdr = [f.readline().split() for _ in range(6)]
-        vals = np.array(f.read().split(), dtype=np.float64)
-    return vals.reshape(int(float(hdr[1][1])), int(float(hdr[0][1]))), float(hdr[4][1])
 
 
 def binding_inventory(hip, dem, min_depth):
@@ -72,14 +55,6 @@ def parse_csv(path):
     return [tuple(k(v) for k, v in zip(kinds, ln.split(","), strict=True)) for ln in lines[1:]]
 
 
-def run_cli(cwd, dem, **env):
-    base = {k: v for k, v in os.environ.items() if k not in ("WDPM_GPUS", "WDPM_DEVICES", "WDPM_PONDS", "WDPM_PONDS_MIN_DEPTH_MM")}
-    p = subprocess.run([HIP_CLI] + job_args(dem), cwd=cwd, capture_output=True, text=True, timeout=600, env=dict(base, **env))
-    assert p.returncode == 0, p.stderr[-3000:]
-    with open(os.path.join(cwd, "out.asc"), "rb") as f:
-        return strip_timing(p.stdout), f.read(), p.stderr
-
-
 @pytest.fixture(scope="module")
 def rasters(tmp_path_factory, hip):
     d = tmp_path_factory.mktemp("ponds_cli")
@@ -100,11 +75,11 @@ def test_csv_is_the_binding_inventory_and_nothing_else_changes(hip, rasters, nam
     want, wet = binding_inventory(hip, dem, 0.001)
     want = expected_rows(want, cellsize)
     assert len(want) >= 1 and sum(r[3] for r in want) == wet          # the default threshold is the reference's wet threshold
-    plain = run_cli(tmp_path, dem_path)
+    plain = run_cli(tmp_path, job_args(dem_path))
     assert not os.path.exists(tmp_path / "ponds.csv")
     for tag, devices in (("one", {}), ("two", {"WDPM_DEVICES": "0,0"})):
         csv = tmp_path / f"ponds_{tag}.csv"
-        out, raster, err = run_cli(tmp_path, dem_path, WDPM_PONDS=str(csv), WDPM_TIMING="1", **devices)
+        out, raster, err = run_cli(tmp_path, job_args(dem_path), WDPM_PONDS=str(csv), WDPM_TIMING="1", **devices)
         assert (out, raster) == plain[:2], tag
         assert ("2 devices" in err) == (tag == "two")
         assert re.search(r"^WDPMCL timing: pond inventory +[0-9.]+ s$", err, flags=re.M), err      # the phase line of WDPM_TIMING=1
@@ -119,5 +94,5 @@ def test_min_depth_variable(hip, rasters, tmp_path, mm):
     dem, cellsize = read_asc(dem_path)
     want, _ = binding_inventory(hip, dem, float(mm) / 1000.0)
     csv = tmp_path / "ponds.csv"
-    run_cli(tmp_path, dem_path, WDPM_PONDS=str(csv), WDPM_PONDS_MIN_DEPTH_MM=mm)
+    run_cli(tmp_path, job_args(dem_path), WDPM_PONDS=str(csv), WDPM_PONDS_MIN_DEPTH_MM=mm)
     assert parse_csv(csv) == expected_rows(want, cellsize)

@@ -5,7 +5,7 @@
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd); W=$(mktemp -d); trap 'rm -rf $W' EXIT
 gcc -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -ffp-contract=off -o $W/WDPMCL_asan \
-    $R/wdpm_amd/csrc/wdpmcl_main.c $R/wdpm_amd/csrc/arcascii.c $R/oracle/wdpm_oracle.c $R/wdpm_amd/csrc/synth.c \
+    $R/wdpm_amd/csrc/wdpmcl_main.c $R/wdpm_amd/csrc/wdpmcl_ponds.c $R/wdpm_amd/csrc/arcascii.c $R/oracle/wdpm_oracle.c $R/wdpm_amd/csrc/synth.c \
     $R/wdpm_amd/csrc/wdpm_rowblock.c -lpthread -lm
 cd $W; zcat $R/tests/golden/basin5.asc.gz > basin5.asc
 run() { echo "== $*"; env "$@" > out.txt 2> err.txt || echo "exit code $?"; grep -E "ERROR|runtime error|leak" err.txt || true; }
@@ -30,7 +30,7 @@ PY
 fi
 # ThreadSanitizer on the threaded parts (checkpoint writer thread, rank threads of the row-block driver, threaded ArcASCII I/O)
 gcc -O1 -g -fsanitize=thread -ffp-contract=off -o $W/WDPMCL_tsan \
-    $R/wdpm_amd/csrc/wdpmcl_main.c $R/wdpm_amd/csrc/arcascii.c $R/oracle/wdpm_oracle.c $R/wdpm_amd/csrc/synth.c \
+    $R/wdpm_amd/csrc/wdpmcl_main.c $R/wdpm_amd/csrc/wdpmcl_ponds.c $R/wdpm_amd/csrc/arcascii.c $R/oracle/wdpm_oracle.c $R/wdpm_amd/csrc/synth.c \
     $R/wdpm_amd/csrc/wdpm_rowblock.c -lpthread -lm
 echo "== tsan"; WDPM_IO_THREADS=6 WDPM_SCRATCH_BINARY=1 ./WDPMCL_tsan add basin5.asc NULL a.asc s.asc 100 1.0 1.0 0 0 0.005 3000 > out.txt 2> err.txt || echo "exit code $?"
 grep -c "WARNING: ThreadSanitizer" err.txt || true

@@ -24,6 +24,7 @@
  *     devices 0..N-1 by row blocks (WDPM_DEVICES=a,b,c names them explicitly), one host thread per device,
  *     exchanging halo rows every WDPM_EXCHANGE_EVERY iterations (default 8) by RCCL send/recv
  *     (WDPM_HALO=peer: peer copies); results do not depend on N.
+ *   - WDPM_PONDS=<path> and its four siblings write CSV files about the ponds of the final water: wdpmcl_ponds.c.
  */
 #include <ctype.h>
 #include <math.h>
@@ -37,37 +38,8 @@
 #include <unistd.h>
 
 #include "../../include/wdpm.h"
-#include "../../include/wdpm_group_ponds.h"
-#include "../../include/wdpm_pond_rims.h"
-#include "../../include/wdpm_pond_catchments.h"
-#include "../../include/wdpm_pond_outlets.h"
-#include "../../include/wdpm_pond_curves.h"
-/* the pond inventory is the HIP library's alone: weak references, so that this file also links against a back-end that
- * exports include/wdpm.h and nothing else (WDPM_PONDS then says so and writes no file) */
-#pragma weak wdpm_ponds_create
-#pragma weak wdpm_ponds_destroy
-#pragma weak wdpm_ponds_label
-#pragma weak wdpm_ponds_table
-#pragma weak wdpm_ponds_guard_bad
-#pragma weak wdpm_group_ponds_create
-#pragma weak wdpm_group_ponds_destroy
-#pragma weak wdpm_group_ponds_label
-#pragma weak wdpm_group_ponds_table
-#pragma weak wdpm_group_ponds_guard_bad
-#pragma weak wdpm_group_ponds_stats
-#pragma weak wdpm_rims_label
-#pragma weak wdpm_rims_table
-#pragma weak wdpm_catch_label
-#pragma weak wdpm_catch_table
-#pragma weak wdpm_catch_stats
-#pragma weak wdpm_outlets_label
-#pragma weak wdpm_outlets_table
-#pragma weak wdpm_outlets_stats
-#pragma weak wdpm_curves_label
-#pragma weak wdpm_curves_table
-#pragma weak wdpm_curves_stats
-#pragma weak wdpm_curves_stage_level
 #include "arcascii.h"
+#include "wdpmcl_ponds.h"
 
 #define ITER_PER_BLOCK 1000 /* IterationNum, WDPMCL.c:597 */
 
@@ -651,263 +623,6 @@ static void relief_finish(relief_helper *h) {
   }
 }
 
-/* ---- pond inventory (include/wdpm_ponds.h) ----
- * WDPM_PONDS=<path>: the 8-connected water bodies of the final water, one CSV line per pond, numbered by first cell.  A pond
- * cell holds more than WDPM_PONDS_MIN_DEPTH_MM of water (default 1.0: the reference's own wet threshold, water > 0.001,
- * WDPMCL.c:1397-1404, so the cells column sums to the wet count of the final statistics).  Nothing of it goes to stdout. */
-typedef struct {
-  wdpm_pond *rows; int64_t n; int64_t guard_bad; int64_t blocks, joined; wdpm_pond_rim *rims;
-  wdpm_pond_catchment *catch; wdpm_pond_catchment_stats catch_stats;
-  wdpm_pond_outlet *outlets; wdpm_pond_outlet_stats outlet_stats;
-  wdpm_pond_curve *curves; wdpm_pond_curve_stats curve_stats;
-} pond_inventory;
-
-/* with_rims (WDPM_POND_RIMS, include/wdpm_pond_rims.h; the caller has seen that the back-end has them): one wdpm_rims_label serves
- * the pond table and the rim table.  with_catch (WDPM_POND_CATCHMENTS, include/wdpm_pond_catchments.h; likewise): one
- * wdpm_catch_label serves all three, whichever of the files are asked for.  with_outlets (WDPM_POND_OUTLETS,
- * include/wdpm_pond_outlets.h; likewise, and the caller then sets with_rims too: the headroom wants the surface): one
- * wdpm_outlets_label serves all four.  with_curves (WDPM_POND_CURVES, include/wdpm_pond_curves.h; likewise): one wdpm_curves_label
- * serves all five. */
-static int take_inventory(wdpm_ctx *c, double min_depth, pond_inventory *inv, int with_rims, int with_catch, int with_outlets,
-                          int with_curves) {
-  wdpm_ponds *h = NULL;
-  inv->rows = NULL;
-  inv->rims = NULL;
-  inv->catch = NULL;
-  inv->outlets = NULL;
-  inv->curves = NULL;
-  inv->n = 0;
-  inv->guard_bad = 0;
-  inv->blocks = 1;
-  inv->joined = 0;
-  if (!wdpm_ponds_create || !wdpm_ponds_destroy || !wdpm_ponds_label || !wdpm_ponds_table || !wdpm_ponds_guard_bad) {
-    fprintf(stderr, "WDPMCL: pond inventory: back-end %s has none, no file written\n", wdpm_backend_name());
-    return 1;
-  }
-  int rc = wdpm_ponds_create(&h, c);
-  if (!rc)
-    rc = with_curves  ? wdpm_curves_label(h, min_depth, &inv->n)
-       : with_outlets ? wdpm_outlets_label(h, min_depth, &inv->n)
-         : with_catch ? wdpm_catch_label(h, min_depth, &inv->n)
-         : with_rims  ? wdpm_rims_label(h, min_depth, &inv->n)
-                      : wdpm_ponds_label(h, min_depth, &inv->n);
-  if (!rc) {
-    inv->rows = (wdpm_pond *)malloc((size_t)(inv->n > 0 ? inv->n : 1) * sizeof(wdpm_pond));
-    if (with_rims) inv->rims = (wdpm_pond_rim *)malloc((size_t)(inv->n > 0 ? inv->n : 1) * sizeof(wdpm_pond_rim));
-    if (with_catch) inv->catch = (wdpm_pond_catchment *)malloc((size_t)(inv->n > 0 ? inv->n : 1) * sizeof(wdpm_pond_catchment));
-    if (with_outlets) inv->outlets = (wdpm_pond_outlet *)malloc((size_t)(inv->n > 0 ? inv->n : 1) * sizeof(wdpm_pond_outlet));
-    if (with_curves) inv->curves = (wdpm_pond_curve *)malloc((size_t)(inv->n > 0 ? inv->n : 1) * sizeof(wdpm_pond_curve));
-    if (!inv->rows || (with_rims && !inv->rims) || (with_catch && !inv->catch) || (with_outlets && !inv->outlets) ||
-        (with_curves && !inv->curves)) {
-      wdpm_set_last_error("out of host memory for the pond table");
-      rc = 1;
-    }
-  }
-  if (!rc) rc = wdpm_ponds_table(h, inv->rows, inv->n);
-  if (!rc && with_rims) rc = wdpm_rims_table(h, inv->rims, inv->n);
-  if (!rc && with_catch) rc = wdpm_catch_table(h, inv->catch, inv->n);
-  if (!rc && with_catch) rc = wdpm_catch_stats(h, &inv->catch_stats);
-  if (!rc && with_outlets) rc = wdpm_outlets_table(h, inv->outlets, inv->n);
-  if (!rc && with_outlets) rc = wdpm_outlets_stats(h, &inv->outlet_stats);
-  if (!rc && with_curves) rc = wdpm_curves_table(h, inv->curves, inv->n);
-  if (!rc && with_curves) rc = wdpm_curves_stats(h, &inv->curve_stats);
-  if (!rc && getenv("WDPM_GUARD_KB")) rc = wdpm_ponds_guard_bad(h, &inv->guard_bad);
-  if (rc) {
-    fprintf(stderr, "WDPMCL: pond inventory failed, no file written: %s\n", wdpm_last_error());
-    free(inv->rows);
-    free(inv->rims);
-    free(inv->catch);
-    free(inv->outlets);
-    free(inv->curves);
-    inv->rows = NULL;
-    inv->rims = NULL;
-    inv->catch = NULL;
-    inv->outlets = NULL;
-    inv->curves = NULL;
-  }
-  wdpm_ponds_destroy(h);
-  return rc;
-}
-
-/* the same of a raster in several row blocks: every block is labelled where it lies (include/wdpm_group_ponds.h) */
-static int take_group_inventory(wdpm_group *grp, double min_depth, pond_inventory *inv) {
-  wdpm_group_ponds *h = NULL;
-  wdpm_group_pond_stats gs;
-  inv->rows = NULL;
-  inv->rims = NULL;
-  inv->catch = NULL;
-  inv->outlets = NULL;
-  inv->curves = NULL;
-  inv->n = 0;
-  inv->guard_bad = 0;
-  inv->blocks = 1;
-  inv->joined = 0;
-  if (!wdpm_group_ponds_create || !wdpm_group_ponds_destroy || !wdpm_group_ponds_label || !wdpm_group_ponds_table ||
-      !wdpm_group_ponds_guard_bad || !wdpm_group_ponds_stats) {
-    fprintf(stderr, "WDPMCL: pond inventory: back-end %s has none, no file written\n", wdpm_backend_name());
-    return 1;
-  }
-  int rc = wdpm_group_ponds_create(&h, grp);
-  if (!rc) rc = wdpm_group_ponds_label(h, min_depth, &inv->n);
-  if (!rc) rc = wdpm_group_ponds_stats(h, &gs);
-  if (!rc) {
-    inv->blocks = gs.ranks;
-    inv->joined = gs.merged;
-    inv->rows = (wdpm_pond *)malloc((size_t)(inv->n > 0 ? inv->n : 1) * sizeof(wdpm_pond));
-    if (!inv->rows) { wdpm_set_last_error("out of host memory for the pond table"); rc = 1; }
-  }
-  if (!rc) rc = wdpm_group_ponds_table(h, inv->rows, inv->n);
-  if (!rc && getenv("WDPM_GUARD_KB")) rc = wdpm_group_ponds_guard_bad(h, &inv->guard_bad);
-  if (rc) {
-    fprintf(stderr, "WDPMCL: pond inventory failed, no file written: %s\n", wdpm_last_error());
-    free(inv->rows);
-    inv->rows = NULL;
-  }
-  if (h) wdpm_group_ponds_destroy(h);
-  return rc;
-}
-
-/* coordinates leave as file coordinates, 0-based (padded - 1); doubles as %.17g so that they read back exactly */
-static int write_inventory(const char *path, const pond_inventory *inv, double cellarea) {
-  FILE *f = fopen(path, "w");
-  if (!f) {
-    fprintf(stderr, "WDPMCL: cannot write pond inventory %s\n", path);
-    return 1;
-  }
-  fprintf(f, "label,row,col,cells,area_m2,volume_q,volume_m3,max_depth_m,row_min,row_max,col_min,col_max\n");
-  for (int64_t k = 0; k < inv->n; k++) {
-    const wdpm_pond *q = &inv->rows[k];
-    fprintf(f, "%lld,%d,%d,%lld,%.17g,%llu,%.17g,%.17g,%d,%d,%d,%d\n", (long long)(k + 1), q->first_row - 1, q->first_col - 1,
-            (long long)q->cells, (double)q->cells * cellarea, (unsigned long long)q->volume_q,
-            ldexp((double)q->volume_q, -24) * cellarea, q->max_depth, q->row_min - 1, q->row_max - 1, q->col_min - 1,
-            q->col_max - 1);
-  }
-  const int bad = ferror(f);
-  if (fclose(f) != 0 || bad) {
-    fprintf(stderr, "WDPMCL: error writing pond inventory %s\n", path);
-    return 1;
-  }
-  fprintf(stderr, "WDPMCL: pond inventory: %lld pond%s written to %s", (long long)inv->n, inv->n == 1 ? "" : "s", path);
-  if (inv->blocks > 1) fprintf(stderr, " (%lld row blocks, %lld joined across them)", (long long)inv->blocks, (long long)inv->joined);
-  fprintf(stderr, "\n");
-  return 0;
-}
-
-/* WDPM_POND_RIMS=<path>: one CSV line per pond of the same inventory: the spread of its water surface, its spill level and where
- * that lies (file coordinates, 0-based; -1 without a rim cell), its freeboard = rim level - highest surface, its shoreline and
- * its walls (include/wdpm_pond_rims.h).  Doubles as %.17g. */
-static int write_rims(const char *path, const pond_inventory *inv) {
-  FILE *f = fopen(path, "w");
-  if (!f) {
-    fprintf(stderr, "WDPMCL: cannot write pond rims %s\n", path);
-    return 1;
-  }
-  fprintf(f, "label,surface_min_m,surface_max_m,rim_level_m,freeboard_m,rim_row,rim_col,rim_cells,wall_cells\n");
-  for (int64_t k = 0; k < inv->n; k++) {
-    const wdpm_pond_rim *q = &inv->rims[k];
-    const int none = q->rim_row < 0;
-    fprintf(f, "%lld,%.17g,%.17g,%.17g,%.17g,%d,%d,%lld,%lld\n", (long long)(k + 1), q->surface_min, q->surface_max, q->rim_level,
-            q->rim_level - q->surface_max, none ? -1 : q->rim_row - 1, none ? -1 : q->rim_col - 1, (long long)q->rim_cells,
-            (long long)q->wall_cells);
-  }
-  const int bad = ferror(f);
-  if (fclose(f) != 0 || bad) {
-    fprintf(stderr, "WDPMCL: error writing pond rims %s\n", path);
-    return 1;
-  }
-  fprintf(stderr, "WDPMCL: pond rims: %lld pond%s written to %s\n", (long long)inv->n, inv->n == 1 ? "" : "s", path);
-  return 0;
-}
-
-/* WDPM_POND_CATCHMENTS=<path>: one CSV line per pond of the same inventory: the dry cells that drain to it and their area, the cells
- * through which the land's water enters it, the highest level among the cells that drain to it (-inf: none does) and the box of
- * pond and catchment together (file coordinates, 0-based) (include/wdpm_pond_catchments.h).  Doubles as %.17g. */
-static int write_catchments(const char *path, const pond_inventory *inv, double cellarea) {
-  FILE *f = fopen(path, "w");
-  if (!f) {
-    fprintf(stderr, "WDPMCL: cannot write pond catchments %s\n", path);
-    return 1;
-  }
-  fprintf(f, "label,catch_cells,catch_area_m2,inflow_cells,head_level_m,row_min,row_max,col_min,col_max\n");
-  for (int64_t k = 0; k < inv->n; k++) {
-    const wdpm_pond_catchment *q = &inv->catch[k];
-    fprintf(f, "%lld,%lld,%.17g,%lld,%.17g,%d,%d,%d,%d\n", (long long)(k + 1), (long long)q->catch_cells,
-            (double)q->catch_cells * cellarea, (long long)q->inflow_cells, q->head_level, q->row_min - 1, q->row_max - 1,
-            q->col_min - 1, q->col_max - 1);
-  }
-  const int bad = ferror(f);
-  if (fclose(f) != 0 || bad) {
-    fprintf(stderr, "WDPMCL: error writing pond catchments %s\n", path);
-    return 1;
-  }
-  const wdpm_pond_catchment_stats *cs = &inv->catch_stats;
-  fprintf(stderr, "WDPMCL: pond catchments: %lld pond%s written to %s (%lld slope cells, %lld pits, %lld cells drain to no pond, %lld rounds)\n",
-          (long long)inv->n, inv->n == 1 ? "" : "s", path, (long long)cs->slope_cells, (long long)cs->pit_cells,
-          (long long)cs->unponded_cells, (long long)cs->rounds);
-  return 0;
-}
-
-/* WDPM_POND_OUTLETS=<path>: one CSV line per pond of the same inventory: the level at which its basin spills and how far the
- * highest water surface is below it, the pass (file coordinates, 0-based; -1 without an outlet) and the basin beyond it (a label,
- * 0: land that ends in a pit, -1: none), the cells on the divide, and the cells flooded and the storage left when it spills
- * (include/wdpm_pond_outlets.h).  Doubles as %.17g. */
-static int write_outlets(const char *path, const pond_inventory *inv, double cellarea) {
-  FILE *f = fopen(path, "w");
-  if (!f) {
-    fprintf(stderr, "WDPMCL: cannot write pond outlets %s\n", path);
-    return 1;
-  }
-  fprintf(f, "label,pour_level_m,headroom_m,from_row,from_col,to_row,to_col,to_label,divide_cells,fill_cells,fill_area_m2,fill_q,fill_m3\n");
-  for (int64_t k = 0; k < inv->n; k++) {
-    const wdpm_pond_outlet *q = &inv->outlets[k];
-    const int none = q->from_row < 0;
-    fprintf(f, "%lld,%.17g,%.17g,%d,%d,%d,%d,%d,%lld,%lld,%.17g,%llu,%.17g\n", (long long)(k + 1), q->pour_level,
-            q->pour_level - inv->rims[k].surface_max, none ? -1 : q->from_row - 1, none ? -1 : q->from_col - 1,
-            none ? -1 : q->to_row - 1, none ? -1 : q->to_col - 1, q->to_basin, (long long)q->divide_cells, (long long)q->fill_cells,
-            (double)q->fill_cells * cellarea, (unsigned long long)q->fill_q, ldexp((double)q->fill_q, -24) * cellarea);
-  }
-  const int bad = ferror(f);
-  if (fclose(f) != 0 || bad) {
-    fprintf(stderr, "WDPMCL: error writing pond outlets %s\n", path);
-    return 1;
-  }
-  const wdpm_pond_outlet_stats *os = &inv->outlet_stats;
-  fprintf(stderr, "WDPMCL: pond outlets: %lld pond%s written to %s (%lld without an outlet, %lld spill onto land that ends in a pit, %lld cells on the divides)\n",
-          (long long)inv->n, inv->n == 1 ? "" : "s", path, (long long)os->no_outlet, (long long)os->to_land, (long long)os->divide_cells);
-  return 0;
-}
-
-/* WDPM_POND_CURVES=<path>: the stage curve of every pond of the same inventory (include/wdpm_pond_curves.h): one line `stage 0` with
- * the lowest ground of the pond's basin and zeros, and - where the pond has an outlet - one line per stage 1..16 with its level
- * (wdpm_curves_stage_level; stage 16 is the pour level), the cells of the basin whose ground lies below it and their area, and the
- * storage below it in quanta of 2^-24 m and in cubic metres.  Doubles as %.17g. */
-static int write_curves(const char *path, const pond_inventory *inv, double cellarea) {
-  FILE *f = fopen(path, "w");
-  if (!f) {
-    fprintf(stderr, "WDPMCL: cannot write pond curves %s\n", path);
-    return 1;
-  }
-  fprintf(f, "label,stage,level_m,cells,area_m2,q,volume_m3\n");
-  for (int64_t k = 0; k < inv->n; k++) {
-    const wdpm_pond_curve *v = &inv->curves[k];
-    fprintf(f, "%lld,0,%.17g,0,%.17g,0,%.17g\n", (long long)(k + 1), v->bed_level, 0.0, 0.0);
-    if (!(v->top_level < INFINITY)) continue;
-    for (int s = 1; s <= WDPM_CURVE_STAGES; s++)
-      fprintf(f, "%lld,%d,%.17g,%lld,%.17g,%llu,%.17g\n", (long long)(k + 1), s, wdpm_curves_stage_level(v->bed_level, v->top_level, s),
-              (long long)v->cells[s - 1], (double)v->cells[s - 1] * cellarea, (unsigned long long)v->q[s - 1],
-              ldexp((double)v->q[s - 1], -24) * cellarea);
-  }
-  const int bad = ferror(f);
-  if (fclose(f) != 0 || bad) {
-    fprintf(stderr, "WDPMCL: error writing pond curves %s\n", path);
-    return 1;
-  }
-  const wdpm_pond_curve_stats *vs = &inv->curve_stats;
-  fprintf(stderr, "WDPMCL: pond curves: %lld pond%s written to %s (%lld without a curve, %lld flat, %lld cells below the last stage)\n",
-          (long long)inv->n, inv->n == 1 ? "" : "s", path, (long long)vs->no_curve, (long long)vs->flat, (long long)vs->stage_cells);
-  return 0;
-}
-
 #define ABI_TRY(call)                                                      \
   do {                                                                     \
     if ((call) != 0) {                                                     \
@@ -1132,92 +847,9 @@ int main(int argc, char **argv) {
   ABI_TRY(wdpm_group_count_stats(ctx, NULL, &wet, &dev_max));
   ABI_TRY(wdpm_group_download_unpadded(ctx, 1, st.water));
   if (cfg.module == WDPM_DRAIN) ABI_TRY(wdpm_group_get_totaldrain(ctx, &totaldrain));
-  /* the pond inventory of the final water (WDPM_PONDS), taken on the group before it goes: on its one context, or over its row
-   * blocks with every block labelled where it lies */
-  const char *ponds_path = getenv("WDPM_PONDS");
-  if (ponds_path && !*ponds_path) ponds_path = NULL;
-  const double ponds_min_depth = (getenv("WDPM_PONDS_MIN_DEPTH_MM") ? atof(getenv("WDPM_PONDS_MIN_DEPTH_MM")) : 1.0) / 1000.0;
-  /* ... and the rims of the same ponds (WDPM_POND_RIMS), alone or beside it: whole rasters only */
-  const char *rims_path = getenv("WDPM_POND_RIMS");
-  if (rims_path && !*rims_path) rims_path = NULL;
-  pond_inventory inv;
-  memset(&inv, 0, sizeof inv);
-  int ponds_failed = 0;
-  if (rims_path && ndev > 1) {
-    fprintf(stderr, "WDPMCL: pond rims: the raster lies in %d row blocks and rims are taken on a whole raster only, no file written to %s\n",
-            ndev, rims_path);
-    ponds_failed = 1;
-    rims_path = NULL;
-  }
-  if (rims_path && (!wdpm_rims_label || !wdpm_rims_table)) {
-    fprintf(stderr, "WDPMCL: pond rims: back-end %s has none, no file written\n", wdpm_backend_name());
-    ponds_failed = 1;
-    rims_path = NULL;
-  }
-  /* ... and their catchments (WDPM_POND_CATCHMENTS), alone or beside either: whole rasters only as well */
-  const char *catch_path = getenv("WDPM_POND_CATCHMENTS");
-  if (catch_path && !*catch_path) catch_path = NULL;
-  if (catch_path && ndev > 1) {
-    fprintf(stderr, "WDPMCL: pond catchments: the raster lies in %d row blocks and catchments are taken on a whole raster only, no file written to %s\n",
-            ndev, catch_path);
-    ponds_failed = 1;
-    catch_path = NULL;
-  }
-  if (catch_path && (!wdpm_catch_label || !wdpm_catch_table || !wdpm_catch_stats || !wdpm_rims_table)) {
-    fprintf(stderr, "WDPMCL: pond catchments: back-end %s has none, no file written\n", wdpm_backend_name());
-    ponds_failed = 1;
-    catch_path = NULL;
-  }
-  /* ... and their outlets (WDPM_POND_OUTLETS), alone or beside any of them: whole rasters only */
-  const char *outlets_path = getenv("WDPM_POND_OUTLETS");
-  if (outlets_path && !*outlets_path) outlets_path = NULL;
-  if (outlets_path && ndev > 1) {
-    fprintf(stderr, "WDPMCL: pond outlets: the raster lies in %d row blocks and outlets are taken on a whole raster only, no file written to %s\n",
-            ndev, outlets_path);
-    ponds_failed = 1;
-    outlets_path = NULL;
-  }
-  if (outlets_path && (!wdpm_outlets_label || !wdpm_outlets_table || !wdpm_outlets_stats || !wdpm_rims_table || !wdpm_catch_table ||
-                       !wdpm_catch_stats)) {
-    fprintf(stderr, "WDPMCL: pond outlets: back-end %s has none, no file written\n", wdpm_backend_name());
-    ponds_failed = 1;
-    outlets_path = NULL;
-  }
-  /* ... and their stage curves (WDPM_POND_CURVES), alone or beside any of them: whole rasters only */
-  const char *curves_path = getenv("WDPM_POND_CURVES");
-  if (curves_path && !*curves_path) curves_path = NULL;
-  if (curves_path && ndev > 1) {
-    fprintf(stderr, "WDPMCL: pond curves: the raster lies in %d row blocks and stage curves are taken on a whole raster only, no file written to %s\n",
-            ndev, curves_path);
-    ponds_failed = 1;
-    curves_path = NULL;
-  }
-  if (curves_path && (!wdpm_curves_label || !wdpm_curves_table || !wdpm_curves_stats || !wdpm_curves_stage_level || !wdpm_outlets_table ||
-                      !wdpm_outlets_stats || !wdpm_rims_table || !wdpm_catch_table || !wdpm_catch_stats)) {
-    fprintf(stderr, "WDPMCL: pond curves: back-end %s has none, no file written\n", wdpm_backend_name());
-    ponds_failed = 1;
-    curves_path = NULL;
-  }
-  if (ponds_path || rims_path || catch_path || outlets_path || curves_path) {
-    phase("statistics + download");
-    const int failed = ndev == 1 ? take_inventory(wdpm_rank_ctx(wdpm_group_rank(ctx, 0)), ponds_min_depth, &inv,
-                                                  rims_path != NULL || catch_path != NULL || outlets_path != NULL,
-                                                  catch_path != NULL || outlets_path != NULL, outlets_path != NULL, curves_path != NULL)
-                                 : take_group_inventory(ctx, ponds_min_depth, &inv);
-    if (failed) ponds_failed = 1;
-    if (!failed && ponds_path && write_inventory(ponds_path, &inv, st.cellarea)) ponds_failed = 1;
-    if (!failed && rims_path && write_rims(rims_path, &inv)) ponds_failed = 1;
-    if (!failed && catch_path && write_catchments(catch_path, &inv, st.cellarea)) ponds_failed = 1;
-    if (!failed && outlets_path && write_outlets(outlets_path, &inv, st.cellarea)) ponds_failed = 1;
-    if (!failed && curves_path && write_curves(curves_path, &inv, st.cellarea)) ponds_failed = 1;
-    free(inv.rows);
-    free(inv.rims);
-    free(inv.catch);
-    free(inv.outlets);
-    free(inv.curves);
-    phase("pond inventory");
-  }
-  int64_t guard_bad = inv.guard_bad;
+  /* the pond files asked for in the environment (wdpmcl_ponds.h), taken on the group before it goes */
+  int64_t guard_bad = 0;
+  const int ponds_failed = wdpmcl_pond_files(ctx, ndev, st.cellarea, &guard_bad, phase);
   if (getenv("WDPM_GUARD_KB")) {   /* debugging aid (include/wdpm.h: WDPM_OPT_GUARD_BAD): did any kernel write outside its buffer? */
     for (int i = 0; i < ndev; i++) {
       int64_t bad = 0;
@@ -1227,7 +859,11 @@ int main(int argc, char **argv) {
     fprintf(stderr, "WDPMCL: guard bands of %d slab%s: %lld bytes overwritten\n", ndev, ndev == 1 ? "" : "s", (long long)guard_bad);
   }
   wdpm_group_destroy(ctx);
-  if (guard_bad) return 3;
+  if (guard_bad) {
+    free(st.dem);
+    if (pinned) wdpm_host_free(st.water); else free(st.water);
+    return 3;
+  }
   phase("statistics + download + destroy");
 
   const int watercount = (int)wet;
