@@ -428,6 +428,17 @@ __device__ __forceinline__ void wait_rows(Prefetched &P) {
 #undef WDPM_ROWS_W
 }
 
+/* "does any lane hold a NODATA offset (0xFFFF) in these three rows?" - the loads zero-extend, so the maximum of the nine says it.
+ * Wave-uniform, the pattern of any_above_3m: four v_max3_u32, one compare, one scalar branch. */
+__device__ __forceinline__ bool any_nodata16(const int (*h)[3]) {
+  auto max3 = [](const unsigned a, const unsigned b, const unsigned c) { const unsigned m = a > b ? a : b; return m > c ? m : c; };
+  unsigned hm = max3((unsigned)h[0][0], (unsigned)h[0][1], (unsigned)h[0][2]);
+  hm = max3(hm, (unsigned)h[1][0], (unsigned)h[1][1]);
+  hm = max3(hm, (unsigned)h[1][2], (unsigned)h[2][0]);
+  hm = max3(hm, (unsigned)h[2][1], (unsigned)h[2][2]);
+  return __ballot(hm >= 0xFFFFu) != 0;
+}
+
 /* consume the prefetched rows into window slots 4..6; the device DEM already holds +inf for
  * NODATA cells, so only edge waves have anything to mask (mask_outside) */
 template <int DEM32, bool FLUSH>
@@ -438,10 +449,28 @@ __device__ __forceinline__ void decode_rows(double (&W)[7][3], double (&D)[7][3]
     for (int j = 0; j < 3; j++) {
       // FLUSH: the block's threshold flush (WDPMCL.c:1059-1062) applied to the water as it arrives
       W[4 + i][j] = FLUSH && P.NW[i][j] < thres ? 0.0 : P.NW[i][j];
-      if (DEM32 == 2) D[4 + i][j] = dem16_decode_nan(P.qh[i][j], P.gbv[i], code.k0, code.D, code.rD, code.rDlo);
+      if (DEM32 == 2) continue;
       else if (DEM32) D[4 + i][j] = dem32_decode_nan(P.qi[i][j], code.k0, code.D, code.rD, code.rDlo);
       else D[4 + i][j] = P.ND[i][j];
     }
+  if (DEM32 == 2) {
+    /* 16-bit offsets: a step whose wave holds no NODATA offset - every step of a raster without NODATA, and of real DEMs all steps
+     * inside the basin - leaves the nine compares and selects out: 24 VALU instructions fewer on that path, the test included
+     * (a two-iteration producer's step: 1658 -> 1634; profiles/r21/isa_loop_stats.txt).  One scalar branch per step, no new instantiation; a wave that does hold one (an edge lane's
+     * clamped columns count) runs the full form on all nine.  16384^2, a block of 1000: -2.2 % and -3.0 % in two interleaved
+     * sessions (profiles/r21/README.md). */
+    if (any_nodata16(P.qh)) {
+#pragma unroll
+      for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) D[4 + i][j] = dem16_decode_nan<false>(P.qh[i][j], P.gbv[i], code.k0, code.D, code.rD, code.rDlo);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) D[4 + i][j] = dem16_decode_nan<true>(P.qh[i][j], P.gbv[i], code.k0, code.D, code.rD, code.rDlo);
+    }
+  }
 }
 
 /* edge waves: cells of window slots 4..6 (slab rows r0 .. r0 + 2) outside the slab hold dem = +inf, w = 0 */

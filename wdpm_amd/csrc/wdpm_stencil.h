@@ -60,10 +60,13 @@ __device__ __forceinline__ double dem32_decode_nan(const int q, const double k0,
  * n = (gb + k0) + h, summed in fp64: both sums are exact integers wherever (double)(gb + h) + k0 was (|gb| < 2^31, |k0| < 4e15,
  * h < 2^16), so n is the same number - and gb + k0 is what a lane's three columns of a row share (they lie in one group), which
  * the compiler computes once per row: per value one unsigned conversion, an add, the two operations of the quotient and the
- * NODATA select. */
+ * NODATA select.  NOSEL leaves that select (a compare and a v_cndmask) out: for steps whose wave holds no offset 0xFFFF at all,
+ * which the caller has tested (wdpm_fused.hip::decode_rows); the encoder uses the full form. */
+template <bool NOSEL = false>
 __device__ __forceinline__ double dem16_decode_nan(const int h, const int gb, const double k0, const double D, const double rD, const double rDlo) {
   const double n = ((double)gb + k0) + (double)(unsigned)h;
   const double v = dem_quotient(n, D, rD, rDlo);
+  if (NOSEL) return v;
   const int hi = h == 0xFFFF ? 0x7ff80000 : __double2hiint(v);
   return __hiloint2double(hi, __double2loint(v));
 }
