@@ -6,7 +6,7 @@
 
 static DeviceFacts facts_of(const SweepDevice &d) {
   DeviceFacts f{d.cus, d.lds_per_cu, d.cus * d.tri_blocks * 4, {}};
-  const int built_for[2][3] = {{2, 2, 2}, {2, 2, 1}};     /* fused_built_for of the six occupancy classes (wdpm_fused.hip) */
+  const int built_for[2][3] = {{2, 2, 2}, {2, 2, 1}};     /* fused_built_for of the six occupancy classes (wdpm_march.hip) */
   for (int m = 0; m < 2; m++)
     for (int k = 0; k < 3; k++) f.resident_waves[m][k] = d.cus * (d.blocks[m][k] < built_for[m][k] ? d.blocks[m][k] : built_for[m][k]) * 4;
   return f;

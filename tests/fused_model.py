@@ -1,4 +1,4 @@
-"""Executable model of the fused-iteration kernel's SCHEDULE (wdpm_amd/csrc/wdpm_fused.hip).
+"""Executable model of the fused-iteration kernel's SCHEDULE (wdpm_amd/csrc/wdpm_march.hip on wdpm_iteration.h).
 
 Test infrastructure: a numpy emulation of what one wave64 of the fused kernel does — lanes own 3
 columns each, a 7-row register window marches down a row chunk, the 9 colour passes of one
@@ -173,7 +173,7 @@ def fused_iteration(win, dem, miss, H=12):
 
 
 # ---------------------------------------------------------------------------------------------------
-# The triangle kernel (wdpm_fused.hip: tri_iteration_kernel): nine rows in, the middle three out.
+# The triangle kernel (wdpm_small.hip: tri_iteration_kernel): nine rows in, the middle three out.
 #   oi = 1 on window rows 0-2, 3-5, 6-8;  oi = 2 on rows 1-3, 4-6;  oi = 3 on rows 2-4.
 # The row blocks of one row alignment are independent (the GPU advances them in lockstep); here they
 # simply run one after the other.

@@ -1,4 +1,4 @@
-"""The row-boundary table of the marching kernel (wdpm_fused.hip::xcd_rebalance_kernel), round 5's `pair` rounding restated in
+"""The row-boundary table of the marching kernel (wdpm_march.hip::xcd_rebalance_kernel), round 5's `pair` rounding restated in
 numpy: the two waves of a SIMD are work items four apart - strips s and s + 4 of one chunk row - and their strips' boundaries are
 rounded half a triple apart, so that a tall chunk of one sits beside a short chunk of the other.  Checked here: the property the
 kernel's comment claims (equal weights: the steps of the two waves of every SIMD add up to the same number to within one, where

@@ -1,4 +1,4 @@
-"""The clamped neighbour step (round 4; wdpm_stencil.h::eighth_clamped, `deep` in wdpm_fused.hip).
+"""The clamped neighbour step (round 4; wdpm_stencil.h::eighth_clamped, `deep` in wdpm_march.hip).
 
 `max(x / 8, -0.0)` of the neighbour step (WDPMCL.c:1947-1957) is ONE instruction on gfx950 - `v_ldexp_f64 f, x, -3 clamp` -
 as long as the flow stays below 1 m; the kernels take it only where the depths they hold guarantee that: every depth of a

@@ -1,5 +1,5 @@
 """The 16-bit DEM codes and their group bases (wdpm_kernels.h::DemCode::h, ::gb) in the marching loops, whose decoder leaves the
-NODATA select out on steps whose wave holds no NODATA offset and runs the full form on the others (wdpm_fused.hip::decode_rows,
+NODATA select out on steps whose wave holds no NODATA offset and runs the full form on the others (wdpm_march.hip::decode_rows,
 wdpm_stencil.h::dem16_decode_nan).  Everything that streams 16-bit codes goes through that decoder: both roles of the
 two-iteration loop (forced onto small rasters with WDPM_ITER2=2) and the single marching loop (WDPM_ITER2=0), played in child processes
 (the switches are read once per process) with the 16-bit codes forced on launches of any size.

@@ -1,4 +1,4 @@
-"""The fused kernel's marching-window schedule (tests/fused_model.py mirrors wdpm_fused.hip) is
+"""The fused kernel's marching-window schedule (tests/fused_model.py mirrors wdpm_march.hip) is
 bit-identical to the oracle for multi-strip, multi-chunk, ragged and degenerate rasters."""
 import numpy as np
 import pytest

@@ -1,4 +1,4 @@
-"""Strips of a two-iteration launch that lie beyond the raster's right edge retire at once (wdpm_fused.hip::iter2_march): a consumer
+"""Strips of a two-iteration launch that lie beyond the raster's right edge retire at once (wdpm_march.hip::iter2_march): a consumer
 whose strip stores nothing, a producer none of whose ring columns lies inside the raster.  The producer leaves +0.0 in its columns of
 the ring, and its neighbours read them.
 

@@ -1,5 +1,5 @@
 """The launch ledger (include/wdpm.h: wdpm_launch_ledger) is the whole kernel inventory of the build: one entry per kernel
-instantiation in the device code of wdpm_fused.hip (both of its units) and wdpm_kernels.hip, named as c++filt names the symbol.
+instantiation in the device code of wdpm_march.hip, wdpm_small.hip and wdpm_kernels.hip, named as c++filt names the symbol.
 An instantiation the dispatch launches without a ledger line, or a ledger line whose arguments are not those of a kernel in the
 build, fails here.  No GPU: the table is filled when the library is loaded, and reading it makes no HIP call."""
 import json
@@ -11,8 +11,8 @@ import sys
 from conftest import ROOT
 
 CSRC = os.path.join(ROOT, "wdpm_amd", "csrc")
-ASM = [os.path.join(CSRC, "build", f) for f in ("wdpm_fused.s", "wdpm_fused_small.s", "wdpm_kernels.s")]
-SOURCES = [os.path.join(CSRC, f) for f in ("wdpm_fused.hip", "wdpm_kernels.hip", "wdpm_kernels.h", "wdpm_stencil.h", "wdpm_ledger.h")]
+ASM = [os.path.join(CSRC, "build", f) for f in ("wdpm_march.s", "wdpm_small.s", "wdpm_kernels.s")]
+SOURCES = [os.path.join(CSRC, f) for f in ("wdpm_iteration.h", "wdpm_march.hip", "wdpm_small.hip", "wdpm_kernels.hip", "wdpm_kernels.h", "wdpm_stencil.h", "wdpm_ledger.h")]
 
 
 def demangled_kernel_name(sym: str) -> str:
@@ -69,8 +69,10 @@ def test_the_ledger_names_every_kernel_of_the_build_and_nothing_else():
     stray = sorted(set(counts) - set(built))
     assert not missing, f"kernels in the build that no launch counts (a launch without WDPM_LEDGER / WDPM_LEDGER_T?): {missing}"
     assert not stray, f"ledger entries that name no kernel of the build (template arguments not written out in full?): {stray}"
-    # the two units of wdpm_fused.hip both emit the probe and the balance kernels: one entry each
-    assert sorted(built["dpp_probe_kernel"]) == ["wdpm_fused.s", "wdpm_fused_small.s"]
+    # no kernel is in two units: the probe and the balance kernels belong to the marching unit, which alone launches them
+    twice = {k: v for k, v in built.items() if len(v) != 1}
+    assert not twice, f"kernels that more than one .s file holds: {twice}"
+    assert built["dpp_probe_kernel"] == ["wdpm_march.s"] and built["xcd_rebalance_kernel"] == ["wdpm_march.s"]
 
 
 def test_a_fresh_process_has_counted_nothing():

@@ -1,4 +1,4 @@
-"""Marching and two-iteration launches (wdpm_dispatch.h::plan_iter2, wdpm_fused.hip::iter2_march) on SLABS: contexts with a live
+"""Marching and two-iteration launches (wdpm_dispatch.h::plan_iter2, wdpm_march.hip::iter2_march) on SLABS: contexts with a live
 first and / or last row, a max diff over a row range, and groups of k iterations that end in the three windows of
 wdpm_iterate_overlapped - what every slab of a multi-GPU run is, forced onto small rasters in child processes with
 WDPM_RELAY=0 WDPM_TRI=0 WDPM_ITER2=2 (the switches are read once per process; tests/slab_worker.py is the child).

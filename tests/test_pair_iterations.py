@@ -1,4 +1,4 @@
-"""Two iterations per marching launch (wdpm_dispatch.h::plan_iter2, wdpm_fused.hip::iter2_march): the planner offers it on the right
+"""Two iterations per marching launch (wdpm_dispatch.h::plan_iter2, wdpm_march.hip::iter2_march): the planner offers it on the right
 side of every condition, leaves plan_iteration() alone, and - forced onto small rasters with WDPM_ITER2=2 in child processes (the
 switches are read once per process) - the launches are bit for bit the oracle's, group edges, raster edges, short last groups, every
 row count mod 3 and every block length included.  The launch ledger says which launches ran two iterations.

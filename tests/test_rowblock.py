@@ -237,7 +237,7 @@ def test_halo_depth_equals_worst_case_dependency_reach():
         t = taint(n, n, k, bad)[:, 100:-100]
         clean = np.nonzero(~t.any(axis=1))[0]
         assert clean.min() == S + up and clean.max() == E - down, (k, clean.min() - S, E - clean.max())
-    # columns, one iteration, strip starting at a multiple of 3 (wdpm_fused.hip: kHaloL / kHaloR)
+    # columns, one iteration, strip starting at a multiple of 3 (wdpm_dispatch.h: kHaloL / kHaloR)
     bad = np.zeros((n, n), bool)
     c0, c1 = 99, 99 + 191
     bad[:, :c0] = True

@@ -45,7 +45,7 @@ def nz_drain_step(dc, wc, dn, wn, gate, nvalid):
     with np.errstate(invalid="ignore", over="ignore"):
         dce = np.where(gate, dc, -np.inf)
         dnn = np.where(nvalid, dn, np.inf)
-        wcl = np.where(gate, wc, 0.0)           # the block runs on a local centre depth (wdpm_fused.hip)
+        wcl = np.where(gate, wc, 0.0)           # the block runs on a local centre depth (wdpm_iteration.h)
         nwe = dnn + wn
         ht = (dce + wcl) - nwe
         s = (dce - dnn) + (wcl - wn)

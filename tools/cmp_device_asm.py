@@ -1,4 +1,4 @@
-"""Are the kernels of two device assembly files (hipcc -S --cuda-device-only, e.g. wdpm_amd/csrc/build/wdpm_fused.s of two revisions)
+"""Are the kernels of two device assembly files (hipcc -S --cuda-device-only, e.g. wdpm_amd/csrc/build/wdpm_march.s of two revisions)
 the same code?  Per .amdhsa_kernel symbol the instruction text and the kernel descriptor (.amdhsa_*: VGPRs, SGPRs, LDS, scratch) must
 be identical.  Functions are emitted in the order of first use, so their order and the function numbers inside local labels
 (.LBB<n>_, .Lfunc_end<n>, .Lpost_getpc<n>) differ after a host-side change: those, and the comments that quote them, are normalised away.

@@ -111,8 +111,6 @@ int wdpm_ledger_register(const char *pretty, const char *args) {
       if (c[0] == ':' && c[1] == ':') { len -= (size_t)(c + 2 - k); k = c + 2; c = k - 1; }
     snprintf(name, sizeof name, "%.*s%s", (int)len, k, args);
   }
-  for (int i = 0; i < g_ledger_entries; i++)
-    if (!strcmp(g_ledger[i].name, name)) return i;      /* (a kernel of both units of wdpm_fused.hip) */
   if (g_ledger_entries == kLedgerMax) return -1;       /* missing from the table: tests/test_launch_ledger.py says which */
   snprintf(g_ledger[g_ledger_entries].name, sizeof g_ledger[0].name, "%s", name);
   return g_ledger_entries++;
@@ -182,7 +180,7 @@ static int free_slot(const wdpm_ctx *x) {            /* a raster that is neither
 }
 
 /* Drain module: drain() after each iteration (WDPMCL.c:1089) has no launch of its own either - the next
- * iteration launch applies it while loading (wdpm_fused.hip: drain_owed).  Anybody else who looks at the
+ * iteration launch applies it while loading (wdpm_march.hip, wdpm_small.hip: drain_owed).  Anybody else who looks at the
  * raster or at totaldrain gets it applied first.  (cur != old whenever it is owed: an iteration has run.) */
 static int ensure_drained(wdpm_ctx *x) {
   if (!x->drain_owed) return 0;

@@ -2,7 +2,7 @@
  * wdpm_dispatch.h — which kernel instantiation an iteration launch uses, with which grid, chunk height, LDS pad and switches
  * (DESIGN.md §4.4 is the specification; nearly every threshold below was bought with an A/B run under profiles/).
  * Plain C++17 and nothing else: no HIP header, no getenv, no statics, no pointer dereferenced.  plan_iteration() only decides;
- * wdpm_fused.hip launches what it decided, wdpm_capi.hip asks.  tests/test_dispatch_plans.py holds every decision against a
+ * wdpm_march.hip and wdpm_small.hip launch what it decided, wdpm_capi.hip asks.  tests/test_dispatch_plans.py holds every decision against a
  * recorded table (tests/golden/dispatch_plans.json.gz) without a GPU.
  */
 #ifndef WDPM_DISPATCH_H
@@ -78,7 +78,7 @@ template <class Get> inline Switches wdpm_read_switches(Get get) {
  * it) that every cell of w_in that may not give water holds +0.0: launches that have such a variant then run without the centre gate.
  * bit 1 (WDPM_LAUNCH_CLAMP_OK): every valid elevation is below 2^30 m in magnitude (wdpm_launch_dem_min), so that half an ulp of an
  * elevation is nothing against a depth: the kernels may take a flow's `max(x / 8, -0.0)` as one clamped instruction wherever
- * the depths they hold are shallow enough for it to be exact (wdpm_stencil.h::eighth_clamped, `deep` in wdpm_fused.hip). */
+ * the depths they hold are shallow enough for it to be exact (wdpm_stencil.h::eighth_clamped, `deep` in wdpm_march.hip). */
 enum { WDPM_LAUNCH_PLAIN = 1, WDPM_LAUNCH_CLAMP_OK = 2 };
 inline int wdpm_launch_flags(const Switches &sw, const bool water_plain, const bool dem_bounded) {
   return (sw.plain != 0 && water_plain ? WDPM_LAUNCH_PLAIN : 0) | (sw.clamp != 0 && dem_bounded ? WDPM_LAUNCH_CLAMP_OK : 0);
@@ -88,7 +88,7 @@ inline int wdpm_launch_flags(const Switches &sw, const bool water_plain, const b
  * +2.5 %, 8192^2 +0.3 %, 4096^2 -2.2 %: nine integer adds more per step; profiles/r04/dem16_bench*_ab.txt) - or when forced (tests) */
 inline bool wdpm_dem16_pays(long long cells_of_the_launch, int force) { return cells_of_the_launch >= 100000000LL || force != 0; }
 
-/* What the dispatch needs to know of a device.  Filled once per device ordinal by the units that own the kernels (wdpm_fused.hip:
+/* What the dispatch needs to know of a device.  Filled once per device ordinal by the units that own the kernels (wdpm_march.hip, wdpm_small.hip:
  * the occupancy API needs their addresses), never on the launch path. */
 struct DeviceFacts {
   int cus;               /* compute units */
@@ -149,8 +149,8 @@ struct LaunchPlan {
   int ring_rows, iter2_prio;   /* Iter2Args */
 };
 
-/* One list per kernel family of the instantiations the library contains: wdpm_fused.hip instantiates the kernels, registers the
- * ledger slots and builds its launch tables from these and nothing else; a plan whose targs are not in its family's list is an
+/* One list per kernel family of the instantiations the library contains: wdpm_march.hip / wdpm_small.hip instantiate the kernels, register the
+ * ledger slots and build their launch tables from these and nothing else; a plan whose targs are not in its family's list is an
  * error at the launch, not a fallback. */
 /* fused_iteration_kernel<module, -0.0-safe, DEM codes (0 fp64, 1 32-bit, 2 16-bit offsets), flush on load, max diff folded in, gate-free> */
 #define WDPM_VARIANTS_MARCHING(X)                                                                          \
@@ -442,7 +442,7 @@ inline int wdpm_groups(const int ncp) {
  * 8192^2 +3.7 %, 16384^2 +3.9 %.  The threshold sits just under the smallest shape measured ahead. */
 constexpr long long kIter2MinCells = 30000000LL;
 
-/* Two iterations in ONE marching launch (wdpm_fused.hip::iter2_march), offered (LaunchPlan::iter2 == 1) or not (== 0: the caller
+/* Two iterations in ONE marching launch (wdpm_march.hip::iter2_march), offered (LaunchPlan::iter2 == 1) or not (== 0: the caller
  * launches plan_iteration()'s plan).  `iterations_left`: launches like this one the caller still has to queue, this one included -
  * neither the block's first (flush) nor its last where that folds the max diff.  Offered only to the gate-free add / subtract
  * instantiations that stream the DEM as codes, on whole-slab steady launches of two waves per SIMD that keep no dry-tile flags and

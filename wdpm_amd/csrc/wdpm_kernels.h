@@ -1,6 +1,6 @@
 /*
  * wdpm_kernels.h — launch interface between the C-ABI layer (wdpm_capi.hip) and the gfx950
- * kernels (wdpm_kernels.hip, wdpm_fused.hip).  Internal; not part of the drop-in boundary.
+ * kernels (wdpm_kernels.hip, wdpm_march.hip, wdpm_small.hip).  Internal; not part of the drop-in boundary.
  */
 #ifndef WDPM_KERNELS_H
 #define WDPM_KERNELS_H
@@ -122,7 +122,7 @@ struct BalanceArgs {             /* kernel argument */
   unsigned long long *rot;
   int parity;
 };
-/* Two iterations in one marching launch (wdpm_fused.hip::iter2_march): the eight waves of a workgroup are four
+/* Two iterations in one marching launch (wdpm_march.hip::iter2_march): the eight waves of a workgroup are four
  * producers (iteration k on four neighbouring strips) and four consumers (iteration k + 1 on the same strips and rows), the
  * producers' exact rows pass through a ring of group rows in LDS and iteration k's raster never reaches memory.  on == 0: the
  * launch is an ordinary one. */
@@ -171,9 +171,9 @@ struct IterationBuffers {
   XcdBalance *bal;       /* LaunchRequest::balance_mode != 0 */
   unsigned *iter2_err;   /* Iter2Args::err (launches of plan_iter2) */
 };
-const DeviceFacts *wdpm_device_facts();      /* of the current device; nullptr: see wdpm_fused.hip */
+const DeviceFacts *wdpm_device_facts();      /* of the current device; nullptr: see wdpm_march.hip */
 hipError_t wdpm_launch_iteration(const LaunchRequest &q, const LaunchPlan &p, const IterationBuffers &b);
-/* between the two translation units of wdpm_fused.hip */
+/* wdpm_small.hip, called by wdpm_march.hip alone */
 void wdpm_small_device_facts(DeviceFacts *f);
 hipError_t wdpm_launch_small(const LaunchRequest &q, const LaunchPlan &p, const IterationBuffers &b);
 /* What kinds of depth do the n cells at p hold (dem: the device DEM of the same cells, NODATA = +inf)?
@@ -181,7 +181,7 @@ hipError_t wdpm_launch_small(const LaunchRequest &q, const LaunchPlan &p, const 
  *   *flag |= 2  a negative depth             (gone once a threshold flush with thres >= 0 has been applied)
  *   *flag |= 4  NaN, a depth above 1e290, or water on a NODATA cell   (stays)
  * With none of them, every cell that may not give water (dry, NODATA, outside the slab) holds +0.0 exactly - and then
- * the centre gate of the reference's sweep (WDPMCL.c:1099) needs no instructions: see PLAIN in wdpm_fused.hip. */
+ * the centre gate of the reference's sweep (WDPMCL.c:1099) needs no instructions: see PLAIN in wdpm_iteration.h. */
 enum { WDPM_WATER_NEGZERO = 1, WDPM_WATER_NEGATIVE = 2, WDPM_WATER_ODD = 4 };
 hipError_t wdpm_launch_scan_water(const double *p, const double *dem, size_t n, unsigned long long *flag, hipStream_t s);
 /* drain() (WDPMCL.c:1859-1897) on the device */

@@ -1,35 +1,19 @@
 /*
- * wdpm_fused.hip — one whole WDPM iteration (all 9 colour passes, reference src/WDPMCL.c:1094-1106,
- * kernels runoff.cl:137-183) in ONE launch, reading each raster from HBM once and writing the
- * water raster once: 24 B per cell-update, the algorithmic minimum.
+ * wdpm_march.hip — the marching kernel (fused_iteration_kernel) and the launch of an iteration: each raster read from HBM once, the
+ * water raster written once, 24 B per cell-update, the algorithmic minimum.  What it shares with the kernels of
+ * small rasters (wdpm_small.hip) - the trapezoid, the lane layout, the DPP borrow, the per-block arithmetic - is wdpm_iteration.h.
+ * This unit is built under the compiler's max-ILP instruction scheduler (Makefile; why: wdpm_small.hip).
  *
- * Design (DESIGN.md §4 has the derivation and the numpy model tests/fused_model.py checks the
- * schedule against the oracle):
- *
- *  - A wave64 is the unit of work; waves never synchronise with each other (no barriers; LDS is
- *    only a wave-private transpose buffer for the stores).  Lane m owns raster columns
- *    c0+3m .. c0+3m+2, so a wave covers a 192-column strip and a 64-lane row load is one
- *    contiguous 1536-byte segment.  Waves per SIMD: two wherever chunks of 18 (add / subtract on the DEM codes) or 12 rows
+ *  - Waves never synchronise with each other (no barriers; LDS is only a wave-private transpose buffer for the stores).
+ *    Waves per SIMD: two wherever chunks of 18 (add / subtract on the DEM codes) or 12 rows
  *    (drain) fill every slot, one otherwise.  With two, a workgroup is eight waves and the two waves of a SIMD tell each other
  *    their step through LDS: whoever is behind is served first (see the marching loop).  Chunk heights follow what each XCD
  *    delivers (wdpm_kernels.h::XcdBalance).  Round 4's counters: fp64 VALU issue in ~89 % of the kernel's cycles, ~4.7 TB/s of
  *    HBM traffic - between both ceilings.
  *  - The wave marches down a chunk of rows with a 7-row window held in registers (dem + water,
  *    3 columns per lane).  Each step loads 3 new rows and applies, in this order, row alignment
- *    oi=1 to rows 3n..3n+2, oi=2 to rows 3n-2..3n, oi=3 to rows 3n-4..3n-2 — a skew that respects
- *    every dependency of the reference's pass order, because a 3x3 block of pass (oi,oj) only
- *    needs its nine cells to have finished all earlier passes.  Rows 3n-4..3n-2 are then final
+ *    oi=1 to rows 3n..3n+2, oi=2 to rows 3n-2..3n, oi=3 to rows 3n-4..3n-2.  Rows 3n-4..3n-2 are then final
  *    and are stored.
- *  - Within a row alignment the three column alignments oj=1,2,3 shift the blocks right by one
- *    column each: the lane borrows column 0 (then column 1) of lane m+1 with a DPP wave_shl:1
- *    register move, updates it, and hands both back with wave_shr:1.  No LDS traffic.
- *  - Information moves at most 8 columns left / 12 right and 2 rows up / 4 down per iteration, so
- *    a wave's 192 x (H+6) input trapezoid yields a 171 x H exact output; neighbouring waves
- *    recompute the overlap (redundant, bit-identical work) instead of communicating.
- *  - Cells with bigdem <= missingvalue and cells outside the slab are held as dem = +inf: as a
- *    neighbour this makes ht_diff -inf/NaN, so `ht_diff > 0` is false with no extra test
- *    (WDPMCL.c:1944); as a centre the gate `dem < +inf` replaces `bigdem > missingvalue` (:1099).
- *
  *  - DEM32: the static DEM can be streamed as 32-bit codes q with dem == (q + k0) / 10^e bit for bit
  *    (verified per cell at upload by the decoder used here, wdpm_stencil.h::dem32_decode): 12 bytes
  *    per lane and row in one global_load_dwordx3, 20 B of HBM traffic per cell-update instead of 24 - on the largest launches
@@ -40,236 +24,20 @@
  *  - The neighbour step is 9 (add) / 14 (drain) VALU instructions where the depths a wave holds allow the one-instruction
  *    clamped max(x / 8, -0.0) (wdpm_stencil.h; `deep` below), 10 / 15 otherwise.
  *
- * Results are bit-identical to the serial reference: same operands, same order, fp64, no FMA in
- * the stencil (the DEM decode uses two, on values it has been verified to reproduce exactly).
- *
- * Three kernels share the per-block arithmetic (block_update / blocks_lockstep) and the trapezoid:
- *   fused_iteration_kernel  the marching window above: rasters that fill the chip (from ~2300^2 add, ~2900^2 drain)
- *   relay_iteration_kernel  workgroups of four / eight waves, one row block per wave and row alignment, shared rows passed
- *                           through LDS: small and mid-size rasters (round 3; 482^2 add 7.3 -> 5.2 us, drain 12.1 -> 8.4)
- *   tri_iteration_kernel    one wave, nine (twelve) rows in, three (six) out, row blocks in lockstep: what is between the two,
- *                           and a small raster's last launch of a block (max diff folded in)
  * The marching kernel has two loops: its own, and iter2_march for launches that run two iterations (producer and consumer waves).
  * What a step of either does with its rows - the lane offsets, the inline-asm prefetch and its exact wait, the decode into the
  * window, the edge mask, `deep`, the staged stores, the window slide - is written once, in the functions in front of iter2_march;
- * the loops themselves hold what is theirs alone.  owed_drain_sum, fold_max_diff and any_above_3m serve all three kernels.
- * plan_iteration (wdpm_dispatch.h) picks by size, module and what is known about the raster.
+ * the loops themselves hold what is theirs alone.  Behind the kernels: the balance kernel (xcd_rebalance_kernel), the DPP probe
+ * (dpp_probe_kernel, dpp_selfcheck), the device facts and wdpm_launch_iteration, which queues what plan_iteration decided and
+ * hands the plans of small rasters to wdpm_launch_small.
  */
-#include "wdpm_kernels.h"
-#include "wdpm_ledger.h"
-#include "wdpm_stencil.h"
+#include "wdpm_iteration.h"
 
 #include <atomic>
-#include <cstring>
 #include <mutex>
 #include <type_traits>
 
 namespace {
-
-/* strip geometry (kLanes, kStripIn, kHaloL / kHaloR, kStripOut): wdpm_dispatch.h, which sizes the launches by it */
-
-#define WDPM_INF (__builtin_inf())
-
-/* value held by lane+1; lane 63 receives 0.0 (DPP bound_ctrl zero fill, so no register has to
- * be preset).  v_mov_b32_dpp wave_shl:1.  Lane 63's borrowed columns lie beyond the strip: its
- * blocks of passes oj=2,3 are inside the right halo whose results are never stored, so
- * any finite fill is as good as the true value there. */
-__device__ __forceinline__ double lane_next(const double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(0, lo, 0x130, 0xF, 0xF, true);
-  hi = __builtin_amdgcn_update_dpp(0, hi, 0x130, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-
-/* value held by lane-1; lane 0 keeps `keep`.  v_mov_b32_dpp wave_shr:1 */
-__device__ __forceinline__ double lane_prev(const double v, const double keep) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_update_dpp(__double2loint(keep), lo, 0x138, 0xF, 0xF, false);
-  hi = __builtin_amdgcn_update_dpp(__double2hiint(keep), hi, 0x138, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double wave_read(const double v, const int src_lane) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), src_lane);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src_lane);
-  return __hiloint2double(hi, lo);
-}
-
-/* drain-module bookkeeping carried through the passes (compiles away for add/subtract) */
-struct DrainState {
-  double td;      // running totaldrain (wave-uniform value, one copy per lane)
-  bool hit;       // this lane drained in the current pass
-};
-
-/* one neighbour step of runoffd() including its outlet branch (WDPMCL.c:1975-2002) */
-__device__ __forceinline__ void step_drain(const double dc, double &wc, const double dn, double &wn,
-                                           const bool gate, const bool is_outlet, DrainState &ds) {
-  const bool hit = gate & is_outlet & (dn < WDPM_INF);   // :1976,1980
-  const double td2 = (ds.td + wn) + wc;                   // :1982
-  ds.td = hit ? td2 : ds.td;
-  ds.hit = ds.hit | hit;
-  wn = hit ? 0.0 : wn;                                    // :1983
-  wc = hit ? 0.0 : wc;                                    // :1984
-  flow_drain(dc, wc, dn, wn, gate & !hit);                // :1988-2000
-}
-
-/* one 3x3 block of one colour pass: centre (1,1), neighbours in row-major order.  OUTLET (drain
- * only): this block may touch the outlet cell, run runoffd()'s outlet branch too; the caller knows
- * wave-uniformly that it cannot for all but a handful of the raster's blocks. */
-/* PLAIN (only with !SZ_SAFE): the caller knows that every cell which may not give water - dry, NODATA, outside the slab - holds
- * +0.0 exactly (wdpm_kernels.h::wdpm_launch_scan_water; no operation of the loop leaves that state).  The centre test of the
- * sweep (WDPMCL.c:1099) then costs nothing: for a centre depth of +0.0 the neighbour steps below come out as f = +-0 by
- * themselves, whatever the elevations - finite centre: dem_c > en gives x = w_c = 0, otherwise ht = dem_c - en <= 0 and
- * max(ht / 8, -0.0) = +-0; NODATA centre (dem = +inf): inf > en gives x = w_c = 0, and next to a NODATA neighbour ht is NaN,
- * which v_max turns into -0.0 - and w + (+-0) == w, w - |+-0| == w for every w that is not -0.0.  (drain: the same through
- * min(max(x / 8, -0.0), w_c = 0).)  Four instructions per block less for add, eight for drain. */
-/* FLAGS: bit 0 = PLAIN, bit 1 = CLAMP (wdpm_stencil.h::eighth_clamped: the caller knows that no depth of this block exceeds 8 m
- * during the pass - see `deep` in the marching kernel; never on the outlet's path) */
-template <int MODULE, bool SZ_SAFE, bool OUTLET = true, int FLAGS = 0>
-__device__ __forceinline__ void block_update(
-    double &w00, double &w01, double &w02, double &w10, double &w11, double &w12, double &w20, double &w21,
-    double &w22, const double d00, const double d01, const double d02, const double d10, const double d11,
-    const double d12, const double d20, const double d21, const double d22,
-    const bool rd0, const bool rd1, const bool rd2, const bool cd0, const bool cd1, const bool cd2,
-    DrainState &ds) {
-  constexpr bool PLAIN = (FLAGS & 1) != 0, CL = (FLAGS & 2) != 0;
-  double wc = w11;
-  bool gate = (wc > 0.0) & (d11 < WDPM_INF);            // WDPMCL.c:1099
-  if (MODULE == 2 && !OUTLET && !SZ_SAFE && PLAIN) {
-    flow_drain_nz<CL>(d11, wc, d00, w00);
-    flow_drain_nz<CL>(d11, wc, d01, w01);
-    flow_drain_nz<CL>(d11, wc, d02, w02);
-    flow_drain_nz<CL>(d11, wc, d10, w10);
-    flow_drain_nz<CL>(d11, wc, d12, w12);
-    flow_drain_nz<CL>(d11, wc, d20, w20);
-    flow_drain_nz<CL>(d11, wc, d21, w21);
-    flow_drain_nz<CL>(d11, wc, d22, w22);
-  } else if (MODULE == 2 && !OUTLET && !SZ_SAFE) {
-    const double dce = gate ? d11 : -WDPM_INF;           // see flow_drain_nz
-    wc = gate ? wc : 0.0;                                // its clamp needs a centre depth >= +0
-    flow_drain_nz<CL>(dce, wc, d00, w00);
-    flow_drain_nz<CL>(dce, wc, d01, w01);
-    flow_drain_nz<CL>(dce, wc, d02, w02);
-    flow_drain_nz<CL>(dce, wc, d10, w10);
-    flow_drain_nz<CL>(dce, wc, d12, w12);
-    flow_drain_nz<CL>(dce, wc, d20, w20);
-    flow_drain_nz<CL>(dce, wc, d21, w21);
-    flow_drain_nz<CL>(dce, wc, d22, w22);
-    wc = gate ? wc : w11;
-  } else if (MODULE == 2 && !OUTLET) {
-    flow_drain(d11, wc, d00, w00, gate);
-    flow_drain(d11, wc, d01, w01, gate);
-    flow_drain(d11, wc, d02, w02, gate);
-    flow_drain(d11, wc, d10, w10, gate);
-    flow_drain(d11, wc, d12, w12, gate);
-    flow_drain(d11, wc, d20, w20, gate);
-    flow_drain(d11, wc, d21, w21, gate);
-    flow_drain(d11, wc, d22, w22, gate);
-  } else if (MODULE == 2 && !SZ_SAFE) {
-    // A block that may hold the outlet, no -0.0 in the raster: the plain neighbour step (flow_drain_nz) plus,
-    // for the ONE neighbour position that can be the outlet in this wave, runoffd()'s sink (:1980-1985).
-    // Which of the block's rows is the outlet's row is wave-uniform (rd*), whether ANY lane has the outlet's
-    // column at block column c takes a ballot (anyc*): the sink's few instructions sit behind a scalar branch
-    // that all but a handful of the raster's blocks never take.  After the sink the centre holds 0, and a
-    // centre without water moves nothing in the remaining steps (f = min(.., 0)), exactly as in the reference,
-    // whose loop also runs on with w[centre] = 0.
-    gate = gate & !(rd1 & cd1);                          // :1082 the outlet is never a centre
-    const double dce = gate ? d11 : -WDPM_INF;
-    wc = gate ? wc : 0.0;
-    const bool any0 = __ballot(cd0) != 0, any1 = __ballot(cd1) != 0, any2 = __ballot(cd2) != 0;
-    bool hit_any = false;
-    auto nb = [&](const double dn, double &wn, const bool rd, const bool anyc, const bool cd) {
-      if (rd & anyc) {                                   // wave-uniform
-        const bool hit = gate & cd & (dn < WDPM_INF);    // :1976,1980
-        const double td2 = (ds.td + wn) + wc;            // :1982
-        ds.td = hit ? td2 : ds.td;
-        wn = hit ? 0.0 : wn;                             // :1983
-        wc = hit ? 0.0 : wc;                             // :1984
-        hit_any = hit_any | hit;
-      }
-      flow_drain_nz<false>(dce, wc, dn, wn);                 // :1988-2000 (never clamped: the outlet's path is off the hot path)
-    };
-    nb(d00, w00, rd0, any0, cd0);
-    nb(d01, w01, rd0, any1, cd1);
-    nb(d02, w02, rd0, any2, cd2);
-    nb(d10, w10, rd1, any0, cd0);
-    nb(d12, w12, rd1, any2, cd2);
-    nb(d20, w20, rd2, any0, cd0);
-    nb(d21, w21, rd2, any1, cd1);
-    nb(d22, w22, rd2, any2, cd2);
-    wc = gate ? wc : w11;
-    // at most one lane of the wave holds the outlet in this pass: make its totaldrain the wave's
-    const unsigned long long m = __ballot(hit_any);
-    if (m) ds.td = wave_read(ds.td, __ffsll((long long)m) - 1);
-  } else if (MODULE == 2) {
-    gate = gate & !(rd1 & cd1);                          // :1082 the outlet is never a centre
-    ds.hit = false;
-    step_drain(d11, wc, d00, w00, gate, rd0 & cd0, ds);
-    step_drain(d11, wc, d01, w01, gate, rd0 & cd1, ds);
-    step_drain(d11, wc, d02, w02, gate, rd0 & cd2, ds);
-    step_drain(d11, wc, d10, w10, gate, rd1 & cd0, ds);
-    step_drain(d11, wc, d12, w12, gate, rd1 & cd2, ds);
-    step_drain(d11, wc, d20, w20, gate, rd2 & cd0, ds);
-    step_drain(d11, wc, d21, w21, gate, rd2 & cd1, ds);
-    step_drain(d11, wc, d22, w22, gate, rd2 & cd2, ds);
-    // at most one lane of the wave holds the outlet in this pass: make its totaldrain the wave's
-    const unsigned long long m = __ballot(ds.hit);
-    if (m) ds.td = wave_read(ds.td, __ffsll((long long)m) - 1);
-  } else if (!SZ_SAFE) {
-    // no -0.0 in the raster: the gate rides on the centre elevation (see flow_add_nz) - or is not needed at all (PLAIN)
-    const double dce = PLAIN ? d11 : (gate ? d11 : -WDPM_INF);
-    flow_add_nz<CL>(dce, wc, d00, w00);
-    flow_add_nz<CL>(dce, wc, d01, w01);
-    flow_add_nz<CL>(dce, wc, d02, w02);
-    flow_add_nz<CL>(dce, wc, d10, w10);
-    flow_add_nz<CL>(dce, wc, d12, w12);
-    flow_add_nz<CL>(dce, wc, d20, w20);
-    flow_add_nz<CL>(dce, wc, d21, w21);
-    flow_add_nz<CL>(dce, wc, d22, w22);
-  } else {
-    flow_add(d11, wc, d00, w00, gate);
-    flow_add(d11, wc, d01, w01, gate);
-    flow_add(d11, wc, d02, w02, gate);
-    flow_add(d11, wc, d10, w10, gate);
-    flow_add(d11, wc, d12, w12, gate);
-    flow_add(d11, wc, d20, w20, gate);
-    flow_add(d11, wc, d21, w21, gate);
-    flow_add(d11, wc, d22, w22, gate);
-  }
-  w11 = wc;
-}
-
-/* the three column alignments oj = 1,2,3 of one row alignment, on window slots S0..S0+2 */
-template <int MODULE, bool SZ_SAFE, int S0, bool OUTLET, int PLAIN = 0>
-__device__ __forceinline__ void stage_impl(double (&W)[7][3], const double (&D)[7][3], const int row_s0,
-                                           const int drain_row, const bool (&cdr)[5], DrainState &ds) {
-  const bool rd0 = MODULE == 2 && OUTLET && row_s0 == drain_row;
-  const bool rd1 = MODULE == 2 && OUTLET && row_s0 + 1 == drain_row;
-  const bool rd2 = MODULE == 2 && OUTLET && row_s0 + 2 == drain_row;
-  constexpr int a = S0, b = S0 + 1, c = S0 + 2;
-  // oj = 1: own columns 0,1,2
-  block_update<MODULE, SZ_SAFE, OUTLET, PLAIN>(W[a][0], W[a][1], W[a][2], W[b][0], W[b][1], W[b][2], W[c][0], W[c][1], W[c][2],
-                       D[a][0], D[a][1], D[a][2], D[b][0], D[b][1], D[b][2], D[c][0], D[c][1], D[c][2],
-                       rd0, rd1, rd2, cdr[0], cdr[1], cdr[2], ds);
-  // oj = 2: own columns 1,2 + column 0 of the next lane
-  double wa0 = lane_next(W[a][0]), wb0 = lane_next(W[b][0]), wc0 = lane_next(W[c][0]);
-  const double da0 = lane_next(D[a][0]), db0 = lane_next(D[b][0]),
-               dc0 = lane_next(D[c][0]);
-  block_update<MODULE, SZ_SAFE, OUTLET, PLAIN>(W[a][1], W[a][2], wa0, W[b][1], W[b][2], wb0, W[c][1], W[c][2], wc0,
-                       D[a][1], D[a][2], da0, D[b][1], D[b][2], db0, D[c][1], D[c][2], dc0,
-                       rd0, rd1, rd2, cdr[1], cdr[2], cdr[3], ds);
-  // oj = 3: own column 2 + columns 0,1 of the next lane
-  double wa1 = lane_next(W[a][1]), wb1 = lane_next(W[b][1]), wc1 = lane_next(W[c][1]);
-  const double da1 = lane_next(D[a][1]), db1 = lane_next(D[b][1]),
-               dc1 = lane_next(D[c][1]);
-  block_update<MODULE, SZ_SAFE, OUTLET, PLAIN>(W[a][2], wa0, wa1, W[b][2], wb0, wb1, W[c][2], wc0, wc1,
-                       D[a][2], da0, da1, D[b][2], db0, db1, D[c][2], dc0, dc1,
-                       rd0, rd1, rd2, cdr[2], cdr[3], cdr[4], ds);
-  // hand the borrowed columns back to lane+1; lane 0 keeps its own (nothing to its left)
-  W[a][0] = lane_prev(wa0, W[a][0]);  W[a][1] = lane_prev(wa1, W[a][1]);
-  W[b][0] = lane_prev(wb0, W[b][0]);  W[b][1] = lane_prev(wb1, W[b][1]);
-  W[c][0] = lane_prev(wc0, W[c][0]);  W[c][1] = lane_prev(wc1, W[c][1]);
-}
 
 /* Drain: the outlet branch of runoffd() costs ten more instructions per neighbour step, and exactly
  * one cell of the raster needs it.  Whether any of the seven rows of this step's window is the outlet's
@@ -297,15 +65,11 @@ __device__ __forceinline__ void three_stages(double (&W)[7][3], const double (&D
 }
 
 #ifdef WDPM_WAVE_TIMES   /* timing builds only (tools/wave_times.py): when each wave of the marching kernel starts and ends, and where */
-static __device__ unsigned long long g_wave_times[4 * 8192];   /* one per translation unit (WDPM_TU): each has its accessor */
+static __device__ unsigned long long g_wave_times[4 * 8192];   /* this unit's own (wdpm_small.hip has one for the relay kernel): each has its accessor */
 /* two-iteration launches: what each wave spent in await(), by where in its chunk (start: steps 0 - 3, end: the last four, steady between).
  * A producer only ever waits for a full ring, a consumer for an empty one.  Per wave: [0] polls start | steady << 32, [1] polls end |
  * awaits that had to poll << 32, [2] 100 MHz ticks from first poll to release, start | steady << 32, [3] the same at the end */
 static __device__ unsigned long long g_wave_waits[4 * 8192];
-/* relay kernel: eight stamps per wave (tools/relay_times.py); the wait in front of each makes the stamp mean "everything before is done" */
-#define WDPM_RSTAMP(k) do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0); rst[k] = wall_clock64(); __builtin_amdgcn_s_waitcnt(0); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define WDPM_RSTAMP(k) do { } while (0)
 #endif
 #ifndef WDPM_FUSED_MIN_WAVES
 #define WDPM_FUSED_MIN_WAVES 2   /* waves per SIMD the register allocator must leave room for */
@@ -487,18 +251,6 @@ __device__ __forceinline__ void mask_outside(double (&W)[7][3], double (&D)[7][3
   }
 }
 
-/* "does any lane hold a depth above 3 m in these three rows?" - the high words of the nine values compared as integers: a negative
- * or NaN depth counts as deep.  Wave-uniform. */
-__device__ __forceinline__ bool any_above_3m(const double (*w)[3]) {
-  auto hi = [](const double v) { return (unsigned)__double2hiint(v); };
-  auto max3 = [](const unsigned a, const unsigned b, const unsigned c) { const unsigned m = a > b ? a : b; return m > c ? m : c; };
-  unsigned hm = max3(hi(w[0][0]), hi(w[0][1]), hi(w[0][2]));
-  hm = max3(hm, hi(w[1][0]), hi(w[1][1]));
-  hm = max3(hm, hi(w[1][2]), hi(w[2][0]));
-  hm = max3(hm, hi(w[2][1]), hi(w[2][2]));
-  return __ballot(hm > 0x40080000u) != 0;               // 0x40080000'00000000 = 3.0
-}
-
 /* CLAMP (round 4; wdpm_stencil.h::eighth_clamped): one instruction less per neighbour step, exact while no flow of the step
  * exceeds 1 m.  A flow is at most (the centre's depth + half an ulp of its elevation) / 8, a cell receives in at most eight
  * of an iteration's nine passes (it is the centre of the ninth), and within one pass in at most one block: if every depth of
@@ -583,31 +335,6 @@ struct StoreSide {
     __builtin_amdgcn_wave_barrier();
   }
 };
-
-/* Drain: the sum the previous iteration's drain() (WDPMCL.c:1089 -> :1859-1897) owes to totaldrain - the outlet's 3x3, row-major
- * from 0.0, valid cells with water (:1877-1884).  The caller knows that the outlet lies inside the slab's border. */
-__device__ __forceinline__ double owed_drain_sum(const double *__restrict__ win, const double *__restrict__ dem, const SlabGeom g) {
-  double sum = 0.0;
-#pragma unroll
-  for (int i = -1; i <= 1; i++)
-#pragma unroll
-    for (int j = -1; j <= 1; j++) {
-      const size_t k = (size_t)(g.dr + i) * g.ncp + (g.dc + j);
-      const double wk = win[k];
-      if (dem[k] < WDPM_INF && wk > 0) sum += wk;
-    }
-  return sum;
-}
-
-/* MD: the lanes' max |w - oldw| folded over the wave, one atomicMax per wave on the uint64 image (>= 0: order-preserving) */
-__device__ __forceinline__ void fold_max_diff(double md_max, const MaxDiffArgs &md, const int lane) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const double o = __shfl_xor(md_max, off, 64);
-    md_max = o > md_max ? o : md_max;
-  }
-  if (lane == 0 && md_max > 0.0) atomicMax(md.bits, (unsigned long long)__double_as_longlong(md_max));
-}
 
 /* ---------------------------------------------------------------------------------------------
  * Two iterations per launch (Iter2Args; geometry: wdpm_dispatch.h::plan_iter2).  A second marching loop of the gate-free add /
@@ -1196,559 +923,6 @@ fused_iteration_kernel(const double *__restrict__ win, double *__restrict__ wout
 #endif
 }
 
-// ---------------------------------------------------------------------------------------------
-// Small rasters: the "triangle" kernel.
-//
-// A raster of a few hundred rows cannot fill the chip, and the marching kernel above then runs at its
-// latency floor: every wave needs H/3 + 2 window steps of nine DEPENDENT 3x3 blocks each (one lane works
-// on one block at a time), about 10 us per launch on a 482 x 471 raster however many SIMDs idle.  Here a
-// wave takes NINE rows at once and produces the three middle ones in one go:
-//       oi = 1 on rows 0-2, 3-5, 6-8      three independent row blocks ...
-//       oi = 2 on rows 1-3, 4-6           ... two ...
-//       oi = 3 on rows 2-4                ... one: rows 2-4 have then seen all nine passes
-// Six stages instead of the marching kernel's nine for a 3-row chunk, and the row blocks of a stage are
-// advanced in LOCKSTEP - neighbour step k of block a, of block b, of block c, then step k+1 ... - so the
-// fp64 pipeline sees up to three independent dependency chains instead of one.
-// Same trapezoid, same pass order per cell, same arithmetic (stage_impl's blocks): bit-identical.
-// ---------------------------------------------------------------------------------------------
-/* NB independent 3x3 blocks of one colour pass, advanced in lockstep (non-outlet form; block b is
- * w[b][row][col] with the centre at [1][1], neighbours in row-major order) */
-template <int MODULE, int NB, int FLAGS = 0>   /* FLAGS as block_update's: bit 0 PLAIN, bit 1 CLAMP */
-__device__ __forceinline__ void blocks_lockstep(double (&w)[NB][3][3], const double (&d)[NB][3][3]) {
-  constexpr bool PLAIN = (FLAGS & 1) != 0, CL = (FLAGS & 2) != 0;
-  double wc[NB], dce[NB];
-  bool gate[NB];
-#pragma unroll
-  for (int b = 0; b < NB; b++) {
-    wc[b] = w[b][1][1];
-    gate[b] = PLAIN || ((wc[b] > 0.0) & (d[b][1][1] < WDPM_INF));  // WDPMCL.c:1099 (PLAIN: see block_update)
-    dce[b] = gate[b] ? d[b][1][1] : -WDPM_INF;                      // see flow_add_nz / flow_drain_nz
-    if (MODULE == 2) wc[b] = gate[b] ? wc[b] : 0.0;
-  }
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    const int r = 1 + nb_dr(k), c = 1 + nb_dc(k);
-#pragma unroll
-    for (int b = 0; b < NB; b++) {
-      if (MODULE == 2) flow_drain_nz<CL>(dce[b], wc[b], d[b][r][c], w[b][r][c]);
-      else flow_add_nz<CL>(dce[b], wc[b], d[b][r][c], w[b][r][c]);
-    }
-  }
-#pragma unroll
-  for (int b = 0; b < NB; b++) w[b][1][1] = MODULE == 2 ? (gate[b] ? wc[b] : w[b][1][1]) : wc[b];
-}
-
-/* one row alignment (three column alignments oj = 1,2,3) on the NB row blocks at window slots
- * S0 + 3b .. S0 + 3b + 2 of a window of NR rows; the lockstep twin of stage_impl */
-template <int MODULE, int NB, int S0, int NR, int FLAGS = 0>
-__device__ __forceinline__ void stage_lockstep(double (&W)[NR][3], const double (&D)[NR][3]) {
-  double w[NB][3][3], d[NB][3][3];
-  double n0[NB][3], n1[NB][3], e0[NB][3], e1[NB][3];      // columns 0 and 1 of the next lane: water, elevation
-  // oj = 1: own columns 0,1,2
-#pragma unroll
-  for (int b = 0; b < NB; b++)
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-      for (int c = 0; c < 3; c++) { w[b][r][c] = W[S0 + 3 * b + r][c]; d[b][r][c] = D[S0 + 3 * b + r][c]; }
-  blocks_lockstep<MODULE, NB, FLAGS>(w, d);
-  // oj = 2: own columns 1,2 + column 0 of the next lane
-#pragma unroll
-  for (int b = 0; b < NB; b++)
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-      n0[b][r] = lane_next(w[b][r][0]);
-      e0[b][r] = lane_next(d[b][r][0]);
-      W[S0 + 3 * b + r][0] = w[b][r][0];                  // column 0 is done for this row alignment (until handed back)
-      w[b][r][0] = w[b][r][1]; w[b][r][1] = w[b][r][2]; w[b][r][2] = n0[b][r];
-      d[b][r][0] = d[b][r][1]; d[b][r][1] = d[b][r][2]; d[b][r][2] = e0[b][r];
-    }
-  blocks_lockstep<MODULE, NB, FLAGS>(w, d);
-  // oj = 3: own column 2 + columns 0,1 of the next lane
-#pragma unroll
-  for (int b = 0; b < NB; b++)
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-      n1[b][r] = lane_next(W[S0 + 3 * b + r][1] = w[b][r][0]);   // own column 1 as updated by oj = 1,2 ...
-      e1[b][r] = lane_next(D[S0 + 3 * b + r][1]);                // ... the next lane's is the one we borrow
-      w[b][r][0] = w[b][r][1]; w[b][r][1] = w[b][r][2]; w[b][r][2] = n1[b][r];
-      d[b][r][0] = d[b][r][1]; d[b][r][1] = d[b][r][2]; d[b][r][2] = e1[b][r];
-    }
-  blocks_lockstep<MODULE, NB, FLAGS>(w, d);
-  // own column 2 back into the window; the borrowed columns back to lane+1 (lane 0 keeps its own)
-#pragma unroll
-  for (int b = 0; b < NB; b++)
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-      W[S0 + 3 * b + r][2] = w[b][r][0];
-      W[S0 + 3 * b + r][0] = lane_prev(w[b][r][1], W[S0 + 3 * b + r][0]);
-      W[S0 + 3 * b + r][1] = lane_prev(w[b][r][2], W[S0 + 3 * b + r][1]);
-    }
-}
-
-template <int MODULE, bool FLUSH, int K = 1, bool PLAIN = false, bool MD = false>
-__global__ void __launch_bounds__(256, 2)
-tri_iteration_kernel(const double *__restrict__ win, double *__restrict__ wout, const double *__restrict__ dem,
-                     const SlabGeom g, const int nstrips, const int nitems, const int A0, const int out_last,
-                     double *__restrict__ totaldrain, const double thres, const int drain_owed, const MaxDiffArgs md) {
-  static_assert(!MD || (K == 1 && MODULE != 2), "the max-diff variant exists for three rows per wave, add / subtract");
-  // K row blocks out per wave: 3K + 6 rows in, oi = 1 on K + 2 row blocks, oi = 2 on K + 1, oi = 3 on K.  K = 1 is the kernel
-  // described above; K = 2 (add / subtract only) does 9 block stages for six rows instead of 12 - for rasters whose waves no
-  // longer fit on the chip in one round, where the launch is bound by instruction issue, not by a single wave's latency.
-  static_assert(K == 1 || MODULE != 2, "the outlet's permutation below is written for K = 1");
-  constexpr int NR = 3 * K + 6;
-  const int lane = threadIdx.x & 63;
-  const int vb = (blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8;       // XCD-contiguous items
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int item = vb * 4 + wave;
-  if (item >= nitems) return;                                               // wave-uniform
-  const int strip = item % nstrips, chunk = item / nstrips;
-  const int c0 = kStripOut * strip;
-  const int oc_lo = strip == 0 ? 0 : c0 + kHaloL;
-  int oc_hi = c0 + kStripIn - 1 - kHaloR;
-  if (oc_hi > g.ncp - 1) oc_hi = g.ncp - 1;
-  const int A = A0 + 3 * K * chunk;               // window rows A .. A+NR-1; exact output rows A+2 .. A+3K+1
-  const int or_lo = A == 0 ? 0 : A + 2;
-  int or_hi = A + 3 * K + 1;
-  if (or_hi > out_last) or_hi = out_last;
-  const int colb = c0 + 3 * lane;
-  const size_t pitch = (size_t)g.ncp;
-
-  DrainState ds;
-  ds.td = MODULE == 2 ? *totaldrain : 0.0;
-  ds.hit = false;
-  bool owner = false;
-  const bool outlet_inside = g.dr >= 1 && g.dr <= g.rows - 2 && g.dc >= 1 && g.dc <= g.ncp - 2;
-  if (MODULE == 2) {
-    owner = g.dr >= or_lo && g.dr <= or_hi && g.dc >= oc_lo && g.dc <= oc_hi;
-    if (drain_owed && owner && outlet_inside) ds.td = ds.td + owed_drain_sum(win, dem, g);   // the previous iteration's drain(), see above
-  }
-
-  // nine rows x three columns per lane; cells outside the slab: dem = +inf, water = 0.  Row bases are
-  // wave-uniform (scalar registers), the lane contributes a 32-bit byte offset: saddr-form loads, no 64-bit
-  // address arithmetic on the vector unit.  Only waves at the slab's right / lower edge mask anything.
-  const bool edge = (c0 + kStripIn > g.ncp) || (A + NR > g.rows);                  // wave-uniform
-  unsigned voff[3];
-#pragma unroll
-  for (int j = 0; j < 3; j++) voff[j] = 8u * (unsigned)(colb + j < g.ncp ? colb + j : g.ncp - 1);
-  double W[NR][3], D[NR][3];
-#pragma unroll
-  for (int i = 0; i < NR; i++) {
-    const int rc = A + i < g.rows ? A + i : g.rows - 1;
-    const char *bw = reinterpret_cast<const char *>(win + (size_t)rc * pitch);
-    const char *bd = reinterpret_cast<const char *>(dem + (size_t)rc * pitch);
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      W[i][j] = *reinterpret_cast<const double *>(bw + voff[j]);
-      D[i][j] = *reinterpret_cast<const double *>(bd + voff[j]);
-    }
-  }
-  // MD (round 3): the block's last launch of a small raster stays with this kernel - the snapshot's rows behind the rows this
-  // wave will store, requested with the window (the snapshot may still be owed the block's flush: applied as it is compared)
-  double O[3 * K + 2][3];
-  if (MD) {
-#pragma unroll
-    for (int i = 0; i < 3 * K + 2; i++) {
-      const int rc = A + i < g.rows ? A + i : g.rows - 1;
-      const char *bo = reinterpret_cast<const char *>(md.old + (size_t)rc * pitch);
-#pragma unroll
-      for (int j = 0; j < 3; j++) O[i][j] = *reinterpret_cast<const double *>(bo + voff[j]);
-    }
-  }
-  if (FLUSH) {
-#pragma unroll
-    for (int i = 0; i < NR; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++) W[i][j] = W[i][j] < thres ? 0.0 : W[i][j];       // WDPMCL.c:1059-1062
-  }
-  if (MODULE == 2 && drain_owed && outlet_inside && A + NR - 1 >= g.dr - 1 && A <= g.dr + 1) {   // wave-uniform, rare
-#pragma unroll
-    for (int i = 0; i < NR; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        const int r = A + i, c = colb + j;
-        W[i][j] = (r >= g.dr - 1 && r <= g.dr + 1 && c >= g.dc - 1 && c <= g.dc + 1) ? 0.0 : W[i][j];   // :1885-1889
-      }
-  }
-  if (edge) {
-#pragma unroll
-    for (int i = 0; i < NR; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        const bool ok = (A + i < g.rows) & (colb + j < g.ncp);
-        W[i][j] = ok ? W[i][j] : 0.0;
-        D[i][j] = ok ? D[i][j] : WDPM_INF;
-      }
-  }
-
-  bool outlet_here = false;
-  if constexpr (MODULE == 2) outlet_here = g.dr >= A && g.dr <= A + 8;
-  if constexpr (MODULE == 2) if (outlet_here) {
-    // The outlet's row is in this window (a handful of waves).  In every row alignment at most ONE row block
-    // holds that row (row blocks of an alignment are disjoint, so totaldrain still accumulates in pass order):
-    // it runs the marching kernel's stage with runoffd()'s sink, the other blocks of the alignment stay in
-    // lockstep.  Which block it is is wave-uniform but only known at run time: the window is permuted with
-    // selects so that one copy of the code serves every position.
-    bool cdr[5];
-#pragma unroll
-    for (int j = 0; j < 5; j++) cdr[j] = colb + j == g.dc;
-    const int off = g.dr - A;                                   // 0 .. 8
-    auto sel = [](const bool c, const double a, const double b) { return c ? a : b; };
-    double P[9][3], Q[9][3];
-    {  // oi = 1: row blocks at slots 0, 3, 6; the outlet's is block ob = off / 3
-      const int ob = off / 3;
-#pragma unroll
-      for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-          P[r][j] = sel(ob == 0, W[r][j], sel(ob == 1, W[3 + r][j], W[6 + r][j]));
-          Q[r][j] = sel(ob == 0, D[r][j], sel(ob == 1, D[3 + r][j], D[6 + r][j]));
-          P[3 + r][j] = sel(ob == 0, W[3 + r][j], W[r][j]);         Q[3 + r][j] = sel(ob == 0, D[3 + r][j], D[r][j]);
-          P[6 + r][j] = sel(ob == 2, W[3 + r][j], W[6 + r][j]);     Q[6 + r][j] = sel(ob == 2, D[3 + r][j], D[6 + r][j]);
-        }
-      double Wm[7][3], Dm[7][3];
-#pragma unroll
-      for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) { Wm[r][j] = P[r][j]; Dm[r][j] = Q[r][j]; }
-      stage_impl<2, false, 0, true>(Wm, Dm, A + 3 * ob, g.dr, cdr, ds);
-      stage_lockstep<2, 2, 3, 9>(P, Q);
-#pragma unroll
-      for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-          const double o = Wm[r][j], x = P[3 + r][j], y = P[6 + r][j];   // outlet block, first other, second other
-          W[r][j] = sel(ob == 0, o, x);
-          W[3 + r][j] = sel(ob == 1, o, sel(ob == 0, x, y));
-          W[6 + r][j] = sel(ob == 2, o, y);
-        }
-    }
-    {  // oi = 2: row blocks at slots 1 and 4 (rows 1-3, 4-6); the outlet's row is in one of them for off = 1 .. 6
-      const int ob = off >= 1 && off <= 6 ? (off - 1) / 3 : -1;
-      if (ob < 0) {
-        stage_lockstep<2, 2, 1, 9>(W, D);
-      } else {
-        double Wm[7][3], Dm[7][3], Wo[3][3], Do[3][3];
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-#pragma unroll
-          for (int j = 0; j < 3; j++) {
-            Wm[r][j] = sel(ob == 0, W[1 + r][j], W[4 + r][j]);   Dm[r][j] = sel(ob == 0, D[1 + r][j], D[4 + r][j]);
-            Wo[r][j] = sel(ob == 0, W[4 + r][j], W[1 + r][j]);   Do[r][j] = sel(ob == 0, D[4 + r][j], D[1 + r][j]);
-          }
-        stage_impl<2, false, 0, true>(Wm, Dm, A + 1 + 3 * ob, g.dr, cdr, ds);
-        stage_lockstep<2, 1, 0, 3>(Wo, Do);
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-#pragma unroll
-          for (int j = 0; j < 3; j++) {
-            W[1 + r][j] = sel(ob == 0, Wm[r][j], Wo[r][j]);
-            W[4 + r][j] = sel(ob == 0, Wo[r][j], Wm[r][j]);
-          }
-      }
-    }
-    // oi = 3: the one row block at slot 2 (rows 2-4)
-    if (off >= 2 && off <= 4) {
-      double Wm[7][3], Dm[7][3];
-#pragma unroll
-      for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) { Wm[r][j] = W[2 + r][j]; Dm[r][j] = D[2 + r][j]; }
-      stage_impl<2, false, 0, true>(Wm, Dm, A + 2, g.dr, cdr, ds);
-#pragma unroll
-      for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) W[2 + r][j] = Wm[r][j];
-    } else {
-      stage_lockstep<2, 1, 2, 9>(W, D);
-    }
-  }
-  if (!outlet_here) {
-    // (no clamped neighbour step here - see `deep` in the marching kernel: this kernel sits at 256 VGPRs, and a second copy of
-    // the stages behind a test of the window's depths made five of its instantiations spill, 8 - 164 bytes, round 4)
-    constexpr int F = PLAIN ? 1 : 0;
-    stage_lockstep<MODULE, K + 2, 0, NR, F>(W, D);   // oi = 1 on rows 0-2, 3-5, 6-8 (, 9-11)
-    stage_lockstep<MODULE, K + 1, 1, NR, F>(W, D);   // oi = 2 on rows 1-3, 4-6 (, 7-9)
-    stage_lockstep<MODULE, K, 2, NR, F>(W, D);       // oi = 3 on rows 2-4 (, 5-7)
-  }
-
-  // rows or_lo .. or_hi, columns oc_lo .. oc_hi (slots 0 and 1 only for the raster's first rows)
-#pragma unroll
-  for (int i = 0; i < 3 * K + 2; i++) {
-    const int r = A + i;
-    if (r < or_lo || r > or_hi) continue;                                    // wave-uniform
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      const int c = colb + j;
-      if (c >= oc_lo && c <= oc_hi) __builtin_nontemporal_store(W[i][j], wout + (size_t)r * pitch + c);
-    }
-  }
-  if (MODULE == 2 && owner && lane == 0) *totaldrain = ds.td;
-  if (MD) {
-    // max |w - oldw| over the cells this wave stored, of the rows asked for, with bigdem > missingvalue - plus the reference's
-    // seed cell [0][0] (WDPMCL.c:1239-1254); `if (d > m)` per lane, wave maximum, one atomicMax
-    double md_max = 0.0;
-#pragma unroll
-    for (int i = 0; i < 3 * K + 2; i++) {
-      const int r = A + i;
-      const bool row_in = r >= or_lo && r <= or_hi && r >= md.row_lo && r < md.row_hi;           // wave-uniform
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        const int c = colb + j;
-        double o = O[i][j];
-        o = o < md.thres ? 0.0 : o;                                                               // :1059-1062
-        const double dd = __builtin_fabs(W[i][j] - o);                                            // :1241
-        const bool cell = row_in & (c >= oc_lo) & (c <= oc_hi) & ((D[i][j] < WDPM_INF) | ((r == 0) & (c == 0)));
-        md_max = (cell & (dd > md_max)) ? dd : md_max;
-      }
-    }
-    fold_max_diff(md_max, md, lane);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Smallest rasters: the "relay" kernel (round 3).  A workgroup of four waves takes twelve rows of one strip and
-// produces the middle six; each wave carries ONE row block through a row alignment - a single dependent chain per lane, which
-// runs at its latency, where the triangle kernel's wave issues three, two, one blocks in lockstep and is bound by instruction
-// issue - and the rows two alignments share pass from wave to wave through LDS:
-//       oi = 1   wave w on rows 3w .. 3w+2                      (w = 0..3)
-//       row 3w+3 (wave w+1's first row) -> wave w               LDS + s_barrier
-//       oi = 2   wave w on rows 3w+1 .. 3w+3                    (w = 0..2)
-//       row 3w+4 (wave w+1's second row) -> wave w              LDS + s_barrier
-//       oi = 3   wave w on rows 3w+2 .. 3w+4, stored            (w = 0, 1)
-// Nine block stages for six rows, as in the six-row triangle wave, but three in a row per wave instead of nine.  Same trapezoid,
-// same pass order per cell, same arithmetic (stage_lockstep with one block): bit-identical.
-// ---------------------------------------------------------------------------------------------
-template <int MODULE, bool FLUSH, bool PLAIN, int NW = 4, bool DEM32 = false>
-__global__ void __launch_bounds__(64 * NW, 2)
-relay_iteration_kernel(const double *__restrict__ win, double *__restrict__ wout, const double *__restrict__ dem,
-                       const SlabGeom g, const int nstrips, const int nwg, const int A0, const int out_last, const double thres,
-                       double *__restrict__ totaldrain, const int drain_owed, const DemCode code, const int store_plain) {
-  static_assert(!DEM32 || (MODULE != 2 && NW == 8), "the DEM as 32-bit codes: add / subtract launches of several rounds");
-  const int lane = threadIdx.x & 63;
-  const int vb = (blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8;       // XCD-contiguous workgroups
-  if (vb >= nwg) return;                                                    // workgroup-uniform: nobody is left at a barrier
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int strip = vb % nstrips, chunk = vb / nstrips;
-  const int c0 = kStripOut * strip;
-  const int oc_lo = strip == 0 ? 0 : c0 + kHaloL;
-  int oc_hi = c0 + kStripIn - 1 - kHaloR;
-  if (oc_hi > g.ncp - 1) oc_hi = g.ncp - 1;
-  // NW waves: rows A .. A + 3 NW - 1 in, the middle 3 (NW - 2) out (NW = 4: twelve in, six out; NW = 8: 24 in, 18 out - fewer
-  // waves and less re-reading per row where the waves no longer fit on the chip at once)
-  constexpr int kOut = 3 * (NW - 2);
-  const int A = A0 + kOut * chunk;                // exact output rows A+2 .. A+kOut+1
-  const int or_lo = A == 0 ? 0 : A + 2;
-  int or_hi = A + kOut + 1;
-  if (or_hi > out_last) or_hi = out_last;
-  const int R0 = A + 3 * wave;                    // this wave's rows R0 .. R0+2, later up to R0+4
-  const int colb = c0 + 3 * lane;
-  const size_t pitch = (size_t)g.ncp;
-#ifdef WDPM_WAVE_TIMES
-  unsigned long long rst[8];
-  rst[0] = wall_clock64();
-#endif
-  const bool rprio = (store_plain & 2) != 0;      // wave-uniform: see the stages
-  if (rprio) __builtin_amdgcn_s_setprio(3);       // the loads of a new workgroup go out ahead of an older one's arithmetic
-  unsigned voff[3];
-#pragma unroll
-  for (int j = 0; j < 3; j++) voff[j] = 8u * (unsigned)(colb + j < g.ncp ? colb + j : g.ncp - 1);
-  double W[7][3], D[7][3];                        // slots 0 .. 4 are used (seven: stage_impl's window type)
-  // Every wave fetches its own three rows of water and of elevations.  The elevations of the two rows it takes over later are
-  // static data the wave below holds anyway: they come with the water through LDS (LDSDEM) where the launch is more than a
-  // round of waves - five rows of DEM fetched per wave made those memory-bound (add 2000^2 32.9 -> 30.0 us, 3000^2 66.7 -> 63.0,
-  // drain 1200^2 15.0 -> 14.3) - and for drain; add / subtract workgroups of four waves, the one-round sizes, fetch all five
-  // themselves: there the extra LDS traffic sits on the latency path (482^2 5.23 against 5.38 us; profiles/r03/relay_ldsdem_ab.txt)
-  constexpr bool LDSDEM = NW == 8 || MODULE == 2;
-#pragma unroll
-  for (int i = 0; i < (LDSDEM ? 3 : 5); i++) {
-    const int rc = R0 + i < g.rows ? R0 + i : g.rows - 1;
-    const char *bw = reinterpret_cast<const char *>(win + (size_t)rc * pitch);
-    const char *bd = reinterpret_cast<const char *>(dem + (size_t)rc * pitch);
-    const char *bq = reinterpret_cast<const char *>(code.q + (size_t)rc * pitch);
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      // DEM32: the elevations as verified-lossless 32-bit codes (wdpm_kernels.h::DemCode): launches of several rounds are bound
-      // by the memory system, and four bytes per cell less are worth nine decodes per wave there
-      if (DEM32) D[i][j] = dem32_decode_nan(*reinterpret_cast<const int *>(bq + voff[j] / 2), code.k0, code.D, code.rD, code.rDlo);
-      else D[i][j] = *reinterpret_cast<const double *>(bd + voff[j]);
-      W[i][j] = i < 3 ? *reinterpret_cast<const double *>(bw + voff[j]) : 0.0;
-    }
-  }
-#pragma unroll
-  for (int i = (LDSDEM ? 3 : 5); i < 7; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) { W[i][j] = 0.0; D[i][j] = WDPM_INF; }
-
-  // Drain: totaldrain is carried from row alignment to row alignment by whichever wave holds the outlet's block (at most one
-  // per alignment and workgroup: wave-uniform arithmetic every wave can do), through LDS; the workgroup whose stored block
-  // holds the outlet has seen every pass that touches it, in the reference's order, and writes it back.
-  DrainState ds;
-  ds.td = 0.0;
-  ds.hit = false;
-  bool owner = false;
-  int wo[3] = {-1, -1, -1};                       // wave that holds the outlet's row in its block of alignment oi = 1, 2, 3
-  bool cdr[5];
-#pragma unroll
-  for (int j = 0; j < 5; j++) cdr[j] = MODULE == 2 && colb + j == g.dc;
-  if (MODULE == 2) {
-    const bool outlet_inside = g.dr >= 1 && g.dr <= g.rows - 2 && g.dc >= 1 && g.dc <= g.ncp - 2;
-    const bool col_here = g.dc >= c0 && g.dc <= c0 + kStripIn + 1;      // the strip and the two columns lane 63 borrows
-#pragma unroll
-    for (int st = 0; st < 3; st++) {
-      const int rel = g.dr - A - st;              // alignment st + 1: wave w on rows A + 3w + st .. + 2
-      if (col_here && rel >= 0 && rel / 3 <= NW - 1 - st) wo[st] = rel / 3;
-    }
-    owner = g.dr >= or_lo && g.dr <= or_hi && g.dc >= oc_lo && g.dc <= oc_hi;
-    ds.td = *totaldrain;
-    if (drain_owed && outlet_inside) {
-      // the previous iteration's drain() (see fused_iteration_kernel): every wave of the owning workgroup adds it up for itself
-      if (owner) ds.td = ds.td + owed_drain_sum(win, dem, g);
-      if (R0 + 2 >= g.dr - 1 && R0 <= g.dr + 1) {                                   // wave-uniform, rare
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-          for (int j = 0; j < 3; j++) {
-            const int r = R0 + i, c = colb + j;
-            W[i][j] = (r >= g.dr - 1 && r <= g.dr + 1 && c >= g.dc - 1 && c <= g.dc + 1) ? 0.0 : W[i][j];   // :1885-1889
-          }
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < (LDSDEM ? 3 : 5); i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      if (FLUSH && i < 3) W[i][j] = W[i][j] < thres ? 0.0 : W[i][j];               // WDPMCL.c:1059-1062
-      const bool ok = (R0 + i < g.rows) & (colb + j < g.ncp);                      // outside the slab: dem = +inf, water = 0
-      W[i][j] = ok ? W[i][j] : 0.0;
-      D[i][j] = ok ? D[i][j] : WDPM_INF;
-    }
-  __shared__ double xch[2][NW][3 * kLanes];
-  __shared__ double xdem[2][LDSDEM ? NW : 1][LDSDEM ? 3 * kLanes : 1];   // elevations of a wave's first two rows, for the wave above
-  __shared__ double td_sh[3];
-  __shared__ int deep_sh[NW];
-  // The clamped neighbour step where the depths are shallow enough for it to be exact (see `deep` in the marching kernel: the same
-  // bound).  A wave tests the three rows it loaded: enough for the first alignment, which stays inside them; the rows it takes
-  // over afterwards have been through other waves' blocks, so from the first barrier on the workgroup's OR decides.  Wave-uniform.
-  bool deep = (store_plain & 4) != 0;              // the host's part: elevations too large (WDPM_LAUNCH_CLAMP_OK not given)
-  deep = deep || any_above_3m(&W[0]);
-  if (lane == 0) deep_sh[wave] = deep ? 1 : 0;
-  // one row alignment on this wave's block at slots S0 .. S0+2 (st = S0): the outlet's block takes block_update's outlet form
-#define WDPM_RELAY_STAGE(S0)                                                                               \
-  do {                                                                                                     \
-    if (MODULE == 2 && wo[S0] == wave) {                                                                   \
-      stage_impl<2, false, S0, true>(W, D, R0 + S0, g.dr, cdr, ds);                                        \
-      if (lane == 0) td_sh[S0] = ds.td;                                                                    \
-    } else if (MODULE == 2 || deep) {      /* drain: never clamped here - the second copy of the stages took the  */ \
-      /* drain instantiations from 112 to 150 VGPRs, one eight-wave workgroup per CU instead of two: -17 % (round 4) */   \
-      stage_lockstep<MODULE, 1, S0, 7, PLAIN ? 1 : 0>(W, D);                                               \
-    } else {                                                                                               \
-      stage_lockstep<MODULE, 1, S0, 7, (PLAIN ? 1 : 0) | 2>(W, D);                                         \
-    }                                                                                                      \
-  } while (0)
-  // rprio (launches of a few rounds of workgroups: the host decides): a workgroup's issue priority falls from stage to stage, so that
-  // of the workgroups sharing a CU's SIMDs the one behind is served first (the arbiter's own rule is oldest first: see the marching
-  // loop).  profiles/r03/relay_prio_ab.txt: 1000^2 add 9.72 -> 9.11 us, drain 13.5 -> 12.0; 1200^2 and 1400^2 add +4.5 %; from five
-  // rounds of workgroups on nothing or a loss (1800^2 drain -4 %, add -10 %; 2400^2 add -10 %: there the old workgroups' early exit is
-  // what feeds the next round), so only launches of up to four rounds carry the flag
-  if (rprio) __builtin_amdgcn_s_setprio(2);
-  WDPM_RSTAMP(1);                                                             // rows loaded
-  WDPM_RELAY_STAGE(0);                                                        // oi = 1
-  WDPM_RSTAMP(2);
-#pragma unroll
-  for (int j = 0; j < 3; j++) {
-    xch[0][wave][j * kLanes + lane] = W[0][j];
-    if (LDSDEM) {
-      xdem[0][wave][j * kLanes + lane] = D[0][j];
-      xdem[1][wave][j * kLanes + lane] = D[1][j];
-    }
-  }
-  __syncthreads();
-  WDPM_RSTAMP(3);
-#pragma unroll
-  for (int w = 0; w < NW; w++) deep = deep || deep_sh[w] != 0;
-  if (MODULE == 2 && wo[0] >= 0) ds.td = td_sh[0];
-  if (wave < NW - 1) {
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      W[3][j] = xch[0][wave + 1][j * kLanes + lane];
-      if (LDSDEM) {
-        D[3][j] = xdem[0][wave + 1][j * kLanes + lane];
-        D[4][j] = xdem[1][wave + 1][j * kLanes + lane];
-      }
-    }
-    if (rprio) __builtin_amdgcn_s_setprio(1);
-    WDPM_RELAY_STAGE(1);                                                      // oi = 2
-  }
-  WDPM_RSTAMP(4);
-#pragma unroll
-  for (int j = 0; j < 3; j++) xch[1][wave][j * kLanes + lane] = W[1][j];
-  __syncthreads();
-  WDPM_RSTAMP(5);
-#ifdef WDPM_WAVE_TIMES
-  if (wave >= NW - 2 && lane == 0) {
-    const int wid = ((int)blockIdx.x * NW + wave);
-    if (wid < 4096) { for (int k = 0; k < 6; k++) g_wave_times[8 * wid + k] = rst[k]; g_wave_times[8 * wid + 6] = rst[5]; g_wave_times[8 * wid + 7] = rst[5]; }
-  }
-#endif
-  if (wave >= NW - 2) return;
-  if (MODULE == 2 && wo[1] >= 0) ds.td = td_sh[1];
-#pragma unroll
-  for (int j = 0; j < 3; j++) W[4][j] = xch[1][wave + 1][j * kLanes + lane];
-  if (rprio) __builtin_amdgcn_s_setprio(0);
-  WDPM_RELAY_STAGE(2);                                                        // oi = 3
-  WDPM_RSTAMP(6);
-#undef WDPM_RELAY_STAGE
-  // wave w stores rows A+3w+2 .. A+3w+4 (wave 0 also rows 0, 1 of the raster's first chunk)
-  if (LDSDEM) {
-    // Through the wave's LDS slices (free since the second barrier), so that one store instruction writes 512 contiguous
-    // bytes - as the marching kernel does.  Lane by lane a wave's three stores per row interleave at 24-byte strides, and as
-    // non-temporal stores they reach the memory as partial lines: 52 MB written per 2000^2 launch for 32 MB of raster
-    // (profiles/r03/add2000_pmc_summary.json; add 2000^2 28.9 -> 26.1 us, 3000^2 58.2 -> 50.8, relay_stores_ab.txt).  Lanes past
-    // the exact output range are clamped onto its last column.  store_plain bit 0: ordinary instead of non-temporal stores (the
-    // host sets it for launches of six rounds and more: relay_stores_ab.txt).
-    double *const t[3] = {&xdem[0][wave][0], &xdem[1][wave][0], &xch[0][wave][0]};
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++) t[i][3 * lane + j] = W[2 + i][j];
-    __builtin_amdgcn_wave_barrier();
-    const int lo = oc_lo - c0, hi = oc_hi - c0;
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-      const int r = R0 + 2 + i;
-      if (r < or_lo || r > or_hi) continue;                                         // wave-uniform
-#pragma unroll
-      for (int kk = 0; kk < 3; kk++) {
-        const int c = lo + 64 * kk + lane < hi ? lo + 64 * kk + lane : hi;
-        double *const q = wout + (size_t)r * pitch + c0 + c;
-        if (store_plain & 1) *q = t[i][c];
-        else __builtin_nontemporal_store(t[i][c], q);
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < (LDSDEM ? 2 : 5); i++) {
-    const int r = R0 + i;
-    if (r < or_lo || r > or_hi || (i < 2 && !(wave == 0 && A == 0))) continue;    // wave-uniform
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      const int c = colb + j;
-      if (c >= oc_lo && c <= oc_hi) __builtin_nontemporal_store(W[i][j], wout + (size_t)r * pitch + c);
-    }
-  }
-  // the wave that ran the last alignment's outlet block holds the final value; if that alignment had none here, wave 0 does
-  if (MODULE == 2 && owner && lane == 0 && wave == (wo[2] >= 0 ? wo[2] : 0)) *totaldrain = ds.td;
-#ifdef WDPM_WAVE_TIMES
-  WDPM_RSTAMP(7);
-  if (lane == 0) {
-    const int wid = ((int)blockIdx.x * NW + wave);
-    if (wid < 4096) for (int k = 0; k < 8; k++) g_wave_times[8 * wid + k] = rst[k];
-  }
-#endif
-}
-
 /* wdpm_kernels.h::XcdBalance: (update) move the weights towards equal mean wave durations - weight 0 .. 7: the relative height of
  * the chunks whose work items run on that XCD (the physical one: BalanceArgs::rot), weight 8: a factor on a strip's last chunk (its
  * waves are the slab's lower edge and take the masking loop), weight 9: one on its first (round 5: the slab's first chunk row ends late);
@@ -1829,12 +1003,6 @@ __global__ void dpp_probe_kernel(int *out) {
 
 }  // namespace
 
-/* One row of a family's launch table: the template arguments, the instantiation, its ledger slot.  Every instantiation of a family
- * has the family's one signature (a row of another type does not compile); the tables are made from the variant lists of
- * wdpm_dispatch.h and from nothing else, so those lists are also what the device code and the ledger contain. */
-template <class Fn> struct VariantRow { int targs[6]; Fn fn; const int *slot; };
-#define WDPM_VARIANT_ROW(KERNEL, ...) {{__VA_ARGS__}, &KERNEL<__VA_ARGS__>, &WdpmLedgerSlot<&KERNEL<__VA_ARGS__>, __VA_ARGS__>::slot},
-
 static hipError_t dpp_selfcheck(hipStream_t s) {
   static std::atomic<int> state{0};   // 0 unknown, 1 ok, -1 bad; rank threads of one process launch concurrently: no plain statics
   if (state == 1) return hipSuccess;
@@ -1858,46 +1026,6 @@ static hipError_t dpp_selfcheck(hipStream_t s) {
   return ok ? hipSuccess : hipErrorUnknown;
 }
 
-/* The launches of small and mid-size rasters (relay and triangle kernels).  Compiled as a
- * translation unit of its own (WDPM_TU == 2; the marching kernel and everything else: WDPM_TU == 1), because the two want different
- * instruction schedulers: the marching kernel is 2 % faster under the compiler's max-ILP strategy (-mllvm -amdgpu-sched-strategy=max-ilp:
- * add 16384^2 1.1425 -> 1.1189 ms), the eight-wave relay instantiations 2.4 % slower (profiles/r03/sched_strategy_ab.txt). */
-#if !defined(WDPM_TU) || WDPM_TU == 2
-using RelayFn = decltype(&relay_iteration_kernel<0, false, false, 4, false>);
-using TriangleFn = decltype(&tri_iteration_kernel<0, false, 1, false, false>);
-#define WDPM_ROW_RELAY(...) WDPM_VARIANT_ROW(relay_iteration_kernel, __VA_ARGS__)
-#define WDPM_ROW_TRIANGLE(...) WDPM_VARIANT_ROW(tri_iteration_kernel, __VA_ARGS__)
-static const VariantRow<RelayFn> kRelayTable[] = {WDPM_VARIANTS_RELAY(WDPM_ROW_RELAY)};
-static const VariantRow<TriangleFn> kTriangleTable[] = {WDPM_VARIANTS_TRIANGLE(WDPM_ROW_TRIANGLE)};
-
-/* this unit's part of DeviceFacts (cus is filled already) */
-void wdpm_small_device_facts(DeviceFacts *f) {
-  int blocks = 1;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, tri_iteration_kernel<0, false, 1, false, false>, 256, 0) != hipSuccess || blocks < 1) blocks = 1;
-  f->tri_slots = f->cus * blocks * 4;
-}
-
-hipError_t wdpm_launch_small(const LaunchRequest &q, const LaunchPlan &p, const IterationBuffers &b) {
-  const int drain_owed = q.module == 2 ? b.drain_owed : 0;
-  if (p.family == WDPM_FAMILY_RELAY) {
-    const int at = wdpm_find_variant(kRelayVariants, p.targs);
-    if (at < 0) return hipErrorInvalidValue;
-    wdpm_ledger_count(*kRelayTable[at].slot, p.ledger_sw);
-    hipLaunchKernelGGL(kRelayTable[at].fn, dim3(p.grid), dim3(p.block), 0, b.stream, b.w_in, b.w_out, b.dem, q.g, p.nstrips, p.nitems, q.A0,
-                       q.out_last, b.thres, b.totaldrain, drain_owed, *b.code, p.relay_flags);
-  } else {
-    const int at = wdpm_find_variant(kTriangleVariants, p.targs);
-    if (at < 0) return hipErrorInvalidValue;
-    const MaxDiffArgs tmd = p.fold_md ? *b.md : MaxDiffArgs{nullptr, 0.0, 0, 0, nullptr};
-    wdpm_ledger_count(*kTriangleTable[at].slot, p.ledger_sw);
-    hipLaunchKernelGGL(kTriangleTable[at].fn, dim3(p.grid), dim3(p.block), 0, b.stream, b.w_in, b.w_out, b.dem, q.g, p.nstrips, p.nitems, q.A0,
-                       q.out_last, b.totaldrain, b.thres, drain_owed, tmd);
-  }
-  return hipGetLastError();
-}
-#endif
-
-#if !defined(WDPM_TU) || WDPM_TU == 1
 using MarchingFn = decltype(&fused_iteration_kernel<0, false, 0, false, false, false>);
 #define WDPM_ROW_MARCHING(...) WDPM_VARIANT_ROW(fused_iteration_kernel, __VA_ARGS__)
 static const VariantRow<MarchingFn> kMarchingTable[] = {WDPM_VARIANTS_MARCHING(WDPM_ROW_MARCHING)};
@@ -2018,10 +1146,7 @@ hipError_t wdpm_launch_iteration(const LaunchRequest &q, const LaunchPlan &p, co
   return hipGetLastError();
 }
 
-#endif   /* WDPM_TU 1 */
-
 #ifdef WDPM_WAVE_TIMES
-#if !defined(WDPM_TU) || WDPM_TU == 1
 extern "C" int wdpm_debug_wave_times(unsigned long long *out, int nwaves) {
   if (hipDeviceSynchronize() != hipSuccess) return 1;
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wave_times), (size_t)nwaves * 32) != hipSuccess;
@@ -2030,11 +1155,4 @@ extern "C" int wdpm_debug_wave_waits(unsigned long long *out, int nwaves) {
   if (hipDeviceSynchronize() != hipSuccess) return 1;
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wave_waits), (size_t)nwaves * 32) != hipSuccess;
 }
-#endif
-#if !defined(WDPM_TU) || WDPM_TU == 2
-extern "C" int wdpm_debug_relay_times(unsigned long long *out, int nwaves) {
-  if (hipDeviceSynchronize() != hipSuccess) return 1;
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wave_times), (size_t)nwaves * 32) != hipSuccess;
-}
-#endif
 #endif

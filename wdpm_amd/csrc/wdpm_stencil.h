@@ -61,7 +61,7 @@ __device__ __forceinline__ double dem32_decode_nan(const int q, const double k0,
  * h < 2^16), so n is the same number - and gb + k0 is what a lane's three columns of a row share (they lie in one group), which
  * the compiler computes once per row: per value one unsigned conversion, an add, the two operations of the quotient and the
  * NODATA select.  NOSEL leaves that select (a compare and a v_cndmask) out: for steps whose wave holds no offset 0xFFFF at all,
- * which the caller has tested (wdpm_fused.hip::decode_rows); the encoder uses the full form. */
+ * which the caller has tested (wdpm_march.hip::decode_rows); the encoder uses the full form. */
 template <bool NOSEL = false>
 __device__ __forceinline__ double dem16_decode_nan(const int h, const int gb, const double k0, const double D, const double rD, const double rDlo) {
   const double n = ((double)gb + k0) + (double)(unsigned)h;
@@ -138,7 +138,7 @@ __device__ __forceinline__ void flow_add(const double dem_c, double &w_c, const 
  * (+0.0 here where the two-instruction form gives -0.0; `w + (+-0)` and `w - |+-0|` return w either way for every w that is not
  * -0.0, which the _nz forms exclude).  For x > 8 the result is 1.0 instead of x / 8, so a caller may use it only where no flow
  * of a neighbour step can exceed 1 m - the kernels establish that per wave and step from the depths they hold
- * (wdpm_fused.hip: `deep`): a flow is at most (centre depth + half an ulp of its elevation) / 8, and a depth grows by at most
+ * (wdpm_march.hip: `deep`): a flow is at most (centre depth + half an ulp of its elevation) / 8, and a depth grows by at most
  * that in each of the eight passes of an iteration in which its cell receives. */
 __device__ __forceinline__ double eighth_clamped(const double x) {
   double r;
