@@ -1,4 +1,4 @@
-"""A numpy model of what wdpm_capi.hip::encode_dem decides for an uploaded DEM, and the rasters the binary-grid tests share.
+"""A numpy model of what wdpm_dem_codes.hip::encode_dem decides for an uploaded DEM, and the rasters the binary-grid tests share.
 
 The library expresses a DEM as 32-bit codes q with dem == (q + k0) / D bit for bit: first D = 10^e, e = 0..6; then, when all
 seven fail, once D = 2^s, 2^-s being the weight of the lowest bit set in any valid non-zero elevation (dem_min_kernel), if

@@ -1,5 +1,5 @@
 """DEMs that were binary all along - Float32 rasters written with all their digits, float -> double through the C ABI - stream as
-verified 32-bit codes on the grid 2^-s of their lowest set bit (wdpm_capi.hip::encode_dem, after the decimal grids 10^-e have
+verified 32-bit codes on the grid 2^-s of their lowest set bit (wdpm_dem_codes.hip::encode_dem, after the decimal grids 10^-e have
 failed).  Results can never depend on the codes, so every case here also proves from the options (WDPM_OPT_DEM32, _DEM_GRID,
 _DEM_GRID_EXP) and from the launch ledger - the third template argument of fused_iteration_kernel, the relay kernel's last - that
 a code-streaming instantiation ran; what the device must find comes from the numpy model (tests/binary_dem_model.py,

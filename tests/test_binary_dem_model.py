@@ -1,4 +1,4 @@
-"""The binary-grid search of wdpm_capi.hip::encode_dem as a numpy model (tests/binary_dem_model.py) held against exact rational
+"""The binary-grid search of wdpm_dem_codes.hip::encode_dem as a numpy model (tests/binary_dem_model.py) held against exact rational
 arithmetic: the lowest-set-bit scan, the accept / refuse rule and the decode.  No GPU needed; tests/test_binary_dem.py holds the
 device against this model."""
 from fractions import Fraction

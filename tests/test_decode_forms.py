@@ -40,7 +40,7 @@ def bits(x):
 
 
 def reciprocal_words(D):
-    """rD and rDlo as wdpm_capi.hip::encode_dem computes them"""
+    """rD and rDlo as wdpm_dem_codes.hip::encode_dem computes them"""
     Df = float(D)
     rD = 1.0 / Df
     rDlo = fma(-rD, Df, 1.0) / Df

@@ -1000,3 +1000,36 @@ def test_water_kinds_and_the_gate_free_variants(hip, oracle, module):
             g.iterate(4)
             o.iterate(4)
             assert n_bit_diff(g.download_water(), o.download_water()) == 0, name
+
+
+def test_captured_graphs_are_keyed_by_what_the_water_held(hip, oracle):
+    """The key of a captured HIP graph (wdpm_ctx.h: GraphKey) states what the water held when it was captured.  A small add raster
+    on the default dispatch captures graphs in its first block; then a -0.0 and, after that, a negative depth are uploaded into the
+    same context, and every block after either must still give the oracle's bits: a graph captured for plain water is never
+    replayed over water that is not."""
+    if os.environ.get("WDPM_GRAPH") == "0":
+        pytest.skip("WDPM_GRAPH=0: no graphs are captured")
+    THRES = 0.005 / 1000
+    R, C = 120, 300                                     # test_iterate_bookkeeping.py's "small-add": the small-raster kernels
+    dem, water, miss = random_case(R * 37 + C, R, C)
+    bd, bw = pad(dem, water, miss)
+    kw = dict(module="add", nrows=R, ncols=C, missingvalue=miss)
+    with hip.context(**kw) as g, oracle.context(**kw) as o:
+        for c in (g, o):
+            c.upload(bd, bw)
+
+        def block(what):
+            assert g.run_block(40, THRES) == o.run_block(40, THRES), what
+            assert n_bit_diff(g.download_water(), o.download_water()) == 0, what
+
+        before = g.get_option(wdpm_amd.capi.OPT_GRAPH_LAUNCHES)
+        block("first block")
+        assert g.get_option(wdpm_amd.capi.OPT_GRAPH_LAUNCHES) > before
+        valid = np.argwhere(bd > miss)
+        row, col = valid[len(valid) // 2]                  # one valid cell
+        for what, depth in (("a -0.0", -0.0), ("a negative depth", -0.25)):
+            w = g.download_water()
+            w[row, col] = depth
+            g.upload_water(w)
+            o.upload_water(w)
+            block(what)

@@ -1,6 +1,6 @@
 """The counters behind the benchmark's headline: bench.py divides the milliseconds of wdpm_timing_get / wdpm_timing_get_steady by
 their launch counts, so what each call of the block loop adds to the two counts is part of the measurement.  The rules
-(wdpm_capi.hip: wdpm_iterate, wdpm_iterate_overlapped), per call of n iterations:
+(wdpm_block.hip: wdpm_iterate, wdpm_iterate_overlapped), per call of n iterations:
   fused kernels   launches += n whether or not iterations went out two per launch; steady launches += n - 2 for n >= 3 (the call's
                   first and last launch may be the flush-on-load and max-diff variants), else 0
   pass kernel     launches += 9 n (nine colour passes an iteration), steady launches stay

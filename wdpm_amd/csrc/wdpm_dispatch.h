@@ -2,7 +2,7 @@
  * wdpm_dispatch.h — which kernel instantiation an iteration launch uses, with which grid, chunk height, LDS pad and switches
  * (DESIGN.md §4.4 is the specification; nearly every threshold below was bought with an A/B run under profiles/).
  * Plain C++17 and nothing else: no HIP header, no getenv, no statics, no pointer dereferenced.  plan_iteration() only decides;
- * wdpm_march.hip and wdpm_small.hip launch what it decided, wdpm_capi.hip asks.  tests/test_dispatch_plans.py holds every decision against a
+ * wdpm_march.hip and wdpm_small.hip launch what it decided, wdpm_block.hip asks.  tests/test_dispatch_plans.py holds every decision against a
  * recorded table (tests/golden/dispatch_plans.json.gz) without a GPU.
  */
 #ifndef WDPM_DISPATCH_H
@@ -65,7 +65,7 @@ struct Switches {
   WDPM_SWITCHES(WDPM_SWITCH_MEMBER)
 #undef WDPM_SWITCH_MEMBER
 };
-/* `get` is getenv or a stand-in.  The library reads its environment through this once per process (wdpm_capi.hip::wdpm_switches) */
+/* `get` is getenv or a stand-in.  The library reads its environment through this once per process (wdpm_ctx.h::wdpm_switches) */
 template <class Get> inline Switches wdpm_read_switches(Get get) {
   Switches sw;
 #define WDPM_SWITCH_READ(member, name, dflt) if (const char *e = get(name)) sw.member = atoi(e);

@@ -1,5 +1,5 @@
 /*
- * wdpm_kernels.h — launch interface between the C-ABI layer (wdpm_capi.hip) and the gfx950
+ * wdpm_kernels.h — launch interface between the C-ABI layer (the units on wdpm_ctx.h: wdpm_capi.hip, wdpm_block.hip, wdpm_dem_codes.hip, wdpm_stats.hip) and the gfx950
  * kernels (wdpm_kernels.hip, wdpm_march.hip, wdpm_small.hip).  Internal; not part of the drop-in boundary.
  */
 #ifndef WDPM_KERNELS_H
@@ -177,7 +177,7 @@ hipError_t wdpm_launch_iteration(const LaunchRequest &q, const LaunchPlan &p, co
 void wdpm_small_device_facts(DeviceFacts *f);
 hipError_t wdpm_launch_small(const LaunchRequest &q, const LaunchPlan &p, const IterationBuffers &b);
 /* What kinds of depth do the n cells at p hold (dem: the device DEM of the same cells, NODATA = +inf)?
- *   *flag |= 1  a -0.0                       (the exact-zero stencil variant must run, see signed_zero_safe)
+ *   *flag |= 1  a -0.0                       (the exact-zero stencil variant must run: LaunchRequest::signed_zero_safe)
  *   *flag |= 2  a negative depth             (gone once a threshold flush with thres >= 0 has been applied)
  *   *flag |= 4  NaN, a depth above 1e290, or water on a NODATA cell   (stays)
  * With none of them, every cell that may not give water (dry, NODATA, outside the slab) holds +0.0 exactly - and then

@@ -18,7 +18,7 @@
 
 #include "../../include/wdpm.h"
 
-/* wdpm_capi.hip: `pretty` is the __PRETTY_FUNCTION__ of wdpm_ledger_pretty<kernel> (the kernel's unqualified name is taken from
+/* wdpm_capi.hip (the ledger table): `pretty` is the __PRETTY_FUNCTION__ of wdpm_ledger_pretty<kernel> (the kernel's unqualified name is taken from
  * it), `args` the template argument list ("<0, false>" or "") */
 int wdpm_ledger_register(const char *pretty, const char *args);
 void wdpm_ledger_count(int slot, int switches);      /* relaxed atomics: the rank threads of a group launch concurrently */

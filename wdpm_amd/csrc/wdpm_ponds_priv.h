@@ -21,13 +21,7 @@
 #include <string>
 #include <vector>
 
-#include "wdpm_ctx.h"
-
-#define HIP_TRY(expr)                                                                                  \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) return wdpm_fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
+#include "wdpm_ctx.h"   /* the context, wdpm_fail, HIP_TRY */
 #endif
 #include <cstddef>
 

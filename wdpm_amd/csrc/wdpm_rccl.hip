@@ -160,11 +160,6 @@ constexpr int kGatherMax = 8;
     if (r_ != ncclSuccess)                                                                             \
       return wdpm_fail("%s failed: %s (%s:%d)", #expr, g_api.GetErrorString(r_), __FILE__, __LINE__);  \
   } while (0)
-#define HIP_TRY(expr)                                                                                  \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) return wdpm_fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
 
 static int attach(wdpm_ctx *x, ncclComm_t comm, int rank, int nranks) {
   wdpm_comm *c = new wdpm_comm{comm, rank, nranks, nullptr, nullptr, nullptr, {false}, false, false};

@@ -21,7 +21,7 @@
 
 /* DEM code -> elevation (wdpm_kernels.h::DemCode).  n = q + k0 is an exact integer in fp64 and the elevation is RN(n / D), D = 10^e
  * - or D = 2^s for a DEM on a binary grid: then rD = 2^-s is exact, rDlo is 0, and the same two operations give n * 2^-s itself.
- * The quotient in two operations: rD = RN(1 / D) and rDlo = RN(1 / D - rD) (the host computes both, wdpm_capi.hip::encode_dem), and
+ * The quotient in two operations: rD = RN(1 / D) and rDlo = RN(1 / D - rD) (the host computes both, wdpm_dem_codes.hip::encode_dem), and
  * n * rD + n * rDlo is n / D to about 2^-104 relative - the product n * rDlo is rounded once (2^-53 of a term that is 2^-53 of the
  * sum) and the FMA rounds the sum once.  A quotient of an integer below 2^53 by a 20-bit denominator cannot lie that close to a
  * rounding boundary without lying on it, so the FMA lands on RN(n / D); for e = 0 rDlo is 0 and the result is n itself.
