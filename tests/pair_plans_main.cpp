@@ -1,5 +1,9 @@
 /* Prints, one JSON object per line, what plan_iter2() (wdpm_amd/csrc/wdpm_dispatch.h) decides for a request that meets every
- * condition of a two-iteration launch and for requests that miss exactly one of them: tests/test_pair_iterations.py.  Host compiler only. */
+ * condition of a two-iteration launch and for requests that miss exactly one of them: tests/test_pair_iterations.py.  Host compiler only.
+ *
+ * With arguments: one line per argument `name:R:C:codes16:balance:ring:clamp_ok` - the forced two-iteration launch (WDPM_RELAY=0
+ * WDPM_TRI=0 WDPM_ITER2=2, codes forced) of an R x C raster as tests/test_iter2_corners.py plays it: 16-bit offsets or 32-bit codes,
+ * WDPM_BALANCE, WDPM_ITER2_RING, and whether the clamped neighbour step is allowed (WDPM_CLAMP and the DEM's bound). */
 #include <cstdio>
 #include <cstring>
 
@@ -37,12 +41,32 @@ static void say(const char *name, const LaunchRequest &q, const Switches &sw, co
   const DeviceFacts f = mi355x();
   const LaunchPlan p = plan_iter2(q, f, sw, left), one = plan_iteration(q, f, sw);
   printf("{\"case\": \"%s\", \"iter2\": %d, \"single_untouched\": %s, \"grid\": %u, \"block\": %u, \"lds\": %u, \"groups\": %d, \"nchunks\": %d, "
-         "\"H\": %d, \"ring_rows\": %d, \"ledger_sw\": %d, \"table\": %s, \"ipx\": %d}\n",
+         "\"H\": %d, \"ring_rows\": %d, \"ledger_sw\": %d, \"table\": %s, \"ipx\": %d, \"codes\": %d, \"single_codes\": %d, "
+         "\"single_ledger_sw\": %d, \"single_marching\": %s}\n",
          name, p.iter2, (p.iter2 || same_plan(p, one)) ? "true" : "false", p.grid, p.block, p.lds, p.nstrips, p.nchunks, p.H, p.ring_rows,
-         p.ledger_sw, p.table ? "true" : "false", p.ipx);
+         p.ledger_sw, p.table ? "true" : "false", p.ipx, p.targs[2], one.targs[2], one.ledger_sw,
+         one.family == WDPM_FAMILY_MARCHING && one.targs[5] == 1 ? "true" : "false");
 }
 
-int main() {
+/* the launches tests/test_iter2_corners.py forces onto small rasters */
+static int corners(const int argc, char **argv) {
+  for (int i = 1; i < argc; i++) {
+    char name[128];
+    int R, C, codes16, balance, ring, clamp_ok;
+    if (sscanf(argv[i], "%127[^:]:%d:%d:%d:%d:%d:%d", name, &R, &C, &codes16, &balance, &ring, &clamp_ok) != 7) return 1;
+    Switches sw; sw.iter2 = 2; sw.relay = 0; sw.tri = 0; sw.iter2_ring = ring;
+    LaunchRequest q = request(R + 2, C + 2);
+    q.force_codes = 1;
+    q.codes16 = codes16 != 0;
+    q.flags = WDPM_LAUNCH_PLAIN | (clamp_ok ? WDPM_LAUNCH_CLAMP_OK : 0);
+    q.balance_mode = balance; q.balance_capacity = 16384;
+    say(name, q, sw, 2);
+  }
+  return 0;
+}
+
+int main(int argc, char **argv) {
+  if (argc > 1) return corners(argc, argv);
   const Switches dflt;
   const LaunchRequest big = request(16386, 16386);
   say("offered", big, dflt, 2);

@@ -12,7 +12,13 @@ cases in a child process (the switches are read once per process), bit for bit a
   the relay kernel on every size             WDPM_RELAY=2, four-wave and eight-wave workgroups, stage priorities forced
   the triangle kernel on every size          WDPM_TRI=2 WDPM_RELAY=0, three and six rows per wave
   (round 5) the marching kernel on every size with every slot of the resident round filled - chunks down to two row triples - and the
-  row boundaries of partner strips rounded half a triple apart    WDPM_BALANCE=2 WDPM_PAIR=2"""
+  row boundaries of partner strips rounded half a triple apart    WDPM_BALANCE=2 WDPM_PAIR=2
+
+Two iterations per marching launch (WDPM_ITER2=2) are not among the variants: the suites replayed here ask for a chunk height or
+iterate fewer than four times, and plan_iter2 refuses either.  That loop has suites of its own - tests/test_pair_iterations.py,
+tests/test_iter2_retired_strips.py, tests/test_marching_slabs.py, tests/test_dem16_bases.py - and tests/test_iter2_corners.py gives it
+what the suites above give the others: the adversarial operand pools, subnormal depths, the unclamped step, every height, every width
+around its strips' and groups' edges, the degenerate shapes."""
 import os
 import subprocess
 import sys
