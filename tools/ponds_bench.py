@@ -33,6 +33,10 @@
                       bed and stages phases beside the table, passes and locate phases of the SAME calls, their ratios, and their
                       rates under the byte model of 12 B per cell and pass (int32 basin, fp64 dem) against the yardstick (default
                       --out profiles/r18/pond_curves.json)
+                      With --devices: GroupPonds.label_stage_curves (include/wdpm_group_pond_curves.h) - per-rank bed and stages
+                      phases and their sums over the ranks, the host's merge_ms, split_basins and remote_beds, the bytes of slot
+                      rows that come down; then the whole-raster call on the same water in the same process, phases and wall
+                      clock, the yardstick of those sums (default --out profiles/r24/pond_curves_group.json)
     ... --iterations K   instead of the job's own number of iterations before the inventory
     ... --lib FILE       another build of the library (tools/build_alt.sh NAME REV) instead of the tree's: the same job on the parent
 
@@ -253,6 +257,30 @@ def group_job(hip, a, bd, bw, iters, rec):
                 group_catchments_job(p, rec, len(devices))
             if a.outlets:
                 group_outlets_job(p, rec, len(devices))
+            if a.curves:
+                group_curves_job(p, rec, len(devices))
+    if a.curves:                                               # the yardstick: the whole-raster call on the same water, same process
+        with hip.context(module="add", nrows=n, ncols=n, missingvalue=MISS) as ctx:
+            ctx.upload(bd, bw)
+            if iters > 0:
+                ctx.run_block(iters, 0.005 / 1000)
+            with Ponds(ctx) as p:
+                p.label_curves(0.001)
+                phases, wall = {k: [] for k in CURVE_PHASES}, []
+                for _ in range(5):
+                    ctx.synchronize()
+                    t0 = time.perf_counter()
+                    p.label_curves(0.001)
+                    wall.append((time.perf_counter() - t0) * 1e3)
+                    for k, v in p.curve_phase_ms().items():
+                        phases[k].append(v)
+                whole = {k: statistics.median(v) for k, v in phases.items()}
+                c = rec["curves"]
+                c.update(whole_raster_phase_ms=whole, whole_raster_phase_ms_all=phases, whole_raster_stats=p.curve_stats(),
+                         whole_raster_wall_ms=statistics.median(wall), whole_raster_wall_ms_all=wall)
+                c["sum_over_ranks_over_whole_raster"] = {k: c["phase_sum_over_ranks_ms"][k] / whole[k] if whole[k] > 0 else None for k in CURVE_PHASES}
+                c["wall_over_whole_raster_wall"] = c["label_stage_curves_wall_ms"] / c["whole_raster_wall_ms"]
+                print(f"whole raster: bed {whole['bed']:.3f} ms  stages {whole['stages']:.3f} ms  wall {c['whole_raster_wall_ms']:.3f} ms", file=sys.stderr)
     if a.outlets:                                              # the yardstick: the whole-raster call on the same water, same process
         with hip.context(module="add", nrows=n, ncols=n, missingvalue=MISS) as ctx:
             ctx.upload(bd, bw)
@@ -372,6 +400,35 @@ def group_outlets_job(p, rec, nranks):
     print(f"merge_ms {rec['outlets']['merge_ms']:.3f}", file=sys.stderr)
 
 
+def group_curves_job(p, rec, nranks):
+    """after the label calls: one untimed label_stage_curves (allocates every rank's slot rows and keys), five timed ones"""
+    p.label_stage_curves(0.001)
+    wall, merge = [], []
+    phases = [{k: [] for k in CURVE_PHASES} for _ in range(nranks)]
+    table_ms = [[] for _ in range(nranks)]
+    for _ in range(5):
+        t0 = time.perf_counter()
+        p.label_stage_curves(0.001)
+        wall.append((time.perf_counter() - t0) * 1e3)
+        merge.append(p.stage_curve_stats()["merge_ms"])
+        for i in range(nranks):
+            for k, v in p.stage_curve_phase_ms(i).items():
+                phases[i][k].append(v)
+            table_ms[i].append(p.phase_ms(i)["table"])
+    table, stats = p.stage_curves(), p.stage_curve_stats()
+    slots = p.catchment_stats()["remote"] + p.rims_stats()["slots"]
+    sums = {k: statistics.median([sum(phases[i][k][j] for i in range(nranks)) for j in range(5)]) for k in CURVE_PHASES}   # per call, over ranks
+    c = rec["curves"] = dict(label_stage_curves_wall_ms=statistics.median(wall), label_stage_curves_wall_ms_all=wall,
+                             rank_phase_ms=[{k: statistics.median(v) for k, v in ph.items()} for ph in phases], rank_phase_ms_all=phases,
+                             phase_sum_over_ranks_ms=sums, rank_table_ms_same_calls=[statistics.median(v) for v in table_ms],
+                             merge_ms=statistics.median(merge), merge_ms_all=merge, stats=stats, split_basins=stats["split_basins"],
+                             remote_beds=stats["remote_beds"], slots=slots, slot_row_bytes_down=272 * slots, bed_key_bytes_each_way=8 * slots,
+                             table_bytes=int(table.nbytes), guard_bad=p.guard_bad())
+    for i in range(nranks):
+        print(f"rank {i}: bed {c['rank_phase_ms'][i]['bed']:.3f} ms  stages {c['rank_phase_ms'][i]['stages']:.3f} ms", file=sys.stderr)
+    print(f"merge_ms {c['merge_ms']:.3f}  wall {c['label_stage_curves_wall_ms']:.3f} ms  slots {slots}", file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("job", choices=["wet", "ponds", "noise"])
@@ -385,12 +442,14 @@ def main():
     ap.add_argument("--catchments", action="store_true",
                     help="time label_catchments as well, interleaved with label_rims: the receiver, jump and tally phases")
     ap.add_argument("--outlets", action="store_true", help="time label_outlets as well: the passes and locate phases beside the table phase")
-    ap.add_argument("--curves", action="store_true", help="time label_curves as well: the bed and stages phases beside table, passes and locate")
+    ap.add_argument("--curves", action="store_true",
+                    help="time label_curves (with --devices: label_stage_curves) as well: the bed and stages phases beside table, passes and locate")
     ap.add_argument("--iterations", type=int, help="iterations before the inventory, instead of the job's own")
     ap.add_argument("--lib", metavar="FILE", help="time this build of the library (tools/build_alt.sh) instead of the tree's own")
     a = ap.parse_args()
     if not a.out:
-        a.out = os.path.join(ROOT, "profiles", *(("r17", "pond_outlets_group.json") if a.devices and a.outlets else
+        a.out = os.path.join(ROOT, "profiles", *(("r24", "pond_curves_group.json") if a.devices and a.curves else
+                                                  ("r17", "pond_outlets_group.json") if a.devices and a.outlets else
                                                   ("r16", "pond_catchments_group.json") if a.devices and a.catchments else
                                                   ("r13", "pond_rims_group.json") if a.devices and a.rims else
                                                   ("r11", "ponds_group.json") if a.devices else
@@ -420,8 +479,6 @@ def main():
     rec = dict(job=a.job, n=n, iterations=iters, build=hip.dll.wdpm_build_info().decode())
     if a.yardstick:
         rec["hbm_yardstick_gbps"] = yardstick_gbps(a.yardstick)
-    if a.devices and a.curves:
-        raise SystemExit("--curves: stage curves are taken on whole rasters only (no --devices)")
     if a.devices:
         group_job(hip, a, bd, bw, iters, rec)
         line = json.dumps(rec)

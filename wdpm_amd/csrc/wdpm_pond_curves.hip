@@ -22,8 +22,16 @@
  *            that is not finite, sets a status word
  *   finish   the bed key back to a double; the counts for wdpm_curves_stats
  *
- * Everything that steers a loop is wave-uniform.  tests/curves_emu_main.cpp compiles the kernels for the host under sanitizers with
- * WDPM_PONDS_EMULATION defined, as tests/outlets_emu_main.cpp does with wdpm_pond_outlets.hip, and leaves the host half out.
+ * Over row blocks (include/wdpm_group_pond_curves.h) every rank runs the same bodies over its owned rows (kRows) and never reads a row
+ * beyond them.  The table is indexed through the label -> slot table of the rims and catchments: once per (wave, label change) in the
+ * bed pass, at the per-lane reload and at the send in the stage pass.  The bed key must be final over ALL ranks before a stage height
+ * is formed, so the host stands between bed and stages (wdpm_curves_merge.h): the ranks' keys come down, the lowest per pond goes back
+ * up - still a key; the host alone turns it into a double, once per pond - and there is no finish on the device.  The top level is
+ * the pour key the group's outlet pass left in every slot's outlet row.
+ *
+ * Everything that steers a loop is wave-uniform.  tests/curves_emu_main.cpp and tests/group_curves_emu_main.cpp compile the kernels for
+ * the host under sanitizers with WDPM_PONDS_EMULATION defined, as tests/outlets_emu_main.cpp does with wdpm_pond_outlets.hip, and leave
+ * the host half out.
  */
 #include "wdpm_ponds_priv.h"
 
@@ -76,14 +84,28 @@ __global__ __launch_bounds__(kBlock) void curves_init_kernel(CurveRow *t, long l
   reinterpret_cast<unsigned long long *>(t)[i] = v;
 }
 
+/* What a row block's kernels know beyond a whole raster's (kRows; wave-uniform all of it): the owned rows [ra, rb) of the view, over
+ * which the strips are cut - neither pass has a stencil, so no row beyond them is ever read, not its dem and not its basins - and
+ * the label -> slot table of the rims and catchments, through which the per-slot table is indexed. */
+struct CurveRows {
+  int ra, rb;
+  const int *slot_of;
+};
+
+template <bool kRows>
+__device__ __forceinline__ int curve_slot(const CurveRows &rw, int L) {
+  return kRows ? rw.slot_of[L] : L - 1;
+}
+
 /* ---- bed ------------------------------------------------------------------------------------------------------------------- */
-__global__ __launch_bounds__(kBlock) void curves_bed_kernel(const double *__restrict__ dem, const int *__restrict__ basins, Geom g, int rpw,
-                                                            int nwaves, CurveRow *table) {
+template <bool kRows>
+__device__ __forceinline__ void curves_bed_body(const double *__restrict__ dem, const int *__restrict__ basins, const Geom &g, int rpw,
+                                                int nwaves, CurveRow *table, const CurveRows &rw) {
   const int wid = blockIdx.x * kWaves + (threadIdx.x >> 6);
   if (wid >= nwaves) return;
   const int lane = threadIdx.x & 63;
   const int strip = wid / g.nsc, s = wid - strip * g.nsc;
-  const int r0 = strip * rpw, r1 = min(r0 + rpw, g.rows);
+  const int r0 = (kRows ? rw.ra : 0) + strip * rpw, r1 = min(r0 + rpw, kRows ? rw.rb : g.rows);
   const int c = s * kSeg + lane;
   const bool inside = c < g.ncp;
   int cy_label = 0;                        /* what the wave holds for one label and has not yet sent */
@@ -101,7 +123,7 @@ __global__ __launch_bounds__(kBlock) void curves_bed_kernel(const double *__rest
       const int L = __shfl(cand, __builtin_ctzll(pending));
       const unsigned long long lo = wave_min(cand == L ? key : kNoBed);
       if (cy_label != L) {                 /* down the rows: the same label goes on gathering, another one sends first */
-        if (cy_label != 0 && lane == 0) atomic_min_if(&table[cy_label - 1].bed_key, cy_min);
+        if (cy_label != 0 && lane == 0) atomic_min_if(&table[curve_slot<kRows>(rw, cy_label)].bed_key, cy_min);
         cy_label = L;
         cy_min = kNoBed;
       }
@@ -109,7 +131,18 @@ __global__ __launch_bounds__(kBlock) void curves_bed_kernel(const double *__rest
       if (cand == L) cand = 0;
     }
   }
-  if (cy_label != 0 && lane == 0) atomic_min_if(&table[cy_label - 1].bed_key, cy_min);
+  if (cy_label != 0 && lane == 0) atomic_min_if(&table[curve_slot<kRows>(rw, cy_label)].bed_key, cy_min);
+}
+
+__global__ __launch_bounds__(kBlock) void curves_bed_kernel(const double *__restrict__ dem, const int *__restrict__ basins, Geom g, int rpw,
+                                                            int nwaves, CurveRow *table) {
+  curves_bed_body<false>(dem, basins, g, rpw, nwaves, table, CurveRows());
+}
+
+/* the same over the owned rows of a row block's view: the rank's own lowest ground of every basin it holds cells of */
+__global__ __launch_bounds__(kBlock) void curves_bed_rows_kernel(const double *__restrict__ dem, const int *__restrict__ basins, Geom g,
+                                                                 int rpw, int nwaves, CurveRow *table, CurveRows rw) {
+  curves_bed_body<true>(dem, basins, g, rpw, nwaves, table, rw);
 }
 
 /* ---- stages ---------------------------------------------------------------------------------------------------------------- */
@@ -122,14 +155,15 @@ struct StageAcc {
 
 /* The lanes with `go` send what they hold: per wave by label, a butterfly sum per stage, lane 0 adds it to the pond's row.  Every
  * lane takes part in the exchanges. */
-__device__ __forceinline__ void stages_send(StageAcc &a, bool go, CurveRow *table, int lane) {
+template <bool kRows>
+__device__ __forceinline__ void stages_send(StageAcc &a, bool go, CurveRow *table, int lane, const CurveRows &rw) {
   int cand = go ? a.label : 0;
   for (;;) {
     const unsigned long long pending = __ballot(cand != 0);
     if (pending == 0ull) break;
     const int L = __shfl(cand, __builtin_ctzll(pending));
     const bool mine = cand == L;
-    CurveRow *t = table + (L - 1);
+    CurveRow *t = table + curve_slot<kRows>(rw, L);
 #pragma unroll
     for (int s = 0; s < kStages; s++) {
       const unsigned cnt = wave_sum(mine ? a.n[s] : 0u);
@@ -152,13 +186,14 @@ __device__ __forceinline__ void stages_send(StageAcc &a, bool go, CurveRow *tabl
   }
 }
 
-__global__ __launch_bounds__(kBlock) void curves_stages_kernel(const double *__restrict__ dem, const int *__restrict__ basins, Geom g,
-                                                               int rpw, int nwaves, CurveRow *table, CurveStatus *st) {
+template <bool kRows>
+__device__ __forceinline__ void curves_stages_body(const double *__restrict__ dem, const int *__restrict__ basins, const Geom &g, int rpw,
+                                                   int nwaves, CurveRow *table, CurveStatus *st, const CurveRows &rw) {
   const int wid = blockIdx.x * kWaves + (threadIdx.x >> 6);
   if (wid >= nwaves) return;
   const int lane = threadIdx.x & 63;
   const int strip = wid / g.nsc, sc = wid - strip * g.nsc;
-  const int r0 = strip * rpw, r1 = min(r0 + rpw, g.rows);
+  const int r0 = (kRows ? rw.ra : 0) + strip * rpw, r1 = min(r0 + rpw, kRows ? rw.rb : g.rows);
   const int c = sc * kSeg + lane;
   const bool inside = c < g.ncp;
   int held = 0;                            /* the basin whose bed and top the lane holds */
@@ -176,8 +211,8 @@ __global__ __launch_bounds__(kBlock) void curves_stages_kernel(const double *__r
   for (int r = r0; r < r1; r++) {
     const int b = inside ? basins[r * g.ncp + c] : -1;
     if (__ballot(b > 0) == 0ull) continue;
-    if (b > 0 && b != held) {              /* every bed key is final: the bed pass has ended */
-      const CurveRow *t = table + (b - 1);
+    if (b > 0 && b != held) {              /* every bed key is final: the bed pass has ended (over all ranks, for a row block) */
+      const CurveRow *t = table + curve_slot<kRows>(rw, b);
       bed = depth_from_key(t->bed_key);
       top = t->top_level;
       topkey = depth_key(top);
@@ -190,7 +225,7 @@ __global__ __launch_bounds__(kBlock) void curves_stages_kernel(const double *__r
     const bool wet = live && ekey < topkey;                     /* below the last stage, or below none */
     if (__ballot(wet) == 0ull) continue;
     const bool turn = wet && a.label != 0 && a.label != b;
-    if (__ballot(turn) != 0ull) stages_send(a, turn, table, lane);
+    if (__ballot(turn) != 0ull) stages_send<kRows>(a, turn, table, lane, rw);
     if (wet) a.label = b;
 #pragma unroll
     for (int s = 1; s <= kStages; s++) {
@@ -205,8 +240,20 @@ __global__ __launch_bounds__(kBlock) void curves_stages_kernel(const double *__r
       }
     }
   }
-  stages_send(a, a.label != 0, table, lane);
+  stages_send<kRows>(a, a.label != 0, table, lane, rw);
   if (bad) st->deep = 1u;
+}
+
+__global__ __launch_bounds__(kBlock) void curves_stages_kernel(const double *__restrict__ dem, const int *__restrict__ basins, Geom g,
+                                                               int rpw, int nwaves, CurveRow *table, CurveStatus *st) {
+  curves_stages_body<false>(dem, basins, g, rpw, nwaves, table, st, CurveRows());
+}
+
+/* the same over the owned rows of a row block's view, against the bed keys the host merged over all ranks: a rank that holds cells of
+ * a basin and not its bed forms the same sixteen heights as the rank that holds the bed */
+__global__ __launch_bounds__(kBlock) void curves_stages_rows_kernel(const double *__restrict__ dem, const int *__restrict__ basins, Geom g,
+                                                                    int rpw, int nwaves, CurveRow *table, CurveStatus *st, CurveRows rw) {
+  curves_stages_body<true>(dem, basins, g, rpw, nwaves, table, st, rw);
 }
 
 /* ---- finish ---------------------------------------------------------------------------------------------------------------- */
@@ -230,6 +277,37 @@ __global__ __launch_bounds__(kBlock) void curves_finish_kernel(CurveRow *t, long
     if (flatm) atomicAdd(&st->flat, (unsigned long long)__popcll(flatm));
     if (cells) atomicAdd(&st->stage_cells, cells);
   }
+}
+
+/* ---- row blocks: what goes between the ranks and the host -------------------------------------------------------------------- */
+/* init over a rank's slots, one thread per 64-bit word as above.  The top level comes from the slot's outlet row as the group's outlet
+ * pass left it on the device: its pour key is the one the host merged over all ranks (~0: no pass anywhere), so the double is the
+ * merged table's pour_level bit for bit, +inf where the pond has no outlet. */
+__global__ __launch_bounds__(kBlock) void curves_init_rows_kernel(CurveRow *t, long long n, const OutletRow *__restrict__ outlets) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n * kCurveWords) return;
+  const long long k = i / kCurveWords;
+  const int j = (int)(i - k * kCurveWords);
+  unsigned long long v = 0ull;
+  if (j == 0) v = kNoBed;
+  if (j == 1) {
+    const unsigned long long pour = outlets[k].pour_key;
+    v = (unsigned long long)__double_as_longlong(pour == ~0ull ? __builtin_inf() : depth_from_key(pour));
+  }
+  reinterpret_cast<unsigned long long *>(t)[i] = v;
+}
+
+/* after the bed pass: every slot's bed key, side by side for one copy down.  The key stays a key: the host turns the lowest of all
+ * ranks into a double, once per pond (wdpm_curves_merge.h). */
+__global__ __launch_bounds__(kBlock) void curves_bed_down_kernel(const CurveRow *__restrict__ t, long long n, unsigned long long *__restrict__ out) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) out[i] = t[i].bed_key;
+}
+
+/* before the stage pass: every slot takes its pond's bed key as the host merged it over all ranks */
+__global__ __launch_bounds__(kBlock) void curves_bed_up_kernel(CurveRow *__restrict__ t, long long n, const unsigned long long *__restrict__ keys) {
+  const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) t[i].bed_key = keys[i];
 }
 
 }  // namespace
@@ -307,5 +385,194 @@ extern "C" int wdpm_curves_stats(wdpm_ponds *h, wdpm_pond_curve_stats *out) {
 
 extern "C" int wdpm_curves_phase_ms(wdpm_ponds *h, double *ms) {
   return phase_ms_out("wdpm_curves_phase_ms", h, &wdpm_ponds::cur, kNoTable, ms);
+}
+
+/* ---- row blocks (include/wdpm_group_pond_curves.h) --------------------------------------------------------------------------- */
+#include "wdpm_curves_merge.h"
+
+static_assert(sizeof(wdpm_curves_merge::SlotRow) == sizeof(CurveRow) && offsetof(wdpm_curves_merge::SlotRow, top_level) == offsetof(CurveRow, top_level) &&
+              offsetof(wdpm_curves_merge::SlotRow, cells) == offsetof(CurveRow, cells) && offsetof(wdpm_curves_merge::SlotRow, q) == offsetof(CurveRow, q),
+              "the merge reads the slots' rows as the device leaves them");
+
+namespace {
+const char kNoGroupTable[] = "no curve table: the last label call on this handle was not a wdpm_group_curves_label that succeeded";
+
+CurveRows rows_of(const wdpm_group_ponds *gh, int i) {
+  const OwnedRows own = owned_rows(gh, i);
+  return {own.ra, own.rb, gh->r[i]->rim.slot_of.p};
+}
+
+/* rank i's buffers for `slots` table rows; nothing is queued */
+int group_curves_buffers(wdpm_ponds *h, int i, long long slots) {
+  HIP_TRY(hipSetDevice(h->x->p.device));
+  const char *what;
+  hipError_t e = ensure(h->cur.status, &what);
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_curves_label: no %s memory for the status words of rank %d: %s", what, i, hipGetErrorString(e));
+  e = grow(h, h->cur.table, slots);
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_curves_label: no device memory for %lld curve rows of rank %d: %s", slots, i, hipGetErrorString(e));
+  e = grow(h, h->cur.keys, slots);
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_curves_label: no device memory for the bed keys of %lld slots of rank %d: %s", slots, i, hipGetErrorString(e));
+  e = grow(h, h->cur.h_keys, 2 * slots);
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_curves_label: no pinned host memory for the bed keys of %lld slots of rank %d: %s", slots, i, hipGetErrorString(e));
+  e = grow(h, h->cur.h_table, slots);
+  if (e != hipSuccess) return wdpm_fail("wdpm_group_curves_label: no pinned host memory for %lld curve rows of rank %d: %s", slots, i, hipGetErrorString(e));
+  return 0;
+}
+
+/* one wait per rank that has work queued; the first message stays */
+int group_curves_wait(wdpm_group_ponds *gh, int ev_a, int ev_b, int phase) {
+  bool bad = false;
+  std::string first_msg;
+  for (int i = 0; i < gh->n; i++) {
+    wdpm_ponds *p = gh->r[i];
+    if (p->cat.slots == 0) continue;
+    bool failed = hipSetDevice(p->x->p.device) != hipSuccess || wdpm_stream_sync(p->x, p->x->stream);
+    if (!failed && p->timing) {
+      const hipError_t e = p->cur.timer.read(ev_a, ev_b, &p->cur.timer.ms[phase]);
+      if (e != hipSuccess) failed = wdpm_fail("wdpm_group_curves_label: the events of rank %d cannot be read: %s", i, hipGetErrorString(e)) != 0;
+    }
+    if (failed) {
+      if (!bad) first_msg = wdpm_last_error();
+      bad = true;
+    }
+  }
+  return bad ? wdpm_fail("%s", first_msg.c_str()) : 0;
+}
+}  // namespace
+
+extern "C" int wdpm_group_curves_label(wdpm_group_ponds *h, double min_depth, int64_t *nponds) {
+  if (!h) return wdpm_fail("wdpm_group_curves_label: null handle");
+  if (check_min_depth("wdpm_group_curves_label", min_depth)) return 1;
+  int64_t n = 0;
+  const int rc = wdpm_group_outlets_label(h, min_depth, &n);  /* leaves basins, slots and, in every slot's outlet row on the device, the merged pour key */
+  h->lab.valid = false;                                       /* a wdpm_group_curves_label that fails leaves no table of any kind */
+  if (rc) return 1;
+  const int nr = h->n;
+  for (int i = 0; i < nr; i++) {
+    wdpm_ponds *p = h->r[i];
+    p->cur.timer.clear();
+    if (n > 0 && p->cat.slots > 0 && group_curves_buffers(p, i, p->cat.slots)) return 1;
+  }
+  h->cur.rows.resize((size_t)n);                              /* the merge writes every row */
+  wdpm_curves_merge::Totals tot;
+  long long split_basins = 0;
+  double merge_ms = 0.0;
+  if (n > 0) {                                                /* no pond, no curve: nothing to launch */
+    /* (A) every rank: init, the bed pass over its owned rows, its slots' keys on their way down */
+    for (int i = 0; i < nr; i++) {
+      wdpm_ponds *p = h->r[i];
+      if (p->cat.slots == 0) continue;                      /* no basin > 0 in its rows */
+      wdpm_ctx *x = p->x;
+      const Geom g = p->g;
+      const hipStream_t sm = x->stream;
+      const CurveRows rw = rows_of(h, i);
+      const long long slots = p->cat.slots;
+      const double *dem = x->d_dem + (size_t)p->row_off * g.ncp;
+      const Waves wv = waves_for(p, rw.rb - rw.ra);
+      const int rpw = wv.rpw, nwaves = wv.nwaves;
+      hipError_t e = hipSetDevice(x->p.device);
+      if (e == hipSuccess) e = hipMemsetAsync(p->cur.status.d, 0, sizeof(CurveStatus), sm);
+      if (e == hipSuccess) e = p->cur.timer.mark(p->timing, 0, sm);
+      if (e == hipSuccess) {
+        hipLaunchKernelGGL(curves_init_rows_kernel, dim3(blocks_for(slots * kCurveWords, kBlock)), dim3(kBlock), 0, sm, p->cur.table.p, slots,
+                           p->out.table.p);
+        hipLaunchKernelGGL(curves_bed_rows_kernel, dim3(blocks_for(nwaves, kWaves)), dim3(kBlock), 0, sm, dem, p->cat.link.p, g, rpw, nwaves,
+                           p->cur.table.p, rw);
+        hipLaunchKernelGGL(curves_bed_down_kernel, dim3(blocks_for(slots, kBlock)), dim3(kBlock), 0, sm, p->cur.table.p, slots, p->cur.keys.p);
+        e = hipGetLastError();
+      }
+      if (e == hipSuccess) e = p->cur.timer.mark(p->timing, 1, sm);
+      if (e == hipSuccess) e = hipMemcpyAsync(p->cur.h_keys.p, p->cur.keys.p, (size_t)slots * sizeof(unsigned long long), hipMemcpyDeviceToHost, sm);
+      if (e != hipSuccess) {
+        (void)wdpm_fail("wdpm_group_curves_label: queueing the bed pass of rank %d failed: %s", i, hipGetErrorString(e));
+        return group_drain(h);
+      }
+    }
+    if (group_curves_wait(h, 0, 1, 0)) return 1;
+
+    timespec t0, t1, t2, t3;
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    std::vector<wdpm_curves_merge::Rank> ranks((size_t)nr);
+    std::vector<unsigned long long *> up((size_t)nr);
+    for (int i = 0; i < nr; i++) {
+      const wdpm_ponds *p = h->r[i];
+      wdpm_curves_merge::Rank &rk = ranks[(size_t)i];
+      rk.label = p->rim.slot_label.data();
+      rk.slots = p->cat.slots;
+      rk.remote = p->cat.remote_label.data();
+      rk.nremote = p->cat.remote;
+      rk.key = p->cur.h_keys.p;
+      rk.rows = reinterpret_cast<const wdpm_curves_merge::SlotRow *>(p->cur.h_table.p);
+      up[(size_t)i] = p->cur.h_keys.p + p->cat.slots;           /* behind the slots words that came down */
+    }
+    std::vector<unsigned long long> bed_key((size_t)n);
+    std::string err;
+    if (wdpm_curves_merge::bed(ranks, n, bed_key.data(), up, split_basins, err)) return wdpm_fail("wdpm_group_curves_label: %s", err.c_str());
+    clock_gettime(CLOCK_MONOTONIC, &t1);
+
+    /* (B) every rank: the merged keys into its slots, the stage pass, its rows and its status word on their way down */
+    for (int i = 0; i < nr; i++) {
+      wdpm_ponds *p = h->r[i];
+      if (p->cat.slots == 0) continue;
+      wdpm_ctx *x = p->x;
+      const Geom g = p->g;
+      const hipStream_t sm = x->stream;
+      const CurveRows rw = rows_of(h, i);
+      const long long slots = p->cat.slots;
+      const double *dem = x->d_dem + (size_t)p->row_off * g.ncp;
+      const Waves wv = waves_for(p, rw.rb - rw.ra);
+      const int rpw = wv.rpw, nwaves = wv.nwaves;
+      hipError_t e = hipSetDevice(x->p.device);
+      if (e == hipSuccess) e = p->cur.timer.mark(p->timing, 1, sm);
+      if (e == hipSuccess) e = hipMemcpyAsync(p->cur.keys.p, up[(size_t)i], (size_t)slots * sizeof(unsigned long long), hipMemcpyHostToDevice, sm);
+      if (e == hipSuccess) {
+        hipLaunchKernelGGL(curves_bed_up_kernel, dim3(blocks_for(slots, kBlock)), dim3(kBlock), 0, sm, p->cur.table.p, slots, p->cur.keys.p);
+        hipLaunchKernelGGL(curves_stages_rows_kernel, dim3(blocks_for(nwaves, kWaves)), dim3(kBlock), 0, sm, dem, p->cat.link.p, g, rpw, nwaves,
+                           p->cur.table.p, p->cur.status.d, rw);
+        e = hipGetLastError();
+      }
+      if (e == hipSuccess) e = p->cur.timer.mark(p->timing, 2, sm);
+      if (e == hipSuccess) e = hipMemcpyAsync(p->cur.h_table.p, p->cur.table.p, (size_t)slots * sizeof(CurveRow), hipMemcpyDeviceToHost, sm);
+      if (e == hipSuccess) e = hipMemcpyAsync(p->cur.status.h, p->cur.status.d, sizeof(CurveStatus), hipMemcpyDeviceToHost, sm);
+      if (e != hipSuccess) {
+        (void)wdpm_fail("wdpm_group_curves_label: queueing the stage pass of rank %d failed: %s", i, hipGetErrorString(e));
+        return group_drain(h);
+      }
+    }
+    if (group_curves_wait(h, 1, 2, 1)) return 1;
+    for (int i = 0; i < nr; i++)
+      if (h->r[i]->cat.slots > 0 && h->r[i]->cur.status.h->deep)
+        return wdpm_fail("wdpm_group_curves_label: a cell of a pond's basin lies 512 m or more below a stage of the pond's curve, or not a finite "
+                         "depth below it: q (64-bit sums of depths in units of 2^-24 m) is only safe below that depth");
+
+    clock_gettime(CLOCK_MONOTONIC, &t2);
+    if (wdpm_curves_merge::merge(ranks, n, bed_key.data(), h->cur.rows.data(), tot, err)) return wdpm_fail("wdpm_group_curves_label: %s", err.c_str());
+    clock_gettime(CLOCK_MONOTONIC, &t3);
+    merge_ms = ms_between(t0, t1) + ms_between(t2, t3);
+  }
+  h->cur.stats.ponds = n;
+  h->cur.stats.no_curve = tot.no_curve;
+  h->cur.stats.flat = tot.flat;
+  h->cur.stats.stage_cells = tot.stage_cells;
+  h->cur.stats.ranks = nr;
+  h->cur.stats.split_basins = split_basins;
+  h->cur.stats.remote_beds = tot.remote_beds;
+  h->cur.stats.merge_ms = merge_ms;
+  h->cur.valid = true;
+  h->lab.valid = true;
+  if (nponds) *nponds = n;
+  return 0;
+}
+
+extern "C" int wdpm_group_curves_table(wdpm_group_ponds *h, wdpm_pond_curve *out, int64_t capacity) {
+  return table_out("wdpm_group_curves_table", h, &wdpm_group_ponds::cur, kNoGroupTable, out, capacity);
+}
+
+extern "C" int wdpm_group_curves_stats(wdpm_group_ponds *h, wdpm_group_curve_stats *out) {
+  return stats_out("wdpm_group_curves_stats", h, &wdpm_group_ponds::cur, kNoGroupTable, out);
+}
+
+extern "C" int wdpm_group_curves_phase_ms(wdpm_group_ponds *h, int32_t rank, double *ms) {
+  return group_phase_ms_out("wdpm_group_curves_phase_ms", h, &wdpm_group_ponds::cur, &wdpm_ponds::cur, kNoGroupTable, rank, ms);
 }
 #endif  /* WDPM_PONDS_EMULATION */

@@ -483,7 +483,7 @@ void release(wdpm_ponds *h) {
   reset(h, h->cat.exits); reset(h, h->cat.h_exits); reset(h, h->cat.h_table);
   reset(h, h->out.table); reset(h, h->out.status); reset(h, h->out.keys); reset(h, h->out.h_keys); reset(h, h->out.h_table);
   reset(h, h->out.h_seam);
-  reset(h, h->cur.table); reset(h, h->cur.status);
+  reset(h, h->cur.table); reset(h, h->cur.status); reset(h, h->cur.keys); reset(h, h->cur.h_keys); reset(h, h->cur.h_table);
   l.allocated = l.valid = h->rim.valid = h->cat.valid = h->out.valid = h->cur.valid = false;
 }
 
@@ -798,6 +798,7 @@ int wdpm_pond_detail::group_label(wdpm_group_ponds *h, double min_depth, int64_t
   h->rim.valid = false;             /* a rim table belongs to the label call that made it */
   h->cat.valid = false;             /* and so does a catchment table */
   h->out.valid = false;             /* and an outlet table */
+  h->cur.valid = false;             /* and a curve table */
   const int n = h->n;
   /* every rank up to its scan, on its own stream and device, before the first wait */
   for (int i = 0; i < n; i++)

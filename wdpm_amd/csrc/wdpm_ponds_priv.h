@@ -33,6 +33,7 @@
 #include "../../include/wdpm_group_pond_catchments.h"
 #include "../../include/wdpm_group_pond_outlets.h"
 #include "../../include/wdpm_pond_curves.h"
+#include "../../include/wdpm_group_pond_curves.h"
 
 namespace wdpm_pond_detail {
 
@@ -354,6 +355,10 @@ struct CurveUnit {                  /* wdpm_pond_curves.hip: likewise for wdpm_c
   bool valid = false;
   PhaseTimer<WDPM_CURVES_PHASES + 1, WDPM_CURVES_PHASES> timer;     /* init, bed | stages, finish */
   wdpm_pond_curve_stats stats = {};
+  /* a row block (wdpm_group_curves_label): the table then holds one row per SLOT, as the outlets' does */
+  DevBuf<unsigned long long> keys;  /* C: every slot's bed key on its way down, the merged keys on their way up */
+  PinBuf<unsigned long long> h_keys;   /* 2 x C: the keys as they came down, then, behind the slots words of the call, the merged keys */
+  PinBuf<CurveRow> h_table;         /* the slots' rows on their way down */
 };
 
 /* a merged table of a group: what the last label call of its kind left; every label call takes `valid` away first */
@@ -386,8 +391,8 @@ struct wdpm_ponds {
   wdpm_pond_detail::CurveUnit cur;
 };
 
-/* the handle of include/wdpm_group_ponds.h, include/wdpm_group_pond_rims.h, include/wdpm_group_pond_catchments.h and
- * include/wdpm_group_pond_outlets.h */
+/* the handle of include/wdpm_group_ponds.h, include/wdpm_group_pond_rims.h, include/wdpm_group_pond_catchments.h,
+ * include/wdpm_group_pond_outlets.h and include/wdpm_group_pond_curves.h */
 struct wdpm_group_ponds {
   wdpm_group *grp = nullptr;
   int n = 0;                               /* ranks */
@@ -399,6 +404,7 @@ struct wdpm_group_ponds {
   wdpm_pond_detail::Merged<wdpm_pond_rim, wdpm_group_rim_stats> rim;
   wdpm_pond_detail::Merged<wdpm_pond_catchment, wdpm_group_catchment_stats> cat;
   wdpm_pond_detail::Merged<wdpm_pond_outlet, wdpm_group_outlet_stats> out;
+  wdpm_pond_detail::Merged<wdpm_pond_curve, wdpm_group_curve_stats> cur;
 };
 
 #pragma GCC visibility push(hidden)

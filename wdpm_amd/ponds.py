@@ -1,8 +1,8 @@
 """ctypes binding of include/wdpm_ponds.h, include/wdpm_group_ponds.h, include/wdpm_pond_rims.h, include/wdpm_group_pond_rims.h,
 include/wdpm_pond_catchments.h, include/wdpm_pond_outlets.h, include/wdpm_group_pond_catchments.h,
-include/wdpm_group_pond_outlets.h and include/wdpm_pond_curves.h: the pond inventory of a context's current water raster, of a raster
-spread over the row blocks of a rowblock.Group, the rim, the catchment and the outlet of every pond of either, and on whole rasters
-the stage curve of every pond.
+include/wdpm_group_pond_outlets.h, include/wdpm_pond_curves.h and include/wdpm_group_pond_curves.h: the pond inventory of a context's
+current water raster, of a raster spread over the row blocks of a rowblock.Group, and the rim, the catchment, the outlet and the stage
+curve of every pond of either.
 
 Product library only (the symbols are not part of the ABI of include/wdpm.h, and ``capi.SYMBOLS`` does not list them).
 
@@ -31,6 +31,8 @@ Product library only (the symbols are not part of the ABI of include/wdpm.h, and
         basins = ponds.basins()     # cross row blocks and adds the ranks' tables up (CATCH_DTYPE, coordinates of the whole raster)
         n = ponds.label_outlets(0.001)      # and every rank's passes; the host makes the pour levels final between the two passes
         outlets = ponds.outlets()   # OUTLET_DTYPE, coordinates of the whole raster
+        n = ponds.label_stage_curves(0.001) # and every rank's bed and stage passes; the host makes the beds final between the two
+        curves = ponds.stage_curves()       # CURVE_DTYPE
 """
 from __future__ import annotations
 
@@ -240,13 +242,28 @@ GROUP_OUTLET_SYMBOLS = {
 }
 
 
+class GroupCurveStatsStruct(C.Structure):
+    """struct wdpm_group_curve_stats"""
+    _fields_ = [("ponds", C.c_int64), ("no_curve", C.c_int64), ("flat", C.c_int64), ("stage_cells", C.c_int64),
+                ("ranks", C.c_int64), ("split_basins", C.c_int64), ("remote_beds", C.c_int64), ("merge_ms", C.c_double)]
+
+
+# every symbol include/wdpm_group_pond_curves.h declares
+GROUP_CURVE_SYMBOLS = {
+    "wdpm_group_curves_label": (C.c_int, [_vp, C.c_double, C.POINTER(C.c_int64)]),
+    "wdpm_group_curves_table": (C.c_int, [_vp, _vp, C.c_int64]),
+    "wdpm_group_curves_stats": (C.c_int, [_vp, C.POINTER(GroupCurveStatsStruct)]),
+    "wdpm_group_curves_phase_ms": (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_double)]),
+}
+
+
 def bind(lib: capi.Lib):
     """Set the prototypes on a loaded product library; a library without the symbols is an error (no fallback)."""
     if getattr(lib, "_ponds_bound", False):
         return lib.dll
     for name, (res, args) in list(SYMBOLS.items()) + list(GROUP_SYMBOLS.items()) + list(RIM_SYMBOLS.items()) + \
             list(GROUP_RIM_SYMBOLS.items()) + list(CATCH_SYMBOLS.items()) + list(OUTLET_SYMBOLS.items()) + list(GROUP_CATCH_SYMBOLS.items()) + \
-            list(GROUP_OUTLET_SYMBOLS.items()) + list(CURVE_SYMBOLS.items()):
+            list(GROUP_OUTLET_SYMBOLS.items()) + list(CURVE_SYMBOLS.items()) + list(GROUP_CURVE_SYMBOLS.items()):
         try:
             fn = getattr(lib.dll, name)
         except AttributeError:
@@ -537,3 +554,22 @@ class GroupPonds(_Handle):
         """milliseconds of one rank's pass over the pairs and of its locate pass in the last label_outlets() (handles made with
         WDPM_PONDS_TIMING=1)"""
         return self._phase_ms(self.dll.wdpm_group_outlets_phase_ms, OUTLET_PHASES, int(rank))
+
+    def label_stage_curves(self, min_depth: float) -> int:
+        """label_outlets(min_depth), and every rank's bed pass and stage pass on the same water; every older query answers as after
+        label_outlets()."""
+        return self._label(self.dll.wdpm_group_curves_label, min_depth)
+
+    def stage_curves(self, capacity: int | None = None) -> np.ndarray:
+        """One row per pond (CURVE_DTYPE) of the last label_stage_curves(), as Ponds.curves() gives it on a whole-raster context
+        holding the same water; fails after any lesser label call."""
+        return self._table(self.dll.wdpm_group_curves_table, CURVE_DTYPE, "stage_curves", capacity, labelled_by="label_stage_curves")
+
+    def stage_curve_stats(self) -> dict:
+        """the counts of Ponds.curve_stats for the whole raster, then ranks, split_basins, remote_beds and merge_ms"""
+        return self._stats(self.dll.wdpm_group_curves_stats, GroupCurveStatsStruct)
+
+    def stage_curve_phase_ms(self, rank: int) -> dict:
+        """milliseconds of one rank's bed pass and of its stage pass in the last label_stage_curves() (handles made with
+        WDPM_PONDS_TIMING=1)"""
+        return self._phase_ms(self.dll.wdpm_group_curves_phase_ms, CURVE_PHASES, int(rank))
