@@ -59,6 +59,8 @@ def make_dem(kind, R, C, seed):
       float32              a DEM that went through Float32: a binary grid
       no-nodata            no NODATA cell inside the raster at all: every interior step takes the select-free decode
       one-nodata           one NODATA cell mid-raster: consecutive steps of one wave take different decode paths
+                           (this and the next two check the geometry of the bases; whether the gate in front of the select-free
+                           decode can MISS a NODATA offset is tests/test_wave_gates.py's: here a miss would change no cell)
       nodata-first-column  NODATA in the first column of every group, on two rows
       nodata-group         a group that is NODATA throughout, on three rows"""
     rng = np.random.default_rng(seed)
