@@ -35,18 +35,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("job", choices=["wet", "noise"])
     ap.add_argument("n", type=int)
-    ap.add_argument("--other", required=True, help="the other build of libwdpm_hip.so (it need not know the group curve calls)")
+    ap.add_argument("--other", required=True, help="the other build of libwdpm_hip.so (it need not know the group curve calls or the spills)")
     ap.add_argument("--copy", required=True, help="a copy of --other under another file name: the A/A")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r24", "whole_raster_beside.json"))
     a = ap.parse_args()
     tree = wdpm_amd.load_hip()
     libs = {"tree": tree, "other": wdpm_amd.load(os.path.abspath(a.other)), "copy": wdpm_amd.load(os.path.abspath(a.copy))}
-    # the other build is bound without the group curve symbols, which it may not have
+    # the other build is bound without the group curve symbols and the spill symbols, which it may not have
     group_symbols, ponds.GROUP_CURVE_SYMBOLS = ponds.GROUP_CURVE_SYMBOLS, {}
+    spill_symbols, ponds.SPILL_SYMBOLS = ponds.SPILL_SYMBOLS, {}
     ponds.bind(libs["other"])
     ponds.bind(libs["copy"])
-    ponds.GROUP_CURVE_SYMBOLS = group_symbols
+    ponds.GROUP_CURVE_SYMBOLS, ponds.SPILL_SYMBOLS = group_symbols, spill_symbols
     ponds.bind(tree)
     n = a.n
     dem = tree.synth_dem(n, n)

@@ -37,6 +37,10 @@
                       phases and their sums over the ranks, the host's merge_ms, split_basins and remote_beds, the bytes of slot
                       rows that come down; then the whole-raster call on the same water in the same process, phases and wall
                       clock, the yardstick of those sums (default --out profiles/r24/pond_curves_group.json)
+    ... --spills      the spills of the ponds as well (include/wdpm_pond_spills.h): five more timed calls of label_spills, the rings,
+                      chains and sums phases beside the table, passes, locate, bed and stages phases of the SAME calls, their
+                      ratios to the table phase, the counts, and the bytes of the unit's working arrays (whole rasters only;
+                      default --out profiles/r26/pond_spills.json)
     ... --iterations K   instead of the job's own number of iterations before the inventory
     ... --lib FILE       another build of the library (tools/build_alt.sh NAME REV) instead of the tree's: the same job on the parent
 
@@ -65,7 +69,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 import wdpm_amd  # noqa: E402
-from wdpm_amd.ponds import CATCH_PHASES, CURVE_PHASES, OUTLET_PHASES, PHASES, RIM_PHASES, GroupPonds, Ponds  # noqa: E402
+from wdpm_amd.ponds import CATCH_PHASES, CURVE_PHASES, OUTLET_PHASES, PHASES, RIM_PHASES, SPILL_PHASES, GroupPonds, Ponds  # noqa: E402
 
 MISS = -99999.0
 
@@ -215,6 +219,36 @@ def curves_job(ctx, p, rec, n):
     c["gbps_12B"] = {k: 12 * cells / (med[k] * 1e6) if med[k] > 0 else None for k in CURVE_PHASES}
     if rec.get("hbm_yardstick_gbps"):
         c["of_yardstick"] = {k: v / rec["hbm_yardstick_gbps"] if v else None for k, v in c["gbps_12B"].items()}
+
+
+def spills_job(ctx, p, rec, n):
+    """after the label calls: one untimed label_spills (allocates the spill table, its working arrays and everything below it), five
+    timed ones"""
+    p.label_spills(0.001, 0.0)
+    beside_names = ("table", "passes", "locate", "bed", "stages")
+    wall, phases, beside = [], {k: [] for k in SPILL_PHASES}, {k: [] for k in beside_names}
+    for _ in range(5):
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        p.label_spills(0.001, 0.0)
+        wall.append((time.perf_counter() - t0) * 1e3)
+        for k, v in p.spill_phase_ms().items():
+            phases[k].append(v)
+        beside["table"].append(p.phase_ms()["table"])
+        for k, v in list(p.outlet_phase_ms().items()) + list(p.curve_phase_ms().items()):
+            beside[k].append(v)
+    table, stats = p.spills(), p.spill_stats()
+    med = {k: statistics.median(v) for k, v in phases.items()}
+    bmed = {k: statistics.median(v) for k, v in beside.items()}
+    npond = len(table)
+    rec["spills"] = dict(
+        label_spills_wall_ms=statistics.median(wall), label_spills_wall_ms_all=wall, phase_ms=med, phase_ms_all=phases,
+        spill_pass_ms=sum(med.values()), beside_ms_same_calls=bmed, beside_ms_all=beside,
+        over_table={k: med[k] / bmed["table"] if bmed["table"] > 0 else None for k in SPILL_PHASES},
+        spill_pass_over_table=sum(med.values()) / bmed["table"] if bmed["table"] > 0 else None, stats=stats,
+        most_direct_feeders=int(np.bincount(table["next"][table["next"] > 0]).max()) if (table["next"] > 0).any() else 0,
+        largest_up_ponds=int(table["up_ponds"].max()) if npond else 0, largest_live_ponds=int(table["live_ponds"].max()) if npond else 0,
+        table_bytes=int(table.nbytes), working_bytes=npond * (15 * 4 + 14 * 8), guard_bad=p.guard_bad())
 
 
 def yardstick_gbps(path):
@@ -444,15 +478,20 @@ def main():
     ap.add_argument("--outlets", action="store_true", help="time label_outlets as well: the passes and locate phases beside the table phase")
     ap.add_argument("--curves", action="store_true",
                     help="time label_curves (with --devices: label_stage_curves) as well: the bed and stages phases beside table, passes and locate")
+    ap.add_argument("--spills", action="store_true",
+                    help="time label_spills as well: the rings, chains and sums phases beside table, passes, locate, bed and stages")
     ap.add_argument("--iterations", type=int, help="iterations before the inventory, instead of the job's own")
     ap.add_argument("--lib", metavar="FILE", help="time this build of the library (tools/build_alt.sh) instead of the tree's own")
     a = ap.parse_args()
+    if a.spills and a.devices:
+        ap.error("--spills: spills are taken on a whole raster only")
     if not a.out:
         a.out = os.path.join(ROOT, "profiles", *(("r24", "pond_curves_group.json") if a.devices and a.curves else
                                                   ("r17", "pond_outlets_group.json") if a.devices and a.outlets else
                                                   ("r16", "pond_catchments_group.json") if a.devices and a.catchments else
                                                   ("r13", "pond_rims_group.json") if a.devices and a.rims else
                                                   ("r11", "ponds_group.json") if a.devices else
+                                                  ("r26", "pond_spills.json") if a.spills else
                                                   ("r18", "pond_curves.json") if a.curves else
                                                   ("r15", "pond_outlets.json") if a.outlets else
                                                   ("r14", "pond_catchments.json") if a.catchments else
@@ -527,6 +566,8 @@ def main():
                 outlets_job(ctx, p, rec, n)
             if a.curves:
                 curves_job(ctx, p, rec, n)
+            if a.spills:
+                spills_job(ctx, p, rec, n)
         if not a.no_scipy:
             try:
                 import scipy.ndimage as ndi

@@ -484,7 +484,8 @@ void release(wdpm_ponds *h) {
   reset(h, h->out.table); reset(h, h->out.status); reset(h, h->out.keys); reset(h, h->out.h_keys); reset(h, h->out.h_table);
   reset(h, h->out.h_seam);
   reset(h, h->cur.table); reset(h, h->cur.status); reset(h, h->cur.keys); reset(h, h->cur.h_keys); reset(h, h->cur.h_table);
-  l.allocated = l.valid = h->rim.valid = h->cat.valid = h->out.valid = h->cur.valid = false;
+  reset(h, h->spl.table); reset(h, h->spl.words); reset(h, h->spl.sums); reset(h, h->spl.status);
+  l.allocated = l.valid = h->rim.valid = h->cat.valid = h->out.valid = h->cur.valid = h->spl.valid = false;
 }
 
 int allocate(wdpm_ponds *h) {
@@ -535,6 +536,7 @@ wdpm_ponds *make_handle(wdpm_ctx *ctx, int row_off, int rows, bool seams) {
   h->cat.timer.create(h->timing);
   h->out.timer.create(h->timing);
   h->cur.timer.create(h->timing);
+  h->spl.timer.create(h->timing);
   return h;
 }
 
@@ -549,6 +551,7 @@ int label_queue(wdpm_ponds *h, double min_depth) {
   h->cat.valid = false;             /* and so does a catchment table (wdpm_pond_catchments.hip) */
   h->out.valid = false;             /* and an outlet table (wdpm_pond_outlets.hip) */
   h->cur.valid = false;             /* and a curve table (wdpm_pond_curves.hip) */
+  h->spl.valid = false;             /* and a spill table (wdpm_pond_spills.hip) */
   /* the raster as a reader sees it: side stream joined, owed drain() and threshold flush applied (what wdpm_count_stats asks for) */
   if (wdpm_synchronize(x)) return 1;
   if (wdpm_apply_owed_flush(x)) return 1;
@@ -674,6 +677,7 @@ void destroy_handle(wdpm_ponds *h) {
   h->cat.timer.destroy();
   h->out.timer.destroy();
   h->cur.timer.destroy();
+  h->spl.timer.destroy();
   delete h;
 }
 

@@ -1,6 +1,6 @@
 /*
  * wdpm_ponds_priv.h — what the units of the pond inventory share: wdpm_ponds.hip (labels and table), wdpm_pond_rims.hip
- * (rims), wdpm_pond_catchments.hip (catchments), wdpm_pond_outlets.hip (outlets) and wdpm_pond_curves.hip (stage curves).  Geometry, the order-preserving image of a
+ * (rims), wdpm_pond_catchments.hip (catchments), wdpm_pond_outlets.hip (outlets), wdpm_pond_curves.hip (stage curves) and wdpm_pond_spills.hip (spills).  Geometry, the order-preserving image of a
  * double, the table rows as the device accumulates them, the wave helpers of the kernels (a lane's neighbour, the wave's extremum,
  * the look before an atomic) and - outside the host emulations of the tests, which define WDPM_PONDS_EMULATION and bring stand-ins
  * for the HIP device language (tests/hip_emu.h) - the host side: the guarded allocator, the holders every buffer, status pair and
@@ -34,6 +34,7 @@
 #include "../../include/wdpm_group_pond_outlets.h"
 #include "../../include/wdpm_pond_curves.h"
 #include "../../include/wdpm_group_pond_curves.h"
+#include "../../include/wdpm_pond_spills.h"
 
 namespace wdpm_pond_detail {
 
@@ -128,6 +129,24 @@ constexpr int kCurveWords = (int)(sizeof(CurveRow) / sizeof(unsigned long long))
 struct CurveStatus {
   unsigned long long no_curve, flat, stage_cells;
   unsigned deep;           /* a term of q of >= 512 m, or one that is not finite */
+  unsigned pad;
+};
+
+/* The spill passes (wdpm_pond_spills.hip) double pointers over the table of N < 2^31 ponds: R = ceil(log2 N) + 1 rounds per pass reach
+ * 2^R >= 2 N steps, past any chain and twice round any ring.  The host and the host emulation both ask here. */
+constexpr int kSpillMaxRounds = 32;
+constexpr int kSpillPasses = 3;      /* rings, chains, sums */
+constexpr int spill_rounds(long long n) {
+  int r = 1;
+  for (long long reach = 1; reach < n; reach <<= 1) r++;
+  return r;
+}
+
+/* what the spill kernels count for the host, and what steers their rounds: work[pass][r] != 0 says that round r of the pass has
+ * something to do; a round that finds 0 there returns at once, and so does every later one */
+struct SpillStatus {
+  unsigned long long rings, ring_ponds, spilling, ends_land, ends_none, ends_ring, max_hops;
+  unsigned work[kSpillPasses][kSpillMaxRounds + 1];
   unsigned pad;
 };
 
@@ -361,6 +380,16 @@ struct CurveUnit {                  /* wdpm_pond_curves.hip: likewise for wdpm_c
   PinBuf<CurveRow> h_table;         /* the slots' rows on their way down */
 };
 
+struct SpillUnit {                  /* wdpm_pond_spills.hip: likewise for wdpm_spill_label; whole rasters only */
+  DevBuf<wdpm_pond_spill> table;
+  DevBuf<int> words;                /* 15 x N: next, flags, ring marks, and the pointers and hop counts of the passes, two buffers each */
+  DevBuf<unsigned long long> sums;  /* 14 x N: per-pond values, path sums (two buffers), the five subtree sums (two buffers) */
+  StatusPair<SpillStatus> status;
+  bool valid = false;
+  PhaseTimer<WDPM_SPILL_PHASES + 1, WDPM_SPILL_PHASES> timer;       /* init, ring rounds, cut | chain rounds | sum rounds, finish */
+  wdpm_pond_spill_stats stats = {};
+};
+
 /* a merged table of a group: what the last label call of its kind left; every label call takes `valid` away first */
 template <class Row, class Stats> struct Merged {
   std::vector<Row> rows;
@@ -389,6 +418,7 @@ struct wdpm_ponds {
   wdpm_pond_detail::CatchUnit cat;
   wdpm_pond_detail::OutletUnit out;
   wdpm_pond_detail::CurveUnit cur;
+  wdpm_pond_detail::SpillUnit spl;
 };
 
 /* the handle of include/wdpm_group_ponds.h, include/wdpm_group_pond_rims.h, include/wdpm_group_pond_catchments.h,

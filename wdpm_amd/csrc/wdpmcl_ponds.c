@@ -9,10 +9,13 @@
  *   WDPM_POND_CATCHMENTS=<path>   the dry land that drains to each of them (include/wdpm_pond_catchments.h)
  *   WDPM_POND_OUTLETS=<path>      where each basin spills and what it holds until then (include/wdpm_pond_outlets.h)
  *   WDPM_POND_CURVES=<path>       flooded area and storage by level (include/wdpm_pond_curves.h)
+ *   WDPM_POND_SPILLS=<path>       where each pond's overflow ends up, what drains through it and what is connected to it now
+ *                                 (include/wdpm_pond_spills.h).  A pond counts as spilling when its surface stands within
+ *                                 WDPM_POND_HEADROOM_MM (default 0) of its pour level
  *
  * The units are the rows of one table, `units`, in that order; everything else here is written once and driven by it.  One label
  * call - that of the highest unit asked for - serves every file of the run; the tables then fetched are those the rows' `needs`
- * name.  A sixth unit is one more row with its typed thunks, its row printer and, if it has statistics, their tail of the stderr
+ * name.  A further unit is one more row with its typed thunks, its row printer and, if it has statistics, their tail of the stderr
  * line; a unit that can be taken over several row blocks fills the row's group_* column.
  *
  * The pond units are the HIP library's alone: weak references, so that the command line also links against a back-end that exports
@@ -29,6 +32,7 @@
 #include "../../include/wdpm_pond_catchments.h"
 #include "../../include/wdpm_pond_outlets.h"
 #include "../../include/wdpm_pond_curves.h"
+#include "../../include/wdpm_pond_spills.h"
 #pragma weak wdpm_ponds_create
 #pragma weak wdpm_ponds_destroy
 #pragma weak wdpm_ponds_label
@@ -52,8 +56,11 @@
 #pragma weak wdpm_curves_table
 #pragma weak wdpm_curves_stats
 #pragma weak wdpm_curves_stage_level
+#pragma weak wdpm_spill_label
+#pragma weak wdpm_spill_table
+#pragma weak wdpm_spill_stats
 
-enum { PONDS, RIMS, CATCH, OUTLETS, CURVES, UNITS };
+enum { PONDS, RIMS, CATCH, OUTLETS, CURVES, SPILLS, UNITS };
 #define BIT(u) (1u << (u))
 
 typedef struct {
@@ -62,6 +69,7 @@ typedef struct {
   wdpm_pond_catchment_stats catch_stats;
   wdpm_pond_outlet_stats outlet_stats;
   wdpm_pond_curve_stats curve_stats;
+  wdpm_pond_spill_stats spill_stats;
   double cellarea;
 } pond_inventory;
 
@@ -90,6 +98,7 @@ static int rims_there(void) { return wdpm_rims_label && wdpm_rims_table; }
 static int catch_there(void) { return wdpm_catch_label && wdpm_catch_table && wdpm_catch_stats; }
 static int outlets_there(void) { return wdpm_outlets_label && wdpm_outlets_table && wdpm_outlets_stats; }
 static int curves_there(void) { return wdpm_curves_label && wdpm_curves_table && wdpm_curves_stats && wdpm_curves_stage_level; }
+static int spills_there(void) { return wdpm_spill_label && wdpm_spill_table && wdpm_spill_stats; }
 
 static int ponds_table(wdpm_ponds *h, pond_inventory *v) { return wdpm_ponds_table(h, (wdpm_pond *)v->table[PONDS], v->n); }
 static int group_ponds_table(wdpm_group_ponds *g, pond_inventory *v) { return wdpm_group_ponds_table(g, (wdpm_pond *)v->table[PONDS], v->n); }
@@ -100,6 +109,11 @@ static int outlets_table(wdpm_ponds *h, pond_inventory *v) { return wdpm_outlets
 static int outlets_stats(wdpm_ponds *h, pond_inventory *v) { return wdpm_outlets_stats(h, &v->outlet_stats); }
 static int curves_table(wdpm_ponds *h, pond_inventory *v) { return wdpm_curves_table(h, (wdpm_pond_curve *)v->table[CURVES], v->n); }
 static int curves_stats(wdpm_ponds *h, pond_inventory *v) { return wdpm_curves_stats(h, &v->curve_stats); }
+/* the spill pass takes a second parameter, read once (wdpmcl_pond_files) before the row's label call */
+static double headroom_tol;
+static int spills_label(wdpm_ponds *h, double min_depth, int64_t *n) { return wdpm_spill_label(h, min_depth, headroom_tol, n); }
+static int spills_table(wdpm_ponds *h, pond_inventory *v) { return wdpm_spill_table(h, (wdpm_pond_spill *)v->table[SPILLS], v->n); }
+static int spills_stats(wdpm_ponds *h, pond_inventory *v) { return wdpm_spill_stats(h, &v->spill_stats); }
 
 /* ---- the row printers: coordinates leave as file coordinates, 0-based (padded - 1), -1 where there is none; doubles as %.17g
  * so that they read back exactly; volumes in quanta of 2^-24 m and in cubic metres ---- */
@@ -150,6 +164,17 @@ static void print_curve(FILE *f, const pond_inventory *v, int64_t k) {
             ldexp((double)q->q[s - 1], -24) * v->cellarea);
 }
 
+/* next_label / end: 0 land that ends in a pit, -1 no outlet, -2 a ring of ponds closed at this pond; up_* once everything above is
+ * full, live_* through the ponds that spill now */
+static void print_spill(FILE *f, const pond_inventory *v, int64_t k) {
+  const wdpm_pond_spill *q = (const wdpm_pond_spill *)v->table[SPILLS] + k;
+  fprintf(f, "%lld,%d,%d,%d,%d,%d,%llu,%.17g,%lld,%lld,%.17g,%llu,%.17g,%d,%d,%lld,%lld,%.17g\n", (long long)(k + 1), q->next, q->spilling,
+          q->sink, q->end, q->hops, (unsigned long long)q->path_fill_q, ldexp((double)q->path_fill_q, -24) * v->cellarea,
+          (long long)q->up_ponds, (long long)q->up_cells, (double)q->up_cells * v->cellarea, (unsigned long long)q->up_fill_q,
+          ldexp((double)q->up_fill_q, -24) * v->cellarea, q->rest, q->rest_hops, (long long)q->live_ponds, (long long)q->live_cells,
+          (double)q->live_cells * v->cellarea);
+}
+
 static void tail_ponds(const pond_inventory *v, char *buf, size_t len) {
   if (v->blocks > 1) snprintf(buf, len, " (%lld row blocks, %lld joined across them)", (long long)v->blocks, (long long)v->joined);
 }
@@ -168,9 +193,15 @@ static void tail_curves(const pond_inventory *v, char *buf, size_t len) {
   snprintf(buf, len, " (%lld without a curve, %lld flat, %lld cells below the last stage)", (long long)s->no_curve, (long long)s->flat,
            (long long)s->stage_cells);
 }
+static void tail_spills(const pond_inventory *v, char *buf, size_t len) {
+  const wdpm_pond_spill_stats *s = &v->spill_stats;
+  snprintf(buf, len, " (%lld rings of %lld ponds, %lld spilling, chains end: %lld on land, %lld without an outlet, %lld at a ring; longest chain %lld)",
+           (long long)s->rings, (long long)s->ring_ponds, (long long)s->spilling, (long long)s->ends_land, (long long)s->ends_none,
+           (long long)s->ends_ring, (long long)s->max_hops);
+}
 
 /* ---- the table.  needs: an outlets file reads the rim table for its headroom and fetches the catchment table with it; a curves
- * file reads its own table alone ---- */
+ * file and a spills file each read their own table alone ---- */
 static const pond_unit units[UNITS] = {
     {"WDPM_PONDS", "pond inventory", NULL, sizeof(wdpm_pond), BIT(PONDS), ponds_there, wdpm_ponds_label, ponds_table, NULL,
      wdpm_group_ponds_label, group_ponds_table,
@@ -186,6 +217,11 @@ static const pond_unit units[UNITS] = {
      print_outlet, tail_outlets},
     {"WDPM_POND_CURVES", "pond curves", "stage curves are", sizeof(wdpm_pond_curve), BIT(PONDS) | BIT(CURVES), curves_there,
      wdpm_curves_label, curves_table, curves_stats, NULL, NULL, "label,stage,level_m,cells,area_m2,q,volume_m3", print_curve, tail_curves},
+    {"WDPM_POND_SPILLS", "pond spills", "spills are", sizeof(wdpm_pond_spill), BIT(PONDS) | BIT(SPILLS), spills_there, spills_label,
+     spills_table, spills_stats, NULL, NULL,
+     "label,next_label,spilling,sink_label,end,hops,path_fill_q,path_fill_m3,up_ponds,up_cells,up_area_m2,up_fill_q,up_fill_m3,rest_label,"
+     "rest_hops,live_ponds,live_cells,live_area_m2",
+     print_spill, tail_spills},
 };
 
 static void free_tables(pond_inventory *v) {
@@ -289,6 +325,7 @@ int wdpmcl_pond_files(wdpm_group *grp, int ndev, double cellarea, int64_t *guard
   }
   if (!asked) return failed;
   const double min_depth = (getenv("WDPM_PONDS_MIN_DEPTH_MM") ? atof(getenv("WDPM_PONDS_MIN_DEPTH_MM")) : 1.0) / 1000.0;
+  headroom_tol = (getenv("WDPM_POND_HEADROOM_MM") ? atof(getenv("WDPM_POND_HEADROOM_MM")) : 0.0) / 1000.0;
   pond_inventory v;
   memset(&v, 0, sizeof v);
   v.blocks = 1;

@@ -1,8 +1,8 @@
 """ctypes binding of include/wdpm_ponds.h, include/wdpm_group_ponds.h, include/wdpm_pond_rims.h, include/wdpm_group_pond_rims.h,
 include/wdpm_pond_catchments.h, include/wdpm_pond_outlets.h, include/wdpm_group_pond_catchments.h,
-include/wdpm_group_pond_outlets.h, include/wdpm_pond_curves.h and include/wdpm_group_pond_curves.h: the pond inventory of a context's
-current water raster, of a raster spread over the row blocks of a rowblock.Group, and the rim, the catchment, the outlet and the stage
-curve of every pond of either.
+include/wdpm_group_pond_outlets.h, include/wdpm_pond_curves.h, include/wdpm_group_pond_curves.h and include/wdpm_pond_spills.h: the pond
+inventory of a context's current water raster, of a raster spread over the row blocks of a rowblock.Group, the rim, the catchment, the
+outlet and the stage curve of every pond of either, and where every pond of a whole raster spills to.
 
 Product library only (the symbols are not part of the ABI of include/wdpm.h, and ``capi.SYMBOLS`` does not list them).
 
@@ -22,6 +22,8 @@ Product library only (the symbols are not part of the ABI of include/wdpm.h, and
         n = ponds.label_curves(0.001)       # all of the above, and every basin's flooded cells and storage at sixteen stages
         curves = ponds.curves()     # bed level, top level (the pour level), cells[16], q[16] (CURVE_DTYPE)
         levels = stage_levels(curves["bed_level"][0], curves["top_level"][0])   # the seventeen heights of pond 1, stage 0..16
+        n = ponds.label_spills(0.001, headroom_tol=0.0)   # all of the above, and every pond's spill followed downstream
+        spills = ponds.spills()     # next, sink, end, hops, storage on the way, what drains through it, what is connected now (SPILL_DTYPE)
 
     with rowblock.Group(...) as grp, GroupPonds(grp) as ponds:     # the same calls, the same answer, every rank labelled in place
         n = ponds.label(0.001)
@@ -50,6 +52,7 @@ CATCH_PHASES = ("receivers", "jump", "tally")                      # wdpm_catch_
 OUTLET_PHASES = ("passes", "locate")                               # wdpm_outlets_phase_ms
 CURVE_PHASES = ("bed", "stages")                                   # wdpm_curves_phase_ms
 CURVE_STAGES = 16                                                  # WDPM_CURVE_STAGES
+SPILL_PHASES = ("rings", "chains", "sums")                         # wdpm_spill_phase_ms
 
 
 class PondStruct(C.Structure):
@@ -176,6 +179,34 @@ CURVE_SYMBOLS = {
 }
 
 
+class SpillStruct(C.Structure):
+    """struct wdpm_pond_spill"""
+    _fields_ = [("next", C.c_int32), ("sink", C.c_int32), ("end", C.c_int32), ("hops", C.c_int32), ("rest", C.c_int32),
+                ("rest_hops", C.c_int32), ("spilling", C.c_int32), ("reserved", C.c_int32), ("path_fill_q", C.c_uint64),
+                ("up_ponds", C.c_int64), ("up_cells", C.c_int64), ("up_fill_q", C.c_uint64), ("live_ponds", C.c_int64),
+                ("live_cells", C.c_int64)]
+
+
+class SpillStatsStruct(C.Structure):
+    """struct wdpm_pond_spill_stats"""
+    _fields_ = [("ponds", C.c_int64), ("rings", C.c_int64), ("ring_ponds", C.c_int64), ("spilling", C.c_int64), ("ends_land", C.c_int64),
+                ("ends_none", C.c_int64), ("ends_ring", C.c_int64), ("max_hops", C.c_int64), ("rounds", C.c_int64)]
+
+
+SPILL_DTYPE = np.dtype([("next", "<i4"), ("sink", "<i4"), ("end", "<i4"), ("hops", "<i4"), ("rest", "<i4"), ("rest_hops", "<i4"),
+                        ("spilling", "<i4"), ("reserved", "<i4"), ("path_fill_q", "<u8"), ("up_ponds", "<i8"), ("up_cells", "<i8"),
+                        ("up_fill_q", "<u8"), ("live_ponds", "<i8"), ("live_cells", "<i8")])
+assert SPILL_DTYPE.itemsize == C.sizeof(SpillStruct) == 80 and C.sizeof(SpillStatsStruct) == 72
+
+# every symbol include/wdpm_pond_spills.h declares
+SPILL_SYMBOLS = {
+    "wdpm_spill_label": (C.c_int, [_vp, C.c_double, C.c_double, C.POINTER(C.c_int64)]),
+    "wdpm_spill_table": (C.c_int, [_vp, _vp, C.c_int64]),
+    "wdpm_spill_stats": (C.c_int, [_vp, C.POINTER(SpillStatsStruct)]),
+    "wdpm_spill_phase_ms": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+}
+
+
 class GroupStatsStruct(C.Structure):
     """struct wdpm_group_pond_stats"""
     _fields_ = [("ranks", C.c_int64), ("ponds", C.c_int64), ("local_ponds", C.c_int64), ("stitch_unions", C.c_int64),
@@ -263,7 +294,7 @@ def bind(lib: capi.Lib):
         return lib.dll
     for name, (res, args) in list(SYMBOLS.items()) + list(GROUP_SYMBOLS.items()) + list(RIM_SYMBOLS.items()) + \
             list(GROUP_RIM_SYMBOLS.items()) + list(CATCH_SYMBOLS.items()) + list(OUTLET_SYMBOLS.items()) + list(GROUP_CATCH_SYMBOLS.items()) + \
-            list(GROUP_OUTLET_SYMBOLS.items()) + list(CURVE_SYMBOLS.items()) + list(GROUP_CURVE_SYMBOLS.items()):
+            list(GROUP_OUTLET_SYMBOLS.items()) + list(CURVE_SYMBOLS.items()) + list(GROUP_CURVE_SYMBOLS.items()) + list(SPILL_SYMBOLS.items()):
         try:
             fn = getattr(lib.dll, name)
         except AttributeError:
@@ -445,6 +476,30 @@ class Ponds(_Handle):
     def curve_phase_ms(self) -> dict:
         """milliseconds of the bed pass and of the stage pass of the last label_curves() (handles made with WDPM_PONDS_TIMING=1)"""
         return self._phase_ms(self.dll.wdpm_curves_phase_ms, CURVE_PHASES)
+
+    def label_spills(self, min_depth: float, headroom_tol: float = 0.0) -> int:
+        """label_curves(min_depth), then the spill pass on the tables it left; every older query answers as after label_curves().
+        A pond is spilling when it has an outlet and pour_level - surface_max <= headroom_tol (metres, finite, >= 0)."""
+        n = C.c_int64()
+        self.n = None
+        self.lib.check(self.dll.wdpm_spill_label(self._h, float(min_depth), float(headroom_tol), C.byref(n)))
+        self.n = n.value
+        return n.value
+
+    def spills(self, capacity: int | None = None) -> np.ndarray:
+        """One row per pond (SPILL_DTYPE) of the last label_spills(); fails after any lesser label call.  next / sink / rest are
+        labels (next 0: land that ends in a pit, -1: no outlet, -2: a ring of ponds closed here); path_fill_q and up_fill_q count
+        in VOLUME_QUANTUM metres; up_* is what drains through the pond once everything above it is full, live_* what is
+        connected to it now."""
+        return self._table(self.dll.wdpm_spill_table, SPILL_DTYPE, "spills", capacity, labelled_by="label_spills")
+
+    def spill_stats(self) -> dict:
+        return self._stats(self.dll.wdpm_spill_stats, SpillStatsStruct)
+
+    def spill_phase_ms(self) -> dict:
+        """milliseconds of the ring pass, the chain pass and the sums of the last label_spills() (handles made with
+        WDPM_PONDS_TIMING=1)"""
+        return self._phase_ms(self.dll.wdpm_spill_phase_ms, SPILL_PHASES)
 
 
 def stage_levels(bed: float, top: float, lib: capi.Lib | None = None) -> np.ndarray:
