@@ -208,6 +208,61 @@ def assert_invariants(table, values, fill_q, pour_level=None):
         assert np.isfinite(pour[heads]).all()
 
 
+def wave_targets(nxt, spilling, steps=1, wave=64):
+    """What the lanes of every wave of `wave` labels hold as a target once every edge reaches `steps` ponds on (1: the table's own
+    next; 2: the links after one doubling round): per wave a pair of histograms {target: lanes}, over the forest - the edges with
+    next > 0 - and over the live forest, where a pond keeps its edge only if it is spilling, and a longer edge only if every pond
+    it passes is.  A walk pond by pond; what a test claims about a scene's waves is read from here."""
+    nxt = [int(v) for v in nxt]
+    spilling = [bool(v) for v in spilling]
+    waves = []
+    for first in range(0, len(nxt), wave):
+        forest, live = {}, {}
+        for k in range(first, min(first + wave, len(nxt))):
+            for hist, alive in ((forest, False), (live, True)):
+                j = k + 1
+                for _ in range(steps):
+                    j = nxt[j - 1] if j > 0 and nxt[j - 1] > 0 and (spilling[j - 1] or not alive) else 0
+                if j > 0:
+                    hist[j] = hist.get(j, 0) + 1
+        waves.append((forest, live))
+    return waves
+
+
+def rounds_run_of(to, spilling):
+    """How many doubling rounds of each pass - rings, chains, sums - find something to do on the graph k -> to[k - 1] (the outlet
+    table's to_basin, rings not yet cut): plain numpy pointer doubling with the kernels' rule that a round runs while the one
+    before it has changed a minimum (rings) or left a link that is not an end (chains, sums), at most ceil(log2 n) + 1 of them.
+    The results of a pass lie in buffer (that number & 1).  Never used to compute an expected table."""
+    to = np.asarray(to, dtype=np.int64)
+    n = len(to)
+    if n == 0:
+        return (0, 0, 0)
+    rounds = rounds_of(n) // 3
+    idx = np.arange(n)
+    p = np.where(to > 0, to, 0)
+    m = np.where(to > 0, to, np.iinfo(np.int64).max)
+    ring, work = 0, bool((to > 0).any())
+    while ring < rounds and work:
+        on = p > 0
+        m2 = np.where(on, m[p - 1], m)
+        work = bool((m2 < m).any())
+        m = np.minimum(m, m2)
+        p = np.where(on, p[p - 1], 0)
+        ring += 1
+    nxt = np.where(m == idx + 1, -2, to)
+    link = np.where(nxt > 0, nxt, 0)
+    live = np.where(np.asarray(spilling, dtype=bool), link, 0)
+    chain = 0
+    while chain < rounds and (link > 0).any():
+        assert (link[live > 0] > 0).all()                      # a live link has a forest link beside it
+        link = np.where(link > 0, link[link - 1], 0)
+        live = np.where(live > 0, live[live - 1], 0)
+        chain += 1
+    assert not (link > 0).any() and not (live > 0).any()       # the heads are cut: every chain has ended
+    return (ring, chain, chain)                                # the sums pass doubles the forest's links again
+
+
 def assert_same_spills(table, stats, ref_table, ref_stats):
     """the whole table and the counts, for equality"""
     assert table.dtype == SPILL_DTYPE and len(table) == len(ref_table), (table.dtype, len(table), len(ref_table))

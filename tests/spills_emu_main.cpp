@@ -11,6 +11,8 @@
  *            ring:   one ring of N ponds with N / 2 + 37 ponds in trees hanging on it, a mutual pair beside it, labels shuffled
  *            chain:  one chain of N ponds, N -> N - 1 -> ... -> 1 -> land (the ring pass lowers its minimum in every round)
  *            hub:    ponds 2..N + 1 all spill into pond 1
+ *            votes:  a wave of hubs and, N times over, five waves made lane by lane for push_group's votes (make_votes), then one
+ *                    pond in a wave of its own
  *     FLAGS  0: spilling at random, 1: every pond with an outlet spills, 2: none does, 3: every second one
  */
 #include "hip_emu.h"
@@ -43,8 +45,44 @@ struct Tables {
   std::vector<wdpm_pond_outlet> out;
 };
 
+/* The table for push_group, lane by lane.  Wave 0 holds the hubs: ponds 8 -> 7 -> ... -> 1 (so the lanes that share a hub share
+ * the next one a round later), 9 onto land, 10 without an outlet, 11 -> 9, 12 -> 10, and 52 ponds that spill into the twelve in turn.
+ * Then `times` times five waves:
+ *   A  groups of 8, 7, 9 and 40 on hubs 1, 2, 3 and 9, scattered over the wave (lane l takes entry 37 l mod 64); lane 0 is one of
+ *      the 8, lane 1 one of the 40, lane 2 one of the 7: two votes succeed, the third fails, the 9 are never asked
+ *   B  four groups of 16 on hubs 4, 5, 11 and 12, lane l on group l mod 4: more hubs than tries
+ *   C  lanes 0..13 on hubs 6 and 7 in turn, lanes 14..33 on hub 8, the last 30 on land or without an outlet: no vote succeeds
+ *   D  the mirror: 20 lanes on hub 9 first, the 30 without a target, then hubs 2 and 11 in turn
+ *   E  lane 0 without an outlet, lanes 1..7 on hub 4, lanes 8..16 on hub 6, the others on hub 12: a failed vote, then two that
+ *      succeed
+ * and at the end one pond on hub 1 in a wave of its own.  Pond 1 spills into the first of wave A's eight that spill into it: a ring
+ * of two whose marked pond - lane 0 of wave A, whose target is the first put to the vote - goes through the butterfly with seven
+ * other lanes. */
+static std::vector<int> make_votes(int times) {
+  std::vector<int> to;
+  for (int k = 1; k <= 64; k++) to.push_back(k == 1 ? 0 : k <= 8 ? k - 1 : k == 9 ? 0 : k == 10 ? -1 : k == 11 ? 9 : k == 12 ? 10 : 1 + k % 12);
+  for (int rep = 0; rep < times; rep++) {
+    std::vector<int> sorted;
+    for (int l = 0; l < 64; l++) sorted.push_back(l < 8 ? 1 : l < 15 ? 2 : l < 24 ? 3 : 9);
+    for (int l = 0; l < 64; l++) to.push_back(sorted[(size_t)(37 * l % 64)]);                       /* A */
+    const int four[4] = {4, 5, 11, 12};
+    for (int l = 0; l < 64; l++) to.push_back(four[l % 4]);                                          /* B */
+    for (int l = 0; l < 64; l++) to.push_back(l < 14 ? 6 + l % 2 : l < 34 ? 8 : -(l % 2));           /* C */
+    for (int l = 0; l < 64; l++) to.push_back(l < 20 ? 9 : l < 50 ? -(l % 2) : l % 2 ? 11 : 2);      /* D */
+    for (int l = 0; l < 64; l++) to.push_back(l == 0 ? -1 : l < 8 ? 4 : l < 17 ? 6 : 12);            /* E */
+  }
+  to.push_back(1);
+  for (size_t k = 64; k < to.size(); k++)
+    if (to[k] == 1) {
+      to[0] = (int)k + 1;
+      break;
+    }
+  return to;
+}
+
 static std::vector<int> make_graph(const std::string &kind, int size, std::mt19937_64 &rng) {
   std::vector<int> to;
+  if (kind == "votes") return make_votes(size);
   auto below = [&](int n) { return (int)(rng() % (unsigned long long)n); };
   if (kind == "random") {
     for (int k = 1; k <= size; k++) {
@@ -202,7 +240,7 @@ static Reference reference(const Tables &t, double tol) {
 
 int main(int argc, char **argv) {
   if (argc < 5) {
-    fprintf(stderr, "usage: %s random|ring|chain|hub N SEED FLAGS\n", argv[0]);
+    fprintf(stderr, "usage: %s random|ring|chain|hub|votes N SEED FLAGS\n", argv[0]);
     return 2;
   }
   std::mt19937_64 rng((unsigned long long)atoll(argv[3]) * 7919u + 13u);

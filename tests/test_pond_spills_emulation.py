@@ -60,3 +60,19 @@ def test_all_none_and_every_second_pond_spilling(emu, kind, size, flags):
         assert got["spilling"] == got["N"]                     # every pond of these two has an outlet
     else:
         assert got["spilling"] > 0
+
+
+@pytest.mark.parametrize("flags", ["random", "all", "none", "alternating"])
+def test_waves_made_lane_by_lane_for_the_votes(emu, flags):
+    """A wave of hubs, then groups of 7, 8, 9 and 40; four groups of 16; 7 + 7 + 20 and its mirror; a wave whose lane 0 has no
+    target; one pond in a last wave of its own.  Pond 1 and one of the eight lanes that share it are a ring of two.  The flags
+    decide which lanes the live forest's votes see: every second lane halves every group - 16 become 8, 9 become 4 or 5."""
+    got, ran = run(emu, "votes", 1, 1, flags)
+    assert got["N"] == 64 + 5 * 64 + 1 and got["rings"] == 1 and got["ring_ponds"] == 2 and got["max_hops"] == 8
+    assert got["spilling"] == {"none": 0, "alternating": 161}.get(flags, got["spilling"]) and (got["spilling"] > 300) == (flags == "all")
+    assert ran[1:] == [4, 4] and 2 <= ran[0] <= got["rounds"] == 10       # links reach 1, 2, 4 and 8 ponds on: four rounds with work
+
+
+def test_the_vote_waves_three_times_over_cross_the_blocks_elsewhere(emu):
+    got, ran = run(emu, "votes", 3, 2, "random")
+    assert got["N"] == 64 + 15 * 64 + 1 and got["rings"] == 1 and got["ring_ponds"] == 2 and ran[1:] == [4, 4]
