@@ -41,6 +41,10 @@
                       chains and sums phases beside the table, passes, locate, bed and stages phases of the SAME calls, their
                       ratios to the table phase, the counts, and the bytes of the unit's working arrays (whole rasters only;
                       default --out profiles/r26/pond_spills.json)
+    ... --routing     a runoff depth sent down the spill graph as well (include/wdpm_pond_routing.h): per depth of --runoff-mm one
+                      untimed label_routing and five timed ones - the order, sweep and finish phases beside the table phase and the
+                      rings, chains and sums phases of the SAME calls - then five timed route() calls, wall clock and phases: what
+                      another depth costs once the ponds are ordered (whole rasters only; default --out profiles/r28/pond_routing.json)
     ... --iterations K   instead of the job's own number of iterations before the inventory
     ... --lib FILE       another build of the library (tools/build_alt.sh NAME REV) instead of the tree's: the same job on the parent
 
@@ -69,7 +73,8 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 import wdpm_amd  # noqa: E402
-from wdpm_amd.ponds import CATCH_PHASES, CURVE_PHASES, OUTLET_PHASES, PHASES, RIM_PHASES, SPILL_PHASES, GroupPonds, Ponds  # noqa: E402
+from wdpm_amd.ponds import (CATCH_PHASES, CURVE_PHASES, OUTLET_PHASES, PHASES, RIM_PHASES, ROUTE_PHASES, SPILL_PHASES, GroupPonds,  # noqa: E402
+                            Ponds)
 
 MISS = -99999.0
 
@@ -249,6 +254,48 @@ def spills_job(ctx, p, rec, n):
         most_direct_feeders=int(np.bincount(table["next"][table["next"] > 0]).max()) if (table["next"] > 0).any() else 0,
         largest_up_ponds=int(table["up_ponds"].max()) if npond else 0, largest_live_ponds=int(table["live_ponds"].max()) if npond else 0,
         table_bytes=int(table.nbytes), working_bytes=npond * (15 * 4 + 14 * 8), guard_bad=p.guard_bad())
+
+
+def routing_job(ctx, p, rec, runoffs_mm):
+    """after the label calls, per runoff depth: one untimed label_routing (allocates), five timed ones, five timed reruns"""
+    rec["routing"] = []
+    for mm in runoffs_mm:
+        r = mm / 1000.0
+        p.label_routing(0.001, r, 0.0)
+        wall, phases = [], {k: [] for k in ROUTE_PHASES}
+        beside = {k: [] for k in ("table",) + SPILL_PHASES}
+        for _ in range(5):
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            p.label_routing(0.001, r, 0.0)
+            wall.append((time.perf_counter() - t0) * 1e3)
+            for k, v in p.routing_phase_ms().items():
+                phases[k].append(v)
+            beside["table"].append(p.phase_ms()["table"])
+            for k, v in p.spill_phase_ms().items():
+                beside[k].append(v)
+        rerun_wall, rerun = [], {k: [] for k in ROUTE_PHASES}
+        for _ in range(5):
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            p.route(r)
+            rerun_wall.append((time.perf_counter() - t0) * 1e3)
+            for k, v in p.routing_phase_ms().items():
+                rerun[k].append(v)
+        table, stats = p.routing(), p.routing_stats()
+        med = {k: statistics.median(v) for k, v in phases.items()}
+        bmed = {k: statistics.median(v) for k, v in beside.items()}
+        npond = len(table)
+        rec["routing"].append(dict(
+            runoff_mm=mm, label_routing_wall_ms=statistics.median(wall), label_routing_wall_ms_all=wall, phase_ms=med, phase_ms_all=phases,
+            routing_pass_ms=sum(med.values()), beside_ms_same_calls=bmed, beside_ms_all=beside,
+            routing_pass_over_table=sum(med.values()) / bmed["table"] if bmed["table"] > 0 else None,
+            routing_pass_over_spill_pass=sum(med.values()) / sum(bmed[k] for k in SPILL_PHASES) if sum(bmed[k] for k in SPILL_PHASES) > 0 else None,
+            rerun_wall_ms=statistics.median(rerun_wall), rerun_wall_ms_all=rerun_wall,
+            rerun_phase_ms={k: statistics.median(v) for k, v in rerun.items()}, stats=stats,
+            largest_reach_ponds=int(table["reach_ponds"].max()) if npond else 0, largest_reach_cells=int(table["reach_cells"].max()) if npond else 0,
+            largest_level=int(np.bincount(table["level"]).max()) if npond else 0, table_bytes=int(table.nbytes),
+            working_bytes=npond * (3 * 4 + 5 * 8) + 8 * (stats["levels"] + 1), guard_bad=p.guard_bad()))
 
 
 def yardstick_gbps(path):
@@ -480,17 +527,23 @@ def main():
                     help="time label_curves (with --devices: label_stage_curves) as well: the bed and stages phases beside table, passes and locate")
     ap.add_argument("--spills", action="store_true",
                     help="time label_spills as well: the rings, chains and sums phases beside table, passes, locate, bed and stages")
+    ap.add_argument("--routing", action="store_true",
+                    help="time label_routing and route() as well: the order, sweep and finish phases beside table, rings, chains and sums")
+    ap.add_argument("--runoff-mm", default="1,10,100", metavar="a,b,...", help="the runoff depths of --routing, in millimetres")
     ap.add_argument("--iterations", type=int, help="iterations before the inventory, instead of the job's own")
     ap.add_argument("--lib", metavar="FILE", help="time this build of the library (tools/build_alt.sh) instead of the tree's own")
     a = ap.parse_args()
     if a.spills and a.devices:
         ap.error("--spills: spills are taken on a whole raster only")
+    if a.routing and a.devices:
+        ap.error("--routing: routing is taken on a whole raster only")
     if not a.out:
         a.out = os.path.join(ROOT, "profiles", *(("r24", "pond_curves_group.json") if a.devices and a.curves else
                                                   ("r17", "pond_outlets_group.json") if a.devices and a.outlets else
                                                   ("r16", "pond_catchments_group.json") if a.devices and a.catchments else
                                                   ("r13", "pond_rims_group.json") if a.devices and a.rims else
                                                   ("r11", "ponds_group.json") if a.devices else
+                                                  ("r28", "pond_routing.json") if a.routing else
                                                   ("r26", "pond_spills.json") if a.spills else
                                                   ("r18", "pond_curves.json") if a.curves else
                                                   ("r15", "pond_outlets.json") if a.outlets else
@@ -568,6 +621,8 @@ def main():
                 curves_job(ctx, p, rec, n)
             if a.spills:
                 spills_job(ctx, p, rec, n)
+            if a.routing:
+                routing_job(ctx, p, rec, [float(v) for v in a.runoff_mm.split(",")])
         if not a.no_scipy:
             try:
                 import scipy.ndimage as ndi

@@ -485,7 +485,8 @@ void release(wdpm_ponds *h) {
   reset(h, h->out.h_seam);
   reset(h, h->cur.table); reset(h, h->cur.status); reset(h, h->cur.keys); reset(h, h->cur.h_keys); reset(h, h->cur.h_table);
   reset(h, h->spl.table); reset(h, h->spl.words); reset(h, h->spl.sums); reset(h, h->spl.status);
-  l.allocated = l.valid = h->rim.valid = h->cat.valid = h->out.valid = h->cur.valid = h->spl.valid = false;
+  reset(h, h->rte.table); reset(h, h->rte.words); reset(h, h->rte.sums); reset(h, h->rte.status); reset(h, h->rte.h_offsets);
+  l.allocated = l.valid = h->rim.valid = h->cat.valid = h->out.valid = h->cur.valid = h->spl.valid = h->rte.valid = false;
 }
 
 int allocate(wdpm_ponds *h) {
@@ -537,6 +538,9 @@ wdpm_ponds *make_handle(wdpm_ctx *ctx, int row_off, int rows, bool seams) {
   h->out.timer.create(h->timing);
   h->cur.timer.create(h->timing);
   h->spl.timer.create(h->timing);
+  h->rte.timer.create(h->timing);
+  h->rte.narrow = route_bound(getenv("WDPM_ROUTE_NARROW"), 1, kBlock, kBlock);
+  h->rte.run_levels = route_bound(getenv("WDPM_ROUTE_RUN_LEVELS"), 1, INT_MAX, kRouteRunLevels);
   return h;
 }
 
@@ -552,6 +556,7 @@ int label_queue(wdpm_ponds *h, double min_depth) {
   h->out.valid = false;             /* and an outlet table (wdpm_pond_outlets.hip) */
   h->cur.valid = false;             /* and a curve table (wdpm_pond_curves.hip) */
   h->spl.valid = false;             /* and a spill table (wdpm_pond_spills.hip) */
+  h->rte.valid = false;             /* and a routing table (wdpm_pond_routing.hip) */
   /* the raster as a reader sees it: side stream joined, owed drain() and threshold flush applied (what wdpm_count_stats asks for) */
   if (wdpm_synchronize(x)) return 1;
   if (wdpm_apply_owed_flush(x)) return 1;
@@ -678,6 +683,7 @@ void destroy_handle(wdpm_ponds *h) {
   h->out.timer.destroy();
   h->cur.timer.destroy();
   h->spl.timer.destroy();
+  h->rte.timer.destroy();
   delete h;
 }
 

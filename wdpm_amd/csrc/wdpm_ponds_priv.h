@@ -1,6 +1,7 @@
 /*
  * wdpm_ponds_priv.h — what the units of the pond inventory share: wdpm_ponds.hip (labels and table), wdpm_pond_rims.hip
- * (rims), wdpm_pond_catchments.hip (catchments), wdpm_pond_outlets.hip (outlets), wdpm_pond_curves.hip (stage curves) and wdpm_pond_spills.hip (spills).  Geometry, the order-preserving image of a
+ * (rims), wdpm_pond_catchments.hip (catchments), wdpm_pond_outlets.hip (outlets), wdpm_pond_curves.hip (stage curves), wdpm_pond_spills.hip (spills)
+ * and wdpm_pond_routing.hip (routing).  Geometry, the order-preserving image of a
  * double, the table rows as the device accumulates them, the wave helpers of the kernels (a lane's neighbour, the wave's extremum,
  * the look before an atomic) and - outside the host emulations of the tests, which define WDPM_PONDS_EMULATION and bring stand-ins
  * for the HIP device language (tests/hip_emu.h) - the host side: the guarded allocator, the holders every buffer, status pair and
@@ -35,6 +36,8 @@
 #include "../../include/wdpm_pond_curves.h"
 #include "../../include/wdpm_group_pond_curves.h"
 #include "../../include/wdpm_pond_spills.h"
+#include "../../include/wdpm_pond_routing.h"
+#include "wdpm_route_plan.h"
 
 namespace wdpm_pond_detail {
 
@@ -149,6 +152,13 @@ struct SpillStatus {
   unsigned work[kSpillPasses][kSpillMaxRounds + 1];
   unsigned pad;
 };
+
+/* what the routing kernels (wdpm_pond_routing.hip) count for the host: the sweep the overflow that leaves the graph, the finish the
+ * rest */
+struct RouteStatus {
+  unsigned long long overflowing, full, own_q, kept_q, out_land_q, out_ring_q;
+};
+static_assert(kRouteBlock == kBlock, "the planner's workgroup is the kernels'");
 
 /* status words the host reads after the scan */
 struct Status {
@@ -390,6 +400,20 @@ struct SpillUnit {                  /* wdpm_pond_spills.hip: likewise for wdpm_s
   wdpm_pond_spill_stats stats = {};
 };
 
+struct RouteUnit {                  /* wdpm_pond_routing.hip: likewise for wdpm_route_label and wdpm_route_rerun; whole rasters only */
+  DevBuf<wdpm_pond_route> table;
+  DevBuf<int> words;                /* 3 x N: next, level and the ponds in level order; then levels + 1 offsets and as many cursors */
+  DevBuf<unsigned long long> sums;  /* 5 x N: area, fill_q, and what the feeders add: in_q, reach_ponds, reach_cells */
+  StatusPair<RouteStatus> status;
+  PinBuf<int> h_offsets;            /* the levels + 1 offsets on their way down, once per label call */
+  bool valid = false;               /* the table, and with it everything a rerun stands on */
+  int narrow = kBlock, run_levels = kRouteRunLevels;   /* WDPM_ROUTE_NARROW, WDPM_ROUTE_RUN_LEVELS when the handle was made */
+  int levels = 0;                   /* of the last label call */
+  RoutePlan plan;
+  PhaseTimer<5, WDPM_ROUTE_PHASES> timer;                           /* order | (the host plans) | sweep | finish */
+  wdpm_pond_route_stats stats = {};
+};
+
 /* a merged table of a group: what the last label call of its kind left; every label call takes `valid` away first */
 template <class Row, class Stats> struct Merged {
   std::vector<Row> rows;
@@ -419,6 +443,7 @@ struct wdpm_ponds {
   wdpm_pond_detail::OutletUnit out;
   wdpm_pond_detail::CurveUnit cur;
   wdpm_pond_detail::SpillUnit spl;
+  wdpm_pond_detail::RouteUnit rte;
 };
 
 /* the handle of include/wdpm_group_ponds.h, include/wdpm_group_pond_rims.h, include/wdpm_group_pond_catchments.h,

@@ -24,7 +24,7 @@
  *     devices 0..N-1 by row blocks (WDPM_DEVICES=a,b,c names them explicitly), one host thread per device,
  *     exchanging halo rows every WDPM_EXCHANGE_EVERY iterations (default 8) by RCCL send/recv
  *     (WDPM_HALO=peer: peer copies); results do not depend on N.
- *   - WDPM_PONDS=<path> and its five siblings write CSV files about the ponds of the final water: wdpmcl_ponds.c.
+ *   - WDPM_PONDS=<path> and its six siblings write CSV files about the ponds of the final water: wdpmcl_ponds.c.
  */
 #include <ctype.h>
 #include <math.h>

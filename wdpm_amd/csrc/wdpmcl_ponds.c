@@ -12,6 +12,8 @@
  *   WDPM_POND_SPILLS=<path>       where each pond's overflow ends up, what drains through it and what is connected to it now
  *                                 (include/wdpm_pond_spills.h).  A pond counts as spilling when its surface stands within
  *                                 WDPM_POND_HEADROOM_MM (default 0) of its pour level
+ *   WDPM_POND_ROUTING=<path>      WDPM_POND_RUNOFF_MM (default 0) of runoff on every basin, sent down the spill graph: what each pond
+ *                                 takes, keeps and passes on, and the land connected to it afterwards (include/wdpm_pond_routing.h)
  *
  * The units are the rows of one table, `units`, in that order; everything else here is written once and driven by it.  One label
  * call - that of the highest unit asked for - serves every file of the run; the tables then fetched are those the rows' `needs`
@@ -33,6 +35,7 @@
 #include "../../include/wdpm_pond_outlets.h"
 #include "../../include/wdpm_pond_curves.h"
 #include "../../include/wdpm_pond_spills.h"
+#include "../../include/wdpm_pond_routing.h"
 #pragma weak wdpm_ponds_create
 #pragma weak wdpm_ponds_destroy
 #pragma weak wdpm_ponds_label
@@ -59,8 +62,11 @@
 #pragma weak wdpm_spill_label
 #pragma weak wdpm_spill_table
 #pragma weak wdpm_spill_stats
+#pragma weak wdpm_route_label
+#pragma weak wdpm_route_table
+#pragma weak wdpm_route_stats
 
-enum { PONDS, RIMS, CATCH, OUTLETS, CURVES, SPILLS, UNITS };
+enum { PONDS, RIMS, CATCH, OUTLETS, CURVES, SPILLS, ROUTING, UNITS };
 #define BIT(u) (1u << (u))
 
 typedef struct {
@@ -70,6 +76,7 @@ typedef struct {
   wdpm_pond_outlet_stats outlet_stats;
   wdpm_pond_curve_stats curve_stats;
   wdpm_pond_spill_stats spill_stats;
+  wdpm_pond_route_stats route_stats;
   double cellarea;
 } pond_inventory;
 
@@ -99,6 +106,7 @@ static int catch_there(void) { return wdpm_catch_label && wdpm_catch_table && wd
 static int outlets_there(void) { return wdpm_outlets_label && wdpm_outlets_table && wdpm_outlets_stats; }
 static int curves_there(void) { return wdpm_curves_label && wdpm_curves_table && wdpm_curves_stats && wdpm_curves_stage_level; }
 static int spills_there(void) { return wdpm_spill_label && wdpm_spill_table && wdpm_spill_stats; }
+static int routing_there(void) { return wdpm_route_label && wdpm_route_table && wdpm_route_stats; }
 
 static int ponds_table(wdpm_ponds *h, pond_inventory *v) { return wdpm_ponds_table(h, (wdpm_pond *)v->table[PONDS], v->n); }
 static int group_ponds_table(wdpm_group_ponds *g, pond_inventory *v) { return wdpm_group_ponds_table(g, (wdpm_pond *)v->table[PONDS], v->n); }
@@ -114,6 +122,11 @@ static double headroom_tol;
 static int spills_label(wdpm_ponds *h, double min_depth, int64_t *n) { return wdpm_spill_label(h, min_depth, headroom_tol, n); }
 static int spills_table(wdpm_ponds *h, pond_inventory *v) { return wdpm_spill_table(h, (wdpm_pond_spill *)v->table[SPILLS], v->n); }
 static int spills_stats(wdpm_ponds *h, pond_inventory *v) { return wdpm_spill_stats(h, &v->spill_stats); }
+/* and the routing pass a third, read beside it */
+static double runoff_m;
+static int routing_label(wdpm_ponds *h, double min_depth, int64_t *n) { return wdpm_route_label(h, min_depth, headroom_tol, runoff_m, n); }
+static int routing_table(wdpm_ponds *h, pond_inventory *v) { return wdpm_route_table(h, (wdpm_pond_route *)v->table[ROUTING], v->n); }
+static int routing_stats(wdpm_ponds *h, pond_inventory *v) { return wdpm_route_stats(h, &v->route_stats); }
 
 /* ---- the row printers: coordinates leave as file coordinates, 0-based (padded - 1), -1 where there is none; doubles as %.17g
  * so that they read back exactly; volumes in quanta of 2^-24 m and in cubic metres ---- */
@@ -175,6 +188,15 @@ static void print_spill(FILE *f, const pond_inventory *v, int64_t k) {
           (double)q->live_cells * v->cellarea);
 }
 
+/* what the pond takes, keeps and passes on in quanta of 2^-24 m times cells, the overflow also in cubic metres; reach_*: the pond
+ * itself and what is connected to it through ponds that overflow */
+static void print_route(FILE *f, const pond_inventory *v, int64_t k) {
+  const wdpm_pond_route *q = (const wdpm_pond_route *)v->table[ROUTING] + k;
+  fprintf(f, "%lld,%d,%llu,%llu,%llu,%llu,%.17g,%d,%d,%lld,%lld,%.17g\n", (long long)(k + 1), q->level, (unsigned long long)q->own_q,
+          (unsigned long long)q->in_q, (unsigned long long)q->kept_q, (unsigned long long)q->out_q, ldexp((double)q->out_q, -24) * v->cellarea,
+          q->full, q->overflows, (long long)q->reach_ponds, (long long)q->reach_cells, (double)q->reach_cells * v->cellarea);
+}
+
 static void tail_ponds(const pond_inventory *v, char *buf, size_t len) {
   if (v->blocks > 1) snprintf(buf, len, " (%lld row blocks, %lld joined across them)", (long long)v->blocks, (long long)v->joined);
 }
@@ -200,8 +222,15 @@ static void tail_spills(const pond_inventory *v, char *buf, size_t len) {
            (long long)s->ends_ring, (long long)s->max_hops);
 }
 
+static void tail_routing(const pond_inventory *v, char *buf, size_t len) {
+  const wdpm_pond_route_stats *s = &v->route_stats;
+  snprintf(buf, len, " (%.17g mm of runoff: %lld full, %lld overflowing, %.17g m3 kept, %.17g m3 left over land, %.17g m3 at rings; %lld levels)",
+           ldexp((double)s->runoff_q, -24) * 1000.0, (long long)s->full, (long long)s->overflowing, ldexp((double)s->kept_q, -24) * v->cellarea,
+           ldexp((double)s->out_land_q, -24) * v->cellarea, ldexp((double)s->out_ring_q, -24) * v->cellarea, (long long)s->levels);
+}
+
 /* ---- the table.  needs: an outlets file reads the rim table for its headroom and fetches the catchment table with it; a curves
- * file and a spills file each read their own table alone ---- */
+ * file, a spills file and a routing file each read their own table alone ---- */
 static const pond_unit units[UNITS] = {
     {"WDPM_PONDS", "pond inventory", NULL, sizeof(wdpm_pond), BIT(PONDS), ponds_there, wdpm_ponds_label, ponds_table, NULL,
      wdpm_group_ponds_label, group_ponds_table,
@@ -222,6 +251,9 @@ static const pond_unit units[UNITS] = {
      "label,next_label,spilling,sink_label,end,hops,path_fill_q,path_fill_m3,up_ponds,up_cells,up_area_m2,up_fill_q,up_fill_m3,rest_label,"
      "rest_hops,live_ponds,live_cells,live_area_m2",
      print_spill, tail_spills},
+    {"WDPM_POND_ROUTING", "pond routing", "routing is", sizeof(wdpm_pond_route), BIT(PONDS) | BIT(ROUTING), routing_there, routing_label,
+     routing_table, routing_stats, NULL, NULL,
+     "label,level,own_q,in_q,kept_q,out_q,out_m3,full,overflows,reach_ponds,reach_cells,reach_area_m2", print_route, tail_routing},
 };
 
 static void free_tables(pond_inventory *v) {
@@ -282,7 +314,7 @@ static int take_inventory(wdpm_group *grp, int ndev, unsigned asked, double min_
 }
 
 static int write_unit(const pond_unit *u, const char *path, const pond_inventory *v) {
-  char tail[256] = "";
+  char tail[384] = "";
   FILE *f = fopen(path, "w");
   if (!f) {
     fprintf(stderr, "WDPMCL: cannot write %s %s\n", u->name, path);
@@ -326,6 +358,7 @@ int wdpmcl_pond_files(wdpm_group *grp, int ndev, double cellarea, int64_t *guard
   if (!asked) return failed;
   const double min_depth = (getenv("WDPM_PONDS_MIN_DEPTH_MM") ? atof(getenv("WDPM_PONDS_MIN_DEPTH_MM")) : 1.0) / 1000.0;
   headroom_tol = (getenv("WDPM_POND_HEADROOM_MM") ? atof(getenv("WDPM_POND_HEADROOM_MM")) : 0.0) / 1000.0;
+  runoff_m = (getenv("WDPM_POND_RUNOFF_MM") ? atof(getenv("WDPM_POND_RUNOFF_MM")) : 0.0) / 1000.0;
   pond_inventory v;
   memset(&v, 0, sizeof v);
   v.blocks = 1;

@@ -1,8 +1,9 @@
 """ctypes binding of include/wdpm_ponds.h, include/wdpm_group_ponds.h, include/wdpm_pond_rims.h, include/wdpm_group_pond_rims.h,
 include/wdpm_pond_catchments.h, include/wdpm_pond_outlets.h, include/wdpm_group_pond_catchments.h,
-include/wdpm_group_pond_outlets.h, include/wdpm_pond_curves.h, include/wdpm_group_pond_curves.h and include/wdpm_pond_spills.h: the pond
-inventory of a context's current water raster, of a raster spread over the row blocks of a rowblock.Group, the rim, the catchment, the
-outlet and the stage curve of every pond of either, and where every pond of a whole raster spills to.
+include/wdpm_group_pond_outlets.h, include/wdpm_pond_curves.h, include/wdpm_group_pond_curves.h, include/wdpm_pond_spills.h and
+include/wdpm_pond_routing.h: the pond inventory of a context's current water raster, of a raster spread over the row blocks of a
+rowblock.Group, the rim, the catchment, the outlet and the stage curve of every pond of either, where every pond of a whole raster
+spills to, and what a runoff depth sent down that graph leaves in every pond.
 
 Product library only (the symbols are not part of the ABI of include/wdpm.h, and ``capi.SYMBOLS`` does not list them).
 
@@ -24,6 +25,9 @@ Product library only (the symbols are not part of the ABI of include/wdpm.h, and
         levels = stage_levels(curves["bed_level"][0], curves["top_level"][0])   # the seventeen heights of pond 1, stage 0..16
         n = ponds.label_spills(0.001, headroom_tol=0.0)   # all of the above, and every pond's spill followed downstream
         spills = ponds.spills()     # next, sink, end, hops, storage on the way, what drains through it, what is connected now (SPILL_DTYPE)
+        n = ponds.label_routing(0.001, runoff_m=0.010)    # all of the above, and 10 mm of runoff sent down the spill graph
+        routing = ponds.routing()   # what each pond takes, keeps and passes on, and what is connected to it afterwards (ROUTE_DTYPE)
+        ponds.route(0.025)          # another depth on the same graph: nothing is labelled again
 
     with rowblock.Group(...) as grp, GroupPonds(grp) as ponds:     # the same calls, the same answer, every rank labelled in place
         n = ponds.label(0.001)
@@ -53,6 +57,7 @@ OUTLET_PHASES = ("passes", "locate")                               # wdpm_outlet
 CURVE_PHASES = ("bed", "stages")                                   # wdpm_curves_phase_ms
 CURVE_STAGES = 16                                                  # WDPM_CURVE_STAGES
 SPILL_PHASES = ("rings", "chains", "sums")                         # wdpm_spill_phase_ms
+ROUTE_PHASES = ("order", "sweep", "finish")                        # wdpm_route_phase_ms
 
 
 class PondStruct(C.Structure):
@@ -207,6 +212,34 @@ SPILL_SYMBOLS = {
 }
 
 
+class RouteStruct(C.Structure):
+    """struct wdpm_pond_route"""
+    _fields_ = [("own_q", C.c_uint64), ("in_q", C.c_uint64), ("kept_q", C.c_uint64), ("out_q", C.c_uint64), ("reach_ponds", C.c_int64),
+                ("reach_cells", C.c_int64), ("overflows", C.c_int32), ("full", C.c_int32), ("level", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RouteStatsStruct(C.Structure):
+    """struct wdpm_pond_route_stats"""
+    _fields_ = [("ponds", C.c_int64), ("runoff_q", C.c_int64), ("levels", C.c_int64), ("wide_levels", C.c_int64), ("launches", C.c_int64),
+                ("overflowing", C.c_int64), ("full", C.c_int64), ("own_q", C.c_uint64), ("kept_q", C.c_uint64), ("out_land_q", C.c_uint64),
+                ("out_ring_q", C.c_uint64)]
+
+
+ROUTE_DTYPE = np.dtype([("own_q", "<u8"), ("in_q", "<u8"), ("kept_q", "<u8"), ("out_q", "<u8"), ("reach_ponds", "<i8"), ("reach_cells", "<i8"),
+                        ("overflows", "<i4"), ("full", "<i4"), ("level", "<i4"), ("reserved", "<i4")])
+assert ROUTE_DTYPE.itemsize == C.sizeof(RouteStruct) == 64 and C.sizeof(RouteStatsStruct) == 88
+
+# every symbol include/wdpm_pond_routing.h declares
+ROUTE_SYMBOLS = {
+    "wdpm_route_label": (C.c_int, [_vp, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int64)]),
+    "wdpm_route_rerun": (C.c_int, [_vp, C.c_double]),
+    "wdpm_route_table": (C.c_int, [_vp, _vp, C.c_int64]),
+    "wdpm_route_stats": (C.c_int, [_vp, C.POINTER(RouteStatsStruct)]),
+    "wdpm_route_phase_ms": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "wdpm_route_runoff_q": (C.c_int64, [C.c_double]),
+}
+
+
 class GroupStatsStruct(C.Structure):
     """struct wdpm_group_pond_stats"""
     _fields_ = [("ranks", C.c_int64), ("ponds", C.c_int64), ("local_ponds", C.c_int64), ("stitch_unions", C.c_int64),
@@ -294,7 +327,8 @@ def bind(lib: capi.Lib):
         return lib.dll
     for name, (res, args) in list(SYMBOLS.items()) + list(GROUP_SYMBOLS.items()) + list(RIM_SYMBOLS.items()) + \
             list(GROUP_RIM_SYMBOLS.items()) + list(CATCH_SYMBOLS.items()) + list(OUTLET_SYMBOLS.items()) + list(GROUP_CATCH_SYMBOLS.items()) + \
-            list(GROUP_OUTLET_SYMBOLS.items()) + list(CURVE_SYMBOLS.items()) + list(GROUP_CURVE_SYMBOLS.items()) + list(SPILL_SYMBOLS.items()):
+            list(GROUP_OUTLET_SYMBOLS.items()) + list(CURVE_SYMBOLS.items()) + list(GROUP_CURVE_SYMBOLS.items()) + list(SPILL_SYMBOLS.items()) + \
+            list(ROUTE_SYMBOLS.items()):
         try:
             fn = getattr(lib.dll, name)
         except AttributeError:
@@ -501,6 +535,33 @@ class Ponds(_Handle):
         WDPM_PONDS_TIMING=1)"""
         return self._phase_ms(self.dll.wdpm_spill_phase_ms, SPILL_PHASES)
 
+    def label_routing(self, min_depth: float, runoff_m: float, headroom_tol: float = 0.0) -> int:
+        """label_spills(min_depth, headroom_tol), then runoff_m metres of runoff on every basin sent down the spill graph; every
+        older query, spills() included, answers as after label_spills().  runoff_m is finite, >= 0 and below 256 m."""
+        n = C.c_int64()
+        self.n = None
+        self.lib.check(self.dll.wdpm_route_label(self._h, float(min_depth), float(headroom_tol), float(runoff_m), C.byref(n)))
+        self.n = n.value
+        return n.value
+
+    def route(self, runoff_m: float) -> None:
+        """another runoff depth on the graph of the last label_routing(): sweep and finish only, nothing is labelled again; fails
+        after any lesser label call"""
+        self.lib.check(self.dll.wdpm_route_rerun(self._h, float(runoff_m)))
+
+    def routing(self, capacity: int | None = None) -> np.ndarray:
+        """One row per pond (ROUTE_DTYPE) of the last label_routing() or route(): own_q, in_q, kept_q and out_q count in
+        VOLUME_QUANTUM metres times cells; reach_* is what is connected to the pond after the event."""
+        return self._table(self.dll.wdpm_route_table, ROUTE_DTYPE, "routing", capacity, labelled_by="label_routing")
+
+    def routing_stats(self) -> dict:
+        return self._stats(self.dll.wdpm_route_stats, RouteStatsStruct)
+
+    def routing_phase_ms(self) -> dict:
+        """milliseconds of the ordering by level (0 after route()), of the sweep and of the finish of the last label_routing() or
+        route() (handles made with WDPM_PONDS_TIMING=1)"""
+        return self._phase_ms(self.dll.wdpm_route_phase_ms, ROUTE_PHASES)
+
 
 def stage_levels(bed: float, top: float, lib: capi.Lib | None = None) -> np.ndarray:
     """The seventeen stage heights 0..16 of a curve row, from the library's own wdpm_curves_stage_level (`lib`: a loaded product
@@ -508,6 +569,13 @@ def stage_levels(bed: float, top: float, lib: capi.Lib | None = None) -> np.ndar
     everything past the bed is not finite."""
     dll = bind(capi.load_hip() if lib is None else lib)
     return np.array([dll.wdpm_curves_stage_level(float(bed), float(top), s) for s in range(CURVE_STAGES + 1)], dtype=np.float64)
+
+
+def runoff_q(runoff_m: float, lib: capi.Lib | None = None) -> int:
+    """The quanta of 2^-24 m a routing call makes of runoff_m, from the library's own wdpm_route_runoff_q; -1 where the call would
+    refuse the depth."""
+    dll = bind(capi.load_hip() if lib is None else lib)
+    return int(dll.wdpm_route_runoff_q(float(runoff_m)))
 
 
 class GroupPonds(_Handle):
